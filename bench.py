@@ -8,6 +8,11 @@ A "step" is one full frame: every rank renders its interleaved rows, then one ga
 
 Launch: `python bench.py --gpus 1 --steps K --warmup W`, or for N>1
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`.
+
+A plain run does what the headline figure needs: scene set-up and tune, one counting launch (the ray count), warm-up, the K timed
+steps, and the result line; its roofline is derived from those numbers.  `--full` adds everything that takes runs of its own: the
+check against the reference's own tree, the frame without rt_scene_tune, a scene's first frame, and the CPU baseline.
+`--dump-outputs DIR` writes the last timed step's frame to DIR/*.npy (see dump_outputs) so two builds can be compared.
 """
 import argparse
 import json
@@ -137,6 +142,27 @@ def cpu_baseline(objs, cam, w, h, seed, target_seconds):
             "rays": st["rays"], "seconds": round(dt, 2)}
 
 
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(frame, out_dir):
+    """What the timed path hands its caller: the gathered PixelStats accumulators [rows, cols, 4] {Count; SumRed; SumGreen; SumBlue},
+    as DIR/accum.npy in float32 (float64 if a value is not exact in float32).  A frame over DUMP_MAX_BYTES is cut to a fixed,
+    seeded sample of whole image rows, in ascending order; their indices go to DIR/accum_rows.npy."""
+    import numpy as np
+
+    a = frame.cpu().numpy()
+    dtype = np.dtype(np.float32 if int(np.abs(a).max(initial=0)) <= 2**24 else np.float64)
+    row_bytes = a[0].size * dtype.itemsize
+    os.makedirs(out_dir, exist_ok=True)
+    if a.shape[0] * row_bytes + 4096 > DUMP_MAX_BYTES:
+        k = (DUMP_MAX_BYTES - 8192) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False))
+        a = a[rows]
+        np.save(os.path.join(out_dir, "accum_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "accum.npy"), a.astype(dtype))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -149,16 +175,21 @@ def main():
     ap.add_argument("--workload", default="c3", choices=["c2", "c3", "c4", "c5"],
                     help="BASELINE.json config: c3 (default, the metric's config) final scene 2401x1601x500spp; c2 three Lambert spheres "
                          "801x451x100spp; c4 final scene 7681x4321x1000spp; c5 final scene + earth texture + plane + Dielectric, 2000spp")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target wall time of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also run the legs beyond the headline figure: the reference-tree check, the frame "
+                                                        "without rt_scene_tune, a scene's first frame, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's frame to DIR/accum.npy (see dump_outputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: target wall time of the CPU baseline sample (0 = skip)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) is the product path; gloo stages the gather through host memory and lets several ranks share one GPU (rehearsal only)")
     ap.add_argument("--block", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=0)
-    ap.add_argument("--no-untuned-leg", action="store_true", help="skip the legs that time the same frame WITHOUT rt_scene_tune and a scene's FIRST frame (tune + frame): "
-                                                                  "for kernel traces, which should hold one configuration of the timed kernel")
+    ap.add_argument("--no-untuned-leg", action="store_true", help="with --full: skip the legs that time the same frame WITHOUT rt_scene_tune and a scene's FIRST frame "
+                                                                  "(tune + frame): for kernel traces, which should hold one configuration of the timed kernel")
     ap.add_argument("--untuned-leg", action="store_true", help=argparse.SUPPRESS)  # the default now; accepted for older command lines
     ap.add_argument("--no-tune", action="store_true", help="walk the surface-area tree as built, without rt_scene_tune's probe")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -226,18 +257,20 @@ def main():
                                  counters=True, want_stats=True)
     # the same launch over BoundingBoxTree.make's own tree: its box-test count is the reference's (and the oracle's); every other
     # counter and every pixel must be the walked (surface-area) tree's -- checked here on the real workload, untimed
-    rt.set_walk_tree("reference")
-    try:
-        ref_scene = rt.Scene.make(objs)
-    finally:
-        rt.set_walk_tree("sah")
-    check = torch.zeros_like(local)
-    st_ref = rtd.render_shard_device(ref_scene, cam, w, h, args.seed, local_rank, first, stride, n, check, stream=stream.cuda_stream,
-                                     counters=True, want_stats=True)
-    torch.cuda.synchronize(dev)
-    if not torch.equal(check, local) or any(st_ref[k] != st[k] for k in ("rays", "prim_tests", "reflections", "samples", "pixels_early")):
-        raise SystemExit("walking the reference's own tree and the tree of this run gave different results")
-    del check, ref_scene
+    st_ref = None
+    if args.full:
+        rt.set_walk_tree("reference")
+        try:
+            ref_scene = rt.Scene.make(objs)
+        finally:
+            rt.set_walk_tree("sah")
+        check = torch.zeros_like(local)
+        st_ref = rtd.render_shard_device(ref_scene, cam, w, h, args.seed, local_rank, first, stride, n, check, stream=stream.cuda_stream,
+                                         counters=True, want_stats=True)
+        torch.cuda.synchronize(dev)
+        if not torch.equal(check, local) or any(st_ref[k] != st[k] for k in ("rays", "prim_tests", "reflections", "samples", "pixels_early")):
+            raise SystemExit("walking the reference's own tree and the tree of this run gave different results")
+        del check, ref_scene
     step()  # untimed, whatever --warmup says: first launch of the timed kernel variant, stream-ordered pool set-up, and (N>1)
             # the first gather, which sets up RCCL's peer-to-peer connections over xGMI
     for _ in range(args.warmup):
@@ -255,11 +288,13 @@ def main():
         k_ms += ev0.elapsed_time(ev1)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(frame, args.dump_outputs)  # before the legs below, which render into the same buffer
 
     # the same frame over the surface-area tree as built (no rt_scene_tune), timed the same way: both numbers from one run
     untuned = None
     first_frame = None
-    if world == 1 and tune is not None and tune["tuned"] and not args.no_untuned_leg:
+    if args.full and world == 1 and tune is not None and tune["tuned"] and not args.no_untuned_leg:
         plain = rt.Scene.make(objs)
         st_plain = rtd.render_shard_device(plain, cam, w, h, args.seed, local_rank, first, stride, n, local, stream=stream.cuda_stream,
                                            counters=True, want_stats=True)
@@ -295,7 +330,7 @@ def main():
                                "whichever is smaller is what ONE frame of this scene costs"}
 
     tot = torch.tensor([dt, float(st["rays"]), float(st["aabb_tests"]), float(st["prim_tests"]), float(st["reflections"]),
-                        float(st["samples"]), float(st["pixels_early"]), k_ms / max(1, args.steps), float(st_ref["aabb_tests"])],
+                        float(st["samples"]), float(st["pixels_early"]), k_ms / max(1, args.steps), float(st_ref["aabb_tests"]) if st_ref else 0.0],
                        dtype=torch.float64, device=dev)
     if world > 1:
         if args.backend == "gloo":
@@ -307,10 +342,10 @@ def main():
         dt = float(mx[0])
         job = {k: int(sm[i + 1]) for i, k in enumerate(("rays", "aabb_tests", "prim_tests", "reflections", "samples", "pixels_early"))}
         kernel_ms = float(mx[7])
-        job["aabb_tests_reference_tree"] = int(sm[8])
+        job["aabb_tests_reference_tree"] = int(sm[8]) if st_ref else None
     else:
         job = {k: int(st[k]) for k in ("rays", "aabb_tests", "prim_tests", "reflections", "samples", "pixels_early")}
-        job["aabb_tests_reference_tree"] = int(st_ref["aabb_tests"])
+        job["aabb_tests_reference_tree"] = int(st_ref["aabb_tests"]) if st_ref else None
         kernel_ms = float(tot[7])
 
     if rank == 0:
@@ -324,8 +359,13 @@ def main():
         rank_flops = algorithmic_flops(st)
         achieved_tf = rank_flops / (kernel_ms * 1e-3) / 1e12
         # the same with the box tests of the reference's own tree ("N_* must equal the oracle's counters"): the work
-        # the reference's algorithm does for this frame, of which the walked tree skips a part
-        ref_flops = algorithmic_flops({**st, "aabb_tests": st_ref["aabb_tests"]})
+        # the reference's algorithm does for this frame, of which the walked tree skips a part (--full: it takes a launch of its own)
+        ref_equiv = None
+        if st_ref:
+            ref_flops = algorithmic_flops({**st, "aabb_tests": st_ref["aabb_tests"]})
+            ref_equiv = {"flops_per_launch": ref_flops, "tflops": round(ref_flops / (kernel_ms * 1e-3) / 1e12, 3),
+                         "note": "the box tests BoundingBoxTree.make's own tree would have cost (the oracle's count), / the same "
+                                 "kernel time: work the reference's algorithm does per frame -- NOT executed here, not a roofline fraction"}
         ceiling_tf, ceiling_src = measured_issue_ceiling()
         info = scene.info()
         traffic, src = profiled_traffic() if (world == 1 and args.workload == "c3") else (None, None)  # the committed PMC passes are of config 3
@@ -363,9 +403,7 @@ def main():
                          "measured_issue_source": ceiling_src,
                          "traffic": traffic, "traffic_source": traffic_src, "physical_from_same_profile": physical,
                          "kernel": "rtd::render_kernel", "kernel_ms": round(kernel_ms, 3), "algorithmic_flops_per_launch": rank_flops,
-                         "reference_tree_equiv": {"flops_per_launch": ref_flops, "tflops": round(ref_flops / (kernel_ms * 1e-3) / 1e12, 3),
-                                                  "note": "the box tests BoundingBoxTree.make's own tree would have cost (the oracle's count), / the same "
-                                                          "kernel time: work the reference's algorithm does per frame -- NOT executed here, not a roofline fraction"},
+                         "reference_tree_equiv": ref_equiv,
                          "limited_by": limited,
                          "algorithmic_hbm_equiv": {"bytes_per_launch": rank_bytes, "gb_per_s": round(rank_bytes / (kernel_ms * 1e-3) / 1e9, 1),
                                                    "of_hbm_peak": round(rank_bytes / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 3),
@@ -375,7 +413,7 @@ def main():
                                  "kernel time.  Since round 3 the box tests ABOVE the leaves run as a conservative single-precision filter (same visits, "
                                  "same hits; DESIGN.md section 4) -- the flops are counted at SURVEY's double-precision figure, the peak is the FP64 vector one"},
         }
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(objs, cam, w, h, args.seed, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -7,7 +7,7 @@ ROUND=${1:-r2}; HASH=${2:-unknown}
 OUT=gpurun_out/$ROUND; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp; cd "${GRAFT_REPO_ROOT:-/root/repo}"
 hipcc --offload-arch=gfx950 -O3 -o /tmp/valu_rates scripts/ubench/valu_rates.hip && /tmp/valu_rates > $OUT/valu_rates.txt 2>&1
-python bench.py --steps 10 --warmup 2 > $OUT/bench_n1_$HASH.json 2> $OUT/bench_n1.err
+python bench.py --steps 10 --warmup 2 --full > $OUT/bench_n1_$HASH.json 2> $OUT/bench_n1.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python bench.py --steps 10 --warmup 2 --cpu-seconds 0 --no-untuned-leg > $OUT/bench_traced.json 2> $OUT/trace.err
 f=$(ls $OUT/trace/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && { echo "# git $HASH: rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --cpu-seconds 0 --no-untuned-leg"; cat "$f"; } > $OUT/bench_n1_${HASH}_kernel_stats.csv
 bash scripts/pmc.sh $OUT/pmc > $OUT/pmc.log 2>&1
