@@ -375,7 +375,10 @@ int rt_dev_bbox_filter(int32_t device, int32_t n, const double *rays, const doub
  * csrc/rt_device.h, pixel_candidates), and a camera ray then starts with those Leaves queued for their exact tests instead of
  * walking.  This hook returns that set for n pixels given as (row, col) pairs in the reference's coordinates (row = maxH - r - 1,
  * col = c - maxW, Scene.fs:219,226): leaves_out[i*4 .. i*4+3] = hittable indices (input order of rt_scene_create), -1 padded;
- * leaves_out[i*4] = -2 when the pixel's camera rays walk the tree as all other rays do (more than four Leaves in reach). */
+ * leaves_out[i*4] = -2 when the pixel's camera rays walk the tree as all other rays do (more than four Leaves in reach, more than
+ * two for a scene of 16384 objects or more, or a degenerate pyramid).  Any scene: one that does not fit the LDS is read through
+ * the timed kernel's global-memory view, with the queue words of its layout (16-bit entries below 16384 objects, full-width ones
+ * from there on). */
 int rt_dev_pixel_candidates(int32_t device, const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
                             int32_t n, const int32_t *row_col, int32_t *leaves_out);
 /* Sphere.firstIntersection (Sphere.fs:349-386). spheres: n*4 (centre xyz, radius). t_out = NaN when ValueNone. */

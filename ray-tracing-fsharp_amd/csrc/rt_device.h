@@ -480,7 +480,7 @@ RTD_INLINE int node_loop_lds(int off, uint32_t &pend, int end, int stop, V3 o, c
 // the final test is `not (tmax < tmin)`, true for a NaN tmax: such an axis (or ray) constrains nothing, as in the exact test,
 // whose NaN products leave tMin/tMax as they were.  The exact BoundingBox.hits of a Leaf box runs in the leaf pass
 // (leaf_test_object_exact), so no sphere is tested that the reference would not test.
-// tests: test_filter_is_conservative (CPU model, 1e8 cases incl. rays through edges and corners, origins on faces, axis-aligned and
+// tests: test_filter_model_is_conservative (CPU model, ~60,000 pairs per class incl. rays through edges and corners, origins on faces, axis-aligned and
 // denormal directions, huge and tiny boxes) and, on the GPU, rt_dev_bbox_filter over the same generators plus every render test
 // (the counting variant walks the exact double-precision records; every render test compares the two variants).
 struct WalkCtx32 {
@@ -1175,13 +1175,22 @@ RTD_INLINE bool camera_ray(const CameraParams &cam, int row, int col, Rng &rng, 
 // Leaf's exact BoundingBox.hits (or knows it implied) and sphere test as for any other queued Leaf.  The result is the reference's:
 // a sphere is tested iff its Leaf box is hit by the ray, exactly -- the candidates only have to CONTAIN every Leaf the ray's exact
 // test could accept.  They do: box and pyramid are convex, so if all of the box lies strictly outside one of the pyramid's four side
-// planes (or behind the eye), no ray of the pixel meets it; the test below rejects a box only then.  The planes are set up in double
+// planes, no ray of the pixel meets it.  (Each side plane holds the eye and two adjacent corners; it is oriented by gc, the sum of the
+// four corner directions, and dot(n_q, gc) = dot(n_q, g_{q+2}) + dot(n_q, g_{q+3}), two terms of one sign for a pointed pyramid.)  The
+// fifth plane, through the eye normal to gc, rejects boxes "behind the eye" -- sound only when every corner lies in front of it,
+// dot(g_q, gc) > 0 for all four: then every point of the patch does (a linear function is smallest at a corner).  Camera.makeBasic
+// guarantees it (orthogonal axes, the perpendicular's foot on a pixel corner, so no patch straddles the foot); a Camera record built
+// by hand need not (a patch that straddles the foot and is wide as seen from the eye, or skewed axes), and the plane is then left out for that pixel,
+// with a relative margin of 2^-30 on the corner test.  The test below rejects a box only in these cases.  The planes are set up in double
 // precision (rounding ~1e-12 relative: the cross products cancel to ~1e-4 of their operands for a 2401-pixel-wide image) and then
 // held, like the box's centre and half extents, in single precision; the per-box test runs in single precision with a margin of
 // 2^-18 of its terms' magnitudes (every operand carries 2^-24, the sums a few times that; a ray that the exact slab test accepts
 // misses the box by at most a few double-precision ulps of its coordinates).  The box tested is the node32 record's (rounded
-// outward: larger).  More than FOUR reachable Leaves, a degenerate pyramid, or a kernel variant without the queue: RTD_CAND_WALK,
-// and the pixel's camera rays walk the tree as all others.
+// outward: larger).  More than FOUR reachable Leaves (two with full-width queue entries), a degenerate pyramid, or a kernel variant
+// without the queue: RTD_CAND_WALK, and the pixel's camera rays walk the tree as all others.  "Degenerate" is an exact zero (or NaN)
+// of dot(n_q, gc): a pyramid flat only to within rounding (eye a few ulps off the viewport's plane, xd nearly parallel to yd) keeps
+// non-zero cross products whose planes hold every ray of the pixel to within far less than outside_plane's margin, whichever way
+// the rounding orients them, so it needs no relative threshold (tests/candidate_cases.py, family_flat).
 // The counting kernel variant never uses candidates, and every render test compares the two variants and the oracle.
 #define RTD_CAND_WALK 0xFFFFFFFFu
 struct F3 { float x, y, z; };
@@ -1213,7 +1222,13 @@ template <bool LDS, bool USE> RTD_INLINE uint32_t pixel_candidates(const SceneVi
             g[q] = vsub(walk(walk(xo, xd, lx), yd, ly), eye);
         }
         const V3 gc = mk((g[0].x + g[1].x) + (g[2].x + g[3].x), (g[0].y + g[1].y) + (g[2].y + g[3].y), (g[0].z + g[1].z) + (g[2].z + g[3].z));
-        gcf = to_f3(gc);
+        // the plane through the eye normal to gc bounds the pyramid only if every corner lies in front of it; otherwise it is left
+        // out (a zero normal rejects nothing: s = m = 0 in outside_plane) and the four side planes alone decide
+        bool front = true;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            front = front && dot(g[q], gc) > 0x1p-30 * ((fabs(g[q].x * gc.x) + fabs(g[q].y * gc.y)) + fabs(g[q].z * gc.z));
+        gcf = to_f3(front ? gc : mk(0.0, 0.0, 0.0));
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             V3 nq = cross3(g[q], g[(q + 1) & 3]);

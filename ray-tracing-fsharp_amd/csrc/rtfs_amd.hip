@@ -1307,6 +1307,17 @@ __global__ void __launch_bounds__(1024) k_pixel_candidates(const RenderParams p,
     out[i * 2] = first;
     out[i * 2 + 1] = second;
 }
+// The same for a scene that does not fit the LDS: the timed variant's global-memory view (make_view<false, true>), whose
+// pixel_candidates reads every record from global memory (the hybrid LDS copy of the tree's top serves only the node loop)
+__global__ void k_pixel_candidates_glb(const RenderParams p, const CameraParams cam, int n, const int32_t *rowcol, uint32_t *out) {
+    const SceneView<false> sc = make_view<false, true>(p, nullptr);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t second = 0u;
+    const uint32_t first = pixel_candidates<false, true>(sc, cam, rowcol[i * 2], rowcol[i * 2 + 1], second);
+    out[i * 2] = first;
+    out[i * 2 + 1] = second;
+}
 // The single-precision filter of the timed node loop next to the exact test, box by box: out[i] = exact | filter << 1.
 // Boxes arrive as (min, max) doubles; the host rounds them outward exactly as the scene image does (rth::f32_down / f32_up).
 __global__ void k_bbox_filter(int n, const double *rays, const double *boxes, const float *boxes32, float bmax, int32_t *out) {
@@ -1587,20 +1598,26 @@ int rt_dev_pixel_candidates(int32_t device, const rt_scene *scene, const rt_came
     int rc = hook_scene_params(guard, device, scene, p);
     if (rc != RT_OK) return rc;
     const size_t ldsBytes = scene->host.off.lds32_total;
-    if (ldsBytes > RT_LDS_BYTES || scene->host.nBounded + scene->host.nUnbounded >= 16384u) return fail(RT_ERR_UNSUPPORTED, "the scene does not fit the LDS");
+    const bool narrow = scene->host.nBounded + scene->host.nUnbounded < 16384u;
+    const bool lds = plan_launch(scene->host, resolve_settings(nullptr)).lds; // the timed render's view of this scene (rt_scene_info.lds_resident)
     CameraParams cam{};
     for (int a = 0; a < 3; ++a) { cam.eye[a] = camera->view_origin[a]; cam.xo[a] = camera->xaxis_origin[a]; cam.xd[a] = camera->xaxis_dir[a]; cam.yd[a] = camera->yaxis_dir[a]; }
     cam.vw = camera->viewport_width; cam.vh = camera->viewport_height; cam.max_w = max_w; cam.max_h = max_h;
     DevBuf<int32_t> drc; DevBuf<uint32_t> dout;
     HIP_TRY(drc.alloc((size_t) n * 2)); HIP_TRY(dout.alloc((size_t) n * 2));
     HIP_TRY(drc.up(row_col));
-    HIP_TRY(hipFuncSetAttribute((const void *) k_pixel_candidates, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
-    if (n) hipLaunchKernelGGL(k_pixel_candidates, dim3((unsigned) ((n + 1023) / 1024)), dim3(1024), ldsBytes, 0, p, cam, n, drc.p, dout.p);
+    if (lds) {
+        HIP_TRY(hipFuncSetAttribute((const void *) k_pixel_candidates, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
+        if (n) hipLaunchKernelGGL(k_pixel_candidates, dim3((unsigned) ((n + 1023) / 1024)), dim3(1024), ldsBytes, 0, p, cam, n, drc.p, dout.p);
+    } else if (n) hipLaunchKernelGGL(k_pixel_candidates_glb, dim3(blocks_for(n)), dim3(256), 0, 0, p, cam, n, drc.p, dout.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     std::vector<uint32_t> w((size_t) n * 2);
     HIP_TRY(dout.down(w.data()));
-    // decode: up to four hittable indices per pixel (-1 = none); leaves_out[i*4] = -2 when the pixel's camera rays walk the tree
+    // decode: up to four hittable indices per pixel (-1 = none); leaves_out[i*4] = -2 when the pixel's camera rays walk the tree.
+    // Below 16384 objects the words hold two 16-bit entries each (RTD_PEND_MARK | object); beyond, one full-width entry each
+    // (RTD_PEND_WIDE | object, at most two candidates).
+    const size_t nObj = scene->host.objToOrig.size();
     for (int i = 0; i < n; ++i) {
         int32_t *o = leaves_out + (size_t) i * 4;
         o[0] = o[1] = o[2] = o[3] = -1;
@@ -1608,9 +1625,12 @@ int rt_dev_pixel_candidates(int32_t device, const rt_scene *scene, const rt_came
         int k = 0;
         for (int h = 0; h < 2; ++h) {
             const uint32_t word = w[(size_t) i * 2 + (size_t) h];
-            for (int half = 0; half < 2; ++half) {
-                const uint32_t e = half == 0 ? (word & 0xFFFFu) : (word >> 16);
-                if (e != 0u && k < 4) o[k++] = scene->host.objToOrig[(size_t) (e & (RTD_PEND_MARK - 1u))];
+            for (int half = 0; half < (narrow ? 2 : 1); ++half) {
+                const uint32_t e = !narrow ? word : half == 0 ? (word & 0xFFFFu) : (word >> 16);
+                if (e == 0u || k >= 4) continue;
+                const uint32_t obj = narrow ? (e & (RTD_PEND_MARK - 1u)) : (e & ~RTD_PEND_WIDE);
+                if (obj >= nObj) return fail(RT_ERR_HIP, "pixel_candidates returned an object out of range");
+                o[k++] = scene->host.objToOrig[(size_t) obj];
             }
         }
     }
