@@ -25,8 +25,8 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 6 /* 5 (round 3): rt_scene_info.leaf_box_implied (was reserved), rt_dev_bbox_filter, rt_dev_pixel_candidates;
-                          * 6: rt_scene_get_filter_tree */
+#define RT_ABI_VERSION 7 /* 5 (round 3): rt_scene_info.leaf_box_implied (was reserved), rt_dev_bbox_filter, rt_dev_pixel_candidates;
+                          * 6: rt_scene_get_filter_tree; 7: rt_hit_objects(_device), rt_trace_rays(_device) */
 
 /* ---- status codes ------------------------------------------------------------------------ */
 enum {
@@ -296,6 +296,44 @@ int rt_render_frame(const rt_scene *scene, const rt_camera *camera,
                     const int32_t *devices, int32_t n_devices, uint32_t flags, int32_t gather,
                     const rt_render_options *options,
                     int32_t *accum_host, uint8_t *rgb_host, rt_stats *stats);
+
+/* ---- Ray lists: the caller's own rays (Scene.hitObject, Scene.traceRay) ------------------------------------------------
+ * The render kernel's persistent grid, work queue, scene placement and lane scheduler, fed with the caller's rays instead of
+ * a camera's (DESIGN.md "Ray lists").  Results are the reference's, bit for bit, for any launch settings.
+ *
+ * Argument checks come before any device call: RT_ERR_INVALID_ARGUMENT for a NULL scene, a NULL rays / hit_index / colour
+ * pointer when n > 0, n > INT32_MAX, bounce_depth < 0 (or > 0xFFFFFF), or bad options; nothing is written then.  n = 0 is a
+ * no-op returning RT_OK.  flags: RT_RENDER_COUNTERS runs the counting variant (the exact walk) and fills stats->rays,
+ * aabb_tests, prim_tests and reflections; kernel_ms and total_ms are always filled; samples and pixels stay 0.
+ *
+ * Device variants follow rt_render_device's contract: the launch is enqueued on `stream` (device pointers on `device`),
+ * with stats == NULL the call returns right after the launch, scratch is stream-ordered (any number of calls may be in
+ * flight), the caller's current device is left as it was.  Host variants copy in, run the device variant and copy out.
+ * options: as for rt_render_device_ex; chunk_pixels counts RAYS per work unit here (default 64); a block of 512 or 768
+ * threads runs as 1024. */
+
+/* Scene.hitObject (Scene.fs:62-91) for n caller rays.  rays: n*6 doubles (origin xyz, vector xyz); ray i is
+ * Ray.make'(origin, vector) (Ray.fs:26-34), computed on the device.  hit_index: n int32, index into
+ * rt_scene_create's array, -1 = ValueNone, -2 = Ray.make' gave ValueNone.  strike: n*3 doubles (Ray.walkAlong ray
+ * bestLength, Scene.fs:91), NaN where hit_index < 0; may be NULL. */
+int rt_hit_objects(const rt_scene *scene, int32_t device, size_t n, const double *rays,
+                   uint32_t flags, int32_t *hit_index, double *strike, rt_stats *stats);
+int rt_hit_objects_device(const rt_scene *scene, int32_t device, size_t n, const void *d_rays,
+                          uint32_t flags, void *d_hit_index, void *d_strike, void *stream,
+                          const rt_render_options *options, rt_stats *stats);
+
+/* Scene.traceRay (Scene.fs:93-114) from LightRay {Ray.make'(origin, vector); Colour.White}, at most
+ * bounce_depth+1 hits.  colour: n*3 uint8; HotPink at the bounce limit; Black (0,0,0) where Ray.make' fails.
+ * rng: n*4 uint32 xorshift128 states (FloatProducer, Float.fs:14-76), read, then written back advanced (unchanged where
+ * Ray.make' fails).  If rng is NULL, ray i draws from the stream keyed (seed, stream_base + i, sample), the same keying
+ * as a render's (pixel, sample), and no state is returned. */
+int rt_trace_rays(const rt_scene *scene, int32_t device, size_t n, const double *rays, uint32_t *rng,
+                  uint64_t seed, uint64_t stream_base, uint32_t sample, int32_t bounce_depth,
+                  uint32_t flags, uint8_t *colour, rt_stats *stats);
+int rt_trace_rays_device(const rt_scene *scene, int32_t device, size_t n, const void *d_rays, void *d_rng,
+                         uint64_t seed, uint64_t stream_base, uint32_t sample, int32_t bounce_depth,
+                         uint32_t flags, void *d_colour, void *stream,
+                         const rt_render_options *options, rt_stats *stats);
 
 /* ---- Output side (ImageOutput.fs:11-30,163-197) -------------------------------------------------- */
 uint8_t rt_gamma_correct(uint8_t b); /* PixelOutput.correct (ImageOutput.fs:11-18) */

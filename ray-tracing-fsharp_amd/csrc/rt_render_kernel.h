@@ -71,6 +71,15 @@ struct RenderParams {
     double *ray_log;               // [ray_log_cap][6]: origin, direction; null outside a probe
     unsigned int *ray_log_count;   // rays that wanted a slot (may exceed the capacity: the probe is then repeated more thinly)
     uint32_t ray_log_cap, ray_log_mask;
+    // the ray-list modes (MODE 4 / 5, run_rays; rt_trace_rays / rt_hit_objects): read only there
+    const double *rays;            // [ray_n][6]: origin, vector (Ray.make' is applied on the device)
+    uint32_t *ray_rng;             // [ray_n][4]: xorshift128 states, read and written back; null: stream (seed, ray_base + i, ray_sample)
+    uint8_t *ray_colour;           // [ray_n][3] (MODE 4)
+    int32_t *ray_hit;              // [ray_n] (MODE 5): index into rt_scene_create's array, -1 none, -2 Ray.make' failed
+    double *ray_strike;            // [ray_n][3] or null (MODE 5)
+    const int32_t *obj_to_orig;    // object-table index -> index into rt_scene_create's array (MODE 5)
+    uint64_t ray_n, ray_base;
+    uint32_t ray_sample;
 };
 
 // Per-wave LDS scratch (in 4-byte words), P = pixels per work unit:
@@ -607,6 +616,116 @@ RTD_INLINE void run_items(const RenderParams &p, const SceneView<LDS> &sc, unsig
     }
 }
 
+// The ray-list modes: MODE 4 is Scene.traceRay (Scene.fs:93-114), MODE 5 Scene.hitObject (Scene.fs:62-91), for the caller's rays
+// [0, p.ray_n).  A wave takes runs of p.chunk ray indices from the global queue -- as many runs at once as it has idle lanes for --
+// and a lane's new item is ray i: Ray.make' of the caller's (origin, vector), its rng state (the caller's, or the stream keyed
+// (seed, ray_base + i, ray_sample), as a render keys (pixel, sample)), colour White.  The walk starts at the root (no pixel
+// candidates: those are a camera's), and every stage is Sched's, so parked paths carry the ray index in slotOff as they carry a
+// pixel's accumulator word in a render.  Where a render adds an ended path's colour to its pixel, the ray's colour and final rng
+// state are stored; MODE 5 instead stores (hit, strike) once the walk and the unbounded tests are done, and shades nothing.
+template <bool LDS, bool COUNT, bool TEX, bool HIT>
+RTD_INLINE void run_rays(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, Counters &cnt, StageStats &ss) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t P = (uint32_t) p.chunk;
+    Sched<LDS, COUNT, TEX, false> L(p, sc, cnt, ss, pool, poolLds);
+    uint64_t next = 0, stop = 0; // wave-uniform: rays [next, stop) of the wave's current runs are not handed out yet
+    bool exhausted = false;
+    // a path's (or a query's) result, at its ray's index
+    auto emit = [&](bool made) {
+        const uint64_t i = (uint64_t) L.slotOff;
+        if (HIT) {
+            p.ray_hit[i] = !made ? -2 : (L.w.best < 0 ? -1 : p.obj_to_orig[L.w.best]);
+            if (p.ray_strike) {
+                const V3 sp = walk(L.o, L.d, L.w.bestLen);
+                const double nanv = __builtin_nan("");
+                const bool none = !made || L.w.best < 0;
+                p.ray_strike[i * 3 + 0] = none ? nanv : sp.x;
+                p.ray_strike[i * 3 + 1] = none ? nanv : sp.y;
+                p.ray_strike[i * 3 + 2] = none ? nanv : sp.z;
+            }
+        } else {
+            const uint32_t c = made ? L.result : RTD_BLACK;
+            p.ray_colour[i * 3 + 0] = (uint8_t) c;
+            p.ray_colour[i * 3 + 1] = (uint8_t) (c >> 8);
+            p.ray_colour[i * 3 + 2] = (uint8_t) (c >> 16);
+            if (p.ray_rng) {
+                uint32_t *r = p.ray_rng + i * 4;
+                r[0] = L.rng.x; r[1] = L.rng.y; r[2] = L.rng.z; r[3] = L.rng.w;
+            }
+        }
+    };
+    for (;;) {
+        L.ended = false;
+        const unsigned long long t0 = (COUNT || RTD_CLK) ? __builtin_amdgcn_s_memtime() : 0ull;
+        // ---- refill: idle lanes take parked paths or the next rays; a new run is taken when the current one is used up ----
+        const unsigned long long idle = __builtin_amdgcn_ballot_w64(L.st == L_IDLE);
+        const uint32_t nIdle = (uint32_t) __popcll(idle);
+        if (nIdle != 0u && (next < stop || !exhausted || (L.parked | L.parkedL | L.parkedT) != 0u) && ((int) nIdle >= p.refill_lanes || nIdle == 64u)) {
+            if (next >= stop && !exhausted) {
+                const uint32_t want = (nIdle + P - 1u) / P; // runs
+                uint32_t unit = 0;
+                if (lane == 0) unit = atomicAdd(p.queue, want);
+                unit = __builtin_amdgcn_readfirstlane(unit);
+                const uint64_t first = (uint64_t) unit * P;
+                if (first >= p.ray_n) exhausted = true;
+                else { next = first; stop = first + (uint64_t) want * P; stop = stop < p.ray_n ? stop : p.ray_n; }
+            }
+            const uint32_t avail = (uint32_t) (stop - next < 64u ? stop - next : 64u);
+            const uint32_t rank = lane_rank(idle);
+            uint32_t nUnL, nUnA, nUnT;
+            L.unpark_plan(nIdle, avail != 0u, nUnL, nUnA, nUnT);
+            const uint32_t nUn = nUnL + nUnA + nUnT;
+            if (COUNT || RTD_CLK) { ss.refill++; ss.refillLanes += nIdle; }
+            const uint32_t rest = nIdle - nUn;
+            const uint32_t take = rest < avail ? rest : avail;
+            if (L.st == L_IDLE) {
+                if (!L.unpark_lane(rank, nUnL, nUnA, nUnT) && rank - nUn < take) {
+                    const uint64_t i = next + (rank - nUn);
+                    const double *r = p.rays + i * 6;
+                    L.o = mk(r[0], r[1], r[2]);
+                    const V3 v = mk(r[3], r[4], r[5]);
+                    if (p.ray_rng) { const uint32_t *g = p.ray_rng + i * 4; L.rng.x = g[0]; L.rng.y = g[1]; L.rng.z = g[2]; L.rng.w = g[3]; }
+                    else L.rng = stream_for(pixel_key(p.seed_key, p.ray_base + i), p.ray_sample);
+                    L.slotOff = (uint32_t) i;
+                    L.colour = RTD_WHITE;
+                    L.bounces = 0;
+                    if (unitise(v, L.d)) { // Ray.make' (Ray.fs:26-34)
+                        L.st = L_WALK;
+                        walk_begin(L.w, sc.first);
+                        if (COUNT) cnt.rays++;
+                    } else emit(false); // ValueNone: no walk; Black (traceRay) or -2 (hitObject)
+                }
+            }
+            L.parked -= nUnA;
+            L.parkedL -= nUnL;
+            L.parkedT -= nUnT;
+            next += take;
+        }
+        if (__builtin_amdgcn_ballot_w64(L.st != L_IDLE) == 0ull) {
+            if (next >= stop && exhausted && (L.parked | L.parkedL | L.parkedT) == 0u) break;
+            continue;
+        }
+        const unsigned long long t1 = (COUNT || RTD_CLK) ? __builtin_amdgcn_s_memtime() : 0ull;
+        if (!HIT) {
+            L.stage_tex();
+            L.stage_slow();
+            L.stage_lamb();
+        }
+        const unsigned long long t2 = (COUNT || RTD_CLK) ? __builtin_amdgcn_s_memtime() : 0ull;
+        L.stage_walk();
+        const unsigned long long t3 = (COUNT || RTD_CLK) ? __builtin_amdgcn_s_memtime() : 0ull;
+        if (HIT) { // the rest of Scene.hitObject (Scene.fs:77-91): the unbounded objects, then the answer
+            if (__builtin_amdgcn_ballot_w64(L.st == L_DONE) != 0ull && L.st == L_DONE) {
+                unbounded_tests<LDS, COUNT>(sc, L.o, L.d, L.w, cnt);
+                emit(true);
+                L.st = L_IDLE; L.w.off = L.end;
+            }
+        } else L.stage_shade();
+        if (COUNT || RTD_CLK) { const unsigned long long t4 = __builtin_amdgcn_s_memtime(); ss.tRefill += t1 - t0; ss.tSlow += t2 - t1; ss.tWalk += t3 - t2; ss.tShade += t4 - t3; }
+        if (!HIT && L.ended) emit(true);
+    }
+}
+
 // Pass B (MODE 2): phase 2 for the pixels of the cost-ordered list, STREAMED.  A wave reserves a run of list entries ("range"),
 // hands out its npx*n2 items, and while the last paths of that range are still in flight it already reserves the next range and
 // hands out its items: two accumulator slots alternate, a range is flushed (its sums added to what pass A left in `accum`) when
@@ -811,6 +930,8 @@ RTD_INLINE uint32_t stage_nodes32(const RenderParams &p, unsigned char *smem) {
 //         (longest job first); run_stream.
 // MODE 3: MODE 0 with the ray log of rt_scene_tune's probe compiled in (a dozen more scalar values live across the loop: kept out
 //         of the kernels that render frames).
+// MODE 4: the caller's rays through Scene.traceRay; MODE 5: the caller's rays through Scene.hitObject (run_rays).  No pixels, so no
+//         per-wave LDS scratch: the LDS holds the scene (or the top of its tree) and the Lambert pools only.
 // Per-pixel cost is heavy-tailed (a pixel on a glass sphere: ~20 rays per sample, 4 ms of one wave), so when a shard has only a few
 // units per wave the fused kernel ends with most waves waiting for a few long units started late; A + sort + B removes that tail.
 // Every mode computes the same integers: which wave traces which sample when has no effect (streams are per item).
@@ -832,7 +953,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     scv.lds_thr = p.lds_node_thr;
     const SceneView<LDS> &sc = scv;
     const uint32_t P = (uint32_t) p.chunk;
-    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * (MODE == 1 ? RTD_WAVE_WORDS_A(P) : RTD_WAVE_WORDS(P));
+    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * (MODE >= 4 ? 0u : MODE == 1 ? RTD_WAVE_WORDS_A(P) : RTD_WAVE_WORDS(P));
     RTD_AS3 uint32_t *acc = wv;
     RTD_AS3 uint32_t *pix = wv + 6u * P;
     RTD_AS3 uint32_t *live = pix + 4u * P;
@@ -840,7 +961,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     unsigned char *pool = p.park_pool + ((size_t) blockIdx.x * (BLOCK / 64) + (size_t) wave) * (size_t) RTD_PARK_ENTRY_BYTES *
                                         (size_t) (p.park + (p.park_l_lds ? 0 : p.park_l) + (TEX ? p.park : 0));
     // the Lambert pools in LDS (if any) follow the waves' scratch
-    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * (MODE == 1 ? RTD_WAVE_WORDS_A(P) : RTD_WAVE_WORDS(P)) * 4u +
+    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * (MODE >= 4 ? 0u : MODE == 1 ? RTD_WAVE_WORDS_A(P) : RTD_WAVE_WORDS(P)) * 4u +
                                      (size_t) wave * (size_t) RTD_PARK_L_LDS_BYTES * (size_t) p.park_l;
 
     const uint64_t nLocal = (uint64_t) p.n_rows * (uint64_t) p.cols;
@@ -858,7 +979,8 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     uint32_t earlyCount = 0;
     uint64_t sampleCount = 0; // Scene.traceOnce calls = sum of PixelStats.Count
 
-    if (MODE == 2) run_stream<LDS, COUNT, TEX>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
+    if constexpr (MODE >= 4) run_rays<LDS, COUNT, TEX, MODE == 5>(p, sc, pool, poolLds, cnt, ss);
+    else if (MODE == 2) run_stream<LDS, COUNT, TEX>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
     else
     for (;;) {
         uint32_t unit = 0;

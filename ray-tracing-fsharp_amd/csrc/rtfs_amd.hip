@@ -65,6 +65,7 @@ struct DeviceScene {
     unsigned char *image = nullptr;
     TexRec *tex = nullptr;
     uint8_t *texels = nullptr;
+    int32_t *obj_to_orig = nullptr; // HostScene::objToOrig (the ray-list hit queries answer in rt_scene_create's indices)
     int cu_count = 0;
 };
 // Per-launch scratch, stream-ordered (hipMallocAsync on the launch stream): counters[16] | queues | camera.  Nothing is
@@ -100,6 +101,10 @@ static int device_scene(rt_scene *s, int device, DeviceScene **out) {
     if (!h.texelBlob.empty()) {
         HIP_TRY(hipMalloc((void **) &d.texels, h.texelBlob.size()));
         HIP_TRY(hipMemcpy(d.texels, h.texelBlob.data(), h.texelBlob.size(), hipMemcpyHostToDevice));
+    }
+    if (!h.objToOrig.empty()) {
+        HIP_TRY(hipMalloc((void **) &d.obj_to_orig, h.objToOrig.size() * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(d.obj_to_orig, h.objToOrig.data(), h.objToOrig.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -352,6 +357,7 @@ void rt_scene_destroy(rt_scene *s) {
         (void) hipFree(kv.second.image);
         (void) hipFree(kv.second.tex);
         (void) hipFree(kv.second.texels);
+        (void) hipFree(kv.second.obj_to_orig);
     }
     if (prev >= 0 && !s->dev.empty()) (void) hipSetDevice(prev);
     delete s;
@@ -888,6 +894,238 @@ int rt_render(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
     return rc;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// ray lists: the caller's rays through Scene.traceRay / Scene.hitObject (render_kernel MODE 4 / MODE 5, run_rays)
+// ------------------------------------------------------------------------------------------------------------
+// 24 instantiations: blocks of 256 or 1024 threads only (a launch asking for 512 or 768 runs at 1024: the block size never changes
+// a result); the hit queries shade nothing, so they have no textured variant.
+template <int MODE, bool TEX> static render_fn pick_rays_mode(bool lds, bool count, int block) {
+    if (block == 256) {
+        if (lds) return count ? render_kernel<true, true, 256, MODE, TEX> : render_kernel<true, false, 256, MODE, TEX>;
+        return count ? render_kernel<false, true, 256, MODE, TEX> : render_kernel<false, false, 256, MODE, TEX>;
+    }
+    if (lds) return count ? render_kernel<true, true, 1024, MODE, TEX> : render_kernel<true, false, 1024, MODE, TEX>;
+    return count ? render_kernel<false, true, 1024, MODE, TEX> : render_kernel<false, false, 1024, MODE, TEX>;
+}
+static render_fn pick_rays(bool hit, bool tex, bool lds, bool count, int block) {
+    if (hit) return pick_rays_mode<5, false>(lds, count, block);
+    return tex ? pick_rays_mode<4, true>(lds, count, block) : pick_rays_mode<4, false>(lds, count, block);
+}
+
+struct RayJob {
+    bool hit;            // MODE 5 (hit queries) or MODE 4 (paths)
+    size_t n;
+    const void *rays;    // [n][6] doubles
+    void *rng;           // [n][4] uint32 or null (MODE 4)
+    void *colour;        // [n][3] uint8 (MODE 4)
+    void *hit_index;     // [n] int32 (MODE 5)
+    void *strike;        // [n][3] doubles or null (MODE 5)
+    uint64_t seed = 0, stream_base = 0;
+    uint32_t sample = 0;
+    int32_t depth = 0;
+};
+
+// Every argument check of the four ray-list entry points, made before anything touches a device.
+static int check_rays(const rt_scene *scene, size_t n, const void *rays, const void *out, int32_t bounce_depth, const rt_render_options *options) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (n > 0 && !rays) return fail(RT_ERR_INVALID_ARGUMENT, "rays is NULL");
+    if (n > 0 && !out) return fail(RT_ERR_INVALID_ARGUMENT, "output is NULL");
+    if (n > (size_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "more than INT32_MAX rays");
+    if (bounce_depth < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth must be >= 0");
+    if (bounce_depth > 0xFFFFFF) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth too large");
+    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
+    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
+    return RT_OK;
+}
+
+// Enqueues one ray-list launch on `stream` (n > 0, arguments checked); as launch_render: never waits, scratch from the stream's
+// pool, events and scratch kept in `pd` when statistics are wanted.  Placement (LDS, hybrid or global) is the render's decision.
+static int launch_rays(const rt_scene *scene, int32_t device, const RayJob &job, uint32_t flags, void *stream, const rt_render_options *options,
+                       bool want_stats, Pending &pd) {
+    DeviceGuard guard;
+    int rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceScene *ds = nullptr;
+    rc = device_scene(const_cast<rt_scene *>(scene), device, &ds);
+    if (rc != RT_OK) return rc;
+    const rth::HostScene &h = scene->host;
+    hipStream_t st = (hipStream_t) stream;
+    const Settings set = resolve_settings(options);
+    const bool count = (flags & RT_RENDER_COUNTERS) != 0;
+    const LaunchPlan plan = plan_launch(h, set, count);
+    const bool lds = plan.lds;
+    const int block = plan.block == 256 ? 256 : 1024;
+
+    RenderParams p{};
+    p.off = h.off;
+    p.scene_image = ds->image;
+    p.tex = ds->tex;
+    p.texels = ds->texels;
+    p.seed_key = mix64(job.seed + 0x9E3779B97F4A7C15ull); // seed_key(), host side: the render's keying of (pixel, sample)
+    p.depth = job.depth;
+    p.chunk = set.chunk ? set.chunk : RTD_MAX_CHUNK; // rays per run of the queue (a wave takes as many runs at once as it has idle lanes)
+    p.park = job.hit ? 0 : plan.park;
+    p.park_l = p.park > 0 ? RTD_PARK_L_DEFAULT : 0;
+    p.yield_lanes = set.yield ? set.yield : RTD_YIELD_DEFAULT;
+    p.leaf_wait = p.yield_lanes + RTD_LEAF_WAIT_EXTRA > 64 ? 64 : p.yield_lanes + RTD_LEAF_WAIT_EXTRA;
+    p.refill_lanes = set.refill ? set.refill : RTD_REFILL_DEFAULT;
+    p.rays = (const double *) job.rays;
+    p.ray_rng = (uint32_t *) job.rng;
+    p.ray_colour = (uint8_t *) job.colour;
+    p.ray_hit = (int32_t *) job.hit_index;
+    p.ray_strike = (double *) job.strike;
+    p.obj_to_orig = ds->obj_to_orig;
+    p.ray_n = job.n;
+    p.ray_base = job.stream_base;
+    p.ray_sample = job.sample;
+
+    const bool tex = !job.hit && !h.texRecs.empty();
+    render_fn fn = pick_rays(job.hit, tex, lds, count, block);
+    size_t ldsBytes = lds ? (size_t) (count ? h.off.lds_total : h.off.lds32_total) : 0u; // no per-wave scratch in these modes
+    p.lds_node_bytes = (int32_t) hybrid_node_bytes(h, ldsBytes, lds, count, block, p.park_l > 0);
+    p.lds_node_thr = RTD_HYBRID_LANES;
+    if (p.park_l > 0) {
+        const int cl = lambert_pool_lds(ldsBytes, block);
+        if (cl) { p.park_l = cl; p.park_l_lds = 1; }
+    }
+    HIP_TRY(hipFuncSetAttribute((const void *) fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
+    int perCu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *) fn, block, ldsBytes));
+    if (perCu < 1) return fail(RT_ERR_HIP, "ray-list kernel does not fit on a CU (occupancy 0)");
+    if (set.blocks_per_cu > 0 && set.blocks_per_cu < perCu) perCu = set.blocks_per_cu;
+    const uint64_t wavesPerBlock = (uint64_t) block / 64u;
+    const uint64_t wavesWanted = ((uint64_t) job.n + 63u) / 64u; // a wave's worth of rays each, at least
+    uint64_t grid = (uint64_t) ds->cu_count * (uint64_t) perCu;
+    const uint64_t needBlocks = (wavesWanted + wavesPerBlock - 1) / wavesPerBlock;
+    if (grid > needBlocks) grid = needBlocks;
+
+    const size_t poolBytes = (size_t) grid * (size_t) wavesPerBlock * (size_t) RTD_PARK_ENTRY_BYTES *
+                             (size_t) (p.park + (p.park > 0 ? RTD_PARK_L_DEFAULT : 0) + (tex ? p.park : 0)); // as launch_render's
+    unsigned char *scr = nullptr;
+    HIP_TRY(hipMallocAsync((void **) &scr, RT_SCRATCH_BYTES + poolBytes, st));
+    Pending &cl = pd;
+    cl.scr = scr; cl.st = st; cl.device = device; cl.t0 = t0;
+    cl.pixels = 0;
+    cl.waves = grid * wavesPerBlock;
+    if (want_stats) {
+        HIP_TRY(hipEventCreate(&cl.a));
+        HIP_TRY(hipEventCreate(&cl.b));
+    }
+    p.counters = (unsigned long long *) scr;
+    p.queue = (unsigned int *) (scr + 128);
+    p.cam_ptr = (const CameraParams *) (scr + 256); // (no camera: never read in these modes)
+    p.park_pool = scr + RT_SCRATCH_BYTES;
+    hipLaunchKernelGGL(launch_init_kernel, dim3(1), dim3(64), 0, st, scr, CameraParams{});
+    HIP_TRY(hipGetLastError());
+    if (want_stats) HIP_TRY(hipEventRecord(cl.a, st));
+    hipLaunchKernelGGL(fn, dim3((unsigned) grid), dim3((unsigned) block), ldsBytes, st, p);
+    HIP_TRY(hipGetLastError());
+    if (want_stats) HIP_TRY(hipEventRecord(cl.b, st));
+    cl.launched = true;
+    if (!want_stats) cl.release();
+    return RT_OK;
+}
+
+static int run_rays_device(const rt_scene *scene, int32_t device, const RayJob &job, uint32_t flags, void *stream,
+                           const rt_render_options *options, rt_stats *stats) {
+    if (job.n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard; // (launch_rays enters it again: a no-op then) so that collect_stats runs on the device too
+    int rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    Pending pd;
+    rc = launch_rays(scene, device, job, flags, stream, options, stats != nullptr, pd);
+    if (rc != RT_OK || !stats) return rc;
+    return collect_stats(pd, stats);
+}
+
+// The host variants: one device allocation for inputs and outputs, the device variant on the null stream, the outputs copied back.
+static int run_rays_host(const rt_scene *scene, int32_t device, RayJob job, uint32_t flags, rt_stats *stats) {
+    if (job.n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    int rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n = job.n;
+    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
+    const size_t bRays = up16(n * 48u), bRng = job.rng ? up16(n * 16u) : 0u, bCol = job.hit ? 0u : up16(n * 3u),
+                 bHit = job.hit ? up16(n * 4u) : 0u, bStrike = (job.hit && job.strike) ? up16(n * 24u) : 0u;
+    unsigned char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **) &buf, bRays + bRng + bCol + bHit + bStrike));
+    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
+    const RayJob host = job;
+    job.rays = buf;
+    job.rng = bRng ? buf + bRays : nullptr;
+    job.colour = bCol ? buf + bRays + bRng : nullptr;
+    job.hit_index = bHit ? buf + bRays + bRng + bCol : nullptr;
+    job.strike = bStrike ? buf + bRays + bRng + bCol + bHit : nullptr;
+    HIP_TRY(hipMemcpy(buf, host.rays, n * 48u, hipMemcpyHostToDevice));
+    if (job.rng) HIP_TRY(hipMemcpy(job.rng, host.rng, n * 16u, hipMemcpyHostToDevice));
+    rt_stats local;
+    rc = run_rays_device(scene, device, job, flags, nullptr, nullptr, &local);
+    if (rc != RT_OK) return rc;
+    if (job.colour) HIP_TRY(hipMemcpy(host.colour, job.colour, n * 3u, hipMemcpyDeviceToHost));
+    if (job.rng) HIP_TRY(hipMemcpy(host.rng, job.rng, n * 16u, hipMemcpyDeviceToHost));
+    if (job.hit_index) HIP_TRY(hipMemcpy(host.hit_index, job.hit_index, n * 4u, hipMemcpyDeviceToHost));
+    if (job.strike) HIP_TRY(hipMemcpy(host.strike, job.strike, n * 24u, hipMemcpyDeviceToHost));
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+static RayJob hit_job(size_t n, const void *rays, void *hit_index, void *strike) {
+    RayJob j{};
+    j.hit = true; j.n = n; j.rays = rays; j.hit_index = hit_index; j.strike = strike;
+    return j;
+}
+static RayJob trace_job(size_t n, const void *rays, void *rng, uint64_t seed, uint64_t stream_base, uint32_t sample, int32_t depth, void *colour) {
+    RayJob j{};
+    j.hit = false; j.n = n; j.rays = rays; j.rng = rng; j.colour = colour;
+    j.seed = seed; j.stream_base = stream_base; j.sample = sample; j.depth = depth;
+    return j;
+}
+
+extern "C" {
+
+int rt_hit_objects(const rt_scene *scene, int32_t device, size_t n, const double *rays, uint32_t flags, int32_t *hit_index, double *strike,
+                   rt_stats *stats) {
+    const int rc = check_rays(scene, n, rays, hit_index, 0, nullptr);
+    if (rc != RT_OK) return rc;
+    return run_rays_host(scene, device, hit_job(n, rays, hit_index, strike), flags, stats);
+}
+
+int rt_hit_objects_device(const rt_scene *scene, int32_t device, size_t n, const void *d_rays, uint32_t flags, void *d_hit_index, void *d_strike,
+                          void *stream, const rt_render_options *options, rt_stats *stats) {
+    const int rc = check_rays(scene, n, d_rays, d_hit_index, 0, options);
+    if (rc != RT_OK) return rc;
+    return run_rays_device(scene, device, hit_job(n, d_rays, d_hit_index, d_strike), flags, stream, options, stats);
+}
+
+int rt_trace_rays(const rt_scene *scene, int32_t device, size_t n, const double *rays, uint32_t *rng, uint64_t seed, uint64_t stream_base,
+                  uint32_t sample, int32_t bounce_depth, uint32_t flags, uint8_t *colour, rt_stats *stats) {
+    const int rc = check_rays(scene, n, rays, colour, bounce_depth, nullptr);
+    if (rc != RT_OK) return rc;
+    return run_rays_host(scene, device, trace_job(n, rays, rng, seed, stream_base, sample, bounce_depth, colour), flags, stats);
+}
+
+int rt_trace_rays_device(const rt_scene *scene, int32_t device, size_t n, const void *d_rays, void *d_rng, uint64_t seed, uint64_t stream_base,
+                         uint32_t sample, int32_t bounce_depth, uint32_t flags, void *d_colour, void *stream, const rt_render_options *options,
+                         rt_stats *stats) {
+    const int rc = check_rays(scene, n, d_rays, d_colour, bounce_depth, options);
+    if (rc != RT_OK) return rc;
+    return run_rays_device(scene, device, trace_job(n, d_rays, d_rng, seed, stream_base, sample, bounce_depth, d_colour), flags, stream, options, stats);
 }
 
 } // extern "C"

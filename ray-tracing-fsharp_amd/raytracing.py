@@ -490,6 +490,80 @@ class Scene:
                                   _i32(accum), _u8(rgb), st))
         return RenderResult(accum, rgb, [x.as_dict() for x in st])
 
+    def hitObject(self, rays, *, device: Optional[int] = None, counters: bool = False, stats: bool = True,
+                  options: Optional[A.rt_render_options] = None):
+        """Scene.hitObject (Scene.fs:62-91) for the caller's rays [n, 6] float64 (origin, vector; Ray.make' is applied on the
+        device) -> (hit_index int32 [n]: index into Scene.make's objects, -1 none, -2 where Ray.make' fails; strike float64 [n, 3],
+        NaN where hit_index < 0).  A numpy array goes through rt_hit_objects; a torch tensor on a GPU through rt_hit_objects_device
+        on torch.cuda.current_stream(), and the results are tensors on that device (stats=False: no wait for the device, and
+        last_stats is None).  device: the GPU (default 0, or the tensor's)."""
+        flags = A.RT_RENDER_COUNTERS if counters else 0
+        if _is_torch(rays):
+            torch = _torch()
+            r = _tensor_arg(rays, "rays", (torch.float64,), 6)
+            dev = _tensor_device(r, device)
+            n = r.shape[0]
+            hit = torch.empty(n, dtype=torch.int32, device=r.device)
+            strike = torch.empty((n, 3), dtype=torch.float64, device=r.device)
+            st = A.rt_stats() if stats else None
+            check(lib.rt_hit_objects_device(self._h, dev, n, r.data_ptr(), flags, hit.data_ptr(), strike.data_ptr(),
+                                            torch.cuda.current_stream(r.device).cuda_stream, _ref(options), _ref(st)))
+            self.last_stats = st.as_dict() if st is not None else None
+            return hit, strike
+        if options is not None:
+            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        r = _array_arg(rays, "rays", np.float64, 6)
+        n = r.shape[0]
+        hit = np.zeros(n, np.int32)
+        strike = np.zeros((n, 3), np.float64)
+        st = A.rt_stats()
+        check(lib.rt_hit_objects(self._h, 0 if device is None else device, n, _f64(r), flags, _i32(hit), _f64(strike), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return hit, strike
+
+    def traceRays(self, rays, bounceDepth: int, *, rng=None, seed: int = 0, stream_base: int = 0, sample: int = 0,
+                  device: Optional[int] = None, counters: bool = False, stats: bool = True, options: Optional[A.rt_render_options] = None):
+        """Scene.traceRay (Scene.fs:93-114) from LightRay {Ray.make'(origin, vector); Colour.White} for the caller's rays [n, 6],
+        at most bounceDepth+1 hits -> (colour uint8 [n, 3], rng_out).  rng: [n, 4] uint32 xorshift128 states (FloatProducer), which
+        are not modified: rng_out holds them advanced.  rng=None: ray i draws from the stream keyed (seed, stream_base + i, sample),
+        as a render's (pixel, sample), and rng_out is None.  numpy arrays / torch tensors as for hitObject (a tensor rng may be
+        uint32 or int32: the bits are the state)."""
+        flags = A.RT_RENDER_COUNTERS if counters else 0
+        if _is_torch(rays):
+            torch = _torch()
+            r = _tensor_arg(rays, "rays", (torch.float64,), 6)
+            dev = _tensor_device(r, device)
+            n = r.shape[0]
+            g = None
+            if rng is not None:
+                if not _is_torch(rng):
+                    raise TypeError("rng must be a torch tensor when rays is one")
+                g = _tensor_arg(rng, "rng", (torch.uint32, torch.int32), 4).clone()
+                if g.shape[0] != n or g.device != r.device:
+                    raise ValueError("rng must be [n, 4] on the rays' device")
+            colour = torch.empty((n, 3), dtype=torch.uint8, device=r.device)
+            st = A.rt_stats() if stats else None
+            check(lib.rt_trace_rays_device(self._h, dev, n, r.data_ptr(), g.data_ptr() if g is not None else None, seed, stream_base, sample,
+                                           bounceDepth, flags, colour.data_ptr(), torch.cuda.current_stream(r.device).cuda_stream,
+                                           _ref(options), _ref(st)))
+            self.last_stats = st.as_dict() if st is not None else None
+            return colour, g
+        if options is not None:
+            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        r = _array_arg(rays, "rays", np.float64, 6)
+        n = r.shape[0]
+        g = None
+        if rng is not None:
+            g = _array_arg(rng, "rng", np.uint32, 4).copy()
+            if g.shape[0] != n:
+                raise ValueError("rng must be [n, 4] for n rays")
+        colour = np.zeros((n, 3), np.uint8)
+        st = A.rt_stats()
+        check(lib.rt_trace_rays(self._h, 0 if device is None else device, n, _f64(r), _u32(g) if g is not None else None, seed, stream_base,
+                                sample, bounceDepth, flags, _u8(colour), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return colour, g
+
     @staticmethod
     def render(progressIncrement: Callable[[float], None], log: Callable[[str], None], maxWidthCoord: int, maxHeightCoord: int,
                camera: Camera, s: "Scene", *, seed: int = 0, device: int = 0, row_block: Optional[int] = None) -> Tuple[float, Image]:
@@ -594,3 +668,43 @@ def _u32(a: np.ndarray):
 
 def _u64(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+# ---- argument checks of the ray-list calls (Scene.hitObject / Scene.traceRays) ----------------------------------------
+def _is_torch(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _array_arg(a, name: str, dtype, width: int) -> np.ndarray:
+    if not isinstance(a, np.ndarray):
+        raise TypeError(f"{name} must be a numpy array or a torch tensor on a GPU, not {type(a).__name__}")
+    if a.dtype != dtype:
+        raise TypeError(f"{name} must have dtype {np.dtype(dtype).name}, not {a.dtype}")
+    if a.ndim != 2 or a.shape[1] != width:
+        raise ValueError(f"{name} must have shape [n, {width}], not {list(a.shape)}")
+    return np.ascontiguousarray(a)
+
+
+def _tensor_arg(t, name: str, dtypes, width: int):
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must have dtype {' or '.join(str(d) for d in dtypes)}, not {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != width:
+        raise ValueError(f"{name} must have shape [n, {width}], not {list(t.shape)}")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be on a GPU (a numpy array takes the host entry point)")
+    return t.contiguous()
+
+
+def _tensor_device(t, device: Optional[int]) -> int:
+    if device is not None and device != t.device.index:
+        raise ValueError(f"device={device} but the tensors are on {t.device}")
+    return t.device.index
+
+
+def _ref(x):
+    return C.byref(x) if x is not None else None
