@@ -832,7 +832,12 @@ RTD_INLINE void leaf_test_object_exact(const SceneView<LDS> &sc, V3 o, V3 d, dou
     bool cand = a < bestF || (a == bestF && prim < w.best);
     if (cand && !(implied && cmp == CMP_GT && dd <= RTD_IMPLIED_DD)) { // the sliver: the leaf's BoundingBox.hits, exactly
         const double r = sc.geo[prim * 3 + 2].y;
-        const double ix = 1.0 / d.x, iy = 1.0 / d.y, iz = 1.0 / d.z;
+        // The divisions are invariant over the walk stage's loop, and LICM would hoist them (speculated) to the stage's entry:
+        // 33 double-precision instructions per lane and stage entry, and the three inverses held in 6 VGPRs across the loop, for
+        // a branch that the implied case almost never leaves.  The empty asm makes the direction a value of this branch; same bits.
+        V3 dv = d;
+        asm volatile("" : "+v"(dv.x), "+v"(dv.y), "+v"(dv.z));
+        const double ix = 1.0 / dv.x, iy = 1.0 / dv.y, iz = 1.0 / dv.z;
         const double rx = ix < 0.0 ? r : -r, ry = iy < 0.0 ? r : -r, rz = iz < 0.0 ? r : -r;
         cand = bbox_hits_nf(ix, iy, iz, o, g0.x + rx, g0.x - rx, g0.y + ry, g0.y - ry, g1.x + rz, g1.x - rz);
     }
