@@ -35,7 +35,10 @@ enum {
     RT_ERR_NO_DEVICE = 2,        /* no HIP device visible: the product path never falls back to a CPU */
     RT_ERR_HIP = 3,              /* a HIP runtime call failed; rt_last_error() carries hipGetErrorString */
     RT_ERR_UNSUPPORTED = 4,      /* e.g. Texture.Arbitrary closures (Texture.fs:8,24) cannot cross a C ABI */
-    RT_ERR_IO = 5
+    RT_ERR_IO = 5,
+    RT_ERR_HOST = 6              /* host resources exhausted: memory (std::bad_alloc) or threads; the call changed nothing.
+                                  * A new return value only -- no struct, field or symbol changed, so RT_ABI_VERSION stays 7: a
+                                  * binding that treats any nonzero status as a failure needs no change. */
 };
 
 /* ---- Hittable (Hittable.fs:3-6) ------------------------------------------------------------ */
@@ -287,6 +290,8 @@ int rt_render_device_ex(const rt_scene *scene, const rt_camera *camera,
  *         RT_GATHER_PEER   hipMemcpyPeerAsync to devices[0] instead of RCCL (also works when `devices` repeats an id);
  *         RT_GATHER_HOST   every device copies its own shard to the host over its own PCIe link (no device-side gather);
  *         RT_GATHER_AUTO   RCCL when n_devices > 1, the ids are distinct and librccl.so loads; else PEER.
+ * Calls from several threads over the same device list share its RCCL communicators; each call's group of sends and receives is
+ * issued under a mutex of that list, so the groups of two calls never interleave.
  * stats (may be NULL): n_devices entries, one per device's shard; kernel_ms is that device's render time, total_ms the
  * wall time of the whole call (the same in every entry).
  */

@@ -4,7 +4,7 @@ import ctypes as C
 
 RT_ABI_VERSION = 7
 
-RT_OK, RT_ERR_INVALID_ARGUMENT, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_UNSUPPORTED, RT_ERR_IO = range(6)
+RT_OK, RT_ERR_INVALID_ARGUMENT, RT_ERR_NO_DEVICE, RT_ERR_HIP, RT_ERR_UNSUPPORTED, RT_ERR_IO, RT_ERR_HOST = range(7)
 
 # rt_hittable_kind
 RT_HITTABLE_SPHERE, RT_HITTABLE_UNBOUNDED_SPHERE, RT_HITTABLE_INFINITE_PLANE = range(3)

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <future>
 #include <string>
+#include <system_error>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -19,6 +20,17 @@
 namespace rth {
 
 struct Box { double mn[3], mx[3]; };
+
+// std::async on a thread of its own when one can be started; otherwise (std::system_error: EAGAIN under a pids cgroup or an
+// address-space limit, many scenes built at once) `f` runs on the calling thread when get() is called.  The builders below
+// hand it independent subtrees, so the tree is the same node for node either way.
+template <class F> static auto spawn(F f) -> std::future<decltype(f())> {
+    try {
+        return std::async(std::launch::async, f);
+    } catch (const std::system_error &) {
+        return std::async(std::launch::deferred, f);
+    }
+}
 
 // BoundingBox.mergeTwo (BoundingBox.fs:96-108)
 static inline Box merge_two(const Box &i, const Box &j) {
@@ -74,7 +86,7 @@ class TreeBuilder {
             const bool threaded = depth <= kParallelDepth && ids.size() >= kParallelMin;
             Split sp[3];
             if (threaded) {
-                auto f1 = std::async(std::launch::async, [&]() { return split(1); }), f2 = std::async(std::launch::async, [&]() { return split(2); });
+                auto f1 = spawn([&]() { return split(1); }), f2 = spawn([&]() { return split(2); });
                 sp[0] = split(0);
                 sp[1] = f1.get();
                 sp[2] = f2.get();
@@ -83,7 +95,7 @@ class TreeBuilder {
             for (int axis = 1; axis < 3; ++axis) if (sp[axis].cost < sp[best].cost) best = axis; // Array.minBy: the first minimum
             if (threaded) {
                 FlatTree left, right;
-                auto fut = std::async(std::launch::async, [&]() { TreeBuilder b(ob, left); b.go(sp[best].l, depth + 1); });
+                auto fut = spawn([&]() { TreeBuilder b(ob, left); b.go(sp[best].l, depth + 1); });
                 { TreeBuilder b(ob, right); b.go(sp[best].r, depth + 1); }
                 fut.get();
                 append(left);
@@ -298,7 +310,7 @@ class SahBuilder {
                 // the two subtrees are independent: the left one on another thread into a tree of its own, appended in pre-order
                 // afterwards -- the same tree, node for node, as the sequential build (rt_scene_tune's host time: 11.5 -> ~3 ms)
                 FlatTree left, right;
-                auto fut = std::async(std::launch::async, [&]() { SahBuilder b(ob, left, rays); b.suffix.resize(ob.size() + 1); b.go(ids, k, depth + 1, hidx, myHits, myArea); });
+                auto fut = spawn([&]() { SahBuilder b(ob, left, rays); b.suffix.resize(ob.size() + 1); b.go(ids, k, depth + 1, hidx, myHits, myArea); });
                 { SahBuilder b(ob, right, rays); b.suffix.resize(ob.size() + 1); b.go(ids + k, n - k, depth + 1, hidx, myHits, myArea); }
                 fut.get();
                 append(left);

@@ -17,7 +17,12 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <new>
+#include <set>
 #include <string>
+#include <system_error>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 using namespace rtd;
@@ -26,12 +31,32 @@ using namespace rtd;
 // error plumbing
 // ------------------------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) { g_err = msg; return code; }
+static int fail(int code, const std::string &msg) noexcept {
+    try { g_err = msg; } catch (...) { g_err.clear(); } // (no memory left for the message: the code still tells)
+    return code;
+}
 #define HIP_TRY(expr)                                                                                                   \
     do {                                                                                                                \
         hipError_t e_ = (expr);                                                                                         \
         if (e_ != hipSuccess) return fail(RT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));               \
     } while (0)
+
+// No exception crosses the C boundary: an entry point that fills host containers or starts threads runs its body through
+// this, and whatever escapes it -- std::bad_alloc, std::system_error from a thread that could not be started -- becomes
+// RT_ERR_HOST (`err`: the value the entry point returns for it).
+template <class R = int, class F> static R guarded(const char *entry, F &&body, R err = RT_ERR_HOST) noexcept {
+    const char *why = "host resources exhausted";
+    try {
+        return body();
+    } catch (const std::bad_alloc &) {
+        why = "host memory exhausted";
+    } catch (const std::system_error &) {
+        why = "host resources exhausted (a thread could not be started)";
+    } catch (...) {
+    }
+    try { g_err = std::string(entry) + ": " + why; } catch (...) { g_err.clear(); }
+    return err;
+}
 
 static int visible_devices() {
     int n = 0;
@@ -109,8 +134,12 @@ static int device_scene(rt_scene *s, int device, DeviceScene **out) {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     d.cu_count = prop.multiProcessorCount;
-    auto ins = s->dev.emplace(device, d);
-    *out = &ins.first->second;
+    try {
+        *out = &s->dev.emplace(device, d).first->second;
+    } catch (const std::bad_alloc &) {
+        (void) hipFree(d.image); (void) hipFree(d.tex); (void) hipFree(d.texels); (void) hipFree(d.obj_to_orig);
+        return fail(RT_ERR_HOST, "host memory exhausted");
+    }
     return RT_OK;
 }
 
@@ -203,6 +232,25 @@ static LaunchPlan plan_launch(const rth::HostScene &h, const Settings &s, bool c
 // launch
 // ------------------------------------------------------------------------------------------------------------
 typedef void (*render_fn)(const RenderParams);
+
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the FUNCTION, which every thread of the process shares: set per launch
+// to that launch's own size, another thread could lower it between the setting and the launch.  It is set once per (function,
+// device), to the most any launch may ask for -- the LDS budget less the function's static LDS; a launch's occupancy and grid
+// still come from its own size (hipOccupancyMaxActiveBlocksPerMultiprocessor takes it explicitly).
+static int allow_full_lds(const void *fn) {
+    static std::mutex mu;
+    static std::set<std::pair<const void *, int>> done;
+    int device = -1;
+    HIP_TRY(hipGetDevice(&device));
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count({fn, device})) return RT_OK;
+    hipFuncAttributes a{};
+    HIP_TRY(hipFuncGetAttributes(&a, fn));
+    if (a.sharedSizeBytes >= RT_LDS_BYTES) return fail(RT_ERR_HIP, "kernel's static LDS fills the budget");
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (RT_LDS_BYTES - a.sharedSizeBytes)));
+    try { done.insert({fn, device}); } catch (const std::bad_alloc &) {} // (set again next time)
+    return RT_OK;
+}
 template <int MODE, bool TEX> static render_fn pick_mode(bool lds, bool count, int block) {
     if (block == 1024) {
         if (lds) return count ? render_kernel<true, true, 1024, MODE, TEX> : render_kernel<true, false, 1024, MODE, TEX>;
@@ -337,12 +385,14 @@ int rt_scene_create_ex(const rt_hittable *hittables, size_t n_hittables, const r
     if (options && options->struct_size >= offsetof(rt_scene_options, walk_tree) + sizeof(int32_t)) walk = options->walk_tree;
     if (walk == -1) walk = g_walk_tree.load();
     if (walk != RT_WALK_TREE_SAH && walk != RT_WALK_TREE_REFERENCE) return fail(RT_ERR_INVALID_ARGUMENT, "walk_tree must be RT_WALK_TREE_SAH, RT_WALK_TREE_REFERENCE or -1");
-    std::unique_ptr<rt_scene> s(new rt_scene());
-    int status = RT_OK;
-    std::string msg = rth::build_scene(hittables, n_hittables, textures, n_textures, walk, s->host, status);
-    if (status != RT_OK) return fail(status, msg);
-    *out = s.release();
-    return RT_OK;
+    return guarded("rt_scene_create", [&]() {
+        std::unique_ptr<rt_scene> s(new rt_scene());
+        int status = RT_OK;
+        std::string msg = rth::build_scene(hittables, n_hittables, textures, n_textures, walk, s->host, status);
+        if (status != RT_OK) return fail(status, msg);
+        *out = s.release();
+        return (int) RT_OK;
+    });
 }
 int rt_scene_create(const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures, rt_scene **out) {
     return rt_scene_create_ex(hittables, n_hittables, textures, n_textures, nullptr, out);
@@ -540,7 +590,8 @@ static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t
         const int cl = lambert_pool_lds(ldsBytes, block);
         if (cl) { p.park_l = cl; p.park_l_lds = 1; }
     }
-    HIP_TRY(hipFuncSetAttribute((const void *) fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
+    rc = allow_full_lds((const void *) fn);
+    if (rc != RT_OK) return rc;
     int perCu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *) fn, block, ldsBytes));
     if (perCu < 1) return fail(RT_ERR_HIP, "render kernel does not fit on a CU (occupancy 0)");
@@ -627,8 +678,7 @@ static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t
             const uint32_t hybA = hybrid_node_bytes(h, ldsA, lds, count, block, plan.park > 0), hybB = hybrid_node_bytes(h, ldsB, lds, count, block, plan.park > 0);
             int clA = 0, clB = 0;
             if (plan.park > 0) { clA = lambert_pool_lds(ldsA, block); clB = lambert_pool_lds(ldsB, block); }
-            HIP_TRY(hipFuncSetAttribute((const void *) fa, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsA));
-            HIP_TRY(hipFuncSetAttribute((const void *) fb, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsB));
+            if ((rc = allow_full_lds((const void *) fa)) != RT_OK || (rc = allow_full_lds((const void *) fb)) != RT_OK) return rc;
             RenderParams pa = p;
             pa.chunk = chunkA;
             pa.lds_node_bytes = (int32_t) hybA; p.lds_node_bytes = (int32_t) hybB;
@@ -731,7 +781,14 @@ static int apply_tune(rt_scene *scene, const std::vector<RawRay> &raw, rt_tune_i
     // allocations first; only when every device has its copy are the old ones released and the pointers swapped.  On any failure
     // the host scene is put back as it was and the new allocations are freed, so no launch can pair an old image with new offsets.
     struct Saved { rth::FlatTree walkTree; int walkKind; std::vector<unsigned char> image; rtd::SceneOffsets off; } saved{h.walkTree, h.walkKind, h.image, h.off};
-    if (!rth::tune_walk_tree(h, rays, tr)) return RT_OK; // a reference-tree scene, or no rays: left as it is
+    bool tuned = false;
+    try {
+        tuned = rth::tune_walk_tree(h, rays, tr);
+    } catch (...) { // (out of host memory part-way: the scene stays as it was, guarded() reports it)
+        h.walkTree = std::move(saved.walkTree); h.walkKind = saved.walkKind; h.image = std::move(saved.image); h.off = saved.off;
+        throw;
+    }
+    if (!tuned) return RT_OK; // a reference-tree scene, or no rays: left as it is
     if (!scene->dev.empty()) {
         int prev = -1;
         if (hipGetDevice(&prev) != hipSuccess) { (void) hipGetLastError(); prev = -1; }
@@ -766,7 +823,7 @@ static int apply_tune(rt_scene *scene, const std::vector<RawRay> &raw, rt_tune_i
 
 extern "C" {
 
-int rt_scene_tune(rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, rt_tune_info *info) {
+static int scene_tune(rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, rt_tune_info *info) {
     rt_tune_info out{};
     auto report = [&]() {
         if (!info) return;
@@ -843,6 +900,9 @@ int rt_scene_tune(rt_scene *scene, const rt_camera *camera, int32_t max_w, int32
     if (rc == RT_OK) report();
     return rc;
 }
+int rt_scene_tune(rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, rt_tune_info *info) {
+    return guarded("rt_scene_tune", [&]() { return scene_tune(scene, camera, max_w, max_h, seed, device, info); });
+}
 
 int rt_scene_tune_rays(rt_scene *scene, const double *rays, size_t n_rays, rt_tune_info *info) {
     rt_tune_info out{};
@@ -850,15 +910,17 @@ int rt_scene_tune_rays(rt_scene *scene, const double *rays, size_t n_rays, rt_tu
     if (n_rays > 0 && !rays) return fail(RT_ERR_INVALID_ARGUMENT, "rays is NULL");
     if (info && info->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_tune_info.struct_size is not set");
     out.nodes_before = out.nodes_after = scene->host.off.n_nodes;
-    std::vector<RawRay> raw(n_rays);
-    if (n_rays) memcpy(raw.data(), rays, n_rays * sizeof(RawRay));
-    const int rc = apply_tune(scene, raw, out);
-    if (rc == RT_OK && info) {
-        const uint32_t sz = info->struct_size;
-        memcpy(info, &out, sz < sizeof(out) ? sz : sizeof(out));
-        info->struct_size = sz;
-    }
-    return rc;
+    return guarded("rt_scene_tune_rays", [&]() {
+        std::vector<RawRay> raw(n_rays);
+        if (n_rays) memcpy(raw.data(), rays, n_rays * sizeof(RawRay));
+        const int rc = apply_tune(scene, raw, out);
+        if (rc == RT_OK && info) {
+            const uint32_t sz = info->struct_size;
+            memcpy(info, &out, sz < sizeof(out) ? sz : sizeof(out));
+            info->struct_size = sz;
+        }
+        return rc;
+    });
 }
 
 int rt_render(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
@@ -993,7 +1055,8 @@ static int launch_rays(const rt_scene *scene, int32_t device, const RayJob &job,
         const int cl = lambert_pool_lds(ldsBytes, block);
         if (cl) { p.park_l = cl; p.park_l_lds = 1; }
     }
-    HIP_TRY(hipFuncSetAttribute((const void *) fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
+    rc = allow_full_lds((const void *) fn);
+    if (rc != RT_OK) return rc;
     int perCu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *) fn, block, ldsBytes));
     if (perCu < 1) return fail(RT_ERR_HIP, "ray-list kernel does not fit on a CU (occupancy 0)");
@@ -1176,17 +1239,21 @@ static RcclApi load_rccl() {
 static RcclApi &rccl() { static RcclApi api = load_rccl(); return api; }
 #define RT_NCCL_INT32 2 /* ncclInt32 (rccl.h) */
 
-// communicators are expensive to set up (~0.1-1 s): kept per device list for the life of the process
+// communicators are expensive to set up (~0.1-1 s): kept per device list for the life of the process.  Calls from several threads
+// over the same list share them, so each call's group (ncclGroupStart .. ncclGroupEnd) is issued under the list's mutex: two
+// groups interleaved op by op could be matched in different orders on different ranks and hang them.
+struct CommSet { std::vector<void *> comms; std::mutex group_mu; };
 static std::mutex g_comm_mu;
-static std::map<std::vector<int>, std::vector<void *>> g_comms;
-static int comms_for(const std::vector<int> &devs, std::vector<void *> **out) {
+static std::map<std::vector<int>, CommSet> g_comms;
+static int comms_for(const std::vector<int> &devs, CommSet **out) {
     std::lock_guard<std::mutex> lock(g_comm_mu);
     auto it = g_comms.find(devs);
     if (it == g_comms.end()) {
         std::vector<void *> c(devs.size(), nullptr);
         const int rc = rccl().CommInitAll(c.data(), (int) devs.size(), devs.data());
         if (rc != 0) return fail(RT_ERR_HIP, std::string("ncclCommInitAll: ") + rccl().GetErrorString(rc));
-        it = g_comms.emplace(devs, c).first;
+        it = g_comms.emplace(std::piecewise_construct, std::forward_as_tuple(devs), std::forward_as_tuple()).first;
+        it->second.comms = std::move(c);
     }
     *out = &it->second;
     return RT_OK;
@@ -1212,9 +1279,9 @@ struct FrameDevice { // one device's share of a frame; everything is released on
 
 extern "C" {
 
-int rt_render_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, const int32_t *devices,
-                    int32_t n_devices, uint32_t flags, int32_t gather, const rt_render_options *options, int32_t *accum_host, uint8_t *rgb_host,
-                    rt_stats *stats) {
+static int render_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, const int32_t *devices,
+                        int32_t n_devices, uint32_t flags, int32_t gather, const rt_render_options *options, int32_t *accum_host, uint8_t *rgb_host,
+                        rt_stats *stats) {
     if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     if (!devices || n_devices < 1 || n_devices > 64) return fail(RT_ERR_INVALID_ARGUMENT, "devices: 1 to 64 device ids");
     if (gather < RT_GATHER_AUTO || gather > RT_GATHER_HOST) return fail(RT_ERR_INVALID_ARGUMENT, "gather must be one of RT_GATHER_*");
@@ -1286,12 +1353,14 @@ int rt_render_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_
             for (int i = 1; i < n_devices; ++i) { HIP_TRY(hipSetDevice(devices[i])); HIP_TRY(hipStreamSynchronize(fd[(size_t) i].stream)); }
         } else { // RCCL over xGMI: every sender on its own render stream, every receive on devices[0]'s
             std::vector<int> devs(devices, devices + n_devices);
-            std::vector<void *> *comms = nullptr;
-            rc = comms_for(devs, &comms);
+            CommSet *set = nullptr;
+            rc = comms_for(devs, &set);
             if (rc != RT_OK) return rc;
+            const std::vector<void *> *comms = &set->comms;
             RcclApi &nc = rccl();
             // nothing returns between GroupStart and GroupEnd: an early return would leave RCCL in group mode for the rest of the
             // process (the communicators are cached); errors are collected and reported after the group has been closed
+            std::unique_lock<std::mutex> group(set->group_mu);
             int e = nc.GroupStart();
             hipError_t he = hipSuccess;
             for (int i = viaSelf ? 0 : 1; i < n_devices && e == 0 && he == hipSuccess; ++i) {
@@ -1306,6 +1375,7 @@ int rt_render_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_
                 e = nc.Recv(fd[(size_t) i].stage, count, RT_NCCL_INT32, i, (*comms)[0], fd[0].stream);
             }
             const int e2 = nc.GroupEnd();
+            group.unlock();
             if (e == 0) e = e2;
             if (he != hipSuccess) return fail(RT_ERR_HIP, std::string("RCCL gather: hipSetDevice: ") + hipGetErrorString(he));
             if (e != 0) return fail(RT_ERR_HIP, std::string("RCCL gather: ") + nc.GetErrorString(e));
@@ -1336,22 +1406,33 @@ int rt_render_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_
     }
     return RT_OK;
 }
+int rt_render_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, const int32_t *devices,
+                    int32_t n_devices, uint32_t flags, int32_t gather, const rt_render_options *options, int32_t *accum_host, uint8_t *rgb_host,
+                    rt_stats *stats) {
+    return guarded("rt_render_frame", [&]() {
+        return render_frame(scene, camera, max_w, max_h, seed, devices, n_devices, flags, gather, options, accum_host, rgb_host, stats);
+    });
+}
 
 // ---- output side ------------------------------------------------------------------------------------------
 uint8_t rt_gamma_correct(uint8_t b) { return rth::gamma_correct(b); }
 
 int64_t rt_format_ppm(const uint8_t *rgb, int32_t rows, int32_t cols, int32_t gamma_correct, char *out, size_t out_capacity) {
     if (!rgb || rows <= 0 || cols <= 0) { fail(RT_ERR_INVALID_ARGUMENT, "bad image"); return -RT_ERR_INVALID_ARGUMENT; }
-    std::string s = rth::format_ppm(rgb, rows, cols, gamma_correct != 0);
-    if (out && out_capacity > s.size()) { memcpy(out, s.data(), s.size()); out[s.size()] = 0; }
-    return (int64_t) s.size();
+    return guarded<int64_t>("rt_format_ppm", [&]() {
+        std::string s = rth::format_ppm(rgb, rows, cols, gamma_correct != 0);
+        if (out && out_capacity > s.size()) { memcpy(out, s.data(), s.size()); out[s.size()] = 0; }
+        return (int64_t) s.size();
+    }, -RT_ERR_HOST);
 }
 
 int64_t rt_format_pixel_map(const uint8_t *rgb, int32_t rows, int32_t cols, uint8_t *out, size_t out_capacity) {
     if (!rgb || rows <= 0 || cols <= 0) { fail(RT_ERR_INVALID_ARGUMENT, "bad image"); return -RT_ERR_INVALID_ARGUMENT; }
-    std::string s = rth::format_pixel_map(rgb, rows, cols);
-    if (out && out_capacity >= s.size()) memcpy(out, s.data(), s.size());
-    return (int64_t) s.size();
+    return guarded<int64_t>("rt_format_pixel_map", [&]() {
+        std::string s = rth::format_pixel_map(rgb, rows, cols);
+        if (out && out_capacity >= s.size()) memcpy(out, s.data(), s.size());
+        return (int64_t) s.size();
+    }, -RT_ERR_HOST);
 }
 
 int64_t rt_parse_pixel_map(const uint8_t *data, size_t n, int32_t rows, int32_t cols, uint8_t *rgb_out, uint8_t *present_out) {
@@ -1364,13 +1445,15 @@ int64_t rt_parse_pixel_map(const uint8_t *data, size_t n, int32_t rows, int32_t 
 
 int rt_write_ppm(const char *path, const uint8_t *rgb, int32_t rows, int32_t cols, int32_t gamma_correct) {
     if (!path || !rgb || rows <= 0 || cols <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad image or path");
-    std::string s = rth::format_ppm(rgb, rows, cols, gamma_correct != 0);
-    FILE *f = fopen(path, "wb");
-    if (!f) return fail(RT_ERR_IO, std::string("cannot open ") + path);
-    const size_t w = fwrite(s.data(), 1, s.size(), f);
-    const int c = fclose(f);
-    if (w != s.size() || c != 0) return fail(RT_ERR_IO, std::string("short write to ") + path);
-    return RT_OK;
+    return guarded("rt_write_ppm", [&]() {
+        std::string s = rth::format_ppm(rgb, rows, cols, gamma_correct != 0);
+        FILE *f = fopen(path, "wb");
+        if (!f) return fail(RT_ERR_IO, std::string("cannot open ") + path);
+        const size_t w = fwrite(s.data(), 1, s.size(), f);
+        const int c = fclose(f);
+        if (w != s.size() || c != 0) return fail(RT_ERR_IO, std::string("short write to ") + path);
+        return (int) RT_OK;
+    });
 }
 
 } // extern "C"
@@ -1818,7 +1901,8 @@ int rt_dev_hit_object_lds(int32_t device, const rt_scene *scene, int32_t n, cons
     DevBuf<double> dr, dsk; DevBuf<int32_t> dh;
     HIP_TRY(dr.alloc((size_t) n * 6)); HIP_TRY(dh.alloc((size_t) n)); HIP_TRY(dsk.alloc((size_t) n * 3));
     HIP_TRY(dr.up(rays));
-    HIP_TRY(hipFuncSetAttribute((const void *) k_hit_object_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
+    rc = allow_full_lds((const void *) k_hit_object_lds);
+    if (rc != RT_OK) return rc;
     if (n) hipLaunchKernelGGL(k_hit_object_lds, dim3((unsigned) ((n + 1023) / 1024)), dim3(1024), ldsBytes, 0, p, n, dr.p, dh.p, dsk.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -1828,7 +1912,7 @@ int rt_dev_hit_object_lds(int32_t device, const rt_scene *scene, int32_t n, cons
     return RT_OK;
 }
 
-int rt_dev_pixel_candidates(int32_t device, const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t n,
+static int pixel_candidates(int32_t device, const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t n,
                             const int32_t *row_col, int32_t *leaves_out) {
     if (!camera || !row_col || !leaves_out || n < 0 || max_w <= 0 || max_h <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
     RenderParams p;
@@ -1845,7 +1929,8 @@ int rt_dev_pixel_candidates(int32_t device, const rt_scene *scene, const rt_came
     HIP_TRY(drc.alloc((size_t) n * 2)); HIP_TRY(dout.alloc((size_t) n * 2));
     HIP_TRY(drc.up(row_col));
     if (lds) {
-        HIP_TRY(hipFuncSetAttribute((const void *) k_pixel_candidates, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ldsBytes));
+        rc = allow_full_lds((const void *) k_pixel_candidates);
+        if (rc != RT_OK) return rc;
         if (n) hipLaunchKernelGGL(k_pixel_candidates, dim3((unsigned) ((n + 1023) / 1024)), dim3(1024), ldsBytes, 0, p, cam, n, drc.p, dout.p);
     } else if (n) hipLaunchKernelGGL(k_pixel_candidates_glb, dim3(blocks_for(n)), dim3(256), 0, 0, p, cam, n, drc.p, dout.p);
     HIP_TRY(hipGetLastError());
@@ -1873,6 +1958,10 @@ int rt_dev_pixel_candidates(int32_t device, const rt_scene *scene, const rt_came
         }
     }
     return RT_OK;
+}
+int rt_dev_pixel_candidates(int32_t device, const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t n,
+                            const int32_t *row_col, int32_t *leaves_out) {
+    return guarded("rt_dev_pixel_candidates", [&]() { return pixel_candidates(device, scene, camera, max_w, max_h, n, row_col, leaves_out); });
 }
 
 int rt_dev_trace_ray(int32_t device, const rt_scene *scene, int32_t bounce_depth, int32_t n, const double *rays, uint32_t *rng_state, uint8_t *colour_out) {

@@ -14,6 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import math
+import threading
 from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -397,7 +398,17 @@ class Scene:
     def __init__(self, handle: int, keep):
         self._h = C.c_void_p(handle)
         self._keep = keep
-        self.last_stats: Optional[dict] = None
+        self._local = threading.local()
+
+    @property
+    def last_stats(self) -> Optional[dict]:
+        """The statistics of the calling THREAD's last render_rows / hitObject / traceRays on this scene (None before its first,
+        or after a device call with stats=False).  Per thread, like rt_last_error: a scene may be used from many threads at once."""
+        return getattr(self._local, "stats", None)
+
+    @last_stats.setter
+    def last_stats(self, value: Optional[dict]) -> None:
+        self._local.stats = value
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -496,7 +507,7 @@ class Scene:
         device) -> (hit_index int32 [n]: index into Scene.make's objects, -1 none, -2 where Ray.make' fails; strike float64 [n, 3],
         NaN where hit_index < 0).  A numpy array goes through rt_hit_objects; a torch tensor on a GPU through rt_hit_objects_device
         on torch.cuda.current_stream(), and the results are tensors on that device (stats=False: no wait for the device, and
-        last_stats is None).  device: the GPU (default 0, or the tensor's)."""
+        last_stats is None).  The statistics go to last_stats, which is per thread.  device: the GPU (default 0, or the tensor's)."""
         flags = A.RT_RENDER_COUNTERS if counters else 0
         if _is_torch(rays):
             torch = _torch()

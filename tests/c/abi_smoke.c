@@ -33,6 +33,7 @@ static int sequential_layout_matches(int which, const int (*fields)[2], int n_fi
 
 int main(void) {
     CHECK(rt_abi_version() == RT_ABI_VERSION);
+    CHECK(RT_ERR_HOST == 6); /* the status the F# RtStatus and _abi.py mirror */
     CHECK(rt_abi_sizeof(0) == sizeof(rt_hittable) && rt_abi_sizeof(1) == sizeof(rt_texture) && rt_abi_sizeof(2) == sizeof(rt_camera));
     CHECK(rt_abi_sizeof(3) == sizeof(rt_scene_info) && rt_abi_sizeof(4) == sizeof(rt_stats));
     CHECK(rt_abi_sizeof(5) == sizeof(rt_render_options) && rt_abi_sizeof(6) == sizeof(rt_scene_options));
