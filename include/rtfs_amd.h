@@ -153,7 +153,12 @@ typedef struct rt_scene_info {
 
 /* Scene.make (Scene.fs:15-28): partitions bounded/unbounded, builds the BoundingBoxTree on the host,
  * builds the tree the device walks over the same Leaf boxes (rt_set_walk_tree), flattens that (DFS pre-order, on-hit and
- * on-miss successor per node) and keeps a host copy; device copies are made lazily per device. */
+ * on-miss successor per node) and keeps a host copy; device copies are made lazily per device.
+ * Textures: at most 254 records (more: RT_ERR_UNSUPPORTED); a Checkered tree of any depth that fits them is evaluated as the
+ * reference's recursion evaluates it (Texture.fs:56-62), with the map of the record the hittable points at; |grid_size| <= 5e5
+ * (beyond, or NaN: RT_ERR_UNSUPPORTED); a child index at or above its parent's or negative, an image without texels or with a
+ * non-positive size, a ramp source that is no rt_ramp_source, a texture id on a style that carries a Pixel:
+ * RT_ERR_INVALID_ARGUMENT. */
 int rt_scene_create(const rt_hittable *hittables, size_t n_hittables,
                     const rt_texture *textures, size_t n_textures, rt_scene **out);
 /* Per-scene settings, handed over at creation instead of through the process-wide rt_set_walk_tree default. */

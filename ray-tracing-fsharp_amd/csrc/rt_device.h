@@ -163,6 +163,7 @@ RTD_INLINE V3 random_unit(Rng &r) {
 // ---- Pixel.fs:136-151 ; colour = R | G<<8 | B<<16 in one register ------------------------------------------------
 #define RTD_WHITE 0x00FFFFFFu
 #define RTD_BLACK 0x00000000u
+#define RTD_MAX_TEXTURES 254 // records per scene: a texture id rides in 8 bits of an object's meta word, 0 = none (textured())
 #define RTD_HOTPINK (205u | (105u << 8) | (180u << 16)) /* Pixel.fs:61-66 */
 // x / 255 for x <= 255 * 255: (x * 0x8081) >> 23, exact on that range (checked for all 65 026 values) and the product stays below
 // 2^32, so it is one full-rate 24-bit multiply and a shift instead of the quarter-rate v_mul_hi_u32 of the generic /255.
@@ -918,7 +919,10 @@ RTD_INLINE uint32_t texture_colour_at_inline(const TexRec *tex, const uint8_t *t
     double y = theta / PI;
     if (uv) { uv[0] = x; uv[1] = y; }
     int cur = id;
-    for (int depth = 0; depth < 16; ++depth) { // Checkered trees descend to strictly smaller indices
+    // Checkered trees descend to strictly smaller indices (checked at creation), so a descent visits each record at most once and
+    // ends by itself, as the reference's recursion does (Texture.fs:56-62): the bound is the record count, which no accepted chain
+    // exceeds (253 Checkered nodes over one leaf at most), so RTD_BLACK below is never returned for a scene rt_scene_create built.
+    for (int depth = 0; depth < RTD_MAX_TEXTURES; ++depth) {
         const TexRec t = tex[cur];
         if (t.kind == 1u) { // Checkered (Texture.fs:56-62)
             double sine = rtt::cr_sin(t.grid * x) * rtt::cr_sin(t.grid * y);

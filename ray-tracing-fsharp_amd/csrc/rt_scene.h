@@ -425,7 +425,7 @@ static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture 
     status = RT_ERR_INVALID_ARGUMENT;
     if (n > 0 && !h) return "hittables is NULL";
     if (ntex > 0 && !tex) return "textures is NULL";
-    if (ntex > 254) { status = RT_ERR_UNSUPPORTED; return "at most 254 textures"; }
+    if (ntex > (size_t) RTD_MAX_TEXTURES) { status = RT_ERR_UNSUPPORTED; return "at most 254 textures"; }
     s.hittables.assign(h, h + n);
     s.textures.assign(tex, tex + ntex);
 

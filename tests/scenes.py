@@ -186,3 +186,21 @@ def require_clear_eye(camera, max_w, max_h, clearance=1e-3):
     if not d >= clearance:
         raise ValueError(f"the viewport passes {d:.3g} from the eye")
     return camera
+
+
+def raw_scene_pair(orc, hs, n, tex, ntex, keep):
+    """(rt.Scene, OracleScene) from the ABI arrays themselves -- for scenes the host mirror cannot express (texture records with
+    shared children, chosen record numbers); both sides are handed the same bytes.  orc=None: the product scene alone."""
+    import ctypes as C
+    from ray_tracing_fsharp_amd._lib import check
+    out = C.c_void_p()
+    check(rt.lib.rt_scene_create(hs, n, tex, ntex, C.byref(out)))
+    s = rt.Scene(out.value, keep)
+    if orc is None:
+        return s, None
+    o = object.__new__(orc.OracleScene)
+    o._keep = keep
+    h = C.c_void_p()
+    orc._check(orc.lib.orc_scene_create(hs, n, tex, ntex, C.byref(h)))
+    o._h = h
+    return s, o
