@@ -34,6 +34,10 @@ RTD_INLINE int fcmp(double a, double b) {
     if (fabs(a - b) < RTD_TOL) return CMP_EQ;
     return (a < b) ? CMP_LT : CMP_GT;
 }
+// fcmp(a, 0.0) as the two predicates its callers branch on, so that no three-way value is formed in a register and tested again:
+// Equal iff |a| < tol; otherwise Greater unless a < 0 (a NaN is Greater, as in fcmp)
+RTD_INLINE bool fzero(double a) { return fabs(a) < RTD_TOL; }
+RTD_INLINE bool fgreater0(double a) { return !fzero(a) && !(a < 0.0); }
 
 // ---- Point.fs:18-45 ------------------------------------------------------------------------------------
 struct V3 { double x, y, z; };
@@ -87,6 +91,18 @@ RTD_INLINE bool unitise(V3 v, V3 &out) {
     out = vscale(factor, v);
     return true;
 }
+
+#ifdef RTD_STAGE_CLOCKS
+// Diagnostic builds only: execution counts for the instruction census (scripts/instruction_census.py), summed over every launch since
+// the last rt_diag_census(.., reset).  Words 0-31 are the wave-uniform counts of StageStats (rt_render_kernel.h); the rare events of this
+// file add themselves here, per lane: [32] random_unit retries, [33] lambert_bounce retries, [34] lanes entering the leaf sliver,
+// [35] the same per wave (sliver blocks executed).  Words 36-47: the kernel's own stage counts (rt_render_kernel.h).
+#define RTD_CENSUS_WORDS 48
+__device__ unsigned long long g_census[RTD_CENSUS_WORDS];
+#define RTD_CENSUS_EVENT(i) atomicAdd(&g_census[i], 1ull)
+#else
+#define RTD_CENSUS_EVENT(i)
+#endif
 
 // ---- FloatProducer (Float.fs:14-76) ------------------------------------------------------------------------
 struct Rng { uint32_t x, y, z, w; };
@@ -156,6 +172,7 @@ RTD_INLINE V3 random_unit(Rng &r) {
         double r1 = rng_get(r), r2 = rng_get(r), r3 = rng_get(r);
         V3 v = mk((2.0 * r1) - 1.0, (2.0 * r2) - 1.0, (2.0 * r3) - 1.0);
         if (unitise(v, out)) break;
+        RTD_CENSUS_EVENT(32);
     }
     return out;
 }
@@ -325,10 +342,9 @@ RTD_INLINE double sphere_first_intersection(V3 o, V3 d, V3 c, double r2) {
     double b = dot(d, diff);
     double cc = dot(diff, diff) - r2;
     double disc = (b * b - cc);
-    int cmp = fcmp(disc, 0.0);
-    if (cmp == CMP_EQ) { double i = (-b); return fpos(i) ? i : __builtin_nan(""); }
+    if (fzero(disc)) { double i = (-b); return fpos(i) ? i : __builtin_nan(""); }
     double i = __builtin_nan("");
-    if (cmp == CMP_GT) { // also taken by a NaN discriminant, which yields NaN roots and so none
+    if (fgreater0(disc)) { // also taken by a NaN discriminant, which yields NaN roots and so none
         double s = sqrt_above_tol(disc); // disc > 1e-8 in this branch
         double i1 = s - b;
         double i2 = -(b + s);
@@ -821,17 +837,21 @@ RTD_INLINE void leaf_test_object_exact(const SceneView<LDS> &sc, V3 o, V3 d, dou
     const double dd = dot(diff, diff);
     const double cc = dd - g1.y;
     const double disc = (b * b - cc);
-    const int cmp = fcmp(disc, 0.0);
+    const bool eq = fzero(disc), gt = fgreater0(disc); // Float.compare disc 0.0: Equal / Greater
     double t = __builtin_nan("");
-    if (cmp == CMP_EQ) { const double i = (-b); t = fpos(i) ? i : t; }
-    else if (cmp == CMP_GT) {
+    if (eq) { const double i = (-b); t = fpos(i) ? i : t; }
+    else if (gt) {
         const double s = sqrt_above_tol(disc);
         const double i1 = s - b, i2 = -(b + s);
         t = fpos(i2) ? i2 : (fpos(i1) ? i1 : t);
     }
     const double a = t * t;
     bool cand = a < bestF || (a == bestF && prim < w.best);
-    if (cand && !(implied && cmp == CMP_GT && dd <= RTD_IMPLIED_DD)) { // the sliver: the leaf's BoundingBox.hits, exactly
+    if (cand && !(implied && gt && dd <= RTD_IMPLIED_DD)) { // the sliver: the leaf's BoundingBox.hits, exactly
+        RTD_CENSUS_EVENT(34);
+#ifdef RTD_STAGE_CLOCKS
+        if (__builtin_amdgcn_mbcnt_hi((uint32_t) (__builtin_amdgcn_ballot_w64(true) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) __builtin_amdgcn_ballot_w64(true), 0u)) == 0u) RTD_CENSUS_EVENT(35);
+#endif
         const double r = sc.geo[prim * 3 + 2].y;
         // The divisions are invariant over the walk stage's loop, and LICM would hoist them (speculated) to the stage's entry:
         // 33 double-precision instructions per lane and stage entry, and the three inverses held in 6 VGPRs across the loop, for
@@ -1146,6 +1166,7 @@ RTD_INLINE void lambert_bounce(const SceneView<LDS> &sc, int obj, i2 m, V3 strik
         V3 target = walk(centre, offset, 1.0);
         V3 nd;
         if (unitise(vsub(target, strike), nd)) { o = strike; d = nd; break; }
+        RTD_CENSUS_EVENT(33);
     }
 }
 template <bool LDS>

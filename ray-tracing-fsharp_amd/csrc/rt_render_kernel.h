@@ -162,7 +162,17 @@ struct StageStats { // wave-uniform, COUNT variant only
     unsigned long long loopTrips, loopLanes;            // -DRTD_STAGE_CLOCKS only: trips of the timed variant's node loop, lanes that stepped in them
     unsigned long long tLoop, tLeaf, tUnb, tCam, tLamb; // -DRTD_STAGE_CLOCKS only: node loop / leaf passes (inside tWalk), unbounded tests (inside tShade),
                                                         // new items (inside tRefill), Lambert batches (inside tSlow)
+#ifdef RTD_STAGE_CLOCKS
+    // the instruction census' execution counts (scripts/instruction_census.py), wave-uniform; they leave through g_census (rt_device.h)
+    uint32_t turns, lambBatches, lambLanes, newRefills, newItems, unparkL, unparkA, storeBlocksL, storeLanesL, storeBlocksA,
+        lightBatches, lightLanes, missLanes, ranges, flushes, leafLanes, unparkBatchesL, unparkBatchesA, slowLanesByStyle[8], slowBatchesByStyle[8];
+#endif
 };
+#ifdef RTD_STAGE_CLOCKS
+#define RTD_CENSUS(S) S
+#else
+#define RTD_CENSUS(S)
+#endif
 
 // Diagnostic builds (-DRTD_STAGE_CLOCKS): the per-stage cycle sums of the counting variant in the timed variant too
 #ifdef RTD_STAGE_CLOCKS
@@ -274,24 +284,26 @@ struct Sched {
     }
 
     // ---- park pools: entry e of field f sits at base + (f * K + e) * 16 (fields 0-4) / base + 80 * K + e * 8 (field 5), K = the pool's capacity ----
+    // (byte offsets are formed in 32 bits -- a wave's pools are a few KB -- so that every access is scalar base + 32-bit lane offset,
+    // one add per field, instead of a 64-bit address built per field)
     RTD_INLINE void park_store(unsigned char *base, uint32_t K, uint32_t e) {
-        d2 *f = (d2 *) base;
+        const uint32_t at = e * 16u, kb = K * 16u;
         d2 v;
-        v.x = o.x; v.y = o.y; f[e] = v;
-        v.x = o.z; v.y = d.x; f[K + e] = v;
-        v.x = d.y; v.y = d.z; f[2u * K + e] = v;
+        v.x = o.x; v.y = o.y; *(d2 *) (base + at) = v;
+        v.x = o.z; v.y = d.x; *(d2 *) (base + (kb + at)) = v;
+        v.x = d.y; v.y = d.z; *(d2 *) (base + (2u * kb + at)) = v;
         i4 r; r.x = __double2loint(w.bestLen); r.y = __double2hiint(w.bestLen); r.z = (int) colour; r.w = (int) slotOff;
-        ((i4 *) base)[3u * K + e] = r;
+        *(i4 *) (base + (3u * kb + at)) = r;
         r.x = (int) rng.x; r.y = (int) rng.y; r.z = (int) rng.z; r.w = (int) rng.w;
-        ((i4 *) base)[4u * K + e] = r;
+        *(i4 *) (base + (4u * kb + at)) = r;
         i2 b; b.x = bounces; b.y = w.best;
-        ((i2 *) (base + 80u * K))[e] = b;
+        *(i2 *) (base + (5u * kb + e * 8u)) = b;
     }
     RTD_INLINE void park_load(const unsigned char *base, uint32_t K, uint32_t e, int state) {
-        const d2 *f = (const d2 *) base;
-        const d2 a = f[e], b = f[K + e], c = f[2u * K + e];
-        const i4 t = ((const i4 *) base)[3u * K + e], r = ((const i4 *) base)[4u * K + e];
-        const i2 bo = ((const i2 *) (base + 80u * K))[e];
+        const uint32_t at = e * 16u, kb = K * 16u;
+        const d2 a = *(const d2 *) (base + at), b = *(const d2 *) (base + (kb + at)), c = *(const d2 *) (base + (2u * kb + at));
+        const i4 t = *(const i4 *) (base + (3u * kb + at)), r = *(const i4 *) (base + (4u * kb + at));
+        const i2 bo = *(const i2 *) (base + (5u * kb + e * 8u));
         o = mk(a.x, a.y, b.x); d = mk(b.y, c.x, c.y);
         w.bestLen = __hiloint2double(t.y, t.x); colour = (uint32_t) t.z; slotOff = (uint32_t) t.w;
         rng.x = (uint32_t) r.x; rng.y = (uint32_t) r.y; rng.z = (uint32_t) r.z; rng.w = (uint32_t) r.w;
@@ -373,6 +385,13 @@ struct Sched {
         const unsigned long long m = __builtin_amdgcn_ballot_w64(st == L_SLOW);
         if (m == 0ull) return;
         if (COUNT || RTD_CLK) { ss.slow++; ss.slowLanes += (uint32_t) __popcll(m); }
+#ifdef RTD_STAGE_CLOCKS
+#pragma unroll
+        for (int sty = 0; sty < 8; ++sty) {
+            const unsigned long long sm = __builtin_amdgcn_ballot_w64(st == L_SLOW && (int) (((uint32_t) sc.meta[w.best < 0 ? 0 : w.best].x >> 2) & 7u) == sty);
+            ss.slowLanesByStyle[sty] += (uint32_t) __popcll(sm); ss.slowBatchesByStyle[sty] += sm != 0ull ? 1u : 0u;
+        }
+#endif
         if (st == L_SLOW) {
             const V3 strike = walk(o, d, w.bestLen); // Ray.walkAlong ray bestLength (Scene.fs:91)
             after_reflection(reflection<LDS, false>(sc, w.best, strike, o, d, colour, rng, TEX ? texc : RTD_NO_TEX));
@@ -395,6 +414,7 @@ struct Sched {
     // ---- lamb: the Lambert bounce (Sphere.fs:202-222) for the lanes that took parked Lambert hits (or whose hit found the pool full) ----
     RTD_INLINE void stage_lamb() {
         if (__builtin_amdgcn_ballot_w64(st == L_LAMB) == 0ull) return;
+        RTD_CENSUS(ss.lambBatches++; ss.lambLanes += (uint32_t) __popcll(__builtin_amdgcn_ballot_w64(st == L_LAMB));)
         const unsigned long long k0 = RTD_CLK ? __builtin_amdgcn_s_memtime() : 0ull;
         if (st == L_LAMB) { // o holds the strike point, bit 31 of bounces "the ray came from inside" (stage_shade)
             const bool inside = bounces < 0;
@@ -409,7 +429,8 @@ struct Sched {
     // A lane steps iff w.off < end: finished walks sit at >= end, pending leaves carry RTD_LEAF (> end), idle lanes are
     // parked at `end`.  So one compare gives the active set, and waiting = busy - active.
     RTD_INLINE void stage_walk() {
-        if (__builtin_amdgcn_ballot_w64(st == L_WALK) == 0ull) return;
+        const unsigned long long walkM0 = __builtin_amdgcn_ballot_w64(st == L_WALK);
+        if (walkM0 == 0ull) return;
         const int nBusy = __popcll(__builtin_amdgcn_ballot_w64(st != L_IDLE));
         const int stop = (nBusy - p.leaf_wait) > 0 ? (nBusy - p.leaf_wait) : 0; // active <= stop  <=>  waiting >= leaf_wait
         if constexpr (!COUNT) {
@@ -421,6 +442,9 @@ struct Sched {
             double bestF = (w.best < 0) ? __builtin_inf() : w.bestLen * w.bestLen; // `a = point * point` (Scene.fs:45), recomputed
             const bool implied = p.off.box_implied != 0; // (rays of this kernel are unitised: Ray.make')
             if (RTD_CLK) ss.trips++; // (diagnostic build: walk-stage entries and leaf passes; the loop's trips are not counted)
+            // the lanes walking and the lanes finished, as wave masks kept up to date by the lanes that finish in a pass: one select
+            // per pass instead of a select and two compares of the new state
+            unsigned long long walkM = walkM0, doneM = __builtin_amdgcn_ballot_w64(st == L_DONE);
             for (;;) {
                 const unsigned long long k0 = RTD_CLK ? __builtin_amdgcn_s_memtime() : 0ull;
 #ifdef RTD_STAGE_CLOCKS
@@ -438,6 +462,7 @@ struct Sched {
 #undef RTD_TRIP_PASS
                 const unsigned long long k1 = RTD_CLK ? __builtin_amdgcn_s_memtime() : 0ull;
                 if (RTD_CLK && __builtin_amdgcn_ballot_w64(pend != 0u) != 0ull) ss.leaf++;
+                RTD_CENSUS(ss.leafLanes += (uint32_t) __popcll(__builtin_amdgcn_ballot_w64(pend != 0u));)
                 if (pend != 0u) {
                     int prim;
                     if (LDS || sc.narrow) {
@@ -449,9 +474,10 @@ struct Sched {
                 if (RTD_CLK) { ss.tLoop += k1 - k0; ss.tLeaf += __builtin_amdgcn_s_memtime() - k1; }
                 const bool fin = (st == L_WALK) && (w.off >= end) && pend == 0u;
                 if (fin) st = L_DONE;
-                const int nWalk = __popcll(__builtin_amdgcn_ballot_w64(st == L_WALK));
-                const int nDone = __popcll(__builtin_amdgcn_ballot_w64(st == L_DONE));
-                if (nWalk == 0 || nDone >= p.yield_lanes) break;
+                // (a ballot per compare, joined as masks: the ballot of a conjunction is first made a 0/1 value per lane and compared again)
+                const unsigned long long finM = walkM & __builtin_amdgcn_ballot_w64(w.off >= end) & __builtin_amdgcn_ballot_w64(pend == 0u);
+                walkM &= ~finM; doneM |= finM;
+                if (walkM == 0ull || __popcll(doneM) >= p.yield_lanes) break;
             }
             return;
         }
@@ -489,6 +515,7 @@ struct Sched {
             const unsigned long long k0 = RTD_CLK ? __builtin_amdgcn_s_memtime() : 0ull;
             unbounded_tests<LDS, COUNT>(sc, o, d, w, cnt);
             if (RTD_CLK) ss.tUnb += __builtin_amdgcn_s_memtime() - k0;
+            RTD_CENSUS(ss.missLanes += (uint32_t) __popcll(__builtin_amdgcn_ballot_w64(w.best < 0));)
             if (w.best < 0) { ended = true; result = RTD_BLACK; st = L_IDLE; w.off = end; } // "never heard from again": Black (Scene.fs:102-104)
             else {
                 if (COUNT) cnt.refl++;
@@ -501,6 +528,7 @@ struct Sched {
                         bounces |= inside ? (int) 0x80000000u : 0;
                         st = L_LAMB;
                     } else {
+                        RTD_CENSUS({ const uint32_t nl = (uint32_t) __popcll(__builtin_amdgcn_ballot_w64(true)); ss.lightBatches++; ss.lightLanes += nl; })
                         const V3 strike = walk(o, d, w.bestLen); // Ray.walkAlong ray bestLength (Scene.fs:91)
                         after_reflection(reflection_fast<LDS>(sc, w.best, m, strike, o, d, colour, rng));
                     }
@@ -526,6 +554,7 @@ struct Sched {
                 const uint32_t n = want < room ? want : room;
                 parked += n;
                 if (COUNT || RTD_CLK) ss.parkedLanes += n;
+                RTD_CENSUS(ss.storeBlocksA++;)
             }
         }
         if (p.park_l > 0) {
@@ -539,6 +568,7 @@ struct Sched {
                     st = L_IDLE; w.off = end;
                 }
                 parkedL += want < room ? want : room;
+                RTD_CENSUS(ss.storeBlocksL++; ss.storeLanesL += want < room ? want : room;)
             }
         }
     }
@@ -767,10 +797,12 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
             }
         }
         __builtin_amdgcn_wave_barrier();
+        RTD_CENSUS(ss.flushes++;)
     };
 
     for (;;) {
         L.ended = false;
+        RTD_CENSUS(ss.turns++;)
         const unsigned long long t0 = (COUNT || RTD_CLK) ? __builtin_amdgcn_s_memtime() : 0ull;
         // ---- ranges: flush what has drained, reserve the next one when the current one has no items left ----
         if (prevNpx != 0u && prevOut == 0u) { flush(prevFirst, prevNpx, prevSlot); prevNpx = 0u; }
@@ -820,6 +852,7 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                     }
                     __builtin_amdgcn_wave_barrier();
                     curFirst = first; curNpx = npx; curNext = 0u; curTotal = npx * n2; curOut = 0u;
+                    RTD_CENSUS(ss.ranges++;)
                 }
             }
         }
@@ -855,6 +888,8 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                 L.parkedT -= nUnT;
                 curNext += take;
                 curOut += (uint32_t) __popcll(__builtin_amdgcn_ballot_w64(started));
+                RTD_CENSUS(ss.newRefills += take != 0u ? 1u : 0u; ss.newItems += take; ss.unparkL += nUnL; ss.unparkA += nUnA;
+                            ss.unparkBatchesL += nUnL != 0u ? 1u : 0u; ss.unparkBatchesA += nUnA != 0u ? 1u : 0u;)
             }
         }
         if (__builtin_amdgcn_ballot_w64(L.st != L_IDLE) == 0ull) continue;
@@ -976,6 +1011,11 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     ss.tRefill = ss.tSlow = ss.tWalk = ss.tShade = 0ull;
     ss.tLoop = ss.tLeaf = ss.tUnb = ss.tCam = ss.tLamb = 0ull;
     ss.loopTrips = ss.loopLanes = 0ull;
+#ifdef RTD_STAGE_CLOCKS
+    ss.turns = ss.lambBatches = ss.lambLanes = ss.newRefills = ss.newItems = ss.unparkL = ss.unparkA = ss.storeBlocksL = ss.storeLanesL = ss.storeBlocksA = 0u;
+    ss.lightBatches = ss.lightLanes = ss.missLanes = ss.ranges = ss.flushes = ss.leafLanes = ss.unparkBatchesL = ss.unparkBatchesA = 0u;
+    for (int i = 0; i < 8; ++i) ss.slowLanesByStyle[i] = ss.slowBatchesByStyle[i] = 0u;
+#endif
     uint32_t earlyCount = 0;
     uint64_t sampleCount = 0; // Scene.traceOnce calls = sum of PixelStats.Count
 
@@ -1109,6 +1149,18 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
             atomicAdd(&p.counters[30], ss.tCam);
             atomicAdd(&p.counters[31], ss.tLamb);
             if (!COUNT) { atomicAdd(&p.counters[14], ss.loopTrips); atomicAdd(&p.counters[15], ss.loopLanes); } // (the counting variant keeps its wave lifetimes there)
+#ifdef RTD_STAGE_CLOCKS
+            if (!COUNT && MODE == 2) { // the census describes pass B's timed kernel
+                const uint32_t cz[16] = {ss.turns, ss.lambBatches, ss.lambLanes, ss.newRefills, ss.newItems, ss.unparkL, ss.unparkA, ss.storeBlocksL, ss.storeLanesL,
+                                         ss.storeBlocksA, ss.lightBatches, ss.lightLanes, ss.missLanes, ss.ranges, ss.flushes, ss.leafLanes};
+                for (int i = 0; i < 16; ++i) atomicAdd(&g_census[i], (unsigned long long) cz[i]);
+                for (int i = 0; i < 8; ++i) { atomicAdd(&g_census[16 + i], (unsigned long long) ss.slowLanesByStyle[i]); atomicAdd(&g_census[24 + i], (unsigned long long) ss.slowBatchesByStyle[i]); }
+                // the stage counts of rt_last_stage_stats, for this kernel alone (those sum pass A and pass B)
+                const unsigned long long sz[12] = {ss.refill, ss.trips, ss.leaf, ss.shade, ss.refillLanes, ss.shadeLanes, ss.slow, ss.slowLanes, ss.loopTrips, ss.loopLanes,
+                                                   ss.unparkBatchesL, ss.unparkBatchesA};
+                for (int i = 0; i < 12; ++i) atomicAdd(&g_census[36 + i], sz[i]);
+            }
+#endif
         }
     }
     if (lane == 0) {

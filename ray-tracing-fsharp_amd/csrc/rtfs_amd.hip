@@ -736,6 +736,20 @@ static int collect_stats(Pending &pd, rt_stats *stats) {
     return RT_OK;
 }
 
+#ifdef RTD_STAGE_CLOCKS
+// Diagnostic builds only (not in include/rtfs_amd.h, not part of the ABI): the instruction census' execution counts of the current
+// device, g_census (rt_device.h), summed over pass B's timed launches since the last reset.
+extern "C" int rt_diag_census(uint64_t *out, int32_t n, int32_t reset) {
+    unsigned long long c[RTD_CENSUS_WORDS] = {0};
+    if (!out || n < 0 || n > RTD_CENSUS_WORDS) return fail(RT_ERR_INVALID_ARGUMENT, "rt_diag_census: bad arguments");
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(c, HIP_SYMBOL(rtd::g_census), sizeof(c)));
+    for (int i = 0; i < n; ++i) out[i] = c[i];
+    if (reset) { memset(c, 0, sizeof(c)); HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rtd::g_census), c, sizeof(c))); }
+    return RT_OK;
+}
+#endif
+
 extern "C" {
 
 int rt_render_device_ex(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,

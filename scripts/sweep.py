@@ -18,10 +18,13 @@ ap.add_argument("--pixels", type=int, default=800)
 ap.add_argument("--spp", type=int, default=500)
 ap.add_argument("--depth", type=int, default=50)
 ap.add_argument("--counters", action="store_true")
+ap.add_argument("--tune", action="store_true", help="tune the walk tree to the camera first (rt_scene_tune), as bench.py does")
 args = ap.parse_args()
 
 objs, cam, w, h = rt.sample_images.config3_final(spp=args.spp, depth=args.depth, pixels=args.pixels)
 scene = rt.Scene.make(objs)
+if args.tune:
+    scene.tune(w, h, cam, seed=2024)
 rows, cols = 2 * h + 1, 2 * w + 1
 dev = torch.device("cuda", 0)
 local = torch.zeros((rows, cols, 4), dtype=torch.int32, device=dev)
