@@ -8,6 +8,7 @@
 // a stackless skip-link walk over a pre-order tree image, byte colour packed in one VGPR, material handling
 // split into decide/refract/reflect/fuzz stages so that lanes with different SphereStyles share instructions.
 #pragma once
+#include "rt_launch_consts.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
@@ -245,7 +246,6 @@ RTD_INLINE double pow5(double x) {
 #ifndef RTD_NODE_BYTES
 #define RTD_NODE_BYTES 112
 #endif
-#define RTD_NODE32_BYTES 64
 #define RTD_LEAF 0x40000000 /* flag in on_hit / in a walk offset: a leaf's primitive test is pending */
 struct TexRec { // global memory only
     uint32_t kind;

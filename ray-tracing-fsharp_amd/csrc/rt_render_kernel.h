@@ -22,14 +22,6 @@
 
 namespace rtd {
 
-#define RTD_MAX_CHUNK 64
-#define RTD_MAX_PARK 256
-#define RTD_PARK_DEFAULT 96 /* entries of a wave's general pool (88 B each, global memory).  Bench frame, ms / GB written to HBM: 45: 124.6, 64: 109.7 / 14.5, 80: 108.8 / 24.0, 96: 108.2 / 28.1, 128: 108.2 / 30.7 (scripts/pool_traffic.sh) */
-#ifndef RTD_PARK_L_DEFAULT
-#define RTD_HYBRID_LANES 16 /* node_loop_glb32: this many lanes at LDS-held records make a trip of their own (measured, rt_device.h) */
-#define RTD_PARK_L_DEFAULT 64 /* entries of a wave's pool of parked Lambert hits; 0: Lambert hits are shaded where they fall */
-#endif
-
 struct RenderParams {
     const CameraParams *cam_ptr;   // device copy of the camera: read where a camera ray is built, not held in SGPRs
     int32_t depth;                 // Camera.BounceDepth
@@ -88,8 +80,7 @@ struct RenderParams {
 //   live [P]        compacted pixel slots for phase 2 (fused mode), or
 //   cost [P]        rays traced for the pixel in phase 1 (pass A: the cost estimate that orders pass B; pass A has no phase 2)
 //   cand [P][2]     the leaves the pixel's camera rays can reach, as two queue words (pixel_candidates, rt_device.h), or RTD_CAND_WALK
-#define RTD_WAVE_WORDS(P) (18u * (uint32_t) (P)) /* fused: 13 P used; pass B: two slots of {acc [P][3], pix [P][4]}, then cand [2][P][2] */
-#define RTD_WAVE_WORDS_A(P) (13u * (uint32_t) (P)) /* pass A: acc, pix, cost, cand [P][2] -- a tighter footprint, so its units can be wider */
+// (RTD_WAVE_WORDS(P), RTD_WAVE_WORDS_A(P): rt_launch_consts.h)
 
 // Wave-private LDS words: adds from many lanes may land on one word (same pixel), so they are ds_add_u32; the owner
 // lane later takes the sum and clears the word in one ds_wrxchg.  One wave's LDS operations execute in order.
@@ -180,9 +171,6 @@ struct StageStats { // wave-uniform, COUNT variant only
 #else
 #define RTD_CLK false
 #endif
-#define RTD_YIELD_DEFAULT 50
-#define RTD_LEAF_WAIT_EXTRA 5 /* RenderParams::leaf_wait = yield_lanes + this (at most 64) */
-#define RTD_REFILL_DEFAULT 8
 
 // ---- the lane scheduler shared by every render mode ------------------------------------------------------------------------
 // Every lane of a wave is a path slot in one of four states: IDLE (wants a new item), WALK (somewhere in the tree walk of its
@@ -201,8 +189,6 @@ struct StageStats { // wave-uniform, COUNT variant only
 // the idle lanes take parked paths instead of new items and run the general `reflection` together.  A pool that is full
 // (or switched off, p.park = 0) leaves the path in its lane and the general code runs for it at the next turn of the loop.
 // Which lane computes what when has no effect on any result: streams are per item.
-#define RTD_PARK_ENTRY_BYTES 96 /* 5 x 16 B + 8 B, padded */
-#define RTD_PARK_L_LDS_BYTES 56 /* a parked Lambert hit in LDS: strike 24, rng 16, colour, slot, bounces | inside << 31, object */
 enum { L_IDLE = 0, L_WALK = 1, L_DONE = 2, L_SLOW = 3, L_LAMB = 4, L_TEX = 5 };
 
 // LOG: the kernel may be asked to log rays (rt_scene_tune's probe): only the fused mode's instantiations carry that code -- the
@@ -1172,7 +1158,6 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
 
 // ---- ordering of the pass-B list: bucket sort of (cost, pixel) pairs, heaviest first -------------------------------------------
 // 64 buckets over rays per phase-1 sample (x4); order inside a bucket is arbitrary (it only changes which wave traces what).
-#define RTD_COST_BUCKETS 64
 RTD_INLINE uint32_t cost_bucket(unsigned long long pair, uint32_t n1) {
     const uint32_t cost = (uint32_t) (pair >> 32);
     const uint32_t b = (cost * 4u) / n1;

@@ -3,6 +3,7 @@
 // There is NO CPU fallback: every compute entry point returns RT_ERR_NO_DEVICE when no HIP device is visible.
 #include "../../include/rtfs_amd.h"
 #include "rt_device.h"
+#include "rt_launch_plan.h"
 #include "rt_render_kernel.h"
 #include "rt_scene.h"
 
@@ -93,9 +94,6 @@ struct DeviceScene {
     int32_t *obj_to_orig = nullptr; // HostScene::objToOrig (the ray-list hit queries answer in rt_scene_create's indices)
     int cu_count = 0;
 };
-// Per-launch scratch, stream-ordered (hipMallocAsync on the launch stream): counters[16] | queues | camera.  Nothing is
-// shared between launches, so any number of them may be in flight on any streams.
-#define RT_SCRATCH_BYTES 512
 
 struct rt_scene {
     rth::HostScene host;
@@ -144,12 +142,12 @@ static int device_scene(rt_scene *s, int device, DeviceScene **out) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// launch plan: ONE place decides block size, unit sizes, LDS residency and the number of passes -- the launch uses it and
-// rt_scene_get_info reports from it, so the two cannot disagree
+// launch plan: ONE place decides block size, unit sizes, LDS residency, the number of passes, the grids and the workspace sizes --
+// rt_launch_plan.h, plain C++ over plain integers (tests/test_launch_plan.py runs it on a CPU).  enqueue() launches what it lists
+// and rt_scene_get_info reports from it, so the two cannot disagree.  Here: only how its inputs are gathered.
 // ------------------------------------------------------------------------------------------------------------
-// LDS budget: 160 KiB per CU (MI355X_MICROARCH.md); the LDS part of the scene image plus every wave's scratch must fit one workgroup.
-#define RT_LDS_BYTES 163840u
-struct Settings { int block, chunk, blocks_per_cu, yield, refill, passes, park; };
+using rtp::Settings;
+using rtp::check_settings;
 static Settings resolve_settings(const rt_render_options *o) {
     rt_render_options v{};
     if (o) memcpy(&v, o, o->struct_size < sizeof(v) ? o->struct_size : sizeof(v));
@@ -163,70 +161,16 @@ static Settings resolve_settings(const rt_render_options *o) {
     s.park = v.park_lanes ? v.park_lanes : g_park_lanes.load();
     return s;
 }
-static const char *check_settings(const Settings &s) {
-    if (s.block != 0 && s.block != 256 && s.block != 512 && s.block != 768 && s.block != 1024) return "block_threads must be 0, 256, 512, 768 or 1024";
-    if (s.chunk < 0 || s.chunk > RTD_MAX_CHUNK) return "chunk_pixels must be in [0, 64]";
-    if (s.blocks_per_cu < 0 || s.blocks_per_cu > 8) return "blocks_per_cu must be in [0, 8]";
-    if (s.yield < 0 || s.yield > 64 || s.refill < 0 || s.refill > 64) return "thresholds must be in [0, 64]";
-    if (s.passes < 0 || s.passes > 2) return "passes must be 0 (auto), 1 (fused) or 2 (two-pass)";
-    if (s.park < -1 || s.park > RTD_MAX_PARK) return "park_lanes must be in [-1, 256]";
-    return nullptr;
+static rtp::SceneSize scene_size(const rth::HostScene &h) {
+    rtp::SceneSize sc;
+    sc.lds_total = h.off.lds_total; sc.lds32_total = h.off.lds32_total;
+    sc.n_nodes = h.off.n_nodes;
+    sc.n_objects = h.nBounded + h.nUnbounded;
+    sc.tex = !h.texRecs.empty();
+    return sc;
 }
-// `count`: the counting kernel variant stages the exact double-precision node records (112 B), the timed one the single-precision
-// filter records (64 B)
-static size_t lds_need(const rth::HostScene &h, bool lds, bool count, int block, int chunk, bool passA = false) {
-    return (lds ? (size_t) (count ? h.off.lds_total : h.off.lds32_total) : 0u) + (size_t) (block / 64) * (passA ? RTD_WAVE_WORDS_A(chunk) : RTD_WAVE_WORDS(chunk)) * 4u;
-}
-// The Lambert pool in LDS: as many 56-byte entries per wave as fit beside the scene and the waves' scratch, at most 64; with room
-// for fewer than 32 the pool stays in global memory (entries of RTD_PARK_ENTRY_BYTES, L2-resident at best).  Returns the capacity
-// and adds the pools' bytes to ldsBytes.
-static int lambert_pool_lds(size_t &ldsBytes, int block) {
-#ifdef RTD_NO_LDS_POOL
-    return 0;
-#endif
-    if (ldsBytes >= RT_LDS_BYTES) return 0;
-    const size_t waves = (size_t) block / 64u;
-    size_t c = (RT_LDS_BYTES - ldsBytes) / (waves * RTD_PARK_L_LDS_BYTES);
-    if (c > 64) c = 64;
-    c &= ~(size_t) 1; // an even capacity keeps every field array 16-byte aligned
-    if (c < 32) return 0;
-    ldsBytes += waves * RTD_PARK_L_LDS_BYTES * c;
-    return (int) c;
-}
-// The timed variant of a scene that is NOT LDS-resident keeps the first records of its depth-ordered node32 section in LDS
-// (stage_nodes32, node_loop_glb32): what fits beside the waves' scratch (`ldsBytes` on entry) and a full Lambert pool.  Returns
-// the bytes (a multiple of the record size; 0 for the counting variant, whose walk reads the exact records) and adds them.
-static uint32_t hybrid_node_bytes(const rth::HostScene &h, size_t &ldsBytes, bool lds, bool count, int block, bool pool) {
-#ifdef RTD_NO_HYBRID
-    return 0u;
-#endif
-    if (lds || count) return 0u;
-    const size_t poolBytes = pool ? (size_t) (block / 64) * RTD_PARK_L_LDS_BYTES * 64u : 0u; // (a pool of 48 measured the same, of 32 2 % slower)
-    if (ldsBytes + poolBytes + RTD_NODE32_BYTES > RT_LDS_BYTES) return 0u;
-    size_t room = (RT_LDS_BYTES - ldsBytes - poolBytes) & ~(size_t) (RTD_NODE32_BYTES - 1);
-    const size_t all = (size_t) h.off.n_nodes * RTD_NODE32_BYTES;
-    if (room > all) room = all;
-    ldsBytes += room;
-    return (uint32_t) room;
-}
-struct LaunchPlan {
-    int block = 1024, chunk = 16, park = 0;
-    bool lds = false;
-};
-// Block size and residency for a scene: LDS-resident if its image fits beside the waves' scratch at the preferred block, else the
-// global-memory variant of the kernel at the same block (whose timed form keeps the top of the tree in LDS: hybrid_node_bytes).
-// (Until round 3 a scene that fitted only beside the scratch of a 256-thread block was kept resident with such blocks: one wave
-// per SIMD -- 899 spheres, tuned: 25.1 ms against 12.3 ms for the global-memory variant at 1024 threads.)
-static LaunchPlan plan_launch(const rth::HostScene &h, const Settings &s, bool count = false) {
-    LaunchPlan p;
-    p.block = s.block ? s.block : 1024;
-    p.chunk = s.chunk ? s.chunk : 16;
-    p.park = s.park < 0 ? 0 : (s.park ? s.park : RTD_PARK_DEFAULT);
-    // (an LDS-resident scene has far fewer than the 16384 objects the node loop's 14-bit queue entries can name: 48 B each of 160 KiB)
-    auto fits = [&](int block, int chunk) { return h.nBounded + h.nUnbounded < 16384u && lds_need(h, true, count, block, chunk) <= RT_LDS_BYTES; };
-    if (fits(p.block, p.chunk)) p.lds = true;
-    return p; // (global-memory variant: the waves' scratch always fits)
-}
+// The decision a timed render with default options takes (rt_scene_info.lds_resident, the pixel_candidates hook)
+static bool default_lds_resident(const rth::HostScene &h) { return rtp::lds_resident(scene_size(h), resolve_settings(nullptr), false); }
 
 // ------------------------------------------------------------------------------------------------------------
 // launch
@@ -251,35 +195,56 @@ static int allow_full_lds(const void *fn) {
     try { done.insert({fn, device}); } catch (const std::bad_alloc &) {} // (set again next time)
     return RT_OK;
 }
-template <int MODE, bool TEX> static render_fn pick_mode(bool lds, bool count, int block) {
-    if (block == 1024) {
-        if (lds) return count ? render_kernel<true, true, 1024, MODE, TEX> : render_kernel<true, false, 1024, MODE, TEX>;
-        return count ? render_kernel<false, true, 1024, MODE, TEX> : render_kernel<false, false, 1024, MODE, TEX>;
-    }
-    if (block == 768) {
-        if (lds) return count ? render_kernel<true, true, 768, MODE, TEX> : render_kernel<true, false, 768, MODE, TEX>;
-        return count ? render_kernel<false, true, 768, MODE, TEX> : render_kernel<false, false, 768, MODE, TEX>;
-    }
-    if (block == 512) {
-        if (lds) return count ? render_kernel<true, true, 512, MODE, TEX> : render_kernel<true, false, 512, MODE, TEX>;
-        return count ? render_kernel<false, true, 512, MODE, TEX> : render_kernel<false, false, 512, MODE, TEX>;
-    }
-    if (lds) return count ? render_kernel<true, true, 256, MODE, TEX> : render_kernel<true, false, 256, MODE, TEX>;
-    return count ? render_kernel<false, true, 256, MODE, TEX> : render_kernel<false, false, 256, MODE, TEX>;
+// The SET of instantiated render_kernel<...> is part of the build (compile time, code size): the ray-list modes 4 and 5 exist for
+// blocks of 256 and 1024 threads only, and the hit queries (mode 5) shade nothing, so they have no textured variant.  The plan
+// never asks for one of the others; if it did, the launch fails (no kernel is substituted).
+template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX> static render_fn kernel_if_built() {
+    if constexpr ((MODE >= 4 && BLOCK != 256 && BLOCK != 1024) || (MODE == 5 && TEX)) return nullptr;
+    else return render_kernel<LDS, COUNT, BLOCK, MODE, TEX>;
+}
+template <int BLOCK, int MODE, bool TEX> static render_fn pick_variant(bool lds, bool count) {
+    if (lds) return count ? kernel_if_built<true, true, BLOCK, MODE, TEX>() : kernel_if_built<true, false, BLOCK, MODE, TEX>();
+    return count ? kernel_if_built<false, true, BLOCK, MODE, TEX>() : kernel_if_built<false, false, BLOCK, MODE, TEX>();
+}
+template <int MODE, bool TEX> static render_fn pick_mode(const rtp::Pass &q) {
+    return q.block == 1024 ? pick_variant<1024, MODE, TEX>(q.lds, q.count) : q.block == 768 ? pick_variant<768, MODE, TEX>(q.lds, q.count) :
+           q.block == 512  ? pick_variant<512, MODE, TEX>(q.lds, q.count)  : pick_variant<256, MODE, TEX>(q.lds, q.count);
 }
 // tex: the scene has parameterised textures (otherwise the variant compiled without the texture call: no scratch, no VGPR spills)
-static render_fn pick_kernel(bool lds, bool count, int block, int mode, bool tex) {
-    if (tex) return mode == 0 ? pick_mode<0, true>(lds, count, block) : (mode == 1 ? pick_mode<1, true>(lds, count, block) : (mode == 2 ? pick_mode<2, true>(lds, count, block) : pick_mode<3, true>(lds, count, block)));
-    return mode == 0 ? pick_mode<0, false>(lds, count, block) : (mode == 1 ? pick_mode<1, false>(lds, count, block) : (mode == 2 ? pick_mode<2, false>(lds, count, block) : pick_mode<3, false>(lds, count, block)));
+static render_fn pick_kernel(const rtp::Pass &q) {
+    switch (q.mode) {
+    case 0: return q.tex ? pick_mode<0, true>(q) : pick_mode<0, false>(q);
+    case 1: return q.tex ? pick_mode<1, true>(q) : pick_mode<1, false>(q);
+    case 2: return q.tex ? pick_mode<2, true>(q) : pick_mode<2, false>(q);
+    case 3: return q.tex ? pick_mode<3, true>(q) : pick_mode<3, false>(q);
+    case 4: return q.tex ? pick_mode<4, true>(q) : pick_mode<4, false>(q);
+    default: return q.tex ? nullptr : pick_mode<5, false>(q);
+    }
 }
+
+// Per-launch scratch, stream-ordered (hipMallocAsync on the launch stream), RT_SCRATCH_BYTES of it; the launch's workspace (pass B's
+// list, the park pools) follows.  The kernels reach it through RenderParams' pointers and index `counters` past its sixteen
+// words (counters[20..31] is `stage`), so every member is pinned to the byte offset they use.
+struct LaunchScratch {
+    unsigned long long counters[16]; // rays, aabb, prim, refl, samples, pixels_early, -, first wave start; [8..13] stage executions, [14] wave lifetimes, [15] last wave end
+    unsigned int queue, pad0;        // RenderParams::queue: next work unit of the fused kernel / pass A, next run of a ray list
+    unsigned long long queue_b;      // pass B: next unassigned list entry
+    unsigned int live_count, pad1[3]; // pass A -> B: number of pairs / list entries
+    unsigned long long stage[12];    // counters[20..31]: slow stages, lanes in them, lanes parked, cycles in refill / slow / walk / shade;
+                                     // diagnostic builds (RTD_STAGE_CLOCKS): cycles in loop / leaf / unbounded / new items / lambert
+    CameraParams cam;                // RenderParams::cam_ptr
+};
+static_assert(offsetof(LaunchScratch, queue) == 128 && offsetof(LaunchScratch, queue_b) == 136 && offsetof(LaunchScratch, live_count) == 144, "queues");
+static_assert(offsetof(LaunchScratch, stage) == 20 * sizeof(unsigned long long) && offsetof(LaunchScratch, stage) == 160, "stage counters are counters[20..31]");
+static_assert(offsetof(LaunchScratch, cam) == 256 && sizeof(LaunchScratch) <= RT_SCRATCH_BYTES, "camera must fit the scratch slot");
 
 // Zeroes a launch's counters and queues and writes its camera: one tiny launch instead of a memset plus a copy from
 // pageable host memory (which may block the host until earlier work on the stream has finished).
 __global__ void launch_init_kernel(unsigned char *scratch, const CameraParams cam) {
-    if (threadIdx.x < 64) ((unsigned int *) scratch)[threadIdx.x] = 0u; // 256 B: counters[16], queue, queue_b, live_count
-    if (threadIdx.x == 0) *(CameraParams *) (scratch + 256) = cam;
+    if (threadIdx.x < (unsigned) (offsetof(LaunchScratch, cam) / 4)) ((unsigned int *) scratch)[threadIdx.x] = 0u; // everything in front of the camera
+    if (threadIdx.x == 0) *(CameraParams *) (scratch + offsetof(LaunchScratch, cam)) = cam;
 }
-static_assert(sizeof(CameraParams) <= RT_SCRATCH_BYTES - 256, "camera must fit the scratch slot");
+static_assert(offsetof(LaunchScratch, cam) / 4 <= 64, "launch_init_kernel runs 64 threads");
 
 extern "C" {
 
@@ -353,18 +318,18 @@ int rt_set_walk_tree(int32_t kind) {
     return RT_OK;
 }
 int rt_set_passes(int32_t passes) {
-    if (passes < 0 || passes > 2) return fail(RT_ERR_INVALID_ARGUMENT, "passes must be 0 (auto), 1 (fused) or 2 (two-pass)");
+    if (const char *m = check_settings(Settings{0, 0, 0, 0, 0, passes, 0})) return fail(RT_ERR_INVALID_ARGUMENT, m);
     g_passes = passes;
     return RT_OK;
 }
 int rt_set_park(int32_t park_lanes) {
-    if (park_lanes < -1 || park_lanes > RTD_MAX_PARK) return fail(RT_ERR_INVALID_ARGUMENT, "park_lanes must be in [-1, 256]");
+    if (const char *m = check_settings(Settings{0, 0, 0, 0, 0, 0, park_lanes})) return fail(RT_ERR_INVALID_ARGUMENT, m);
     g_park_lanes = park_lanes;
     return RT_OK;
 }
 
 int rt_set_schedule(int32_t yield_lanes, int32_t refill_lanes) {
-    if (yield_lanes < 0 || yield_lanes > 64 || refill_lanes < 0 || refill_lanes > 64) return fail(RT_ERR_INVALID_ARGUMENT, "thresholds must be in [0, 64]");
+    if (const char *m = check_settings(Settings{0, 0, 0, yield_lanes, refill_lanes, 0, 0})) return fail(RT_ERR_INVALID_ARGUMENT, m);
     g_yield_lanes = yield_lanes;
     g_refill_lanes = refill_lanes;
     return RT_OK;
@@ -425,7 +390,7 @@ int rt_scene_get_info(const rt_scene *s, rt_scene_info *out) {
     out->walk_tree = h.walkKind;
     out->walk_tree_depth = h.walkTree.depth;
     out->n_textures = (int32_t) h.texRecs.size();
-    out->lds_resident = plan_launch(h, resolve_settings(nullptr)).lds ? 1 : 0; // the decision a render with default options takes
+    out->lds_resident = default_lds_resident(h) ? 1 : 0; // the decision a render with default options takes
     out->scene_bytes = (int64_t) h.off.total;
     out->texel_bytes = (int64_t) h.texelBlob.size();
     return RT_OK;
@@ -485,10 +450,10 @@ static int check_geometry(const rt_camera *camera, int32_t max_w, int32_t max_h,
 
 } // extern "C"
 
-// What a launch leaves behind when its statistics are wanted: events around the kernels and the launch's scratch, which
-// then stays allocated until the counters have been read.
 struct RayLog { double *rays; unsigned int *count; uint32_t cap, mask; }; // rt_scene_tune's probe (RenderParams::ray_log)
 
+// What a launch leaves behind when its statistics are wanted: events around the kernels and the launch's scratch, which
+// then stays allocated until the counters have been read.
 struct Pending {
     hipEvent_t a = nullptr, b = nullptr;
     unsigned char *scr = nullptr;
@@ -506,21 +471,39 @@ struct Pending {
     ~Pending() { release(); }
 };
 
-// Enqueues one shard's render on `stream`; never waits for the device.  With want_stats the launch is bracketed by events
-// and its scratch is kept in `pd` for collect_stats.
-static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
-                         int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
-                         const rt_render_options *options, bool want_stats, Pending &pd, const RayLog *log = nullptr) {
-    rt_stats *stats = want_stats ? (rt_stats *) 1 : nullptr; // only tested for NULL below
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    int rc = check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows);
-    if (rc != RT_OK) return rc;
-    if (n_rows > 0 && !d_accum) return fail(RT_ERR_INVALID_ARGUMENT, "d_accum is NULL");
-    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
-    const Settings set = resolve_settings(options);
-    if (const char *m = check_settings(set)) return fail(RT_ERR_INVALID_ARGUMENT, m);
+static CameraParams camera_params(const rt_camera *camera, int32_t max_w, int32_t max_h) {
+    CameraParams c{};
+    for (int a = 0; a < 3; ++a) {
+        c.eye[a] = camera->view_origin[a];
+        c.xo[a] = camera->xaxis_origin[a];
+        c.xd[a] = camera->xaxis_dir[a];
+        c.yd[a] = camera->yaxis_dir[a];
+    }
+    c.vw = camera->viewport_width;
+    c.vh = camera->viewport_height;
+    c.max_w = max_w; c.max_h = max_h;
+    c.spp = camera->samples_per_pixel;
+    c.depth = camera->bounce_depth;
+    return c;
+}
+static void set_plan_fields(RenderParams &p, const rtp::Pass &q) {
+    p.chunk = q.chunk;
+    p.park = q.park; p.park_l = q.park_l; p.park_l_lds = q.park_l_lds;
+    p.lds_node_bytes = q.lds_node_bytes; p.lds_node_thr = q.lds_node_thr;
+    p.yield_lanes = q.yield_lanes; p.leaf_wait = q.leaf_wait; p.refill_lanes = q.refill_lanes;
+    p.k = q.k;
+    p.total_waves = q.total_waves;
+}
+
+// The one enqueue path of frames and ray lists (arguments checked, settings valid): plans the launch, takes its scratch and workspace
+// from the stream's pool, launches what the plan lists -- one kernel, or pass A, the three sort kernels and pass B -- and never waits
+// for the device.  `p` arrives with the caller's own fields filled (camera and rows and buffers, or the ray list's pointers); the
+// scene's and the plan's are set here.  With want_stats the launch is bracketed by events and its scratch is kept in `pd` for
+// collect_stats.
+static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, const Settings &set, uint32_t flags, void *stream, RenderParams p,
+                   const CameraParams &cam, bool want_stats, Pending &pd) {
     DeviceGuard guard;
-    rc = guard.enter(device);
+    int rc = guard.enter(device);
     if (rc != RT_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     DeviceScene *ds = nullptr;
@@ -528,191 +511,126 @@ static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t
     if (rc != RT_OK) return rc;
     const rth::HostScene &h = scene->host;
     hipStream_t st = (hipStream_t) stream;
-
-    const bool count = (flags & RT_RENDER_COUNTERS) != 0;
-    const LaunchPlan plan = plan_launch(h, set, count);
-    const int block = plan.block;
-    const bool lds = plan.lds;
-    // Units of the fused kernel: 16 pixels -- except for frames of few samples per pixel (always fused: the two-pass rule below needs
-    // at least 64 samples in phase 2).  A unit is drained before the next, and one of 16 pixels x 11 samples is three rounds of a wave that
-    // then waits for its longest path: as wide as still leaves a wave seven units, the scene in LDS permitting (2401x1601 px:
-    // 4 spp 8.5 -> 16.0 Gray/s, 16 spp 12.3 -> 19.6 with 64 pixels; 1201x801: 7.0 -> 9.3, 10.5 -> 12.5 with 32).
-    int chunk = plan.chunk;
-    if (!set.chunk && set.passes != 2 && camera->samples_per_pixel <= 74) { // (below the two-pass rule's 64 samples in phase 2)
-        const uint64_t px = (uint64_t) n_rows * (uint64_t) (2 * max_w + 1), waves = (uint64_t) ds->cu_count * (uint64_t) (block / 64);
-        for (int c = 64; c > chunk; c /= 2)
-            if (px >= 7ull * (uint64_t) c * waves && (!lds || lds_need(h, true, count, block, c) <= RT_LDS_BYTES)) { chunk = c; break; }
-    }
-
-    RenderParams p{};
-    CameraParams hostCam{};
-    for (int a = 0; a < 3; ++a) {
-        hostCam.eye[a] = camera->view_origin[a];
-        hostCam.xo[a] = camera->xaxis_origin[a];
-        hostCam.xd[a] = camera->xaxis_dir[a];
-        hostCam.yd[a] = camera->yaxis_dir[a];
-    }
-    hostCam.vw = camera->viewport_width;
-    hostCam.vh = camera->viewport_height;
-    hostCam.max_w = max_w; hostCam.max_h = max_h;
-    hostCam.spp = camera->samples_per_pixel;
-    hostCam.depth = camera->bounce_depth;
-    p.max_w = max_w; p.max_h = max_h;
-    p.spp = camera->samples_per_pixel;
-    p.depth = camera->bounce_depth;
     p.off = h.off;
     p.scene_image = ds->image;
     p.tex = ds->tex;
     p.texels = ds->texels;
-    p.seed_key = mix64(seed + 0x9E3779B97F4A7C15ull); // seed_key(), host side
-    p.cols = 2 * max_w + 1;
-    p.row_first = row_first; p.row_stride = row_stride; p.n_rows = n_rows;
-    const int half = camera->samples_per_pixel / 2;
-    p.k = half < 5 ? half : 5; // min 5 (spp / 2), Scene.fs:172
-    p.chunk = chunk;
-    p.park = plan.park;
-    p.park_l = plan.park > 0 ? RTD_PARK_L_DEFAULT : 0; // the Lambert pool rides with the general one ("never park" switches both off)
-    p.yield_lanes = set.yield ? set.yield : RTD_YIELD_DEFAULT;
-    // the node loop runs on a little past the point where the STAGE would yield before it hands over to a leaf pass: fewer, fuller
-    // leaf passes (measured on the bench frame, yield / hand-over: 52/52 110.9 ms, 52/56 109.9, 50/55 109.5, 48/56 109.5, 50/58 110.4)
-    p.leaf_wait = p.yield_lanes + RTD_LEAF_WAIT_EXTRA > 64 ? 64 : p.yield_lanes + RTD_LEAF_WAIT_EXTRA;
-    p.refill_lanes = set.refill ? set.refill : RTD_REFILL_DEFAULT;
-    p.accum = (int32_t *) d_accum;
-    p.rgb = (uint8_t *) d_rgb;
-    if (log) { p.ray_log = log->rays; p.ray_log_count = log->count; p.ray_log_cap = log->cap; p.ray_log_mask = log->mask; }
+    p.obj_to_orig = ds->obj_to_orig; // (read by the hit queries only)
 
-    const bool tex = !h.texRecs.empty();
-    render_fn fn = pick_kernel(lds, count, block, log ? 3 : 0, tex); // (the ray log of rt_scene_tune's probe: a kernel of its own)
-    size_t ldsBytes = lds_need(h, lds, count, block, chunk);
-    p.lds_node_bytes = (int32_t) hybrid_node_bytes(h, ldsBytes, lds, count, block, p.park_l > 0);
-    p.lds_node_thr = RTD_HYBRID_LANES;
-    if (p.park_l > 0) { // the fused launch's Lambert pool: in LDS if it fits (the two-pass launches decide for themselves below)
-        const int cl = lambert_pool_lds(ldsBytes, block);
-        if (cl) { p.park_l = cl; p.park_l_lds = 1; }
-    }
+    rtp::LaunchPlan plan = rtp::plan_begin(scene_size(h), set, (flags & RT_RENDER_COUNTERS) != 0, job, ds->cu_count);
+    const int block = plan.one.block;
+    const size_t ldsBytes = plan.one.lds_bytes;
+    render_fn fn = pick_kernel(plan.one);
+    if (!fn) return fail(RT_ERR_HIP, "no kernel is built for this launch");
     rc = allow_full_lds((const void *) fn);
     if (rc != RT_OK) return rc;
+    // the one device answer the plan needs: asked once, for the fused (or ray-list) kernel at its own LDS size; both passes of a
+    // two-pass launch use the grid that follows from it
     int perCu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *) fn, block, ldsBytes));
-    if (perCu < 1) return fail(RT_ERR_HIP, "render kernel does not fit on a CU (occupancy 0)");
-    if (set.blocks_per_cu > 0 && set.blocks_per_cu < perCu) perCu = set.blocks_per_cu;
-    const uint64_t nLocal = (uint64_t) n_rows * (uint64_t) p.cols;
-    const uint64_t units = (nLocal + (uint64_t) chunk - 1) / (uint64_t) chunk;
-    const uint64_t fullGrid = (uint64_t) ds->cu_count * (uint64_t) perCu;
-    uint64_t grid = fullGrid;
-    const uint64_t wavesPerBlock = (uint64_t) block / 64u;
-    const uint64_t needBlocks = (units + wavesPerBlock - 1) / wavesPerBlock;
-    if (grid > needBlocks) grid = needBlocks;
-    // Few units per wave => the fused kernel ends with most waves waiting for a few long units (a 16-pixel unit on a glass sphere
-    // takes tens of ms): render in two passes with the second one ordered longest-job-first.  Many units per wave => the fused
-    // kernel's tail is ~2 % and it saves the second launch (break-even measured at ~60 units per wave: config 3 whole, 59 per wave,
-    // 221 ms in two passes against 227 ms fused; config 4 whole, 507 per wave, 3.75 s against 3.66 s).  spp <= 2k+1 has no second phase at all, and with few remaining samples
-    // per pixel a unit is short, so is the tail, and the second launch costs more than it removes (config 2, 100 spp: fused 3.0 ms,
-    // two passes 3.5 ms; config 3's 1/8 shard, 500 spp: 51 ms against 30 ms).
-    const int n2 = camera->samples_per_pixel - 2 * p.k - 1;
-    const bool twoPass = n2 > 0 && nLocal > 0 && nLocal < (1ull << 32) &&
-                         (set.passes == 2 || (set.passes == 0 && (n2 >= 128 || (n2 >= 64 && nLocal >= (1ull << 21))) && units < 64ull * fullGrid * wavesPerBlock));
-    // (frames of 2 Mpx and more pay for the second launch from ~75 spp: 2401x1601 at 100 spp 23.1 Gray/s fused, 26.9 in two passes; 1201x801: 19.6 / 19.8)
+    if (perCu < 1) return fail(RT_ERR_HIP, job.kind == rtp::Job::FRAME ? "render kernel does not fit on a CU (occupancy 0)" : "ray-list kernel does not fit on a CU (occupancy 0)");
+    rtp::plan_finish(plan, perCu);
+    const uint64_t grid = plan.one.grid;
+    const size_t pairsBytes = plan.pairs_bytes, listBytes = plan.list_bytes, sortBytes = plan.sort_bytes, poolBytes = plan.pool_bytes;
 
     // Everything below is stream-ordered: scratch and workspace come from the stream's pool and go back to it after the last
     // launch that uses them, so no launch shares state with another and the call returns without waiting for the device.
-    const size_t pairsBytes = twoPass ? (((size_t) nLocal * 8u + 15u) & ~(size_t) 15u) : 0u, listBytes = twoPass ? (((size_t) nLocal * 4u + 15u) & ~(size_t) 15u) : 0u;
-    const size_t sortBytes = twoPass ? (3u * RTD_COST_BUCKETS * 4u + 15u) & ~(size_t) 15u : 0u;
-    const size_t poolBytes = (size_t) (twoPass ? fullGrid : grid) * (size_t) wavesPerBlock * (size_t) RTD_PARK_ENTRY_BYTES *
-                             (size_t) (p.park + (p.park > 0 ? RTD_PARK_L_DEFAULT : 0) + (tex ? p.park : 0)); // general + Lambert (unless in LDS) + textured
     unsigned char *scr = nullptr;
-    if (grid > 0 || stats) HIP_TRY(hipMallocAsync((void **) &scr, RT_SCRATCH_BYTES + pairsBytes + listBytes + sortBytes + poolBytes, st));
+    if (grid > 0 || want_stats) HIP_TRY(hipMallocAsync((void **) &scr, RT_SCRATCH_BYTES + pairsBytes + listBytes + sortBytes + poolBytes, st));
     Pending &cl = pd; // on every exit path its destructor (or collect_stats) gives the scratch back
     cl.scr = scr; cl.st = st; cl.device = device; cl.t0 = t0;
-    cl.pixels = nLocal;
-    cl.waves = (twoPass ? fullGrid : grid) * wavesPerBlock;
-    if (stats) {
+    cl.pixels = plan.pixels;
+    cl.waves = plan.waves;
+    if (want_stats) {
         HIP_TRY(hipEventCreate(&cl.a));
         HIP_TRY(hipEventCreate(&cl.b));
     }
-    unsigned char *ws = scr ? scr + RT_SCRATCH_BYTES : nullptr;
-    p.counters = (unsigned long long *) scr;
-    p.queue = (unsigned int *) (scr + 128);
-    p.cam_ptr = (const CameraParams *) (scr + 256);
-    p.park_pool = ws ? ws + pairsBytes + listBytes + sortBytes : nullptr;
     if (scr) {
-        hipLaunchKernelGGL(launch_init_kernel, dim3(1), dim3(64), 0, st, scr, hostCam);
+        LaunchScratch *ls = (LaunchScratch *) scr;
+        p.counters = ls->counters;
+        p.queue = &ls->queue;
+        p.queue_b = &ls->queue_b;
+        p.live_count = &ls->live_count;
+        p.cam_ptr = &ls->cam;
+        p.park_pool = scr + RT_SCRATCH_BYTES + pairsBytes + listBytes + sortBytes;
+        hipLaunchKernelGGL(launch_init_kernel, dim3(1), dim3(64), 0, st, scr, cam);
         HIP_TRY(hipGetLastError());
     }
     if (grid > 0) {
-        if (stats) HIP_TRY(hipEventRecord(cl.a, st));
-        if (!twoPass) {
+        if (want_stats) HIP_TRY(hipEventRecord(cl.a, st));
+        if (!plan.two_pass) {
+            set_plan_fields(p, plan.one);
             hipLaunchKernelGGL(fn, dim3((unsigned) grid), dim3((unsigned) block), ldsBytes, st, p);
             HIP_TRY(hipGetLastError());
         } else {
             // workspace: pairs[nLocal] u64, list[nLocal] u32, hist/offsets/cursor[64] u32
+            unsigned char *ws = scr + RT_SCRATCH_BYTES;
             unsigned int *sortBuf = (unsigned int *) (ws + pairsBytes + listBytes);
             HIP_TRY(hipMemsetAsync(sortBuf, 0, sortBytes, st));
             p.pairs = (unsigned long long *) ws;
             p.live_list = (const unsigned int *) (ws + pairsBytes);
-            p.queue_b = (unsigned long long *) (scr + 136);
-            p.live_count = (unsigned int *) (scr + 144);
-            p.total_waves = (uint32_t) (fullGrid * wavesPerBlock);
-            render_fn fa = pick_kernel(lds, count, block, 1, tex), fb = pick_kernel(lds, count, block, 2, tex);
-            // Unit sizes: pass A traces only 2k+1 samples per pixel, so its units are wide (below); pass B's largest unit is about a
-            // sixteenth of a wave's share of the shard (measured best: 32 px at 1/2 frame, 16 at 1/4, 8 at 1/8 of config 3),
-            // and shrinks towards the end of the cost-ordered list.
-            int chunkA = set.chunk ? set.chunk : 64, chunkB = set.chunk ? set.chunk : 4;
-            if (!set.chunk) {
-                // pass A drains every unit before the next (its last paths run with most lanes idle), so wide units pay -- as long as a
-                // wave still gets seven or so of them (measured: whole frame 64 px 5.4 ms, 32 px 6.2, 16 px 8.2; an eighth: 16 px best)
-                while (chunkA > 8 && nLocal < 7ull * (uint64_t) chunkA * fullGrid * wavesPerBlock) chunkA /= 2;
-                const uint64_t share = nLocal / (fullGrid * wavesPerBlock * 16u);
-                while (chunkB < 32 && (uint64_t) chunkB * 3u / 2u <= share) chunkB *= 2; // nearest power of two
-            }
-            // both passes must fit the LDS beside the scene image, decided BEFORE anything is launched (a misfit found after
-            // pass A would leave a half-rendered buffer); 
-            while (lds && chunkA > 1 && lds_need(h, true, count, block, chunkA, true) > RT_LDS_BYTES) chunkA /= 2;
-            while (lds && chunkB > 1 && lds_need(h, true, count, block, chunkB) > RT_LDS_BYTES) chunkB /= 2;
-            if (lds && plan.park > 0 && !set.chunk) { // ... and not so wide that the Lambert pool no longer fits beside them
-                auto pool_fits = [&](int c) { size_t b = lds_need(h, true, count, block, c, true); return lambert_pool_lds(b, block) != 0; };
-                while (chunkA > 16 && !pool_fits(chunkA) && pool_fits(chunkA / 2)) chunkA /= 2;
-            }
-            size_t ldsA = lds_need(h, lds, count, block, chunkA, true), ldsB = lds_need(h, lds, count, block, chunkB);
-            if (lds && (ldsA > RT_LDS_BYTES || ldsB > RT_LDS_BYTES)) return fail(RT_ERR_HIP, "two-pass launch does not fit the LDS");
-            const uint32_t hybA = hybrid_node_bytes(h, ldsA, lds, count, block, plan.park > 0), hybB = hybrid_node_bytes(h, ldsB, lds, count, block, plan.park > 0);
-            int clA = 0, clB = 0;
-            if (plan.park > 0) { clA = lambert_pool_lds(ldsA, block); clB = lambert_pool_lds(ldsB, block); }
+            // both passes fit the LDS beside the scene image or nothing is launched (a misfit found after pass A would leave a
+            // half-rendered buffer)
+            if (plan.error) return fail(RT_ERR_HIP, plan.error);
+            render_fn fa = pick_kernel(plan.a), fb = pick_kernel(plan.b);
+            if (!fa || !fb) return fail(RT_ERR_HIP, "no kernel is built for this launch");
             if ((rc = allow_full_lds((const void *) fa)) != RT_OK || (rc = allow_full_lds((const void *) fb)) != RT_OK) return rc;
             RenderParams pa = p;
-            pa.chunk = chunkA;
-            pa.lds_node_bytes = (int32_t) hybA; p.lds_node_bytes = (int32_t) hybB;
-            pa.park_l = clA ? clA : (plan.park > 0 ? RTD_PARK_L_DEFAULT : 0); pa.park_l_lds = clA ? 1 : 0;
-            p.park_l = clB ? clB : (plan.park > 0 ? RTD_PARK_L_DEFAULT : 0); p.park_l_lds = clB ? 1 : 0;
-            const uint64_t unitsA = (nLocal + (uint64_t) chunkA - 1) / (uint64_t) chunkA;
-            uint64_t gridA = (unitsA + wavesPerBlock - 1) / wavesPerBlock;
-            if (gridA > fullGrid) gridA = fullGrid;
-            hipLaunchKernelGGL(fa, dim3((unsigned) gridA), dim3((unsigned) block), ldsA, st, pa);
-            p.chunk = chunkB;
-            hipLaunchKernelGGL(sort_hist_kernel, dim3(256), dim3(256), 0, st, (const unsigned long long *) p.pairs, (const unsigned int *) p.live_count,
-                               (uint32_t) (2 * p.k + 1), sortBuf);
+            set_plan_fields(pa, plan.a);
+            set_plan_fields(p, plan.b);
+            const uint32_t n1 = (uint32_t) (2 * p.k + 1);
+            hipLaunchKernelGGL(fa, dim3((unsigned) plan.a.grid), dim3((unsigned) block), plan.a.lds_bytes, st, pa);
+            hipLaunchKernelGGL(sort_hist_kernel, dim3(256), dim3(256), 0, st, (const unsigned long long *) p.pairs, (const unsigned int *) p.live_count, n1, sortBuf);
             hipLaunchKernelGGL(sort_offsets_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) sortBuf, sortBuf + RTD_COST_BUCKETS);
-            hipLaunchKernelGGL(sort_scatter_kernel, dim3(256), dim3(256), 0, st, (const unsigned long long *) p.pairs, (const unsigned int *) p.live_count,
-                               (uint32_t) (2 * p.k + 1), (const unsigned int *) (sortBuf + RTD_COST_BUCKETS), sortBuf + 2 * RTD_COST_BUCKETS,
-                               (unsigned int *) (ws + pairsBytes));
-            hipLaunchKernelGGL(fb, dim3((unsigned) fullGrid), dim3((unsigned) block), ldsB, st, p);
+            hipLaunchKernelGGL(sort_scatter_kernel, dim3(256), dim3(256), 0, st, (const unsigned long long *) p.pairs, (const unsigned int *) p.live_count, n1,
+                               (const unsigned int *) (sortBuf + RTD_COST_BUCKETS), sortBuf + 2 * RTD_COST_BUCKETS, (unsigned int *) (ws + pairsBytes));
+            hipLaunchKernelGGL(fb, dim3((unsigned) plan.b.grid), dim3((unsigned) block), plan.b.lds_bytes, st, p);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("two-pass launch: ") + hipGetErrorString(e));
         }
-        if (stats) HIP_TRY(hipEventRecord(cl.b, st));
+        if (want_stats) HIP_TRY(hipEventRecord(cl.b, st));
     }
     cl.launched = grid > 0;
-    if (!stats) cl.release();
+    if (!want_stats) cl.release();
     return RT_OK;
+}
+
+// Enqueues one shard's render on `stream`: the argument checks and the frame's own RenderParams fields, then enqueue().
+static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
+                         int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
+                         const rt_render_options *options, bool want_stats, Pending &pd, const RayLog *log = nullptr) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    int rc = check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows);
+    if (rc != RT_OK) return rc;
+    if (n_rows > 0 && !d_accum) return fail(RT_ERR_INVALID_ARGUMENT, "d_accum is NULL");
+    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
+    const Settings set = resolve_settings(options);
+    if (const char *m = check_settings(set)) return fail(RT_ERR_INVALID_ARGUMENT, m);
+
+    RenderParams p{};
+    p.max_w = max_w; p.max_h = max_h;
+    p.spp = camera->samples_per_pixel;
+    p.depth = camera->bounce_depth;
+    p.seed_key = mix64(seed + 0x9E3779B97F4A7C15ull); // seed_key(), host side
+    p.cols = 2 * max_w + 1;
+    p.row_first = row_first; p.row_stride = row_stride; p.n_rows = n_rows;
+    p.accum = (int32_t *) d_accum;
+    p.rgb = (uint8_t *) d_rgb;
+    if (log) { p.ray_log = log->rays; p.ray_log_count = log->count; p.ray_log_cap = log->cap; p.ray_log_mask = log->mask; }
+    rtp::Job job;
+    job.kind = rtp::Job::FRAME;
+    job.n_rows = (uint64_t) n_rows; job.max_w = max_w; job.spp = camera->samples_per_pixel;
+    job.ray_log = log != nullptr;
+    return enqueue(scene, device, job, set, flags, stream, p, camera_params(camera, max_w, max_h), want_stats, pd);
 }
 
 // Waits for the launch's stream and reads its counters (the device of the launch must be current).
 static int collect_stats(Pending &pd, rt_stats *stats) {
     HIP_TRY(hipStreamSynchronize(pd.st));
-    unsigned long long c[32] = {0};
+    unsigned long long c[32] = {0}; // LaunchScratch: counters[16], then stage[12]
     if (pd.scr) {
-        HIP_TRY(hipMemcpy(c, pd.scr, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(c + 16, pd.scr + 160, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c, pd.scr + offsetof(LaunchScratch, counters), sizeof(LaunchScratch::counters), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c + 16, pd.scr + offsetof(LaunchScratch, stage), sizeof(LaunchScratch::stage), hipMemcpyDeviceToHost));
     }
 #ifdef RTD_STAGE_CLOCKS
     if (getenv("RTFS_STAGE_CLOCKS")) // diagnostic build: the finer clocks of rt_render_kernel.h's StageStats
@@ -977,21 +895,6 @@ int rt_render(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int
 // ------------------------------------------------------------------------------------------------------------
 // ray lists: the caller's rays through Scene.traceRay / Scene.hitObject (render_kernel MODE 4 / MODE 5, run_rays)
 // ------------------------------------------------------------------------------------------------------------
-// 24 instantiations: blocks of 256 or 1024 threads only (a launch asking for 512 or 768 runs at 1024: the block size never changes
-// a result); the hit queries shade nothing, so they have no textured variant.
-template <int MODE, bool TEX> static render_fn pick_rays_mode(bool lds, bool count, int block) {
-    if (block == 256) {
-        if (lds) return count ? render_kernel<true, true, 256, MODE, TEX> : render_kernel<true, false, 256, MODE, TEX>;
-        return count ? render_kernel<false, true, 256, MODE, TEX> : render_kernel<false, false, 256, MODE, TEX>;
-    }
-    if (lds) return count ? render_kernel<true, true, 1024, MODE, TEX> : render_kernel<true, false, 1024, MODE, TEX>;
-    return count ? render_kernel<false, true, 1024, MODE, TEX> : render_kernel<false, false, 1024, MODE, TEX>;
-}
-static render_fn pick_rays(bool hit, bool tex, bool lds, bool count, int block) {
-    if (hit) return pick_rays_mode<5, false>(lds, count, block);
-    return tex ? pick_rays_mode<4, true>(lds, count, block) : pick_rays_mode<4, false>(lds, count, block);
-}
-
 struct RayJob {
     bool hit;            // MODE 5 (hit queries) or MODE 4 (paths)
     size_t n;
@@ -1018,94 +921,25 @@ static int check_rays(const rt_scene *scene, size_t n, const void *rays, const v
     return RT_OK;
 }
 
-// Enqueues one ray-list launch on `stream` (n > 0, arguments checked); as launch_render: never waits, scratch from the stream's
-// pool, events and scratch kept in `pd` when statistics are wanted.  Placement (LDS, hybrid or global) is the render's decision.
+// Enqueues one ray-list launch on `stream` (n > 0, arguments checked by check_rays): the list's own RenderParams fields, then
+// enqueue().  Placement (LDS, hybrid or global) is the render's decision.
 static int launch_rays(const rt_scene *scene, int32_t device, const RayJob &job, uint32_t flags, void *stream, const rt_render_options *options,
                        bool want_stats, Pending &pd) {
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    DeviceScene *ds = nullptr;
-    rc = device_scene(const_cast<rt_scene *>(scene), device, &ds);
-    if (rc != RT_OK) return rc;
-    const rth::HostScene &h = scene->host;
-    hipStream_t st = (hipStream_t) stream;
-    const Settings set = resolve_settings(options);
-    const bool count = (flags & RT_RENDER_COUNTERS) != 0;
-    const LaunchPlan plan = plan_launch(h, set, count);
-    const bool lds = plan.lds;
-    const int block = plan.block == 256 ? 256 : 1024;
-
     RenderParams p{};
-    p.off = h.off;
-    p.scene_image = ds->image;
-    p.tex = ds->tex;
-    p.texels = ds->texels;
     p.seed_key = mix64(job.seed + 0x9E3779B97F4A7C15ull); // seed_key(), host side: the render's keying of (pixel, sample)
     p.depth = job.depth;
-    p.chunk = set.chunk ? set.chunk : RTD_MAX_CHUNK; // rays per run of the queue (a wave takes as many runs at once as it has idle lanes)
-    p.park = job.hit ? 0 : plan.park;
-    p.park_l = p.park > 0 ? RTD_PARK_L_DEFAULT : 0;
-    p.yield_lanes = set.yield ? set.yield : RTD_YIELD_DEFAULT;
-    p.leaf_wait = p.yield_lanes + RTD_LEAF_WAIT_EXTRA > 64 ? 64 : p.yield_lanes + RTD_LEAF_WAIT_EXTRA;
-    p.refill_lanes = set.refill ? set.refill : RTD_REFILL_DEFAULT;
     p.rays = (const double *) job.rays;
     p.ray_rng = (uint32_t *) job.rng;
     p.ray_colour = (uint8_t *) job.colour;
     p.ray_hit = (int32_t *) job.hit_index;
     p.ray_strike = (double *) job.strike;
-    p.obj_to_orig = ds->obj_to_orig;
     p.ray_n = job.n;
     p.ray_base = job.stream_base;
     p.ray_sample = job.sample;
-
-    const bool tex = !job.hit && !h.texRecs.empty();
-    render_fn fn = pick_rays(job.hit, tex, lds, count, block);
-    size_t ldsBytes = lds ? (size_t) (count ? h.off.lds_total : h.off.lds32_total) : 0u; // no per-wave scratch in these modes
-    p.lds_node_bytes = (int32_t) hybrid_node_bytes(h, ldsBytes, lds, count, block, p.park_l > 0);
-    p.lds_node_thr = RTD_HYBRID_LANES;
-    if (p.park_l > 0) {
-        const int cl = lambert_pool_lds(ldsBytes, block);
-        if (cl) { p.park_l = cl; p.park_l_lds = 1; }
-    }
-    rc = allow_full_lds((const void *) fn);
-    if (rc != RT_OK) return rc;
-    int perCu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *) fn, block, ldsBytes));
-    if (perCu < 1) return fail(RT_ERR_HIP, "ray-list kernel does not fit on a CU (occupancy 0)");
-    if (set.blocks_per_cu > 0 && set.blocks_per_cu < perCu) perCu = set.blocks_per_cu;
-    const uint64_t wavesPerBlock = (uint64_t) block / 64u;
-    const uint64_t wavesWanted = ((uint64_t) job.n + 63u) / 64u; // a wave's worth of rays each, at least
-    uint64_t grid = (uint64_t) ds->cu_count * (uint64_t) perCu;
-    const uint64_t needBlocks = (wavesWanted + wavesPerBlock - 1) / wavesPerBlock;
-    if (grid > needBlocks) grid = needBlocks;
-
-    const size_t poolBytes = (size_t) grid * (size_t) wavesPerBlock * (size_t) RTD_PARK_ENTRY_BYTES *
-                             (size_t) (p.park + (p.park > 0 ? RTD_PARK_L_DEFAULT : 0) + (tex ? p.park : 0)); // as launch_render's
-    unsigned char *scr = nullptr;
-    HIP_TRY(hipMallocAsync((void **) &scr, RT_SCRATCH_BYTES + poolBytes, st));
-    Pending &cl = pd;
-    cl.scr = scr; cl.st = st; cl.device = device; cl.t0 = t0;
-    cl.pixels = 0;
-    cl.waves = grid * wavesPerBlock;
-    if (want_stats) {
-        HIP_TRY(hipEventCreate(&cl.a));
-        HIP_TRY(hipEventCreate(&cl.b));
-    }
-    p.counters = (unsigned long long *) scr;
-    p.queue = (unsigned int *) (scr + 128);
-    p.cam_ptr = (const CameraParams *) (scr + 256); // (no camera: never read in these modes)
-    p.park_pool = scr + RT_SCRATCH_BYTES;
-    hipLaunchKernelGGL(launch_init_kernel, dim3(1), dim3(64), 0, st, scr, CameraParams{});
-    HIP_TRY(hipGetLastError());
-    if (want_stats) HIP_TRY(hipEventRecord(cl.a, st));
-    hipLaunchKernelGGL(fn, dim3((unsigned) grid), dim3((unsigned) block), ldsBytes, st, p);
-    HIP_TRY(hipGetLastError());
-    if (want_stats) HIP_TRY(hipEventRecord(cl.b, st));
-    cl.launched = true;
-    if (!want_stats) cl.release();
-    return RT_OK;
+    rtp::Job list;
+    list.kind = job.hit ? rtp::Job::HIT : rtp::Job::TRACE;
+    list.n = job.n;
+    return enqueue(scene, device, list, resolve_settings(options), flags, stream, p, CameraParams{}, want_stats, pd); // (no camera: never read in these modes)
 }
 
 static int run_rays_device(const rt_scene *scene, int32_t device, const RayJob &job, uint32_t flags, void *stream,
@@ -1477,14 +1311,25 @@ int rt_write_ppm(const char *path, const uint8_t *rgb, int32_t rows, int32_t col
 // ============================================================================================================
 namespace {
 
+// A device buffer of a hook: `from` is uploaded before the launch, `to` downloaded after it (either may be null).
 template <typename T> struct DevBuf {
     T *p = nullptr;
-    size_t n = 0;
+    size_t n;
+    const T *from;
+    T *to;
+    DevBuf(size_t count, const T *from_, T *to_) : n(count), from(from_), to(to_) {}
+    DevBuf(const DevBuf &) = delete;
     ~DevBuf() { if (p) (void) hipFree(p); }
-    hipError_t alloc(size_t count) { n = count; return count ? hipMalloc((void **) &p, count * sizeof(T)) : hipSuccess; }
-    hipError_t up(const T *h) { return n ? hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice) : hipSuccess; }
-    hipError_t down(T *h) { return n ? hipMemcpy(h, p, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess; }
+    hipError_t up() {
+        if (!n) return hipSuccess;
+        const hipError_t e = hipMalloc((void **) &p, n * sizeof(T));
+        return e != hipSuccess || !from ? e : hipMemcpy(p, from, n * sizeof(T), hipMemcpyHostToDevice);
+    }
+    hipError_t down() { return n && to ? hipMemcpy(to, p, n * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess; }
 };
+template <typename T> static DevBuf<T> dev_in(const T *h, size_t n) { return DevBuf<T>(n, h, nullptr); }
+template <typename T> static DevBuf<T> dev_out(T *h, size_t n) { return DevBuf<T>(n, nullptr, h); }
+template <typename T> static DevBuf<T> dev_inout(T *h, size_t n) { return DevBuf<T>(n, h, h); }
 
 __global__ void k_float_producer(Rng r, int n, double *out) {
     if (threadIdx.x == 0 && blockIdx.x == 0)
@@ -1545,16 +1390,6 @@ __global__ void k_arith(int op, int n, const double *a, const double *b, double 
     default: r = rtt::cr_atan2(a[i], b[i]); break;
     }
     out[i] = r;
-}
-
-struct HookScene { RenderParams p; };
-static SceneView<false> host_view_params(const DeviceScene *ds, const rth::HostScene &h, RenderParams &p) {
-    p = RenderParams{};
-    p.off = h.off;
-    p.scene_image = ds->image;
-    p.tex = ds->tex;
-    p.texels = ds->texels;
-    return SceneView<false>{};
 }
 
 __global__ void k_reflection(const RenderParams p, int n, const int32_t *obj, const double *ray_in, const uint8_t *col_in,
@@ -1698,16 +1533,46 @@ __global__ void k_texture(const RenderParams p, int tex, int n, const double *pt
     st_rgb(col + i * 3, c);
 }
 
-static inline unsigned blocks_for(int n) { return (unsigned) ((n + 255) / 256); }
+template <class K, class... A> static void launch_n(K kernel, int n, A... args) { // n items, 256 per block, on the null stream
+    if (n) hipLaunchKernelGGL(kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, args...);
+}
 
-static int hook_scene_params(DeviceGuard &guard, int device, const rt_scene *scene, RenderParams &p) {
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    DeviceScene *ds = nullptr;
-    rc = device_scene(const_cast<rt_scene *>(scene), device, &ds);
-    if (rc != RT_OK) return rc;
-    (void) host_view_params(ds, scene->host, p);
+// What every rt_dev_* entry point shares (each keeps its argument check, its kernel, its buffer shapes and its host pre/post step).
+// hook(): the body runs inside guarded() with `device` current; scene_hook(): the same, with the scene's device copy described in a
+// RenderParams.  hook_run(): the buffers go up, `launch` enqueues the kernel, the device is waited for, the buffers come down.
+template <class F> static int hook(const char *entry, int32_t device, F &&body) {
+    return guarded(entry, [&]() -> int {
+        DeviceGuard guard;
+        const int rc = guard.enter(device);
+        return rc != RT_OK ? rc : body();
+    });
+}
+template <class F> static int scene_hook(const char *entry, int32_t device, const rt_scene *scene, F &&body) {
+    return guarded(entry, [&]() -> int {
+        if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+        DeviceGuard guard;
+        int rc = guard.enter(device);
+        if (rc != RT_OK) return rc;
+        DeviceScene *ds = nullptr;
+        rc = device_scene(const_cast<rt_scene *>(scene), device, &ds);
+        if (rc != RT_OK) return rc;
+        RenderParams p{};
+        p.off = scene->host.off;
+        p.scene_image = ds->image;
+        p.tex = ds->tex;
+        p.texels = ds->texels;
+        return body(p);
+    });
+}
+template <class Launch, class... Bufs> static int hook_run(Launch &&launch, Bufs &...bufs) {
+    hipError_t e = hipSuccess;
+    ((e = e != hipSuccess ? e : bufs.up()), ...);
+    if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("hook buffers: ") + hipGetErrorString(e));
+    launch();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    ((e = e != hipSuccess ? e : bufs.down()), ...);
+    if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("hook results: ") + hipGetErrorString(e));
     return RT_OK;
 }
 
@@ -1717,240 +1582,173 @@ extern "C" {
 
 int rt_dev_float_producer(int32_t device, const uint32_t state[4], int32_t n, double *out) {
     if (!state || !out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    DevBuf<double> d;
-    HIP_TRY(d.alloc((size_t) n));
-    Rng r; r.x = state[0]; r.y = state[1]; r.z = state[2]; r.w = state[3];
-    if (n) hipLaunchKernelGGL(k_float_producer, dim3(1), dim3(64), 0, 0, r, n, d.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(d.down(out));
-    return RT_OK;
+    return hook("rt_dev_float_producer", device, [&]() -> int {
+        auto d = dev_out(out, (size_t) n);
+        Rng r; r.x = state[0]; r.y = state[1]; r.z = state[2]; r.w = state[3];
+        return hook_run([&] { if (n) hipLaunchKernelGGL(k_float_producer, dim3(1), dim3(64), 0, 0, r, n, d.p); }, d);
+    });
 }
 
 int rt_dev_stream_state(int32_t device, uint64_t seed, int32_t n, const uint64_t *pixel, const uint32_t *sample, uint32_t *state_out) {
     if (!pixel || !sample || !state_out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    DevBuf<uint64_t> dp; DevBuf<uint32_t> dsm, dout;
-    HIP_TRY(dp.alloc((size_t) n)); HIP_TRY(dsm.alloc((size_t) n)); HIP_TRY(dout.alloc((size_t) n * 4));
-    HIP_TRY(dp.up(pixel)); HIP_TRY(dsm.up(sample));
-    if (n) hipLaunchKernelGGL(k_stream_state, dim3(blocks_for(n)), dim3(256), 0, 0, mix64(seed + 0x9E3779B97F4A7C15ull), n, dp.p, dsm.p, dout.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dout.down(state_out));
-    return RT_OK;
+    return hook("rt_dev_stream_state", device, [&]() -> int {
+        auto dp = dev_in(pixel, (size_t) n);
+        auto dsm = dev_in(sample, (size_t) n);
+        auto dout = dev_out(state_out, (size_t) n * 4);
+        return hook_run([&] { launch_n(k_stream_state, n, mix64(seed + 0x9E3779B97F4A7C15ull), n, dp.p, dsm.p, dout.p); }, dp, dsm, dout);
+    });
 }
 
 int rt_dev_bbox_hits(int32_t device, int32_t n, const double *rays, const double *boxes, int32_t *hit_out) {
     if (!rays || !boxes || !hit_out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    DevBuf<double> dr, db; DevBuf<int32_t> dh;
-    HIP_TRY(dr.alloc((size_t) n * 6)); HIP_TRY(db.alloc((size_t) n * 6)); HIP_TRY(dh.alloc((size_t) n));
-    HIP_TRY(dr.up(rays)); HIP_TRY(db.up(boxes));
-    if (n) hipLaunchKernelGGL(k_bbox_hits, dim3(blocks_for(n)), dim3(256), 0, 0, n, dr.p, db.p, dh.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dh.down(hit_out));
-    return RT_OK;
+    return hook("rt_dev_bbox_hits", device, [&]() -> int {
+        auto dr = dev_in(rays, (size_t) n * 6), db = dev_in(boxes, (size_t) n * 6);
+        auto dh = dev_out(hit_out, (size_t) n);
+        return hook_run([&] { launch_n(k_bbox_hits, n, n, dr.p, db.p, dh.p); }, dr, db, dh);
+    });
 }
 
 int rt_dev_bbox_filter(int32_t device, int32_t n, const double *rays, const double *boxes, double bmax, int32_t *out) {
     if (!rays || !boxes || !out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    std::vector<float> b32((size_t) n * 6);
-    float bm = 1e-30f; // as encode_image: >= every |coordinate| of the batch's rounded boxes, unless the caller names a larger scale
-    for (int i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) {
-            const float lo = rth::f32_down(boxes[(size_t) i * 6 + a]), hi = rth::f32_up(boxes[(size_t) i * 6 + 3 + a]);
-            b32[(size_t) i * 6 + a] = lo; b32[(size_t) i * 6 + 3 + a] = hi;
-            if (std::fabs(lo) > bm) bm = std::fabs(lo);
-            if (std::fabs(hi) > bm) bm = std::fabs(hi);
-        }
-    if (bmax > (double) bm) bm = rth::f32_up(bmax);
-    DevBuf<double> dr, db; DevBuf<float> df; DevBuf<int32_t> dh;
-    HIP_TRY(dr.alloc((size_t) n * 6)); HIP_TRY(db.alloc((size_t) n * 6)); HIP_TRY(df.alloc((size_t) n * 6)); HIP_TRY(dh.alloc((size_t) n));
-    HIP_TRY(dr.up(rays)); HIP_TRY(db.up(boxes)); HIP_TRY(df.up(b32.data()));
-    if (n) hipLaunchKernelGGL(k_bbox_filter, dim3(blocks_for(n)), dim3(256), 0, 0, n, dr.p, db.p, df.p, bm, dh.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dh.down(out));
-    return RT_OK;
+    return hook("rt_dev_bbox_filter", device, [&]() -> int {
+        std::vector<float> b32((size_t) n * 6);
+        float bm = 1e-30f; // as encode_image: >= every |coordinate| of the batch's rounded boxes, unless the caller names a larger scale
+        for (int i = 0; i < n; ++i)
+            for (int a = 0; a < 3; ++a) {
+                const float lo = rth::f32_down(boxes[(size_t) i * 6 + a]), hi = rth::f32_up(boxes[(size_t) i * 6 + 3 + a]);
+                b32[(size_t) i * 6 + a] = lo; b32[(size_t) i * 6 + 3 + a] = hi;
+                if (std::fabs(lo) > bm) bm = std::fabs(lo);
+                if (std::fabs(hi) > bm) bm = std::fabs(hi);
+            }
+        if (bmax > (double) bm) bm = rth::f32_up(bmax);
+        auto dr = dev_in(rays, (size_t) n * 6), db = dev_in(boxes, (size_t) n * 6);
+        auto df = dev_in((const float *) b32.data(), (size_t) n * 6);
+        auto dh = dev_out(out, (size_t) n);
+        return hook_run([&] { launch_n(k_bbox_filter, n, n, dr.p, db.p, df.p, bm, dh.p); }, dr, db, df, dh);
+    });
 }
 
 int rt_dev_sphere_first_intersection(int32_t device, int32_t n, const double *rays, const double *spheres, double *t_out) {
     if (!rays || !spheres || !t_out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    DevBuf<double> dr, dsph, dt;
-    HIP_TRY(dr.alloc((size_t) n * 6)); HIP_TRY(dsph.alloc((size_t) n * 4)); HIP_TRY(dt.alloc((size_t) n));
-    HIP_TRY(dr.up(rays)); HIP_TRY(dsph.up(spheres));
-    if (n) hipLaunchKernelGGL(k_sphere_isect, dim3(blocks_for(n)), dim3(256), 0, 0, n, dr.p, dsph.p, dt.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dt.down(t_out));
-    return RT_OK;
+    return hook("rt_dev_sphere_first_intersection", device, [&]() -> int {
+        auto dr = dev_in(rays, (size_t) n * 6), dsph = dev_in(spheres, (size_t) n * 4);
+        auto dt = dev_out(t_out, (size_t) n);
+        return hook_run([&] { launch_n(k_sphere_isect, n, n, dr.p, dsph.p, dt.p); }, dr, dsph, dt);
+    });
 }
 
 int rt_dev_plane_intersection(int32_t device, int32_t n, const double *rays, const double *planes, double *t_out) {
     if (!rays || !planes || !t_out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    DevBuf<double> dr, dpl, dt;
-    HIP_TRY(dr.alloc((size_t) n * 6)); HIP_TRY(dpl.alloc((size_t) n * 6)); HIP_TRY(dt.alloc((size_t) n));
-    HIP_TRY(dr.up(rays)); HIP_TRY(dpl.up(planes));
-    if (n) hipLaunchKernelGGL(k_plane_isect, dim3(blocks_for(n)), dim3(256), 0, 0, n, dr.p, dpl.p, dt.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dt.down(t_out));
-    return RT_OK;
+    return hook("rt_dev_plane_intersection", device, [&]() -> int {
+        auto dr = dev_in(rays, (size_t) n * 6), dpl = dev_in(planes, (size_t) n * 6);
+        auto dt = dev_out(t_out, (size_t) n);
+        return hook_run([&] { launch_n(k_plane_isect, n, n, dr.p, dpl.p, dt.p); }, dr, dpl, dt);
+    });
 }
 
 int rt_dev_pixel_combine(int32_t device, int32_t n, const uint8_t *a, const uint8_t *b, uint8_t *out) {
     if (!a || !b || !out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    DevBuf<uint8_t> da, db, dout;
-    HIP_TRY(da.alloc((size_t) n * 3)); HIP_TRY(db.alloc((size_t) n * 3)); HIP_TRY(dout.alloc((size_t) n * 3));
-    HIP_TRY(da.up(a)); HIP_TRY(db.up(b));
-    if (n) hipLaunchKernelGGL(k_pixel_combine, dim3(blocks_for(n)), dim3(256), 0, 0, n, da.p, db.p, dout.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dout.down(out));
-    return RT_OK;
+    return hook("rt_dev_pixel_combine", device, [&]() -> int {
+        auto da = dev_in(a, (size_t) n * 3), db = dev_in(b, (size_t) n * 3);
+        auto dout = dev_out(out, (size_t) n * 3);
+        return hook_run([&] { launch_n(k_pixel_combine, n, n, da.p, db.p, dout.p); }, da, db, dout);
+    });
 }
 
 int rt_dev_pixel_darken(int32_t device, int32_t n, const uint8_t *p, const double *albedo, uint8_t *out) {
     if (!p || !albedo || !out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    DevBuf<uint8_t> dp, dout; DevBuf<double> da;
-    HIP_TRY(dp.alloc((size_t) n * 3)); HIP_TRY(da.alloc((size_t) n)); HIP_TRY(dout.alloc((size_t) n * 3));
-    HIP_TRY(dp.up(p)); HIP_TRY(da.up(albedo));
-    if (n) hipLaunchKernelGGL(k_pixel_darken, dim3(blocks_for(n)), dim3(256), 0, 0, n, dp.p, da.p, dout.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dout.down(out));
-    return RT_OK;
+    return hook("rt_dev_pixel_darken", device, [&]() -> int {
+        auto dp = dev_in(p, (size_t) n * 3);
+        auto da = dev_in(albedo, (size_t) n);
+        auto dout = dev_out(out, (size_t) n * 3);
+        return hook_run([&] { launch_n(k_pixel_darken, n, n, dp.p, da.p, dout.p); }, dp, da, dout);
+    });
 }
 
 int rt_dev_arith(int32_t device, int32_t op, int32_t n, const double *a, const double *b, double *out) {
     if (!a || !out || n < 0 || op < 0 || op > 9 || ((op == 3 || op == 9) && !b)) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    DevBuf<double> da, db, dout;
-    HIP_TRY(da.alloc((size_t) n)); HIP_TRY(db.alloc(b ? (size_t) n : 0)); HIP_TRY(dout.alloc((size_t) n));
-    HIP_TRY(da.up(a));
-    if (b) HIP_TRY(db.up(b));
-    if (n) hipLaunchKernelGGL(k_arith, dim3(blocks_for(n)), dim3(256), 0, 0, op, n, da.p, db.p, dout.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dout.down(out));
-    return RT_OK;
+    return hook("rt_dev_arith", device, [&]() -> int {
+        auto da = dev_in(a, (size_t) n), db = dev_in(b, b ? (size_t) n : 0);
+        auto dout = dev_out(out, (size_t) n);
+        return hook_run([&] { launch_n(k_arith, n, op, n, da.p, db.p, dout.p); }, da, db, dout);
+    });
 }
 
 int rt_dev_reflection(int32_t device, const rt_scene *scene, int32_t n, const int32_t *index, const double *ray_in, const uint8_t *colour_in,
                       const double *strike, uint32_t *rng_state, int32_t *absorbed, uint8_t *colour_out, double *ray_out) {
     if (!index || !ray_in || !colour_in || !strike || !rng_state || !absorbed || !colour_out || !ray_out || n < 0)
         return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    RenderParams p;
-    DeviceGuard guard;
-    int rc = hook_scene_params(guard, device, scene, p);
-    if (rc != RT_OK) return rc;
-    std::vector<int32_t> obj((size_t) n);
-    for (int i = 0; i < n; ++i) {
-        if (index[i] < 0 || (size_t) index[i] >= scene->host.origToObj.size()) return fail(RT_ERR_INVALID_ARGUMENT, "hittable index out of range");
-        obj[(size_t) i] = scene->host.origToObj[(size_t) index[i]];
-    }
-    DevBuf<int32_t> dobj, dab; DevBuf<double> dri, dst, dro; DevBuf<uint8_t> dci, dco; DevBuf<uint32_t> drng;
-    HIP_TRY(dobj.alloc((size_t) n)); HIP_TRY(dab.alloc((size_t) n)); HIP_TRY(dri.alloc((size_t) n * 6)); HIP_TRY(dst.alloc((size_t) n * 3));
-    HIP_TRY(dro.alloc((size_t) n * 6)); HIP_TRY(dci.alloc((size_t) n * 3)); HIP_TRY(dco.alloc((size_t) n * 3)); HIP_TRY(drng.alloc((size_t) n * 4));
-    HIP_TRY(dobj.up(obj.data())); HIP_TRY(dri.up(ray_in)); HIP_TRY(dst.up(strike)); HIP_TRY(dci.up(colour_in)); HIP_TRY(drng.up(rng_state));
-    if (n) hipLaunchKernelGGL(k_reflection, dim3(blocks_for(n)), dim3(256), 0, 0, p, n, dobj.p, dri.p, dci.p, dst.p, drng.p, dab.p, dco.p, dro.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dab.down(absorbed)); HIP_TRY(dco.down(colour_out)); HIP_TRY(dro.down(ray_out)); HIP_TRY(drng.down(rng_state));
-    return RT_OK;
+    return scene_hook("rt_dev_reflection", device, scene, [&](const RenderParams &p) -> int {
+        std::vector<int32_t> obj((size_t) n);
+        for (int i = 0; i < n; ++i) {
+            if (index[i] < 0 || (size_t) index[i] >= scene->host.origToObj.size()) return fail(RT_ERR_INVALID_ARGUMENT, "hittable index out of range");
+            obj[(size_t) i] = scene->host.origToObj[(size_t) index[i]];
+        }
+        auto dobj = dev_in((const int32_t *) obj.data(), (size_t) n);
+        auto dab = dev_out(absorbed, (size_t) n);
+        auto dri = dev_in(ray_in, (size_t) n * 6), dst = dev_in(strike, (size_t) n * 3);
+        auto dro = dev_out(ray_out, (size_t) n * 6);
+        auto dci = dev_in(colour_in, (size_t) n * 3);
+        auto dco = dev_out(colour_out, (size_t) n * 3);
+        auto drng = dev_inout(rng_state, (size_t) n * 4);
+        return hook_run([&] { launch_n(k_reflection, n, p, n, dobj.p, dri.p, dci.p, dst.p, drng.p, dab.p, dco.p, dro.p); }, dobj, dab, dri, dst, dro, dci, dco, drng);
+    });
+}
+
+// hittable indices of the scene's object table -> rt_scene_create's
+static void to_orig(const rt_scene *scene, int32_t n, int32_t *hit_index) {
+    for (int i = 0; i < n; ++i) if (hit_index[i] >= 0) hit_index[i] = scene->host.objToOrig[(size_t) hit_index[i]];
 }
 
 int rt_dev_hit_object(int32_t device, const rt_scene *scene, int32_t n, const double *rays, int32_t *hit_index, double *strike, uint32_t *counters) {
     if (!rays || !hit_index || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    RenderParams p;
-    DeviceGuard guard;
-    int rc = hook_scene_params(guard, device, scene, p);
-    if (rc != RT_OK) return rc;
-    DevBuf<double> dr, dsk; DevBuf<int32_t> dh; DevBuf<uint32_t> dc;
-    HIP_TRY(dr.alloc((size_t) n * 6)); HIP_TRY(dh.alloc((size_t) n)); HIP_TRY(dsk.alloc(strike ? (size_t) n * 3 : 0)); HIP_TRY(dc.alloc(counters ? (size_t) n * 2 : 0));
-    HIP_TRY(dr.up(rays));
-    if (n) hipLaunchKernelGGL(k_hit_object, dim3(blocks_for(n)), dim3(256), 0, 0, p, n, dr.p, dh.p, dsk.p, dc.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dh.down(hit_index));
-    for (int i = 0; i < n; ++i) if (hit_index[i] >= 0) hit_index[i] = scene->host.objToOrig[(size_t) hit_index[i]];
-    if (strike) HIP_TRY(dsk.down(strike));
-    if (counters) HIP_TRY(dc.down(counters));
-    return RT_OK;
+    return scene_hook("rt_dev_hit_object", device, scene, [&](const RenderParams &p) -> int {
+        auto dr = dev_in(rays, (size_t) n * 6);
+        auto dh = dev_out(hit_index, (size_t) n);
+        auto dsk = dev_out(strike, strike ? (size_t) n * 3 : 0);
+        auto dc = dev_out(counters, counters ? (size_t) n * 2 : 0);
+        const int rc = hook_run([&] { launch_n(k_hit_object, n, p, n, dr.p, dh.p, dsk.p, dc.p); }, dr, dh, dsk, dc);
+        if (rc == RT_OK) to_orig(scene, n, hit_index);
+        return rc;
+    });
 }
 
 int rt_dev_hit_object_lds(int32_t device, const rt_scene *scene, int32_t n, const double *rays, int32_t *hit_index, double *strike) {
     if (!rays || !hit_index || !strike || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    RenderParams p;
-    DeviceGuard guard;
-    int rc = hook_scene_params(guard, device, scene, p);
-    if (rc != RT_OK) return rc;
-    const size_t ldsBytes = scene->host.off.lds32_total;
-    if (ldsBytes > RT_LDS_BYTES || scene->host.nBounded + scene->host.nUnbounded >= 16384u) return fail(RT_ERR_UNSUPPORTED, "the scene does not fit the LDS");
-    DevBuf<double> dr, dsk; DevBuf<int32_t> dh;
-    HIP_TRY(dr.alloc((size_t) n * 6)); HIP_TRY(dh.alloc((size_t) n)); HIP_TRY(dsk.alloc((size_t) n * 3));
-    HIP_TRY(dr.up(rays));
-    rc = allow_full_lds((const void *) k_hit_object_lds);
-    if (rc != RT_OK) return rc;
-    if (n) hipLaunchKernelGGL(k_hit_object_lds, dim3((unsigned) ((n + 1023) / 1024)), dim3(1024), ldsBytes, 0, p, n, dr.p, dh.p, dsk.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dh.down(hit_index));
-    for (int i = 0; i < n; ++i) if (hit_index[i] >= 0) hit_index[i] = scene->host.objToOrig[(size_t) hit_index[i]];
-    HIP_TRY(dsk.down(strike));
-    return RT_OK;
+    return scene_hook("rt_dev_hit_object_lds", device, scene, [&](const RenderParams &p) -> int {
+        // (a fit test of its own: the image alone, no wave scratch -- this kernel has none)
+        const size_t ldsBytes = scene->host.off.lds32_total;
+        if (ldsBytes > RT_LDS_BYTES || scene->host.nBounded + scene->host.nUnbounded >= 16384u) return fail(RT_ERR_UNSUPPORTED, "the scene does not fit the LDS");
+        int rc = allow_full_lds((const void *) k_hit_object_lds);
+        if (rc != RT_OK) return rc;
+        auto dr = dev_in(rays, (size_t) n * 6);
+        auto dh = dev_out(hit_index, (size_t) n);
+        auto dsk = dev_out(strike, (size_t) n * 3);
+        rc = hook_run([&] { if (n) hipLaunchKernelGGL(k_hit_object_lds, dim3((unsigned) ((n + 1023) / 1024)), dim3(1024), ldsBytes, 0, p, n, dr.p, dh.p, dsk.p); }, dr, dh, dsk);
+        if (rc == RT_OK) to_orig(scene, n, hit_index);
+        return rc;
+    });
 }
 
-static int pixel_candidates(int32_t device, const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t n,
+// (on the device, inside guarded: rt_dev_pixel_candidates)
+static int pixel_candidates(const RenderParams &p, const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t n,
                             const int32_t *row_col, int32_t *leaves_out) {
-    if (!camera || !row_col || !leaves_out || n < 0 || max_w <= 0 || max_h <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    RenderParams p;
-    DeviceGuard guard;
-    int rc = hook_scene_params(guard, device, scene, p);
-    if (rc != RT_OK) return rc;
     const size_t ldsBytes = scene->host.off.lds32_total;
     const bool narrow = scene->host.nBounded + scene->host.nUnbounded < 16384u;
-    const bool lds = plan_launch(scene->host, resolve_settings(nullptr)).lds; // the timed render's view of this scene (rt_scene_info.lds_resident)
-    CameraParams cam{};
-    for (int a = 0; a < 3; ++a) { cam.eye[a] = camera->view_origin[a]; cam.xo[a] = camera->xaxis_origin[a]; cam.xd[a] = camera->xaxis_dir[a]; cam.yd[a] = camera->yaxis_dir[a]; }
-    cam.vw = camera->viewport_width; cam.vh = camera->viewport_height; cam.max_w = max_w; cam.max_h = max_h;
-    DevBuf<int32_t> drc; DevBuf<uint32_t> dout;
-    HIP_TRY(drc.alloc((size_t) n * 2)); HIP_TRY(dout.alloc((size_t) n * 2));
-    HIP_TRY(drc.up(row_col));
+    const bool lds = default_lds_resident(scene->host); // the timed render's view of this scene (rt_scene_info.lds_resident)
+    const CameraParams cam = camera_params(camera, max_w, max_h);
     if (lds) {
-        rc = allow_full_lds((const void *) k_pixel_candidates);
+        const int rc = allow_full_lds((const void *) k_pixel_candidates);
         if (rc != RT_OK) return rc;
-        if (n) hipLaunchKernelGGL(k_pixel_candidates, dim3((unsigned) ((n + 1023) / 1024)), dim3(1024), ldsBytes, 0, p, cam, n, drc.p, dout.p);
-    } else if (n) hipLaunchKernelGGL(k_pixel_candidates_glb, dim3(blocks_for(n)), dim3(256), 0, 0, p, cam, n, drc.p, dout.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
+    }
     std::vector<uint32_t> w((size_t) n * 2);
-    HIP_TRY(dout.down(w.data()));
+    auto drc = dev_in(row_col, (size_t) n * 2);
+    auto dout = dev_out(w.data(), (size_t) n * 2);
+    const int rc = hook_run([&] {
+        if (lds && n) hipLaunchKernelGGL(k_pixel_candidates, dim3((unsigned) ((n + 1023) / 1024)), dim3(1024), ldsBytes, 0, p, cam, n, drc.p, dout.p);
+        if (!lds) launch_n(k_pixel_candidates_glb, n, p, cam, n, drc.p, dout.p);
+    }, drc, dout);
+    if (rc != RT_OK) return rc;
     // decode: up to four hittable indices per pixel (-1 = none); leaves_out[i*4] = -2 when the pixel's camera rays walk the tree.
     // Below 16384 objects the words hold two 16-bit entries each (RTD_PEND_MARK | object); beyond, one full-width entry each
     // (RTD_PEND_WIDE | object, at most two candidates).
@@ -1975,41 +1773,31 @@ static int pixel_candidates(int32_t device, const rt_scene *scene, const rt_came
 }
 int rt_dev_pixel_candidates(int32_t device, const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t n,
                             const int32_t *row_col, int32_t *leaves_out) {
-    return guarded("rt_dev_pixel_candidates", [&]() { return pixel_candidates(device, scene, camera, max_w, max_h, n, row_col, leaves_out); });
+    if (!camera || !row_col || !leaves_out || n < 0 || max_w <= 0 || max_h <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
+    return scene_hook("rt_dev_pixel_candidates", device, scene, [&](const RenderParams &p) -> int {
+        return pixel_candidates(p, scene, camera, max_w, max_h, n, row_col, leaves_out);
+    });
 }
 
 int rt_dev_trace_ray(int32_t device, const rt_scene *scene, int32_t bounce_depth, int32_t n, const double *rays, uint32_t *rng_state, uint8_t *colour_out) {
     if (!rays || !rng_state || !colour_out || n < 0 || bounce_depth < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
-    RenderParams p;
-    DeviceGuard guard;
-    int rc = hook_scene_params(guard, device, scene, p);
-    if (rc != RT_OK) return rc;
-    DevBuf<double> dr; DevBuf<uint32_t> drng; DevBuf<uint8_t> dc;
-    HIP_TRY(dr.alloc((size_t) n * 6)); HIP_TRY(drng.alloc((size_t) n * 4)); HIP_TRY(dc.alloc((size_t) n * 3));
-    HIP_TRY(dr.up(rays)); HIP_TRY(drng.up(rng_state));
-    if (n) hipLaunchKernelGGL(k_trace_ray, dim3(blocks_for(n)), dim3(256), 0, 0, p, bounce_depth, n, dr.p, drng.p, dc.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(dc.down(colour_out)); HIP_TRY(drng.down(rng_state));
-    return RT_OK;
+    return scene_hook("rt_dev_trace_ray", device, scene, [&](const RenderParams &p) -> int {
+        auto dr = dev_in(rays, (size_t) n * 6);
+        auto drng = dev_inout(rng_state, (size_t) n * 4);
+        auto dc = dev_out(colour_out, (size_t) n * 3);
+        return hook_run([&] { launch_n(k_trace_ray, n, p, bounce_depth, n, dr.p, drng.p, dc.p); }, dr, drng, dc);
+    });
 }
 
 int rt_dev_texture_colour_at(int32_t device, const rt_scene *scene, int32_t texture, int32_t n, const double *points, double *uv_out, uint8_t *colour_out) {
     if (!points || !colour_out || n < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
     if (!scene || texture < 0 || (size_t) texture >= scene->host.texRecs.size()) return fail(RT_ERR_INVALID_ARGUMENT, "texture index out of range");
-    RenderParams p;
-    DeviceGuard guard;
-    int rc = hook_scene_params(guard, device, scene, p);
-    if (rc != RT_OK) return rc;
-    DevBuf<double> dp, duv; DevBuf<uint8_t> dc;
-    HIP_TRY(dp.alloc((size_t) n * 3)); HIP_TRY(duv.alloc(uv_out ? (size_t) n * 2 : 0)); HIP_TRY(dc.alloc((size_t) n * 3));
-    HIP_TRY(dp.up(points));
-    if (n) hipLaunchKernelGGL(k_texture, dim3(blocks_for(n)), dim3(256), 0, 0, p, texture, n, dp.p, duv.p, dc.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (uv_out) HIP_TRY(duv.down(uv_out));
-    HIP_TRY(dc.down(colour_out));
-    return RT_OK;
+    return scene_hook("rt_dev_texture_colour_at", device, scene, [&](const RenderParams &p) -> int {
+        auto dp = dev_in(points, (size_t) n * 3);
+        auto duv = dev_out(uv_out, uv_out ? (size_t) n * 2 : 0);
+        auto dc = dev_out(colour_out, (size_t) n * 3);
+        return hook_run([&] { launch_n(k_texture, n, p, texture, n, dp.p, duv.p, dc.p); }, dp, duv, dc);
+    });
 }
 
 } // extern "C"

@@ -17,7 +17,7 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import instruction_census as ic  # noqa: E402
 
-HEADERS = ("rt_device.h", "rt_render_kernel.h", "rt_scene.h", "rt_trig.h", "rt_trig_tables.h")
+HEADERS = ("rt_device.h", "rt_render_kernel.h", "rt_launch_consts.h", "rt_scene.h", "rt_trig.h", "rt_trig_tables.h")
 
 
 def strip_diag(text):
@@ -69,7 +69,13 @@ def main():
         for h in HEADERS + ("../../include/rtfs_amd.h",):
             src = os.path.normpath(os.path.join(ic.CSRC, h))
             rel = os.path.relpath(src, ic.ROOT)
-            text = subprocess.run(["git", "-C", ic.ROOT, "show", f"{a.rev}:{rel}"], stdout=subprocess.PIPE, text=True, check=True).stdout if a.rev else strip_diag(open(src).read())
+            if a.rev:
+                shown = subprocess.run(["git", "-C", ic.ROOT, "show", f"{a.rev}:{rel}"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+                if shown.returncode != 0:
+                    continue  # (a header that revision does not have yet)
+                text = shown.stdout
+            else:
+                text = strip_diag(open(src).read())
             open(os.path.normpath(os.path.join(other_csrc, h)), "w").write(text)
         other = listing(other_csrc, None, os.path.join(tmp, "other_out"))
     finally:

@@ -59,7 +59,7 @@ def test_strip_diag_keeps_the_else_part():
 
 def test_census_counters_exist_in_diagnostic_builds_only(rt):
     csrc = os.path.join(ROOT, "ray-tracing-fsharp_amd", "csrc")
-    for f in ("rt_device.h", "rt_render_kernel.h", "rtfs_amd.hip"):
+    for f in ("rt_device.h", "rt_render_kernel.h", "rt_launch_consts.h", "rt_launch_plan.h", "rtfs_amd.hip"):
         plain = chk.strip_diag(open(os.path.join(csrc, f)).read())
         assert "g_census" not in plain and "rt_diag_census" not in plain, f
     assert "rt_diag_census" not in open(os.path.join(ROOT, "include", "rtfs_amd.h")).read()
