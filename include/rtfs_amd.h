@@ -397,6 +397,23 @@ int rt_set_park(int32_t park_lanes);
  * wave lifetimes and first-start-to-last-end span (both in 100 MHz ticks), waves launched, general-reflection stages, lanes in them,
  * lanes parked, shader-clock cycles summed over the waves inside the refill / general-reflection / walk / shade stages}. */
 int rt_last_stage_stats(uint64_t out[16]);
+/* Diagnostic: the launch plan (csrc/rt_launch_plan.h) of the calling THREAD's last launch -- a render shard, rt_scene_tune's probe
+ * or a ray list; of rt_render_frame, its last device's -- as the library gathered its inputs and executed its outputs.  Read-only
+ * host bookkeeping: no device work, nothing launched depends on it.  Words, under the names tests/c/launch_plan_table.cpp reads
+ * and prints:
+ *   [0]      1 once this thread has planned a launch (all words are 0 before)
+ *   [1..21]  inputs: kind (0 frame shard, 1 traceRays list, 2 hitObject list) lds_total lds32_total n_nodes n_obj has_tex
+ *            s_block s_chunk s_bpc s_yield s_refill s_passes s_park (the resolved settings, 0 = "the plan decides") count log
+ *            n_rows max_w spp n cu_count per_cu (what the occupancy query answered, before blocks_per_cu)
+ *   [22..34] q_lds q_count q_block q_mode q_tex q_lds_bytes two_pass pairs list sort pool waves error
+ *   [35..48] the fused or ray-list kernel (F_), [49..62] pass A (A_), [63..76] pass B (B_), each: mode grid lds_bytes chunk park
+ *            park_l park_l_lds lds_node_bytes lds_node_thr yield leaf_wait refill k total_waves.  F_ is what ran unless two_pass;
+ *            A_ and B_ are filled only with two_pass and no error.
+ * A call that fails before its plan is complete (bad arguments, no kernel built for the launch, occupancy 0) leaves the previous
+ * launch's report in place: read it after a call that returned RT_OK.
+ * An added diagnostic symbol only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */
+#define RT_LAUNCH_PLAN_WORDS 80
+int rt_dev_last_launch_plan(int64_t out[RT_LAUNCH_PLAN_WORDS]);
 
 /*
  * ---- Device unit hooks ---------------------------------------------------------------------------

@@ -108,6 +108,7 @@ static std::atomic<int> g_passes{0}; // 0 auto, 1 fused kernel, 2 two-pass (A, s
 static std::atomic<int> g_park_lanes{0};
 static std::atomic<int> g_walk_tree{RT_WALK_TREE_SAH};
 static thread_local unsigned long long g_last_stage_stats[16] = {0};
+static thread_local int64_t g_last_launch_plan[RT_LAUNCH_PLAN_WORDS] = {0};
 
 static int device_scene(rt_scene *s, int device, DeviceScene **out) {
     std::lock_guard<std::mutex> lock(s->mu);
@@ -312,6 +313,12 @@ int rt_last_stage_stats(uint64_t out[16]) {
     return RT_OK;
 }
 
+int rt_dev_last_launch_plan(int64_t out[RT_LAUNCH_PLAN_WORDS]) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (int i = 0; i < RT_LAUNCH_PLAN_WORDS; ++i) out[i] = g_last_launch_plan[i];
+    return RT_OK;
+}
+
 int rt_set_walk_tree(int32_t kind) {
     if (kind != RT_WALK_TREE_SAH && kind != RT_WALK_TREE_REFERENCE) return fail(RT_ERR_INVALID_ARGUMENT, "walk tree must be RT_WALK_TREE_SAH or RT_WALK_TREE_REFERENCE");
     g_walk_tree = kind;
@@ -495,6 +502,32 @@ static void set_plan_fields(RenderParams &p, const rtp::Pass &q) {
     p.total_waves = q.total_waves;
 }
 
+// rt_dev_last_launch_plan: the plan enqueue() is about to execute, inputs and outputs, as plain integers in the order
+// include/rtfs_amd.h gives (tests/c/launch_plan_table.cpp's names).  Host bookkeeping only: nothing that is launched reads it.
+static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
+    int64_t *o = g_last_launch_plan;
+    int n = 0;
+    auto put = [&](int64_t v) { o[n++] = v; };
+    const rtp::SceneSize &sc = pl.scene;
+    const Settings &s = pl.set;
+    const rtp::Job &j = pl.job;
+    put(1);
+    put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : 2));
+    put((int64_t) sc.lds_total); put((int64_t) sc.lds32_total); put(sc.n_nodes); put((int64_t) sc.n_objects); put(sc.tex);
+    put(s.block); put(s.chunk); put(s.blocks_per_cu); put(s.yield); put(s.refill); put(s.passes); put(s.park);
+    put(pl.one.count); put(j.ray_log); put((int64_t) j.n_rows); put(j.max_w); put(j.spp); put((int64_t) j.n); put(pl.cu_count); put(per_cu);
+    const rtp::Pass &q = pl.one;
+    put(q.lds); put(q.count); put(q.block); put(q.mode); put(q.tex); put((int64_t) q.lds_bytes); put(pl.two_pass);
+    put((int64_t) pl.pairs_bytes); put((int64_t) pl.list_bytes); put((int64_t) pl.sort_bytes); put((int64_t) pl.pool_bytes); put((int64_t) pl.waves);
+    put(pl.error ? 1 : 0);
+    for (const rtp::Pass *r : {&pl.one, &pl.a, &pl.b}) {
+        put(r->mode); put((int64_t) r->grid); put((int64_t) r->lds_bytes); put(r->chunk); put(r->park); put(r->park_l); put(r->park_l_lds);
+        put(r->lds_node_bytes); put(r->lds_node_thr); put(r->yield_lanes); put(r->leaf_wait); put(r->refill_lanes); put(r->k); put(r->total_waves);
+    }
+    static_assert(1 + 21 + 13 + 3 * 14 <= RT_LAUNCH_PLAN_WORDS, "rt_dev_last_launch_plan's words");
+    while (n < RT_LAUNCH_PLAN_WORDS) put(0);
+}
+
 // The one enqueue path of frames and ray lists (arguments checked, settings valid): plans the launch, takes its scratch and workspace
 // from the stream's pool, launches what the plan lists -- one kernel, or pass A, the three sort kernels and pass B -- and never waits
 // for the device.  `p` arrives with the caller's own fields filled (camera and rows and buffers, or the ray list's pointers); the
@@ -530,6 +563,7 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *) fn, block, ldsBytes));
     if (perCu < 1) return fail(RT_ERR_HIP, job.kind == rtp::Job::FRAME ? "render kernel does not fit on a CU (occupancy 0)" : "ray-list kernel does not fit on a CU (occupancy 0)");
     rtp::plan_finish(plan, perCu);
+    remember_plan(plan, perCu);
     const uint64_t grid = plan.one.grid;
     const size_t pairsBytes = plan.pairs_bytes, listBytes = plan.list_bytes, sortBytes = plan.sort_bytes, poolBytes = plan.pool_bytes;
 

@@ -132,3 +132,32 @@ def texture_colour_at(scene: Scene, texture, points, device=0):
     uv, col = np.zeros((len(points), 2), np.float64), np.zeros((len(points), 3), np.uint8)
     check(lib.rt_dev_texture_colour_at(device, scene.handle, int(texture), len(points), _f64(points), _f64(uv), _u8(col)))
     return uv, col
+
+
+# rt_dev_last_launch_plan's words, under the names tests/c/launch_plan_table.cpp reads and prints
+PLAN_INPUTS = ("kind", "lds_total", "lds32_total", "n_nodes", "n_obj", "has_tex", "s_block", "s_chunk", "s_bpc", "s_yield", "s_refill",
+               "s_passes", "s_park", "count", "log", "n_rows", "max_w", "spp", "n", "cu_count", "per_cu")
+PLAN_HEAD = ("q_lds", "q_count", "q_block", "q_mode", "q_tex", "q_lds_bytes", "two_pass", "pairs", "list", "sort", "pool", "waves", "error")
+PLAN_PASS = ("mode", "grid", "lds_bytes", "chunk", "park", "park_l", "park_l_lds", "lds_node_bytes", "lds_node_thr", "yield", "leaf_wait",
+             "refill", "k", "total_waves")
+PLAN_WORDS = 80
+
+
+def last_launch_plan():
+    """The launch plan (csrc/rt_launch_plan.h) of the calling thread's last launch as the library executed it: {"in": the planner's
+    inputs, "out": its decisions}, keyed as launch_plan_table.cpp's lines are (F_ for a fused or ray-list launch, A_ and B_ for a
+    two-pass one).  None before this thread's first launch."""
+    w = (C.c_int64 * PLAN_WORDS)()
+    check(lib.rt_dev_last_launch_plan(w))
+    if not w[0]:
+        return None
+    at = 1
+    inp = dict(zip(PLAN_INPUTS, w[at:at + len(PLAN_INPUTS)]))
+    at += len(PLAN_INPUTS)
+    out = dict(zip(PLAN_HEAD, w[at:at + len(PLAN_HEAD)]))
+    at += len(PLAN_HEAD)
+    for name in "FAB":
+        if (name == "F") != bool(out["two_pass"]) and not out["error"]:
+            out.update({f"{name}_{k}": v for k, v in zip(PLAN_PASS, w[at:at + len(PLAN_PASS)])})
+        at += len(PLAN_PASS)
+    return {"in": inp, "out": out}

@@ -75,6 +75,10 @@ def test_per_call_options_override_nothing_global(rt):
                                       None, C.byref(opt), C.byref(st)))
         assert np.array_equal(out.cpu().numpy(), base.accum), kw
         assert st.rays == base.stats["rays"] and st.samples == base.stats["samples"], kw
+        # flags 0: the same options through the timed kernel (its own walk stage, leaf queue and hand-over point)
+        out = torch.zeros((rows, cols, 4), dtype=torch.int32, device="cuda:0")
+        check(lib.rt_render_device_ex(s.handle, C.byref(camabi), w, h, 4, 0, 0, 1, rows, 0, C.c_void_p(out.data_ptr()), None, None, C.byref(opt), C.byref(st)))
+        assert np.array_equal(out.cpu().numpy(), base.accum), kw
     bad = A.rt_render_options(block_threads=100)
     assert lib.rt_render_device_ex(s.handle, C.byref(camabi), w, h, 4, 0, 0, 1, rows, 0, C.c_void_p(out.data_ptr()), None, None, C.byref(bad), None) == A.RT_ERR_INVALID_ARGUMENT
     assert s.info()["lds_resident"] == 1
@@ -101,9 +105,14 @@ def test_two_pass_unit_sizes_at_the_edge_of_the_lds(rt):
             fused = s.render_rows(w, h, cam, seed=9, counters=True)
             rt.set_passes(2)
             two = s.render_rows(w, h, cam, seed=9, counters=True)
+            timed_two = s.render_rows(w, h, cam, seed=9)  # the timed kernels: their LDS image and unit sizes are their own
+            rt.set_passes(1)
+            timed_fused = s.render_rows(w, h, cam, seed=9)
         finally:
             rt.set_passes(0)
         assert np.array_equal(fused.accum, two.accum) and fused.stats["rays"] == two.stats["rays"], n
+        assert np.array_equal(timed_fused.accum, fused.accum) and np.array_equal(timed_fused.rgb, fused.rgb), n
+        assert np.array_equal(timed_two.accum, two.accum) and np.array_equal(timed_two.rgb, two.rgb), n
 
 
 def test_render_frame_one_process_several_devices(rt):

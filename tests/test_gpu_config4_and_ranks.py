@@ -35,6 +35,9 @@ def test_config4_full_frame_properties_rows_and_shard(rt, orc):
         assert np.array_equal(a.accum[row], acc[0]) and np.array_equal(a.rgb[row], rgb[0]), row
     part = s.render_rows(w, h, cam, seed=2024, row_first=3, row_stride=8, counters=True)
     assert np.array_equal(part.accum, a.accum[3::8]) and part.stats["samples"] == int(cnt[3::8].sum(dtype=np.int64))
+    # the kernel that is timed (no counters): the same frame, every PixelStats
+    timed = s.render_rows(w, h, cam, seed=2024)
+    assert np.array_equal(timed.accum, a.accum) and np.array_equal(timed.rgb, a.rgb)
 
 
 CONFIG4_COUNTERS = (59957428074, 196481361316, 18394792971)  # rays, leaf + unbounded tests, samples: deterministic in the seed

@@ -896,6 +896,9 @@ def test_config5_whole_frame_at_100_spp(rt, orc):
     acc, rgb, st = orc.OracleScene(objs).render_rows(w, h, cam.to_abi(), seed=5, threads=min(32, _cpu_quota()))
     _assert_render_equal(res, acc, rgb, st)
     assert res.stats["pixels"] == (2 * w + 1) * (2 * h + 1)
+    # the textured kernel that is timed (no counters): the same frame
+    timed = rt.Scene.make(objs).render_rows(w, h, cam, seed=5)
+    assert np.array_equal(timed.accum, acc) and np.array_equal(timed.rgb, rgb)
 
 
 @pytest.mark.parametrize("chunk", [0, 1, 5, 64])
