@@ -345,6 +345,35 @@ int rt_trace_rays_device(const rt_scene *scene, int32_t device, size_t n, const 
                          uint32_t flags, void *d_colour, void *stream,
                          const rt_render_options *options, rt_stats *stats);
 
+/* ---- Footprints: Scene.renderPixel for caller-defined cameras ----------------------------------------------------------
+ * A pixel's camera as data (DESIGN.md "Footprints"): footprint i is 12 doubles, origin[3] base[3] du[3] dv[3].  Sample s
+ * (0, 1, 2, ... as a render counts them) of pixel i draws (r1, r2) = GetTwo from the stream keyed (seed, stream_base + i, s)
+ * -- a render's (pixel, sample) keying -- and traces Ray.make'(origin, (base + r1*du) + r2*dv) (each product and sum rounded
+ * on its own) from White with the same generator, at most bounce_depth+1 hits.  Where Ray.make' gives ValueNone the sample is
+ * Black: Count goes up, the sums do not, nothing more is drawn.  How many samples a pixel gets is Scene.renderPixel's rule
+ * (Scene.fs:172-194) with samples_per_pixel: firstTrial = min 5 (spp/2); firstTrial+1 samples, then firstTrial more; the
+ * pixel stops there if Pixel.difference of the two means is 0, else takes the remaining spp - 2*firstTrial - 1.
+ * accum: n*4 int32 {Count, SumRed, SumGreen, SumBlue}; rgb: n*3 uint8 = PixelStats.mean, may be NULL.  Which image the n
+ * pixels form is the caller's business; the slice [a, b) of a list rendered with stream_base + a equals that slice of the
+ * whole list's result.  One launch (or pass A, the ordering and pass B) through the kernel stages of a frame; the footprints'
+ * first rays walk the tree as every other ray does.
+ *
+ * Argument checks come before any device call: RT_ERR_INVALID_ARGUMENT for a NULL scene, NULL footprints or accum when
+ * n > 0, n > INT32_MAX, samples_per_pixel < 1, bounce_depth < 0 (or > 0xFFFFFF), or bad options; nothing is written then.
+ * n = 0 is a no-op returning RT_OK with zeroed stats.  stats is filled as a render fills it: samples, pixels (= n),
+ * pixels_early, kernel_ms and total_ms always, the four counters under RT_RENDER_COUNTERS.
+ * The device variant follows rt_render_device's contract: enqueued on `stream`, with stats == NULL it returns right after
+ * the launch, scratch is stream-ordered, the caller's current device is left as it was.  options: as for a frame shard
+ * (chunk_pixels is pixels per unit, passes 0/1/2 chooses fused or two-pass); a block of 512 or 768 threads runs as 1024.
+ * Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */
+int rt_render_footprints(const rt_scene *scene, int32_t device, size_t n, const double *footprints,
+                         int32_t samples_per_pixel, int32_t bounce_depth, uint64_t seed, uint64_t stream_base,
+                         uint32_t flags, int32_t *accum, uint8_t *rgb /* may be NULL */, rt_stats *stats);
+int rt_render_footprints_device(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints,
+                                int32_t samples_per_pixel, int32_t bounce_depth, uint64_t seed, uint64_t stream_base,
+                                uint32_t flags, void *d_accum, void *d_rgb, void *stream,
+                                const rt_render_options *options, rt_stats *stats);
+
 /* ---- Output side (ImageOutput.fs:11-30,163-197) -------------------------------------------------- */
 uint8_t rt_gamma_correct(uint8_t b); /* PixelOutput.correct (ImageOutput.fs:11-18) */
 /* ImageOutput.writePpm gammaCorrect pixels file (ImageOutput.fs:163-197): P3, no trailing newline. */
@@ -398,11 +427,11 @@ int rt_set_park(int32_t park_lanes);
  * lanes parked, shader-clock cycles summed over the waves inside the refill / general-reflection / walk / shade stages}. */
 int rt_last_stage_stats(uint64_t out[16]);
 /* Diagnostic: the launch plan (csrc/rt_launch_plan.h) of the calling THREAD's last launch -- a render shard, rt_scene_tune's probe
- * or a ray list; of rt_render_frame, its last device's -- as the library gathered its inputs and executed its outputs.  Read-only
+ * a ray list or a footprint list; of rt_render_frame, its last device's -- as the library gathered its inputs and executed its outputs.  Read-only
  * host bookkeeping: no device work, nothing launched depends on it.  Words, under the names tests/c/launch_plan_table.cpp reads
  * and prints:
  *   [0]      1 once this thread has planned a launch (all words are 0 before)
- *   [1..21]  inputs: kind (0 frame shard, 1 traceRays list, 2 hitObject list) lds_total lds32_total n_nodes n_obj has_tex
+ *   [1..21]  inputs: kind (0 frame shard, 1 traceRays list, 2 hitObject list, 3 footprint list: n pixels) lds_total lds32_total n_nodes n_obj has_tex
  *            s_block s_chunk s_bpc s_yield s_refill s_passes s_park (the resolved settings, 0 = "the plan decides") count log
  *            n_rows max_w spp n cu_count per_cu (what the occupancy query answered, before blocks_per_cu)
  *   [22..34] q_lds q_count q_block q_mode q_tex q_lds_bytes two_pass pairs list sort pool waves error

@@ -1194,6 +1194,15 @@ RTD_INLINE bool camera_ray(const CameraParams &cam, int row, int col, Rng &rng, 
     o = mk(cam.eye[0], cam.eye[1], cam.eye[2]);
     return unitise(vsub(end, o), d);
 }
+// The same step for a caller-defined camera (rt_render_footprints): the pixel's footprint is 12 doubles in global memory --
+// origin, base, du, dv -- and a sample's ray is Ray.make' (origin, (base + r1 * du) + r2 * dv), every product and sum rounded on
+// its own, in the order written.  false: Ray.make' gave ValueNone, the sample is Black and draws nothing more.
+RTD_INLINE bool footprint_ray(const double *fp, Rng &rng, V3 &o, V3 &d) {
+    const double r1 = rng_get(rng), r2 = rng_get(rng); // GetTwo
+    o = mk(fp[0], fp[1], fp[2]);
+    const V3 v = mk((fp[3] + r1 * fp[6]) + r2 * fp[9], (fp[4] + r1 * fp[7]) + r2 * fp[10], (fp[5] + r1 * fp[8]) + r2 * fp[11]);
+    return unitise(v, d);
+}
 
 // ---- the leaves a pixel's camera rays can reach, found ONCE per pixel -----------------------------------------------------------
 // Every sample of a pixel starts with a ray from the eye through the pixel's patch of the viewport (Scene.fs:129-144: the patch is

@@ -35,12 +35,15 @@ struct SceneSize {
     uint64_t n_objects = 0;
     bool tex = false;                        // has parameterised textures
 };
-// A frame shard (render_kernel modes 0..3) or a caller's ray list (mode 4 paths, mode 5 hit queries)
+// A frame shard (render_kernel modes 0..3), a caller's ray list (mode 4 paths, mode 5 hit queries) or a caller's footprint list
+// (modes 6..8: planned as a FRAME of n pixels -- chunk widening, fused or two passes, placement, pools -- run by the footprint kernels)
 struct Job {
-    enum Kind { FRAME, TRACE, HIT } kind = FRAME;
+    enum Kind { FRAME, TRACE, HIT, FOOTPRINTS } kind = FRAME;
     uint64_t n_rows = 0; int32_t max_w = 0, spp = 1; // FRAME
     bool ray_log = false;                            // FRAME: rt_scene_tune's probe
-    uint64_t n = 0;                                  // TRACE, HIT: rays
+    uint64_t n = 0;                                  // TRACE, HIT: rays; FOOTPRINTS: pixels (with spp)
+    bool pixels() const { return kind == FRAME || kind == FOOTPRINTS; } // planned by the pixel rules, not the ray lists'
+    uint64_t pixel_count() const { return kind == FOOTPRINTS ? n : n_rows * (uint64_t) (2 * max_w + 1); }
 };
 
 // One kernel launch: which render_kernel<lds, count, block, mode, tex>, its grid and dynamic LDS, and the RenderParams fields the
@@ -131,7 +134,9 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     LaunchPlan pl;
     pl.scene = sc; pl.set = set; pl.job = job; pl.cu_count = cu_count;
     Pass &q = pl.one;
-    q.lds = lds_resident(sc, set, count); // (ray lists too: the render's decision, taken at the block the settings ask for)
+    Settings eff = set; // (a footprint list asked to run at 512 or 768 threads runs at 1024: residency is decided at the block that runs)
+    if (job.kind == Job::FOOTPRINTS && eff.block != 0 && eff.block != 256) eff.block = 1024;
+    q.lds = lds_resident(sc, eff, count); // (ray lists too: the render's decision, taken at the block the settings ask for)
     q.count = count;
     q.park = set.park < 0 ? 0 : (set.park ? set.park : RTD_PARK_DEFAULT);
     q.yield_lanes = set.yield ? set.yield : RTD_YIELD_DEFAULT;
@@ -140,7 +145,7 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     // Never above 64, the lanes of a wave: a hand-over point beyond them is one the node loop cannot reach.
     q.leaf_wait = q.yield_lanes + RTD_LEAF_WAIT_EXTRA > 64 ? 64 : q.yield_lanes + RTD_LEAF_WAIT_EXTRA;
     q.refill_lanes = set.refill ? set.refill : RTD_REFILL_DEFAULT;
-    if (job.kind != Job::FRAME) {
+    if (!job.pixels()) {
         // 24 instantiations: blocks of 256 or 1024 threads only (a launch asking for 512 or 768 runs at 1024: the block size never
         // changes a result); the hit queries shade nothing, so they have no textured variant and park nothing.
         q.block = default_block(set) == 256 ? 256 : 1024;
@@ -153,6 +158,10 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     }
     q.block = default_block(set);
     q.mode = job.ray_log ? 3 : 0; // (the ray log of rt_scene_tune's probe: a kernel of its own)
+    if (job.kind == Job::FOOTPRINTS) { // modes 6 / 7 / 8, built for blocks of 256 and 1024 threads only, as the ray lists are
+        q.block = q.block == 256 ? 256 : 1024;
+        q.mode = 6;
+    }
     q.tex = sc.tex;               // otherwise the variant compiled without the texture call: no scratch, no VGPR spills
     const int half = job.spp / 2;
     q.k = half < 5 ? half : 5; // min 5 (spp / 2), Scene.fs:172
@@ -162,7 +171,7 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     // 4 spp 8.5 -> 16.0 Gray/s, 16 spp 12.3 -> 19.6 with 64 pixels; 1201x801: 7.0 -> 9.3, 10.5 -> 12.5 with 32).
     q.chunk = set.chunk ? set.chunk : 16;
     if (!set.chunk && set.passes != 2 && job.spp <= 74) { // (below the two-pass rule's 64 samples in phase 2)
-        const uint64_t px = job.n_rows * (uint64_t) (2 * job.max_w + 1), waves = (uint64_t) cu_count * (uint64_t) (q.block / 64);
+        const uint64_t px = job.pixel_count(), waves = (uint64_t) cu_count * (uint64_t) (q.block / 64);
         for (int c = 64; c > q.chunk; c /= 2)
             if (px >= 7ull * (uint64_t) c * waves && (!q.lds || lds_need(sc, true, count, q.block, RTD_WAVE_WORDS(c)) <= RT_LDS_BYTES)) { q.chunk = c; break; }
     }
@@ -183,7 +192,7 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     if (set.blocks_per_cu > 0 && set.blocks_per_cu < per_cu) per_cu = set.blocks_per_cu;
     const uint64_t fullGrid = (uint64_t) pl.cu_count * (uint64_t) per_cu;
     const uint64_t wavesPerBlock = (uint64_t) q.block / 64u;
-    if (pl.job.kind != Job::FRAME) {
+    if (!pl.job.pixels()) {
         const uint64_t wavesWanted = (pl.job.n + 63u) / 64u; // a wave's worth of rays each, at least
         const uint64_t needBlocks = (wavesWanted + wavesPerBlock - 1) / wavesPerBlock;
         q.grid = fullGrid > needBlocks ? needBlocks : fullGrid;
@@ -191,7 +200,7 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
         pl.waves = q.grid * wavesPerBlock;
         return;
     }
-    const uint64_t nLocal = pl.job.n_rows * (uint64_t) (2 * pl.job.max_w + 1);
+    const uint64_t nLocal = pl.job.pixel_count();
     const uint64_t units = (nLocal + (uint64_t) q.chunk - 1) / (uint64_t) q.chunk;
     const uint64_t needBlocks = (units + wavesPerBlock - 1) / wavesPerBlock;
     q.grid = fullGrid > needBlocks ? needBlocks : fullGrid;
@@ -240,8 +249,9 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     }
     pl.a = pl.b = q;
     pl.a.total_waves = pl.b.total_waves = (uint32_t) (fullGrid * wavesPerBlock);
-    pl.a.mode = 1; pl.a.chunk = chunkA;
-    pl.b.mode = 2; pl.b.chunk = chunkB;
+    const int fp = pl.job.kind == Job::FOOTPRINTS ? 6 : 0;
+    pl.a.mode = fp + 1; pl.a.chunk = chunkA;
+    pl.b.mode = fp + 2; pl.b.chunk = chunkB;
     place_pass(pl.a, sc, RTD_WAVE_WORDS_A(chunkA));
     place_pass(pl.b, sc, RTD_WAVE_WORDS(chunkB));
     const uint64_t unitsA = (nLocal + (uint64_t) chunkA - 1) / (uint64_t) chunkA;

@@ -63,14 +63,15 @@ struct RenderParams {
     double *ray_log;               // [ray_log_cap][6]: origin, direction; null outside a probe
     unsigned int *ray_log_count;   // rays that wanted a slot (may exceed the capacity: the probe is then repeated more thinly)
     uint32_t ray_log_cap, ray_log_mask;
-    // the ray-list modes (MODE 4 / 5, run_rays; rt_trace_rays / rt_hit_objects): read only there
-    const double *rays;            // [ray_n][6]: origin, vector (Ray.make' is applied on the device)
+    // the ray-list modes (MODE 4 / 5, run_rays; rt_trace_rays / rt_hit_objects): read only there -- and, `rays` and `ray_base`, in the
+    // footprint modes (MODE 6 / 7 / 8), where the pixels are cols = n, n_rows = 1, row_first = 0, row_stride = 1
+    const double *rays;            // [ray_n][6]: origin, vector (Ray.make' is applied on the device); footprints: [n][12] origin, base, du, dv
     uint32_t *ray_rng;             // [ray_n][4]: xorshift128 states, read and written back; null: stream (seed, ray_base + i, ray_sample)
     uint8_t *ray_colour;           // [ray_n][3] (MODE 4)
     int32_t *ray_hit;              // [ray_n] (MODE 5): index into rt_scene_create's array, -1 none, -2 Ray.make' failed
     double *ray_strike;            // [ray_n][3] or null (MODE 5)
     const int32_t *obj_to_orig;    // object-table index -> index into rt_scene_create's array (MODE 5)
-    uint64_t ray_n, ray_base;
+    uint64_t ray_n, ray_base;      // (footprints: ray_base is stream_base)
     uint32_t ray_sample;
 };
 
@@ -193,7 +194,8 @@ enum { L_IDLE = 0, L_WALK = 1, L_DONE = 2, L_SLOW = 3, L_LAMB = 4, L_TEX = 5 };
 
 // LOG: the kernel may be asked to log rays (rt_scene_tune's probe): only the fused mode's instantiations carry that code -- the
 // log's four kernel arguments otherwise sit in scalar registers across the whole loop of the two-pass kernels, which have none to spare
-template <bool LDS, bool COUNT, bool TEX, bool LOG>
+// FP: the pixels are the caller's footprints (MODE 6 / 7 / 8): a sample's ray comes from footprint_ray instead of camera_ray
+template <bool LDS, bool COUNT, bool TEX, bool LOG, bool FP = false>
 struct Sched {
     const RenderParams &p;
     const SceneView<LDS> &sc;
@@ -253,12 +255,17 @@ struct Sched {
         slotOff = slot_off;
         colour = RTD_WHITE;
         bounces = 0;
-        const CameraParams *cp = p.cam_ptr;
-        asm volatile("" : "+s"(cp)); // keep the camera's 32 dwords out of the loop-carried SGPR set
-        if (camera_ray(*cp, row, col, rng, o, d)) {
+        bool made;
+        if constexpr (FP) made = footprint_ray(p.rays + 12u * (size_t) (uint32_t) row, rng, o, d); // `row` is the footprint's list index
+        else {
+            const CameraParams *cp = p.cam_ptr;
+            asm volatile("" : "+s"(cp)); // keep the camera's 32 dwords out of the loop-carried SGPR set
+            made = camera_ray(*cp, row, col, rng, o, d);
+        }
+        if (made) {
             st = L_WALK;
             walk_begin(w, sc.first);
-            if (!COUNT && cand != RTD_CAND_WALK) { // the tree walk of this pixel's camera rays was made once (pixel_candidates)
+            if (!FP && !COUNT && cand != RTD_CAND_WALK) { // the tree walk of this pixel's camera rays was made once (pixel_candidates)
                 w.off = end; pend = cand; pend1 = cand2;
                 if (cand == 0u) st = L_DONE; // nothing in reach: straight to the unbounded objects
             }
@@ -571,11 +578,11 @@ struct Sched {
 
 // Trace `total` items of the current unit.  Item i belongs to pixel slot map[i / per] (or i / per when map is null)
 // and is sample s_base + i % per of that pixel; its colour is added to accumulator slot (sample < split ? 0 : 1).
-template <bool LDS, bool COUNT, bool COST, bool TEX, bool LOG>
+template <bool LDS, bool COUNT, bool COST, bool TEX, bool LOG, bool FP>
 RTD_INLINE void run_items(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, RTD_AS3 uint32_t *acc, const RTD_AS3 uint32_t *pix,
                           const RTD_AS3 uint32_t *cand, const RTD_AS3 uint32_t *live, bool use_live, uint32_t total, uint32_t per, uint32_t s_base,
                           uint32_t split, Counters &cnt, StageStats &ss) {
-    Sched<LDS, COUNT, TEX, LOG> L(p, sc, cnt, ss, pool, poolLds);
+    Sched<LDS, COUNT, TEX, LOG, FP> L(p, sc, cnt, ss, pool, poolLds);
     uint32_t next = 0; // wave-uniform
     const bool fastDiv = total < (1u << 22) && per < (1u << 23); // see div_uniform
     const float perRcp = 1.0f / (float) per;
@@ -602,7 +609,8 @@ RTD_INLINE void run_items(const RenderParams &p, const SceneView<LDS> &sc, unsig
                         int row = (int) pix[slot * 4 + 0], col = (int) pix[slot * 4 + 1];
                         uint64_t pkey = (uint64_t) pix[slot * 4 + 2] | ((uint64_t) pix[slot * 4 + 3] << 32);
                         // low half: acc word, high half: pixel slot
-                        L.start_item(pkey, s, row, col, (((s < split) ? 0u : (uint32_t) p.chunk * 3u) + slot * 3u) | (slot << 16), cand[slot * 2], cand[slot * 2 + 1]);
+                        L.start_item(pkey, s, row, col, (((s < split) ? 0u : (uint32_t) p.chunk * 3u) + slot * 3u) | (slot << 16), FP ? RTD_CAND_WALK : cand[slot * 2],
+                                     FP ? RTD_CAND_WALK : cand[slot * 2 + 1]); // (footprint rays walk the tree: no pixel candidates)
                     }
                 }
             }
@@ -747,14 +755,14 @@ RTD_INLINE void run_rays(const RenderParams &p, const SceneView<LDS> &sc, unsign
 // hands out its items: two accumulator slots alternate, a range is flushed (its sums added to what pass A left in `accum`) when
 // its last path has ended.  There is no dependency between ranges, so no lane waits at a range boundary -- which is what makes
 // small ranges (good load balance across waves) affordable.  Lane states and stage scheduling are Sched's.
-template <bool LDS, bool COUNT, bool TEX>
+template <bool LDS, bool COUNT, bool TEX, bool FP>
 RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, RTD_AS3 uint32_t *wv, uint32_t n1, uint32_t n2, Counters &cnt,
                            StageStats &ss, uint64_t &sampleCount) {
     const int lane = threadIdx.x & 63;
     const uint32_t P = (uint32_t) p.chunk;
     const uint32_t SW = 7u * P; // words per slot: acc [P][3] then pix [P][4]
     const unsigned long long nList = (unsigned long long) *p.live_count;
-    Sched<LDS, COUNT, TEX, false> L(p, sc, cnt, ss, pool, poolLds); // slotOff: word offset from wv of the path's accumulator triple (>= SW: slot 1)
+    Sched<LDS, COUNT, TEX, false, FP> L(p, sc, cnt, ss, pool, poolLds); // slotOff: word offset from wv of the path's accumulator triple (>= SW: slot 1)
 
     // wave-uniform: the range being handed out (cur) and the one draining (prev)
     unsigned long long curFirst = 0, prevFirst = 0;
@@ -821,6 +829,13 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                     for (uint32_t i = (uint32_t) lane; i < 3u * P; i += 64u) acc[i] = 0u;
                     if ((uint32_t) lane < npx) {
                         const unsigned long long lp = (unsigned long long) p.live_list[first + (uint32_t) lane];
+                        if constexpr (FP) { // the list index where a frame keeps (row, col); the stream of (seed, stream_base + index)
+                            const uint64_t pkey = pixel_key(p.seed_key, p.ray_base + lp);
+                            pix[lane * 4 + 0] = (uint32_t) lp;
+                            pix[lane * 4 + 1] = 0u;
+                            pix[lane * 4 + 2] = (uint32_t) pkey;
+                            pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
+                        } else {
                         uint32_t lr = (uint32_t) (lp / (unsigned long long) p.cols);
                         uint32_t c = (uint32_t) (lp - (unsigned long long) lr * (unsigned long long) p.cols);
                         uint32_t r = (uint32_t) p.row_first + lr * (uint32_t) p.row_stride;
@@ -835,6 +850,7 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                         const uint32_t c1 = pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, c2);
                         wv[14u * P + (curSlot * P + lane) * 2u] = c1;
                         wv[14u * P + (curSlot * P + lane) * 2u + 1u] = c2;
+                        }
                     }
                     __builtin_amdgcn_wave_barrier();
                     curFirst = first; curNpx = npx; curNext = 0u; curTotal = npx * n2; curOut = 0u;
@@ -866,7 +882,8 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                         const RTD_AS3 uint32_t *pix = wv + curSlot * SW + 3u * P;
                         const int row = (int) pix[j * 4 + 0], col = (int) pix[j * 4 + 1];
                         const uint64_t pkey = (uint64_t) pix[j * 4 + 2] | ((uint64_t) pix[j * 4 + 3] << 32);
-                        started = L.start_item(pkey, smp, row, col, curSlot * SW + j * 3u, wv[14u * P + (curSlot * P + j) * 2u], wv[14u * P + (curSlot * P + j) * 2u + 1u]);
+                        started = L.start_item(pkey, smp, row, col, curSlot * SW + j * 3u, FP ? RTD_CAND_WALK : wv[14u * P + (curSlot * P + j) * 2u],
+                                               FP ? RTD_CAND_WALK : wv[14u * P + (curSlot * P + j) * 2u + 1u]);
                     }
                 }
                 L.parked -= nUnA;
@@ -953,6 +970,9 @@ RTD_INLINE uint32_t stage_nodes32(const RenderParams &p, unsigned char *smem) {
 //         of the kernels that render frames).
 // MODE 4: the caller's rays through Scene.traceRay; MODE 5: the caller's rays through Scene.hitObject (run_rays).  No pixels, so no
 //         per-wave LDS scratch: the LDS holds the scene (or the top of its tree) and the Lambert pools only.
+// MODE 6 / 7 / 8: MODE 0 / 1 / 2 over a caller's footprint list (rt_render_footprints): pixel i of p.n_rows * p.cols is footprint i of
+//         p.rays ([n][12]: origin, base, du, dv), its stream that of (seed, p.ray_base + i); a sample's ray is footprint_ray's; no pixel
+//         candidates.  Everything else -- units, accumulators, the decision, the compaction, pass B's ordered list -- is the frame's.
 // Per-pixel cost is heavy-tailed (a pixel on a glass sphere: ~20 rays per sample, 4 ms of one wave), so when a shard has only a few
 // units per wave the fused kernel ends with most waves waiting for a few long units started late; A + sort + B removes that tail.
 // Every mode computes the same integers: which wave traces which sample when has no effect (streams are per item).
@@ -960,7 +980,10 @@ RTD_INLINE uint32_t stage_nodes32(const RenderParams &p, unsigned char *smem) {
 template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX>
 __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr bool FUSED = MODE == 0 || MODE == 3;
+    constexpr bool FP = MODE >= 6;             // the pixels are the caller's footprints
+    constexpr int PM = FP ? MODE - 6 : MODE;   // ... and run as this pixel mode
+    constexpr bool RAYS = MODE == 4 || MODE == 5;
+    constexpr bool FUSED = PM == 0 || PM == 3;
     const int lane = threadIdx.x & 63;
     // the wave's index as a SCALAR: everything derived from it (the wave's LDS scratch, its park pools) then has a scalar base, and the
     // pools' field addresses are scalar base + 32-bit lane offset instead of 64-bit vector arithmetic kept alive across the loop
@@ -974,7 +997,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     scv.lds_thr = p.lds_node_thr;
     const SceneView<LDS> &sc = scv;
     const uint32_t P = (uint32_t) p.chunk;
-    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * (MODE >= 4 ? 0u : MODE == 1 ? RTD_WAVE_WORDS_A(P) : RTD_WAVE_WORDS(P));
+    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * (RAYS ? 0u : PM == 1 ? RTD_WAVE_WORDS_A(P) : RTD_WAVE_WORDS(P));
     RTD_AS3 uint32_t *acc = wv;
     RTD_AS3 uint32_t *pix = wv + 6u * P;
     RTD_AS3 uint32_t *live = pix + 4u * P;
@@ -982,7 +1005,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     unsigned char *pool = p.park_pool + ((size_t) blockIdx.x * (BLOCK / 64) + (size_t) wave) * (size_t) RTD_PARK_ENTRY_BYTES *
                                         (size_t) (p.park + (p.park_l_lds ? 0 : p.park_l) + (TEX ? p.park : 0));
     // the Lambert pools in LDS (if any) follow the waves' scratch
-    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * (MODE >= 4 ? 0u : MODE == 1 ? RTD_WAVE_WORDS_A(P) : RTD_WAVE_WORDS(P)) * 4u +
+    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * (RAYS ? 0u : PM == 1 ? RTD_WAVE_WORDS_A(P) : RTD_WAVE_WORDS(P)) * 4u +
                                      (size_t) wave * (size_t) RTD_PARK_L_LDS_BYTES * (size_t) p.park_l;
 
     const uint64_t nLocal = (uint64_t) p.n_rows * (uint64_t) p.cols;
@@ -1005,8 +1028,8 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     uint32_t earlyCount = 0;
     uint64_t sampleCount = 0; // Scene.traceOnce calls = sum of PixelStats.Count
 
-    if constexpr (MODE >= 4) run_rays<LDS, COUNT, TEX, MODE == 5>(p, sc, pool, poolLds, cnt, ss);
-    else if (MODE == 2) run_stream<LDS, COUNT, TEX>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
+    if constexpr (RAYS) run_rays<LDS, COUNT, TEX, MODE == 5>(p, sc, pool, poolLds, cnt, ss);
+    else if (PM == 2) run_stream<LDS, COUNT, TEX, FP>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
     else
     for (;;) {
         uint32_t unit = 0;
@@ -1018,10 +1041,18 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
 
         // per-pixel coordinates (Scene.fs:219,226) and stream key; clear the accumulators
         for (uint32_t i = (uint32_t) lane; i < 6u * P; i += 64u) acc[i] = 0u;
-        if (MODE == 1 && (uint32_t) lane < P) acc[10u * P + lane] = 0u;
+        if (PM == 1 && (uint32_t) lane < P) acc[10u * P + lane] = 0u;
         unsigned long long lp = 0; // local pixel of lane j < npx
         if ((uint32_t) lane < npx) {
             lp = first + (uint32_t) lane;
+            if constexpr (FP) { // a footprint list (a frame of one row): the list index where a frame keeps (row, col), the stream of
+                                // (seed, stream_base + index), and no pixel candidates -- its camera rays walk the tree (run_items)
+                const uint64_t pkey = pixel_key(p.seed_key, p.ray_base + lp);
+                pix[lane * 4 + 0] = (uint32_t) lp;
+                pix[lane * 4 + 1] = 0u;
+                pix[lane * 4 + 2] = (uint32_t) pkey;
+                pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
+            } else {
             uint32_t lr = (uint32_t) (lp / (unsigned long long) p.cols);
             uint32_t c = (uint32_t) (lp - (unsigned long long) lr * (unsigned long long) p.cols);
             uint32_t r = (uint32_t) p.row_first + lr * (uint32_t) p.row_stride;
@@ -1036,11 +1067,12 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
             const uint32_t c1 = pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, c2);
             cand[lane * 2] = c1;
             cand[lane * 2 + 1] = c2;
+            }
         }
         __builtin_amdgcn_wave_barrier();
 
         // ---- phase 1: 2k+1 samples per pixel, sums split after sample k (Scene.fs:172-182) ----
-        run_items<LDS, COUNT, MODE == 1, TEX, MODE == 3>(p, sc, pool, poolLds, acc, pix, cand, live, false, npx * n1, n1, 0u, k + 1u, cnt, ss);
+        run_items<LDS, COUNT, PM == 1, TEX, PM == 3, FP>(p, sc, pool, poolLds, acc, pix, cand, live, false, npx * n1, n1, 0u, k + 1u, cnt, ss);
         __builtin_amdgcn_wave_barrier();
 
         // ---- decide (Scene.fs:177-188) and compact the pixels that continue ----
@@ -1075,7 +1107,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
 
         // ---- phase 2: the remaining spp-2k-1 samples of the surviving pixels (Scene.fs:191-192) ----
         if (FUSED && nLive > 0u) {
-            run_items<LDS, COUNT, false, TEX, MODE == 3>(p, sc, pool, poolLds, acc, pix, cand, live, true, nLive * n2, n2, n1, 0xFFFFFFFFu, cnt, ss);
+            run_items<LDS, COUNT, false, TEX, PM == 3, FP>(p, sc, pool, poolLds, acc, pix, cand, live, true, nLive * n2, n2, n1, 0xFFFFFFFFu, cnt, ss);
             __builtin_amdgcn_wave_barrier();
         }
 
@@ -1136,7 +1168,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
             atomicAdd(&p.counters[31], ss.tLamb);
             if (!COUNT) { atomicAdd(&p.counters[14], ss.loopTrips); atomicAdd(&p.counters[15], ss.loopLanes); } // (the counting variant keeps its wave lifetimes there)
 #ifdef RTD_STAGE_CLOCKS
-            if (!COUNT && MODE == 2) { // the census describes pass B's timed kernel
+            if (!COUNT && PM == 2) { // the census describes pass B's timed kernel
                 const uint32_t cz[16] = {ss.turns, ss.lambBatches, ss.lambLanes, ss.newRefills, ss.newItems, ss.unparkL, ss.unparkA, ss.storeBlocksL, ss.storeLanesL,
                                          ss.storeBlocksA, ss.lightBatches, ss.lightLanes, ss.missLanes, ss.ranges, ss.flushes, ss.leafLanes};
                 for (int i = 0; i < 16; ++i) atomicAdd(&g_census[i], (unsigned long long) cz[i]);

@@ -200,7 +200,7 @@ static int allow_full_lds(const void *fn) {
 // blocks of 256 and 1024 threads only, and the hit queries (mode 5) shade nothing, so they have no textured variant.  The plan
 // never asks for one of the others; if it did, the launch fails (no kernel is substituted).
 template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX> static render_fn kernel_if_built() {
-    if constexpr ((MODE >= 4 && BLOCK != 256 && BLOCK != 1024) || (MODE == 5 && TEX)) return nullptr;
+    if constexpr ((MODE >= 4 && BLOCK != 256 && BLOCK != 1024) || (MODE == 5 && TEX)) return nullptr; // (the footprint modes 6-8: as the ray lists)
     else return render_kernel<LDS, COUNT, BLOCK, MODE, TEX>;
 }
 template <int BLOCK, int MODE, bool TEX> static render_fn pick_variant(bool lds, bool count) {
@@ -219,7 +219,11 @@ static render_fn pick_kernel(const rtp::Pass &q) {
     case 2: return q.tex ? pick_mode<2, true>(q) : pick_mode<2, false>(q);
     case 3: return q.tex ? pick_mode<3, true>(q) : pick_mode<3, false>(q);
     case 4: return q.tex ? pick_mode<4, true>(q) : pick_mode<4, false>(q);
-    default: return q.tex ? nullptr : pick_mode<5, false>(q);
+    case 5: return q.tex ? nullptr : pick_mode<5, false>(q);
+    case 6: return q.tex ? pick_mode<6, true>(q) : pick_mode<6, false>(q);
+    case 7: return q.tex ? pick_mode<7, true>(q) : pick_mode<7, false>(q);
+    case 8: return q.tex ? pick_mode<8, true>(q) : pick_mode<8, false>(q);
+    default: return nullptr;
     }
 }
 
@@ -512,7 +516,7 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
     const Settings &s = pl.set;
     const rtp::Job &j = pl.job;
     put(1);
-    put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : 2));
+    put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : (j.kind == rtp::Job::HIT ? 2 : 3)));
     put((int64_t) sc.lds_total); put((int64_t) sc.lds32_total); put(sc.n_nodes); put((int64_t) sc.n_objects); put(sc.tex);
     put(s.block); put(s.chunk); put(s.blocks_per_cu); put(s.yield); put(s.refill); put(s.passes); put(s.park);
     put(pl.one.count); put(j.ray_log); put((int64_t) j.n_rows); put(j.max_w); put(j.spp); put((int64_t) j.n); put(pl.cu_count); put(per_cu);
@@ -561,7 +565,7 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     // two-pass launch use the grid that follows from it
     int perCu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *) fn, block, ldsBytes));
-    if (perCu < 1) return fail(RT_ERR_HIP, job.kind == rtp::Job::FRAME ? "render kernel does not fit on a CU (occupancy 0)" : "ray-list kernel does not fit on a CU (occupancy 0)");
+    if (perCu < 1) return fail(RT_ERR_HIP, job.pixels() ? "render kernel does not fit on a CU (occupancy 0)" : "ray-list kernel does not fit on a CU (occupancy 0)");
     rtp::plan_finish(plan, perCu);
     remember_plan(plan, perCu);
     const uint64_t grid = plan.one.grid;
@@ -1071,6 +1075,102 @@ int rt_trace_rays_device(const rt_scene *scene, int32_t device, size_t n, const 
     const int rc = check_rays(scene, n, d_rays, d_colour, bounce_depth, options);
     if (rc != RT_OK) return rc;
     return run_rays_device(scene, device, trace_job(n, d_rays, d_rng, seed, stream_base, sample, bounce_depth, d_colour), flags, stream, options, stats);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// footprints: Scene.renderPixel over the caller's pixels, each with a camera of its own (render_kernel MODE 6 / 7 / 8)
+// ------------------------------------------------------------------------------------------------------------
+// Every argument check of the two footprint entry points, made before anything touches a device.
+static int check_footprints(const rt_scene *scene, size_t n, const void *footprints, const void *accum, int32_t spp, int32_t bounce_depth,
+                            const rt_render_options *options) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (n > 0 && !footprints) return fail(RT_ERR_INVALID_ARGUMENT, "footprints is NULL");
+    if (n > 0 && !accum) return fail(RT_ERR_INVALID_ARGUMENT, "accum is NULL");
+    if (n > (size_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "more than INT32_MAX footprints");
+    if (spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel must be >= 1");
+    if (spp > 8000000) return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel too large for int32 sums (255*spp)");
+    if (bounce_depth < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth must be >= 0");
+    if (bounce_depth > 0xFFFFFF) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth too large");
+    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
+    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
+    return RT_OK;
+}
+
+// Enqueues one footprint launch on `stream` (n > 0, arguments checked): to the kernel the list is a frame of one row and n columns
+// whose pixel i reads footprint i and owns the stream of (seed, stream_base + i); then enqueue(), as for a frame shard.
+static int launch_footprints(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints, int32_t spp, int32_t bounce_depth,
+                             uint64_t seed, uint64_t stream_base, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
+                             const rt_render_options *options, bool want_stats, Pending &pd) {
+    RenderParams p{};
+    p.spp = spp;
+    p.depth = bounce_depth;
+    p.seed_key = mix64(seed + 0x9E3779B97F4A7C15ull); // seed_key(), host side
+    p.cols = (int32_t) n;
+    p.row_first = 0; p.row_stride = 1; p.n_rows = 1;
+    p.accum = (int32_t *) d_accum;
+    p.rgb = (uint8_t *) d_rgb;
+    p.rays = (const double *) d_footprints;
+    p.ray_n = n;
+    p.ray_base = stream_base;
+    rtp::Job job;
+    job.kind = rtp::Job::FOOTPRINTS;
+    job.n = n; job.spp = spp;
+    return enqueue(scene, device, job, resolve_settings(options), flags, stream, p, CameraParams{}, want_stats, pd); // (no camera: never read in these modes)
+}
+
+extern "C" {
+
+int rt_render_footprints_device(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints, int32_t samples_per_pixel,
+                                int32_t bounce_depth, uint64_t seed, uint64_t stream_base, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
+                                const rt_render_options *options, rt_stats *stats) {
+    int rc = check_footprints(scene, n, d_footprints, d_accum, samples_per_pixel, bounce_depth, options);
+    if (rc != RT_OK) return rc;
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    Pending pd;
+    rc = launch_footprints(scene, device, n, d_footprints, samples_per_pixel, bounce_depth, seed, stream_base, flags, d_accum, d_rgb, stream, options,
+                           stats != nullptr, pd);
+    if (rc != RT_OK || !stats) return rc;
+    return collect_stats(pd, stats);
+}
+
+// The host variant: one device allocation for the footprints and the outputs, the device variant on the null stream, the outputs copied back.
+int rt_render_footprints(const rt_scene *scene, int32_t device, size_t n, const double *footprints, int32_t samples_per_pixel, int32_t bounce_depth,
+                         uint64_t seed, uint64_t stream_base, uint32_t flags, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
+    int rc = check_footprints(scene, n, footprints, accum, samples_per_pixel, bounce_depth, nullptr);
+    if (rc != RT_OK) return rc;
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
+    const size_t bFp = up16(n * 96u), bAcc = up16(n * 16u), bRgb = rgb ? up16(n * 3u) : 0u;
+    unsigned char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **) &buf, bFp + bAcc + bRgb));
+    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
+    HIP_TRY(hipMemcpy(buf, footprints, n * 96u, hipMemcpyHostToDevice));
+    rt_stats local;
+    rc = rt_render_footprints_device(scene, device, n, buf, samples_per_pixel, bounce_depth, seed, stream_base, flags, buf + bFp,
+                                     bRgb ? buf + bFp + bAcc : nullptr, nullptr, nullptr, &local);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpy(accum, buf + bFp, n * 16u, hipMemcpyDeviceToHost));
+    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bFp + bAcc, n * 3u, hipMemcpyDeviceToHost));
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
 }
 
 } // extern "C"

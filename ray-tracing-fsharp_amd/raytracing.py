@@ -402,7 +402,7 @@ class Scene:
 
     @property
     def last_stats(self) -> Optional[dict]:
-        """The statistics of the calling THREAD's last render_rows / hitObject / traceRays on this scene (None before its first,
+        """The statistics of the calling THREAD's last render_rows / hitObject / traceRays / renderFootprints on this scene (None before its first,
         or after a device call with stats=False).  Per thread, like rt_last_error: a scene may be used from many threads at once."""
         return getattr(self._local, "stats", None)
 
@@ -574,6 +574,41 @@ class Scene:
                                 sample, bounceDepth, flags, _u8(colour), C.byref(st)))
         self.last_stats = st.as_dict()
         return colour, g
+
+    def renderFootprints(self, footprints, samplesPerPixel: int, bounceDepth: int, *, seed: int = 0, stream_base: int = 0,
+                         device: Optional[int] = None, counters: bool = False, stats: bool = True,
+                         options: Optional[A.rt_render_options] = None) -> RenderResult:
+        """Scene.renderPixel (Scene.fs:157-194) for caller-defined cameras: footprints [n, 12] float64, per pixel origin, base, du,
+        dv.  Sample s of pixel i draws (r1, r2) from the stream keyed (seed, stream_base + i, s) and traces
+        Ray.make'(origin, (base + r1*du) + r2*dv) at most bounceDepth+1 hits; the adaptive stop is the reference's, with
+        samplesPerPixel -> RenderResult(accum [n, 4] int32, rgb [n, 3] uint8, stats).  numpy arrays / torch tensors as for hitObject:
+        a tensor goes through rt_render_footprints_device on torch.cuda.current_stream() and the results are tensors (stats=False: no
+        wait for the device, stats and last_stats are None)."""
+        flags = A.RT_RENDER_COUNTERS if counters else 0
+        if _is_torch(footprints):
+            torch = _torch()
+            f = _tensor_arg(footprints, "footprints", (torch.float64,), 12)
+            dev = _tensor_device(f, device)
+            n = f.shape[0]
+            accum = torch.empty((n, 4), dtype=torch.int32, device=f.device)
+            rgb = torch.empty((n, 3), dtype=torch.uint8, device=f.device)
+            st = A.rt_stats() if stats else None
+            check(lib.rt_render_footprints_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
+                                                  accum.data_ptr(), rgb.data_ptr(), torch.cuda.current_stream(f.device).cuda_stream,
+                                                  _ref(options), _ref(st)))
+            self.last_stats = st.as_dict() if st is not None else None
+            return RenderResult(accum, rgb, self.last_stats)
+        if options is not None:
+            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        f = _array_arg(footprints, "footprints", np.float64, 12)
+        n = f.shape[0]
+        accum = np.zeros((n, 4), np.int32)
+        rgb = np.zeros((n, 3), np.uint8)
+        st = A.rt_stats()
+        check(lib.rt_render_footprints(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed, stream_base,
+                                       flags, _i32(accum), _u8(rgb), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return RenderResult(accum, rgb, self.last_stats)
 
     @staticmethod
     def render(progressIncrement: Callable[[float], None], log: Callable[[str], None], maxWidthCoord: int, maxHeightCoord: int,
