@@ -374,6 +374,58 @@ int rt_render_footprints_device(const rt_scene *scene, int32_t device, size_t n,
                                 uint32_t flags, void *d_accum, void *d_rgb, void *stream,
                                 const rt_render_options *options, rt_stats *stats);
 
+/* ---- Extending a rendered buffer to a higher sample count --------------------------------------------------------------
+ * render at a, then extend a -> b  ==  render at b, for every PixelStats word and every rgb byte, for any 12 <= a <= b
+ * (DESIGN.md "Extending a frame"): sample s of a pixel is the same ray tree whenever it is traced, the sums are integers, and
+ * Scene.renderPixel's stopping rule (Scene.fs:172-188) reads only the first 11 samples at every spp >= 10.  A preview, a
+ * time-budgeted render, a checkpoint or "more samples, please" therefore costs only the samples it adds.
+ *
+ * camera->samples_per_pixel (footprints: samples_per_pixel) is the TARGET b; samples_done is the sample count `accum` was
+ * rendered or last extended with.  Every other argument means what it meant in the call that produced the buffer and must
+ * be the same: scene, camera, geometry, seed, row shard, footprints, stream_base.  accum is read and written; rgb is output
+ * only and may be NULL.
+ *
+ * Pixel classes: Count == samples_done -- the pixel is continued with samples samples_done .. b-1; Count == 11 -- it stopped
+ * early, is final at every such spp, and its PixelStats are not touched; any other Count -- the buffer is not what the
+ * arguments say (MALFORMED).  If the shard holds even one such pixel the call continues NO pixel: accum stays as it was, bit
+ * for bit, rgb is not written, and the host variants return RT_ERR_INVALID_ARGUMENT; so does the device variant when stats is
+ * given (it synchronises).  With stats == NULL the device variant cannot report it: the unchanged Counts are the caller's
+ * evidence.  Otherwise rgb, when given, is written for EVERY pixel of the shard, final ones included, as PixelStats.mean of
+ * the resulting sums.
+ *
+ * Argument checks come before any device call: RT_ERR_INVALID_ARGUMENT for samples_done < 12 (below, firstTrial differs and
+ * Count cannot tell a stopped pixel from a finished one), a target below samples_done, a NULL accum with pixels to do, a
+ * shard of 2^32 pixels or more, and everything the base call rejects; nothing is written then.  Target == samples_done and
+ * empty shards (n_rows = 0, n = 0) are no-ops returning RT_OK with zeroed stats.
+ *
+ * stats describe this call alone: samples = the samples added, pixels = the shard's pixels, pixels_early = the final pixels
+ * found, kernel_ms = list building plus pass B; under RT_RENDER_COUNTERS the four counters cover the samples this call traced,
+ * so the counters of render(a) plus extend(a -> b) equal render(b)'s.
+ *
+ * The device variants follow rt_render_device's contract: enqueued on `stream`, scratch is stream-ordered, with
+ * stats == NULL the call returns right after the launch, any number of calls may be in flight, the caller's current device
+ * is left as it was.  options: as for the base call; `passes` is accepted and ignored -- an extension is pass B alone (a
+ * list-building kernel over the stored Counts in place of pass A and the ordering), there is no fused form of it.
+ * Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */
+int rt_render_extend(const rt_scene *scene, const rt_camera *camera,
+                     int32_t max_width_coord, int32_t max_height_coord, uint64_t seed,
+                     int32_t device, int32_t row_first, int32_t row_stride, int32_t n_rows,
+                     uint32_t flags, int32_t samples_done, int32_t *accum /* in, out */, uint8_t *rgb /* out, may be NULL */,
+                     rt_stats *stats);
+int rt_render_extend_device(const rt_scene *scene, const rt_camera *camera,
+                            int32_t max_width_coord, int32_t max_height_coord, uint64_t seed,
+                            int32_t device, int32_t row_first, int32_t row_stride, int32_t n_rows,
+                            uint32_t flags, int32_t samples_done, void *d_accum, void *d_rgb, void *stream,
+                            const rt_render_options *options, rt_stats *stats);
+int rt_render_footprints_extend(const rt_scene *scene, int32_t device, size_t n, const double *footprints,
+                                int32_t samples_per_pixel /* target */, int32_t bounce_depth, uint64_t seed, uint64_t stream_base,
+                                uint32_t flags, int32_t samples_done, int32_t *accum /* in, out */, uint8_t *rgb /* out, may be NULL */,
+                                rt_stats *stats);
+int rt_render_footprints_extend_device(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints,
+                                       int32_t samples_per_pixel /* target */, int32_t bounce_depth, uint64_t seed, uint64_t stream_base,
+                                       uint32_t flags, int32_t samples_done, void *d_accum, void *d_rgb, void *stream,
+                                       const rt_render_options *options, rt_stats *stats);
+
 /* ---- Output side (ImageOutput.fs:11-30,163-197) -------------------------------------------------- */
 uint8_t rt_gamma_correct(uint8_t b); /* PixelOutput.correct (ImageOutput.fs:11-18) */
 /* ImageOutput.writePpm gammaCorrect pixels file (ImageOutput.fs:163-197): P3, no trailing newline. */
@@ -438,6 +490,9 @@ int rt_last_stage_stats(uint64_t out[16]);
  *   [35..48] the fused or ray-list kernel (F_), [49..62] pass A (A_), [63..76] pass B (B_), each: mode grid lds_bytes chunk park
  *            park_l park_l_lds lds_node_bytes lds_node_thr yield leaf_wait refill k total_waves.  F_ is what ran unless two_pass;
  *            A_ and B_ are filled only with two_pass and no error.
+ *   [77]     first_sample: 0 for a fresh render; for an extension (rt_render_extend*, rt_render_footprints_extend*) its samples_done.
+ *            An extension reports kind 0 or 3, two_pass 1, pairs and sort 0, every A_ word 0 (no pass A is launched) and pass B as
+ *            the same job gets it with passes = 2.  [78..79] are 0.
  * A call that fails before its plan is complete (bad arguments, no kernel built for the launch, occupancy 0) leaves the previous
  * launch's report in place: read it after a call that returned RT_OK.
  * An added diagnostic symbol only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */

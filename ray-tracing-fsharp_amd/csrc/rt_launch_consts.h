@@ -27,6 +27,10 @@
 // ---- pass B's cost-ordered list: bucket sort of (cost, pixel) pairs ----
 #define RTD_COST_BUCKETS 64
 
+// ---- extending a rendered buffer (rt_render_extend; DESIGN.md "Extending a frame") ----
+#define RTD_EARLY_COUNT 11     /* PixelStats.Count of a pixel that stopped early at any spp >= 10: 2k+1 with k = min 5 (spp/2) = 5 */
+#define RTD_EXTEND_MIN_DONE 12 /* the least samples_done: k is 5 on both sides, and Count tells a stopped pixel (11) from a finished one */
+
 // ---- scene image (rt_device.h) ----
 #define RTD_NODE32_BYTES 64 /* a single-precision filter record of the timed node loop */
 

@@ -42,6 +42,9 @@ struct Job {
     uint64_t n_rows = 0; int32_t max_w = 0, spp = 1; // FRAME
     bool ray_log = false;                            // FRAME: rt_scene_tune's probe
     uint64_t n = 0;                                  // TRACE, HIT: rays; FOOTPRINTS: pixels (with spp)
+    int32_t first_sample = 0;                        // FRAME, FOOTPRINTS: 0 = a fresh render; >= RTD_EXTEND_MIN_DONE: an EXTENSION of a buffer that
+                                                     // holds this many samples per continued pixel, to spp (rt_render_extend): pass B alone
+    bool extend() const { return first_sample != 0; }
     bool pixels() const { return kind == FRAME || kind == FOOTPRINTS; } // planned by the pixel rules, not the ray lists'
     uint64_t pixel_count() const { return kind == FOOTPRINTS ? n : n_rows * (uint64_t) (2 * max_w + 1); }
 };
@@ -62,6 +65,7 @@ struct LaunchPlan {
     bool two_pass = false;
     Pass one;  // the fused kernel or the ray-list kernel; with two_pass only its (kernel, block, lds_bytes) were used, for the occupancy
     Pass a, b; // two_pass: pass A (mode 1) and pass B (mode 2); the three sort kernels run between them
+               // (an extension: two_pass with pass B only -- a.grid = 0, its list comes from the list-building kernel, unordered)
     size_t pairs_bytes = 0, list_bytes = 0, sort_bytes = 0, pool_bytes = 0; // workspace sections behind the launch's scratch, in this order
     uint64_t pixels = 0, waves = 0;                                         // what the statistics report
     const char *error = nullptr; // plan_finish: the launch cannot be made (reported as RT_ERR_HIP, after the scratch was allocated: as before)
@@ -170,7 +174,8 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     // then waits for its longest path: as wide as still leaves a wave seven units, the scene in LDS permitting (2401x1601 px:
     // 4 spp 8.5 -> 16.0 Gray/s, 16 spp 12.3 -> 19.6 with 64 pixels; 1201x801: 7.0 -> 9.3, 10.5 -> 12.5 with 32).
     q.chunk = set.chunk ? set.chunk : 16;
-    if (!set.chunk && set.passes != 2 && job.spp <= 74) { // (below the two-pass rule's 64 samples in phase 2)
+    // (an extension is the same job at the target spp with two passes forced: it never widens for "few samples")
+    if (!set.chunk && set.passes != 2 && !job.extend() && job.spp <= 74) { // (below the two-pass rule's 64 samples in phase 2)
         const uint64_t px = job.pixel_count(), waves = (uint64_t) cu_count * (uint64_t) (q.block / 64);
         for (int c = 64; c > q.chunk; c /= 2)
             if (px >= 7ull * (uint64_t) c * waves && (!q.lds || lds_need(sc, true, count, q.block, RTD_WAVE_WORDS(c)) <= RT_LDS_BYTES)) { q.chunk = c; break; }
@@ -211,18 +216,22 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     // 221 ms in two passes against 227 ms fused; config 4 whole, 507 per wave, 3.75 s against 3.66 s).  spp <= 2k+1 has no second phase at all, and with few remaining samples
     // per pixel a unit is short, so is the tail, and the second launch costs more than it removes (config 2, 100 spp: fused 3.0 ms,
     // two passes 3.5 ms; config 3's 1/8 shard, 500 spp: 51 ms against 30 ms).
-    const int n2 = pl.job.spp - 2 * q.k - 1;
+    const bool ext = pl.job.extend(); // pass B alone, from sample first_sample on: planned as this job with two passes forced
+    const int n2 = pl.job.spp - (ext ? pl.job.first_sample : 2 * q.k + 1);
     pl.two_pass = n2 > 0 && nLocal > 0 && nLocal < (1ull << 32) &&
-                  (set.passes == 2 || (set.passes == 0 && (n2 >= 128 || (n2 >= 64 && nLocal >= (1ull << 21))) && units < 64ull * fullGrid * wavesPerBlock));
+                  (set.passes == 2 || ext || (set.passes == 0 && (n2 >= 128 || (n2 >= 64 && nLocal >= (1ull << 21))) && units < 64ull * fullGrid * wavesPerBlock));
     // (frames of 2 Mpx and more pay for the second launch from ~75 spp: 2401x1601 at 100 spp 23.1 Gray/s fused, 26.9 in two passes; 1201x801: 19.6 / 19.8)
     // (the fused launch sizes its pools by its own grid, the two-pass launch by the full grid: pass B always launches that)
     pl.pool_bytes = park_pool_bytes(pl.two_pass ? fullGrid : q.grid, q);
     pl.waves = (pl.two_pass ? fullGrid : q.grid) * wavesPerBlock;
-    if (!pl.two_pass) return;
-    // workspace: pairs[nLocal] u64, list[nLocal] u32, hist/offsets/cursor[64] u32
-    pl.pairs_bytes = ((size_t) nLocal * 8u + 15u) & ~(size_t) 15u;
+    if (!pl.two_pass) {
+        if (ext && nLocal > 0) pl.error = "an extension needs samples to add and fewer than 2^32 pixels"; // (the entry points refuse both first)
+        return;
+    }
+    // workspace: pairs[nLocal] u64, list[nLocal] u32, hist/offsets/cursor[64] u32 (an extension: the list alone, nothing is sorted)
+    pl.pairs_bytes = ext ? 0u : ((size_t) nLocal * 8u + 15u) & ~(size_t) 15u;
     pl.list_bytes = ((size_t) nLocal * 4u + 15u) & ~(size_t) 15u;
-    pl.sort_bytes = (3u * RTD_COST_BUCKETS * 4u + 15u) & ~(size_t) 15u;
+    pl.sort_bytes = ext ? 0u : (3u * RTD_COST_BUCKETS * 4u + 15u) & ~(size_t) 15u;
     // Unit sizes: pass A traces only 2k+1 samples per pixel, so its units are wide (below); pass B's largest unit is about a
     // sixteenth of a wave's share of the shard (measured best: 32 px at 1/2 frame, 16 at 1/4, 8 at 1/8 of config 3),
     // and shrinks towards the end of the cost-ordered list.
@@ -243,7 +252,7 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
         auto pool_fits = [&](int c) { size_t b = needA(c); return lambert_pool_lds(b, q.block) != 0; };
         while (chunkA > 16 && !pool_fits(chunkA) && pool_fits(chunkA / 2)) chunkA /= 2;
     }
-    if (q.lds && (needA(chunkA) > RT_LDS_BYTES || lds_need(sc, true, q.count, q.block, RTD_WAVE_WORDS(chunkB)) > RT_LDS_BYTES)) {
+    if (q.lds && ((!ext && needA(chunkA) > RT_LDS_BYTES) || lds_need(sc, true, q.count, q.block, RTD_WAVE_WORDS(chunkB)) > RT_LDS_BYTES)) {
         pl.error = "two-pass launch does not fit the LDS";
         return;
     }
@@ -252,12 +261,13 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     const int fp = pl.job.kind == Job::FOOTPRINTS ? 6 : 0;
     pl.a.mode = fp + 1; pl.a.chunk = chunkA;
     pl.b.mode = fp + 2; pl.b.chunk = chunkB;
-    place_pass(pl.a, sc, RTD_WAVE_WORDS_A(chunkA));
     place_pass(pl.b, sc, RTD_WAVE_WORDS(chunkB));
+    pl.b.grid = fullGrid;                            // pass B always launches the full grid (its units shrink along the list)
+    if (ext) { pl.a = Pass{}; pl.a.chunk = 0; return; } // no pass A: nothing of it is launched or reported
+    place_pass(pl.a, sc, RTD_WAVE_WORDS_A(chunkA));
     const uint64_t unitsA = (nLocal + (uint64_t) chunkA - 1) / (uint64_t) chunkA;
     const uint64_t gridA = (unitsA + wavesPerBlock - 1) / wavesPerBlock;
-    pl.a.grid = gridA > fullGrid ? fullGrid : gridA; // pass A's grid is capped by its own unit count,
-    pl.b.grid = fullGrid;                            // pass B always launches the full grid (its units shrink along the list)
+    pl.a.grid = gridA > fullGrid ? fullGrid : gridA; // pass A's grid is capped by its own unit count
 }
 
 } // namespace rtp

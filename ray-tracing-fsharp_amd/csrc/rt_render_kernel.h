@@ -59,6 +59,8 @@ struct RenderParams {
     unsigned int *live_count;      // number of pairs / list entries (device side)
     unsigned long long *queue_b;   // next unassigned list entry
     uint32_t total_waves;          // waves of the grid (guided unit sizes in pass B)
+    int32_t first_b;               // pass B's first sample; 0: 2k+1 (after pass A).  An extension (rt_render_extend) passes samples_done:
+                                   // the list is then extend_list_kernel's, and `accum` holds samples 0 .. first_b-1 of its pixels
     // rt_scene_tune's probe: every ray whose stream-state hash has `ray_log_mask` clear is appended
     double *ray_log;               // [ray_log_cap][6]: origin, direction; null outside a probe
     unsigned int *ray_log_count;   // rays that wanted a slot (may exceed the capacity: the probe is then repeated more thinly)
@@ -1010,8 +1012,8 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
 
     const uint64_t nLocal = (uint64_t) p.n_rows * (uint64_t) p.cols;
     const uint32_t k = (uint32_t) p.k;
-    const uint32_t n1 = 2u * k + 1u;
-    const int n2s = p.spp - 2 * p.k - 1; // Scene.fs:191
+    const uint32_t n1 = (PM == 2 && p.first_b != 0) ? (uint32_t) p.first_b : 2u * k + 1u; // (pass B of an extension starts where the buffer ends)
+    const int n2s = p.spp - (int) n1; // Scene.fs:191
     const uint32_t n2 = n2s > 0 ? (uint32_t) n2s : 0u;
 
     const unsigned long long tStart = COUNT ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -1187,6 +1189,57 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     }
 }
 
+
+// ---- extending a rendered buffer (rt_render_extend): pass B's list from the stored PixelStats, instead of pass A and the sort ----
+// A pixel of a buffer rendered (or last extended) with `done` >= RTD_EXTEND_MIN_DONE samples holds Count == done (it continues: it
+// needs samples done .. spp-1) or Count == RTD_EARLY_COUNT (it stopped early and is final at every such spp).  Any other Count is
+// FOREIGN: the buffer is not what the arguments say.  One coalesced 16-byte load per lane; per wave one agent-scope atomicAdd
+// reserves the list entries of its continuing pixels (pass A's compaction), one counts its final pixels where pass A counts
+// them (counters[5]), one its foreign ones.  The list's order is whatever the compaction gives: no result depends on it.
+__global__ void __launch_bounds__(256) extend_list_kernel(const int32_t *accum, unsigned long long n, int32_t done, unsigned int *live_list,
+                                                          unsigned int *live_count, unsigned long long *counters, unsigned int *foreign) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull;
+    const unsigned long long trips = (n + stride - 1ull) / stride; // uniform over the grid: every lane of a wave makes every ballot
+    unsigned long long nFinal = 0ull, nForeign = 0ull;
+    for (unsigned long long t = 0; t < trips; ++t) {
+        const unsigned long long i = t * stride + (unsigned long long) blockIdx.x * 256ull + threadIdx.x;
+        int count = RTD_EARLY_COUNT;
+        if (i < n) count = ((const i4 *) accum)[i].x;
+        const bool cont = i < n && count == done, foreignPx = i < n && count != done && count != RTD_EARLY_COUNT;
+        const unsigned long long liveMask = __builtin_amdgcn_ballot_w64(cont);
+        const uint32_t nLive = (uint32_t) __popcll(liveMask);
+        if (nLive > 0u) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(live_count, nLive);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (cont) live_list[base + lane_rank(liveMask)] = (unsigned int) i;
+        }
+        nForeign += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(foreignPx));
+        nFinal += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(i < n && count == RTD_EARLY_COUNT));
+    }
+    if (lane == 0) {
+        if (nFinal != 0ull) atomicAdd(&counters[5], nFinal);
+        if (nForeign != 0ull) atomicAdd(foreign, (unsigned int) nForeign); // (n < 2^32: the sum cannot wrap to 0)
+    }
+}
+// One wave, between the list and pass B: a buffer with even one foreign pixel is left as it is -- pass B reads its list length from
+// `live_count`, so zeroing that continues NO pixel -- and `malformed` tells collect_stats (RT_ERR_INVALID_ARGUMENT).
+__global__ void extend_seal_kernel(const unsigned int *foreign, unsigned int *live_count, unsigned int *malformed) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && *foreign != 0u) { *live_count = 0u; *malformed = 1u; }
+}
+// After the seal (so that a malformed buffer gets no byte written): PixelStats.mean of the FINAL pixels; pass B writes the others'.
+__global__ void __launch_bounds__(256) extend_final_rgb_kernel(const int32_t *accum, unsigned long long n, const unsigned int *malformed, uint8_t *rgb) {
+    if (*malformed != 0u) return;
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull;
+    for (unsigned long long i = (unsigned long long) blockIdx.x * 256ull + threadIdx.x; i < n; i += stride) {
+        const i4 v = ((const i4 *) accum)[i];
+        if (v.x != RTD_EARLY_COUNT) continue;
+        rgb[i * 3 + 0] = (uint8_t) (v.y / v.x);
+        rgb[i * 3 + 1] = (uint8_t) (v.z / v.x);
+        rgb[i * 3 + 2] = (uint8_t) (v.w / v.x);
+    }
+}
 
 // ---- ordering of the pass-B list: bucket sort of (cost, pixel) pairs, heaviest first -------------------------------------------
 // 64 buckets over rays per phase-1 sample (x4); order inside a bucket is arbitrary (it only changes which wave traces what).

@@ -234,12 +234,14 @@ struct LaunchScratch {
     unsigned long long counters[16]; // rays, aabb, prim, refl, samples, pixels_early, -, first wave start; [8..13] stage executions, [14] wave lifetimes, [15] last wave end
     unsigned int queue, pad0;        // RenderParams::queue: next work unit of the fused kernel / pass A, next run of a ray list
     unsigned long long queue_b;      // pass B: next unassigned list entry
-    unsigned int live_count, pad1[3]; // pass A -> B: number of pairs / list entries
+    unsigned int live_count;         // pass A -> B: number of pairs / list entries
+    unsigned int ext_foreign, ext_malformed, pad1; // an extension: pixels whose Count the arguments do not explain (extend_list_kernel); 1 = nothing was continued (extend_seal_kernel)
     unsigned long long stage[12];    // counters[20..31]: slow stages, lanes in them, lanes parked, cycles in refill / slow / walk / shade;
                                      // diagnostic builds (RTD_STAGE_CLOCKS): cycles in loop / leaf / unbounded / new items / lambert
     CameraParams cam;                // RenderParams::cam_ptr
 };
 static_assert(offsetof(LaunchScratch, queue) == 128 && offsetof(LaunchScratch, queue_b) == 136 && offsetof(LaunchScratch, live_count) == 144, "queues");
+static_assert(offsetof(LaunchScratch, ext_foreign) == 148 && offsetof(LaunchScratch, ext_malformed) == 152, "zeroed by launch_init_kernel with the queues");
 static_assert(offsetof(LaunchScratch, stage) == 20 * sizeof(unsigned long long) && offsetof(LaunchScratch, stage) == 160, "stage counters are counters[20..31]");
 static_assert(offsetof(LaunchScratch, cam) == 256 && sizeof(LaunchScratch) <= RT_SCRATCH_BYTES, "camera must fit the scratch slot");
 
@@ -472,6 +474,7 @@ struct Pending {
     int device = -1;
     uint64_t pixels = 0, waves = 0;
     bool launched = false, keep = false;
+    bool extend = false; // an extension: collect_stats reads LaunchScratch::ext_malformed
     std::chrono::steady_clock::time_point t0;
     void release() { // events destroyed, scratch handed back to the stream's pool in stream order
         if (a) (void) hipEventDestroy(a);
@@ -528,7 +531,8 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
         put(r->mode); put((int64_t) r->grid); put((int64_t) r->lds_bytes); put(r->chunk); put(r->park); put(r->park_l); put(r->park_l_lds);
         put(r->lds_node_bytes); put(r->lds_node_thr); put(r->yield_lanes); put(r->leaf_wait); put(r->refill_lanes); put(r->k); put(r->total_waves);
     }
-    static_assert(1 + 21 + 13 + 3 * 14 <= RT_LAUNCH_PLAN_WORDS, "rt_dev_last_launch_plan's words");
+    put(j.first_sample); // [77]: 0 = a fresh render, else the samples_done of an extension
+    static_assert(1 + 21 + 13 + 3 * 14 + 1 <= RT_LAUNCH_PLAN_WORDS, "rt_dev_last_launch_plan's words");
     while (n < RT_LAUNCH_PLAN_WORDS) put(0);
 }
 
@@ -579,6 +583,7 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     cl.scr = scr; cl.st = st; cl.device = device; cl.t0 = t0;
     cl.pixels = plan.pixels;
     cl.waves = plan.waves;
+    cl.extend = job.extend();
     if (want_stats) {
         HIP_TRY(hipEventCreate(&cl.a));
         HIP_TRY(hipEventCreate(&cl.b));
@@ -596,7 +601,31 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     }
     if (grid > 0) {
         if (want_stats) HIP_TRY(hipEventRecord(cl.a, st));
-        if (!plan.two_pass) {
+        if (job.extend()) {
+            // pass B alone, from sample first_sample on: its list comes from the stored Counts (extend_list_kernel) instead of pass A
+            // and the sort; the seal between them makes "malformed buffer => nothing written" hold (rt_render_kernel.h)
+            if (plan.error || !plan.two_pass) return fail(RT_ERR_HIP, plan.error ? plan.error : "an extension needs a pass B");
+            LaunchScratch *ls = (LaunchScratch *) scr;
+            unsigned int *list = (unsigned int *) (scr + RT_SCRATCH_BYTES + pairsBytes);
+            p.live_list = list;
+            render_fn fb = pick_kernel(plan.b);
+            if (!fb) return fail(RT_ERR_HIP, "no kernel is built for this launch");
+            if ((rc = allow_full_lds((const void *) fb)) != RT_OK) return rc;
+            set_plan_fields(p, plan.b);
+            p.first_b = job.first_sample;
+            const unsigned long long nLocal = plan.pixels; // (< 2^32: the plan's condition for a list)
+            const unsigned long long want = (nLocal + 255ull) / 256ull, most = (unsigned long long) ds->cu_count * 8ull;
+            const unsigned listGrid = (unsigned) (want < most ? want : most);
+            hipLaunchKernelGGL(extend_list_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, nLocal, job.first_sample, list, p.live_count,
+                               p.counters, &ls->ext_foreign);
+            hipLaunchKernelGGL(extend_seal_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) &ls->ext_foreign, p.live_count, &ls->ext_malformed);
+            if (p.rgb)
+                hipLaunchKernelGGL(extend_final_rgb_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, nLocal,
+                                   (const unsigned int *) &ls->ext_malformed, p.rgb);
+            hipLaunchKernelGGL(fb, dim3((unsigned) plan.b.grid), dim3((unsigned) block), plan.b.lds_bytes, st, p);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("extension launch: ") + hipGetErrorString(e));
+        } else if (!plan.two_pass) {
             set_plan_fields(p, plan.one);
             hipLaunchKernelGGL(fn, dim3((unsigned) grid), dim3((unsigned) block), ldsBytes, st, p);
             HIP_TRY(hipGetLastError());
@@ -636,7 +665,7 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
 // Enqueues one shard's render on `stream`: the argument checks and the frame's own RenderParams fields, then enqueue().
 static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
                          int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
-                         const rt_render_options *options, bool want_stats, Pending &pd, const RayLog *log = nullptr) {
+                         const rt_render_options *options, bool want_stats, Pending &pd, const RayLog *log = nullptr, int32_t first_sample = 0) {
     if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     int rc = check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows);
     if (rc != RT_OK) return rc;
@@ -659,6 +688,7 @@ static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t
     job.kind = rtp::Job::FRAME;
     job.n_rows = (uint64_t) n_rows; job.max_w = max_w; job.spp = camera->samples_per_pixel;
     job.ray_log = log != nullptr;
+    job.first_sample = first_sample;
     return enqueue(scene, device, job, set, flags, stream, p, camera_params(camera, max_w, max_h), want_stats, pd);
 }
 
@@ -680,6 +710,14 @@ static int collect_stats(Pending &pd, rt_stats *stats) {
     g_last_stage_stats[7] = c[15] - (0x4000000000000000ull - c[7]); // first wave start -> last wave end, ticks
     g_last_stage_stats[8] = pd.waves;
     for (int i = 0; i < 7; ++i) g_last_stage_stats[9 + i] = c[16 + i]; // slow stages, lanes in them, lanes parked, cycles in refill / slow / walk / shade
+    if (pd.extend && pd.scr) { // the seal found a Count the arguments do not explain: nothing was continued, nothing written
+        unsigned int malformed = 0u;
+        HIP_TRY(hipMemcpy(&malformed, pd.scr + offsetof(LaunchScratch, ext_malformed), sizeof(malformed), hipMemcpyDeviceToHost));
+        if (malformed) {
+            pd.release();
+            return fail(RT_ERR_INVALID_ARGUMENT, "accum is not a buffer of samples_done samples per pixel (a Count that is neither samples_done nor 11); left unchanged");
+        }
+    }
     float ms = 0.f;
     if (pd.launched) HIP_TRY(hipEventElapsedTime(&ms, pd.a, pd.b));
     memset(stats, 0, sizeof(*stats));
@@ -1102,7 +1140,7 @@ static int check_footprints(const rt_scene *scene, size_t n, const void *footpri
 // whose pixel i reads footprint i and owns the stream of (seed, stream_base + i); then enqueue(), as for a frame shard.
 static int launch_footprints(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints, int32_t spp, int32_t bounce_depth,
                              uint64_t seed, uint64_t stream_base, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
-                             const rt_render_options *options, bool want_stats, Pending &pd) {
+                             const rt_render_options *options, bool want_stats, Pending &pd, int32_t first_sample = 0) {
     RenderParams p{};
     p.spp = spp;
     p.depth = bounce_depth;
@@ -1117,6 +1155,7 @@ static int launch_footprints(const rt_scene *scene, int32_t device, size_t n, co
     rtp::Job job;
     job.kind = rtp::Job::FOOTPRINTS;
     job.n = n; job.spp = spp;
+    job.first_sample = first_sample;
     return enqueue(scene, device, job, resolve_settings(options), flags, stream, p, CameraParams{}, want_stats, pd); // (no camera: never read in these modes)
 }
 
@@ -1163,6 +1202,136 @@ int rt_render_footprints(const rt_scene *scene, int32_t device, size_t n, const 
     rt_stats local;
     rc = rt_render_footprints_device(scene, device, n, buf, samples_per_pixel, bounce_depth, seed, stream_base, flags, buf + bFp,
                                      bRgb ? buf + bFp + bAcc : nullptr, nullptr, nullptr, &local);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpy(accum, buf + bFp, n * 16u, hipMemcpyDeviceToHost));
+    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bFp + bAcc, n * 3u, hipMemcpyDeviceToHost));
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// extending a rendered buffer to a higher sample count (DESIGN.md "Extending a frame"): pass B alone, from the stored PixelStats
+// ------------------------------------------------------------------------------------------------------------
+static int check_extend(int32_t target, int32_t samples_done) {
+    if (samples_done < RTD_EXTEND_MIN_DONE)
+        return fail(RT_ERR_INVALID_ARGUMENT, "samples_done must be >= 12 (below, firstTrial differs and Count cannot tell a stopped pixel from a finished one)");
+    if (target < samples_done) return fail(RT_ERR_INVALID_ARGUMENT, "the target samples_per_pixel is below samples_done");
+    return RT_OK;
+}
+// Every argument check of the two frame entry points, made before anything touches a device.
+static int check_extend_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t row_first, int32_t row_stride,
+                              int32_t n_rows, const void *accum, const rt_render_options *options, int32_t samples_done) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    int rc = check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows);
+    if (rc != RT_OK) return rc;
+    if (n_rows > 0 && !accum) return fail(RT_ERR_INVALID_ARGUMENT, "accum is NULL");
+    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
+    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
+    if ((rc = check_extend(camera->samples_per_pixel, samples_done)) != RT_OK) return rc;
+    if ((uint64_t) n_rows * (uint64_t) (2 * max_w + 1) >= (1ull << 32)) return fail(RT_ERR_INVALID_ARGUMENT, "an extension takes shards of fewer than 2^32 pixels");
+    return RT_OK;
+}
+
+extern "C" {
+
+int rt_render_extend_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
+                            int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, int32_t samples_done, void *d_accum, void *d_rgb,
+                            void *stream, const rt_render_options *options, rt_stats *stats) {
+    int rc = check_extend_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, d_accum, options, samples_done);
+    if (rc != RT_OK) return rc;
+    if (n_rows == 0 || camera->samples_per_pixel == samples_done) { // nothing to add
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    Pending pd;
+    rc = launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d_accum, d_rgb, stream, options, stats != nullptr, pd,
+                       nullptr, samples_done);
+    if (rc != RT_OK || !stats) return rc;
+    return collect_stats(pd, stats);
+}
+
+// The host variant: the buffer copied in, the device variant on the null stream, the outputs copied back -- unless it failed.
+int rt_render_extend(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
+                     int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, int32_t samples_done, int32_t *accum, uint8_t *rgb,
+                     rt_stats *stats) {
+    int rc = check_extend_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, accum, nullptr, samples_done);
+    if (rc != RT_OK) return rc;
+    if (n_rows == 0 || camera->samples_per_pixel == samples_done) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
+    const size_t npx = (size_t) n_rows * (size_t) (2 * max_w + 1), bAcc = up16(npx * 16u), bRgb = rgb ? up16(npx * 3u) : 0u;
+    unsigned char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **) &buf, bAcc + bRgb));
+    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
+    HIP_TRY(hipMemcpy(buf, accum, npx * 16u, hipMemcpyHostToDevice));
+    rt_stats local; // (always asked for: the malformed-buffer error is reported through it)
+    rc = rt_render_extend_device(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, samples_done, buf,
+                                 bRgb ? buf + bAcc : nullptr, nullptr, nullptr, &local);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpy(accum, buf, npx * 16u, hipMemcpyDeviceToHost));
+    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bAcc, npx * 3u, hipMemcpyDeviceToHost));
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+int rt_render_footprints_extend_device(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints, int32_t samples_per_pixel,
+                                       int32_t bounce_depth, uint64_t seed, uint64_t stream_base, uint32_t flags, int32_t samples_done, void *d_accum,
+                                       void *d_rgb, void *stream, const rt_render_options *options, rt_stats *stats) {
+    int rc = check_footprints(scene, n, d_footprints, d_accum, samples_per_pixel, bounce_depth, options);
+    if (rc != RT_OK || (rc = check_extend(samples_per_pixel, samples_done)) != RT_OK) return rc;
+    if (n == 0 || samples_per_pixel == samples_done) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    Pending pd;
+    rc = launch_footprints(scene, device, n, d_footprints, samples_per_pixel, bounce_depth, seed, stream_base, flags, d_accum, d_rgb, stream, options,
+                           stats != nullptr, pd, samples_done);
+    if (rc != RT_OK || !stats) return rc;
+    return collect_stats(pd, stats);
+}
+
+int rt_render_footprints_extend(const rt_scene *scene, int32_t device, size_t n, const double *footprints, int32_t samples_per_pixel, int32_t bounce_depth,
+                                uint64_t seed, uint64_t stream_base, uint32_t flags, int32_t samples_done, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
+    int rc = check_footprints(scene, n, footprints, accum, samples_per_pixel, bounce_depth, nullptr);
+    if (rc != RT_OK || (rc = check_extend(samples_per_pixel, samples_done)) != RT_OK) return rc;
+    if (n == 0 || samples_per_pixel == samples_done) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
+    const size_t bFp = up16(n * 96u), bAcc = up16(n * 16u), bRgb = rgb ? up16(n * 3u) : 0u;
+    unsigned char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **) &buf, bFp + bAcc + bRgb));
+    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
+    HIP_TRY(hipMemcpy(buf, footprints, n * 96u, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(buf + bFp, accum, n * 16u, hipMemcpyHostToDevice));
+    rt_stats local;
+    rc = rt_render_footprints_extend_device(scene, device, n, buf, samples_per_pixel, bounce_depth, seed, stream_base, flags, samples_done, buf + bFp,
+                                            bRgb ? buf + bFp + bAcc : nullptr, nullptr, nullptr, &local);
     if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpy(accum, buf + bFp, n * 16u, hipMemcpyDeviceToHost));
     if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bFp + bAcc, n * 3u, hipMemcpyDeviceToHost));

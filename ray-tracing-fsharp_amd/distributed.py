@@ -38,6 +38,19 @@ def render_shard_device(scene: Scene, camera: Camera, maxWidthCoord: int, maxHei
     return st.as_dict() if want_stats else None
 
 
+def extend_shard_device(scene: Scene, camera: Camera, maxWidthCoord: int, maxHeightCoord: int, seed: int, device: int,
+                         row_first: int, row_stride: int, n_rows: int, accum, samples_done: int, stream: int = 0, counters: bool = False,
+                         want_stats: bool = False):
+    """rt_render_extend_device on `accum` as render_shard_device left it at `samples_done` samples: a rank extends its own
+    interleaved shard to camera.SamplesPerPixel in place; the gather is the same."""
+    cam = camera.to_abi()
+    st = A.rt_stats() if want_stats else None
+    check(lib.rt_render_extend_device(scene.handle, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, device, row_first, row_stride, n_rows,
+                                      A.RT_RENDER_COUNTERS if counters else 0, samples_done, C.c_void_p(accum.data_ptr()), None,
+                                      C.c_void_p(stream), None, C.byref(st) if want_stats else None))
+    return st.as_dict() if want_stats else None
+
+
 def gather_frame(local_accum, rows: int, cols: int, rank: int, world: int, group=None):
     """Gather the padded per-rank accumulators ([ceil(rows/world), cols, 4] int32 each) to rank 0 and de-interleave.
     Returns the [rows, cols, 4] frame on rank 0, None elsewhere."""

@@ -146,7 +146,7 @@ PLAN_WORDS = 80
 def last_launch_plan():
     """The launch plan (csrc/rt_launch_plan.h) of the calling thread's last launch as the library executed it: {"in": the planner's
     inputs, "out": its decisions}, keyed as launch_plan_table.cpp's lines are (F_ for a fused or ray-list launch, A_ and B_ for a
-    two-pass one).  None before this thread's first launch."""
+    two-pass one; an extension reports both, A_ all zeros).  None before this thread's first launch."""
     w = (C.c_int64 * PLAN_WORDS)()
     check(lib.rt_dev_last_launch_plan(w))
     if not w[0]:
@@ -160,4 +160,5 @@ def last_launch_plan():
         if (name == "F") != bool(out["two_pass"]) and not out["error"]:
             out.update({f"{name}_{k}": v for k, v in zip(PLAN_PASS, w[at:at + len(PLAN_PASS)])})
         at += len(PLAN_PASS)
+    inp["first_sample"] = w[at]  # word 77: 0 = a fresh render, else the samples_done of an extension (pass B alone: A_ words 0)
     return {"in": inp, "out": out}

@@ -280,6 +280,31 @@ class Scene {
         return info;
     }
 
+    // rt_render_extend / rt_render_footprints_extend (no counterpart in the reference): `accum` -- the PixelStats ({Count; SumRed; SumGreen;
+    // SumBlue} per pixel) of the rows rowFirst + i*rowStride, or of the footprints, rendered or last extended with samplesDone >= 12
+    // samples -- continued IN PLACE to camera.SamplesPerPixel (samplesPerPixel): bit for bit a render at that count.  Returns
+    // PixelStats.mean per pixel.  Everything but the sample count as in the call that made the buffer.
+    std::vector<uint8_t> extendRows(int maxWidthCoord, int maxHeightCoord, const Camera &camera, std::vector<int32_t> &accum, int samplesDone,
+                                    uint64_t seed = 0, int device = 0, int rowFirst = 0, int rowStride = 1) {
+        const size_t cols = (size_t) (2 * maxWidthCoord + 1);
+        if (accum.size() % (cols * 4) != 0) throw std::invalid_argument("extendRows: accum is not [n_rows][cols][4]");
+        const int nRows = (int) (accum.size() / (cols * 4));
+        std::vector<uint8_t> rgb((size_t) nRows * cols * 3);
+        rt_camera cam = camera.toAbi();
+        check(rt_render_extend(h_, &cam, maxWidthCoord, maxHeightCoord, seed, device, rowFirst, rowStride, nRows, 0u, samplesDone, accum.data(), rgb.data(),
+                               &lastStats));
+        return rgb;
+    }
+    std::vector<uint8_t> extendFootprints(const std::vector<double> &footprints, int samplesPerPixel, int bounceDepth, std::vector<int32_t> &accum,
+                                          int samplesDone, uint64_t seed = 0, uint64_t streamBase = 0, int device = 0) {
+        const size_t n = footprints.size() / 12;
+        if (footprints.size() % 12 != 0 || accum.size() != n * 4) throw std::invalid_argument("extendFootprints: footprints [n][12], accum [n][4]");
+        std::vector<uint8_t> rgb(n * 3);
+        check(rt_render_footprints_extend(h_, device, n, footprints.data(), samplesPerPixel, bounceDepth, seed, streamBase, 0u, samplesDone, accum.data(),
+                                          rgb.data(), &lastStats));
+        return rgb;
+    }
+
     rt_scene *handle() const { return h_; }
     rt_stats lastStats{};
 

@@ -486,6 +486,43 @@ class Scene:
         self.last_stats = st.as_dict()
         return RenderResult(accum, rgb, self.last_stats)
 
+    def extend_rows(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, accum, samplesDone: int, *, seed: int = 0,
+                    device: Optional[int] = None, row_first: int = 0, row_stride: int = 1, counters: bool = False, stats: bool = True,
+                    options: Optional[A.rt_render_options] = None) -> RenderResult:
+        """rt_render_extend: continues `accum` -- the PixelStats of the rows row_first + i*row_stride, rendered or last extended with
+        samplesDone (>= 12) samples per pixel -- to camera.SamplesPerPixel; the result is, bit for bit, a render at that count.
+        Everything but the sample count as in the call that made the buffer.  A numpy array [n_rows, cols, 4] int32 is left as it
+        is and a new one returned; a torch tensor on a GPU is extended IN PLACE through rt_render_extend_device on
+        torch.cuda.current_stream() (stats=False: no wait for the device; a malformed buffer then goes unreported and unchanged)."""
+        cols = 2 * maxWidthCoord + 1
+        flags = A.RT_RENDER_COUNTERS if counters else 0
+        cam = camera.to_abi()
+        if _is_torch(accum):
+            torch = _torch()
+            if accum.dtype != torch.int32 or accum.dim() != 3 or tuple(accum.shape[1:]) != (cols, 4) or not accum.is_cuda or not accum.is_contiguous():
+                raise ValueError(f"accum must be a contiguous int32 tensor [n_rows, {cols}, 4] on a GPU")
+            dev = _tensor_device(accum, device)
+            n_rows = accum.shape[0]
+            rgb = torch.empty((n_rows, cols, 3), dtype=torch.uint8, device=accum.device)
+            st = A.rt_stats() if stats else None
+            check(lib.rt_render_extend_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, row_first, row_stride, n_rows, flags,
+                                              samplesDone, accum.data_ptr(), rgb.data_ptr(), torch.cuda.current_stream(accum.device).cuda_stream,
+                                              _ref(options), _ref(st)))
+            self.last_stats = st.as_dict() if st is not None else None
+            return RenderResult(accum, rgb, self.last_stats)
+        if options is not None:
+            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        if not isinstance(accum, np.ndarray) or accum.dtype != np.int32 or accum.ndim != 3 or accum.shape[1:] != (cols, 4):
+            raise ValueError(f"accum must be an int32 array [n_rows, {cols}, 4] or such a tensor on a GPU")
+        out = np.array(accum, dtype=np.int32, order="C")
+        n_rows = out.shape[0]
+        rgb = np.zeros((n_rows, cols, 3), np.uint8)
+        st = A.rt_stats()
+        check(lib.rt_render_extend(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, row_first, row_stride,
+                                   n_rows, flags, samplesDone, _i32(out), _u8(rgb), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return RenderResult(out, rgb, self.last_stats)
+
     def render_frame(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, *, seed: int = 0, devices: Sequence[int] = (0,),
                      gather: int = A.RT_GATHER_AUTO, counters: bool = False, options: Optional[A.rt_render_options] = None) -> RenderResult:
         """rt_render_frame: the whole frame on several GPUs from this one process (rows interleaved over `devices`, one gather);
@@ -577,36 +614,53 @@ class Scene:
 
     def renderFootprints(self, footprints, samplesPerPixel: int, bounceDepth: int, *, seed: int = 0, stream_base: int = 0,
                          device: Optional[int] = None, counters: bool = False, stats: bool = True,
-                         options: Optional[A.rt_render_options] = None) -> RenderResult:
+                         options: Optional[A.rt_render_options] = None, extend=None) -> RenderResult:
         """Scene.renderPixel (Scene.fs:157-194) for caller-defined cameras: footprints [n, 12] float64, per pixel origin, base, du,
         dv.  Sample s of pixel i draws (r1, r2) from the stream keyed (seed, stream_base + i, s) and traces
         Ray.make'(origin, (base + r1*du) + r2*dv) at most bounceDepth+1 hits; the adaptive stop is the reference's, with
         samplesPerPixel -> RenderResult(accum [n, 4] int32, rgb [n, 3] uint8, stats).  numpy arrays / torch tensors as for hitObject:
         a tensor goes through rt_render_footprints_device on torch.cuda.current_stream() and the results are tensors (stats=False: no
-        wait for the device, stats and last_stats are None)."""
+        wait for the device, stats and last_stats are None).
+        extend=(accum, samplesDone): rt_render_footprints_extend -- `accum` [n, 4] int32, these footprints' PixelStats at samplesDone
+        (>= 12) samples, is continued to samplesPerPixel; bit for bit a render at that count.  An array is copied, a tensor (on the
+        footprints' device) extended in place."""
         flags = A.RT_RENDER_COUNTERS if counters else 0
         if _is_torch(footprints):
             torch = _torch()
             f = _tensor_arg(footprints, "footprints", (torch.float64,), 12)
             dev = _tensor_device(f, device)
             n = f.shape[0]
-            accum = torch.empty((n, 4), dtype=torch.int32, device=f.device)
             rgb = torch.empty((n, 3), dtype=torch.uint8, device=f.device)
             st = A.rt_stats() if stats else None
-            check(lib.rt_render_footprints_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
-                                                  accum.data_ptr(), rgb.data_ptr(), torch.cuda.current_stream(f.device).cuda_stream,
-                                                  _ref(options), _ref(st)))
+            stream = torch.cuda.current_stream(f.device).cuda_stream
+            if extend is not None:
+                accum, done = extend
+                if not _is_torch(accum) or accum.dtype != torch.int32 or tuple(accum.shape) != (n, 4) or accum.device != f.device or not accum.is_contiguous():
+                    raise ValueError("extend=(accum, samplesDone): accum must be a contiguous int32 tensor [n, 4] on the footprints' device")
+                check(lib.rt_render_footprints_extend_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
+                                                             done, accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
+            else:
+                accum = torch.empty((n, 4), dtype=torch.int32, device=f.device)
+                check(lib.rt_render_footprints_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
+                                                      accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
             self.last_stats = st.as_dict() if st is not None else None
             return RenderResult(accum, rgb, self.last_stats)
         if options is not None:
             raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
         f = _array_arg(footprints, "footprints", np.float64, 12)
         n = f.shape[0]
-        accum = np.zeros((n, 4), np.int32)
         rgb = np.zeros((n, 3), np.uint8)
         st = A.rt_stats()
-        check(lib.rt_render_footprints(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed, stream_base,
-                                       flags, _i32(accum), _u8(rgb), C.byref(st)))
+        if extend is not None:
+            accum = np.array(_array_arg(extend[0], "extend's accum", np.int32, 4), order="C")
+            if accum.shape[0] != n:
+                raise ValueError("extend=(accum, samplesDone): accum must be [n, 4] for n footprints")
+            check(lib.rt_render_footprints_extend(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed,
+                                                  stream_base, flags, extend[1], _i32(accum), _u8(rgb), C.byref(st)))
+        else:
+            accum = np.zeros((n, 4), np.int32)
+            check(lib.rt_render_footprints(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed, stream_base,
+                                           flags, _i32(accum), _u8(rgb), C.byref(st)))
         self.last_stats = st.as_dict()
         return RenderResult(accum, rgb, self.last_stats)
 
