@@ -426,6 +426,55 @@ int rt_render_footprints_extend_device(const rt_scene *scene, int32_t device, si
                                        uint32_t flags, int32_t samples_done, void *d_accum, void *d_rgb, void *stream,
                                        const rt_render_options *options, rt_stats *stats);
 
+/* ---- Extending by map: every pixel to a sample count of its own --------------------------------------------------------------
+ * The extension above has one target for the whole shard; here `targets` holds one int32 per pixel of the shard, numbered as
+ * accum is laid out (i = local_row * cols + col; footprints: the list index).  The stored Count of a pixel is the whole state
+ * needed to continue that pixel alone (DESIGN.md "Extending by map"), so there is no samples_done argument.  With c the
+ * pixel's Count, t = targets[i] and cap = camera->samples_per_pixel (footprints: samples_per_pixel -- here only the upper
+ * bound on every target):
+ *   c == 11                       FINAL: the pixel stopped early; untouched whatever t is
+ *   c >= 12 and c < t <= cap      CONTINUED with samples c .. t-1; Count becomes t
+ *   c >= 12 and t <= c            LEFT as it is (0 and negative targets included)
+ *   c < 11, or t > cap (c != 11)  MALFORMED
+ * If the shard holds even one malformed pixel the call continues NO pixel: accum stays as it was, bit for bit, rgb is not
+ * written, and the status is reported as for rt_render_extend (RT_ERR_INVALID_ARGUMENT from the host variants, and from the
+ * device variants when stats is given; with stats == NULL the unchanged Counts are the caller's evidence).  Otherwise rgb,
+ * when given, is written for EVERY pixel of the shard as PixelStats.mean.
+ *
+ * After any sequence of such calls on a buffer that began as a render at some spp >= 12, every pixel equals that pixel of a
+ * direct render at spp = its Count (or is the early-stopped pixel every such render holds).  Every other argument as in the
+ * call that made the buffer.
+ *
+ * Argument checks come before any device call, nothing is written when one fails: cap < 12, cap > 8000000, a NULL targets or
+ * accum with pixels to do, a shard of 2^32 pixels or more, and everything the base call rejects.  Empty shards are no-ops
+ * returning RT_OK with zeroed stats.
+ *
+ * stats describe this call alone: samples = the sum of t - c over the continued pixels, pixels = the shard's pixels,
+ * pixels_early = the final pixels found; under RT_RENDER_COUNTERS the four counters cover the samples traced.
+ *
+ * The device variants (d_targets on `device`, like d_accum) follow rt_render_extend_device's contract: stream-ordered scratch,
+ * any number of calls in flight, return right after the launch when stats == NULL, the caller's current device left as it was.
+ * options->passes is accepted and ignored.  The map must not change until the launch has finished.
+ * Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */
+int rt_render_extend_map(const rt_scene *scene, const rt_camera *camera,
+                         int32_t max_width_coord, int32_t max_height_coord, uint64_t seed,
+                         int32_t device, int32_t row_first, int32_t row_stride, int32_t n_rows,
+                         uint32_t flags, const int32_t *targets, int32_t *accum /* in, out */, uint8_t *rgb /* out, may be NULL */,
+                         rt_stats *stats);
+int rt_render_extend_map_device(const rt_scene *scene, const rt_camera *camera,
+                                int32_t max_width_coord, int32_t max_height_coord, uint64_t seed,
+                                int32_t device, int32_t row_first, int32_t row_stride, int32_t n_rows,
+                                uint32_t flags, const void *d_targets, void *d_accum, void *d_rgb, void *stream,
+                                const rt_render_options *options, rt_stats *stats);
+int rt_render_footprints_extend_map(const rt_scene *scene, int32_t device, size_t n, const double *footprints,
+                                    int32_t samples_per_pixel /* cap */, int32_t bounce_depth, uint64_t seed, uint64_t stream_base,
+                                    uint32_t flags, const int32_t *targets, int32_t *accum /* in, out */, uint8_t *rgb /* out, may be NULL */,
+                                    rt_stats *stats);
+int rt_render_footprints_extend_map_device(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints,
+                                           int32_t samples_per_pixel /* cap */, int32_t bounce_depth, uint64_t seed, uint64_t stream_base,
+                                           uint32_t flags, const void *d_targets, void *d_accum, void *d_rgb, void *stream,
+                                           const rt_render_options *options, rt_stats *stats);
+
 /* ---- Output side (ImageOutput.fs:11-30,163-197) -------------------------------------------------- */
 uint8_t rt_gamma_correct(uint8_t b); /* PixelOutput.correct (ImageOutput.fs:11-18) */
 /* ImageOutput.writePpm gammaCorrect pixels file (ImageOutput.fs:163-197): P3, no trailing newline. */
@@ -492,7 +541,10 @@ int rt_last_stage_stats(uint64_t out[16]);
  *            A_ and B_ are filled only with two_pass and no error.
  *   [77]     first_sample: 0 for a fresh render; for an extension (rt_render_extend*, rt_render_footprints_extend*) its samples_done.
  *            An extension reports kind 0 or 3, two_pass 1, pairs and sort 0, every A_ word 0 (no pass A is launched) and pass B as
- *            the same job gets it with passes = 2.  [78..79] are 0.
+ *            the same job gets it with passes = 2.
+ *   [78]     1 for an extension by map (rt_render_extend_map*, rt_render_footprints_extend_map*), else 0.  Such a launch reports
+ *            first_sample 12 and spp = the cap (it is planned as the extension 12 -> cap) and pass B's mode as 9 (frame) or 10
+ *            (footprints), its lds_bytes and chunk following from the map variant's larger per-wave scratch.  [79] is 0.
  * A call that fails before its plan is complete (bad arguments, no kernel built for the launch, occupancy 0) leaves the previous
  * launch's report in place: read it after a call that returned RT_OK.
  * An added diagnostic symbol only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */

@@ -107,6 +107,16 @@ SIGNATURES = {
     "rt_render_footprints_extend_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64,
                                                      C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      _P(A.rt_render_options), _P(A.rt_stats)]),
+    "rt_render_extend_map": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_uint32, _i32p, _i32p, _u8p, _P(A.rt_stats)]),
+    "rt_render_extend_map_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              _P(A.rt_render_options), _P(A.rt_stats)]),
+    "rt_render_footprints_extend_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t, _dp, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
+                                                  C.c_uint32, _i32p, _i32p, _u8p, _P(A.rt_stats)]),
+    "rt_render_footprints_extend_map_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64,
+                                                         C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         _P(A.rt_render_options), _P(A.rt_stats)]),
     "rt_gamma_correct": (C.c_uint8, [C.c_uint8]),
     "rt_write_ppm": (C.c_int, [C.c_char_p, _u8p, C.c_int32, C.c_int32, C.c_int32]),
     "rt_format_ppm": (C.c_int64, [_u8p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),

@@ -14,6 +14,7 @@
 // Per-wave LDS scratch in 4-byte words, P = pixels per work unit (layout: rt_render_kernel.h)
 #define RTD_WAVE_WORDS(P) (18u * (uint32_t) (P)) /* fused: 13 P used; pass B: two slots of {acc [P][3], pix [P][4]}, then cand [2][P][2] */
 #define RTD_WAVE_WORDS_A(P) (13u * (uint32_t) (P)) /* pass A: acc, pix, cost, cand [P][2] -- a tighter footprint, so its units can be wider */
+#define RTD_WAVE_WORDS_MAP(P) (22u * (uint32_t) (P)) /* pass B of an extension by map: pass B's 18 P, then per slot first item [P] and sample base [P] */
 
 // ---- the lane scheduler's thresholds (rt_render_kernel.h, Sched) ----
 #define RTD_YIELD_DEFAULT 50

@@ -44,6 +44,8 @@ struct Job {
     uint64_t n = 0;                                  // TRACE, HIT: rays; FOOTPRINTS: pixels (with spp)
     int32_t first_sample = 0;                        // FRAME, FOOTPRINTS: 0 = a fresh render; >= RTD_EXTEND_MIN_DONE: an EXTENSION of a buffer that
                                                      // holds this many samples per continued pixel, to spp (rt_render_extend): pass B alone
+    bool map = false;                                // an extension BY MAP (rt_render_extend_map): every pixel from its own Count to its own target <= spp.
+                                                     // Planned as the extension RTD_EXTEND_MIN_DONE -> spp (first_sample is that) with the map variant's scratch
     bool extend() const { return first_sample != 0; }
     bool pixels() const { return kind == FRAME || kind == FOOTPRINTS; } // planned by the pixel rules, not the ray lists'
     uint64_t pixel_count() const { return kind == FOOTPRINTS ? n : n_rows * (uint64_t) (2 * max_w + 1); }
@@ -217,7 +219,9 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     // per pixel a unit is short, so is the tail, and the second launch costs more than it removes (config 2, 100 spp: fused 3.0 ms,
     // two passes 3.5 ms; config 3's 1/8 shard, 500 spp: 51 ms against 30 ms).
     const bool ext = pl.job.extend(); // pass B alone, from sample first_sample on: planned as this job with two passes forced
-    const int n2 = pl.job.spp - (ext ? pl.job.first_sample : 2 * q.k + 1);
+    int n2 = pl.job.spp - (ext ? pl.job.first_sample : 2 * q.k + 1);
+    if (pl.job.map && n2 < 1) n2 = 1; // (a map with cap == 12 continues nothing, but still classifies every pixel and writes rgb)
+    const auto wordsB = [&](int c) { return pl.job.map ? RTD_WAVE_WORDS_MAP(c) : RTD_WAVE_WORDS(c); }; // pass B's scratch per wave
     pl.two_pass = n2 > 0 && nLocal > 0 && nLocal < (1ull << 32) &&
                   (set.passes == 2 || ext || (set.passes == 0 && (n2 >= 128 || (n2 >= 64 && nLocal >= (1ull << 21))) && units < 64ull * fullGrid * wavesPerBlock));
     // (frames of 2 Mpx and more pay for the second launch from ~75 spp: 2401x1601 at 100 spp 23.1 Gray/s fused, 26.9 in two passes; 1201x801: 19.6 / 19.8)
@@ -247,12 +251,12 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     // pass A would leave a half-rendered buffer);
     auto needA = [&](int c) { return lds_need(sc, true, q.count, q.block, RTD_WAVE_WORDS_A(c)); };
     while (q.lds && chunkA > 1 && needA(chunkA) > RT_LDS_BYTES) chunkA /= 2;
-    while (q.lds && chunkB > 1 && lds_need(sc, true, q.count, q.block, RTD_WAVE_WORDS(chunkB)) > RT_LDS_BYTES) chunkB /= 2;
+    while (q.lds && chunkB > 1 && lds_need(sc, true, q.count, q.block, wordsB(chunkB)) > RT_LDS_BYTES) chunkB /= 2;
     if (q.lds && q.park > 0 && !set.chunk) { // ... and not so wide that the Lambert pool no longer fits beside them
         auto pool_fits = [&](int c) { size_t b = needA(c); return lambert_pool_lds(b, q.block) != 0; };
         while (chunkA > 16 && !pool_fits(chunkA) && pool_fits(chunkA / 2)) chunkA /= 2;
     }
-    if (q.lds && ((!ext && needA(chunkA) > RT_LDS_BYTES) || lds_need(sc, true, q.count, q.block, RTD_WAVE_WORDS(chunkB)) > RT_LDS_BYTES)) {
+    if (q.lds && ((!ext && needA(chunkA) > RT_LDS_BYTES) || lds_need(sc, true, q.count, q.block, wordsB(chunkB)) > RT_LDS_BYTES)) {
         pl.error = "two-pass launch does not fit the LDS";
         return;
     }
@@ -260,8 +264,8 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     pl.a.total_waves = pl.b.total_waves = (uint32_t) (fullGrid * wavesPerBlock);
     const int fp = pl.job.kind == Job::FOOTPRINTS ? 6 : 0;
     pl.a.mode = fp + 1; pl.a.chunk = chunkA;
-    pl.b.mode = fp + 2; pl.b.chunk = chunkB;
-    place_pass(pl.b, sc, RTD_WAVE_WORDS(chunkB));
+    pl.b.mode = pl.job.map ? (fp ? 10 : 9) : fp + 2; pl.b.chunk = chunkB; // (9 / 10: pass B with per-pixel ranges)
+    place_pass(pl.b, sc, wordsB(chunkB));
     pl.b.grid = fullGrid;                            // pass B always launches the full grid (its units shrink along the list)
     if (ext) { pl.a = Pass{}; pl.a.chunk = 0; return; } // no pass A: nothing of it is launched or reported
     place_pass(pl.a, sc, RTD_WAVE_WORDS_A(chunkA));

@@ -19,6 +19,7 @@
 //   device atomics, and pass B only reads what the stream-ordered earlier launches wrote.
 #pragma once
 #include "rt_device.h"
+#include "rt_extend_map.h"
 
 namespace rtd {
 
@@ -75,6 +76,8 @@ struct RenderParams {
     const int32_t *obj_to_orig;    // object-table index -> index into rt_scene_create's array (MODE 5)
     uint64_t ray_n, ray_base;      // (footprints: ray_base is stream_base)
     uint32_t ray_sample;
+    // an extension by map (MODE 9 / 10, rt_render_extend_map): read only there and by its list builder
+    const int32_t *ext_targets;    // [n_rows*cols]: the Count each pixel is to reach (the classes: extend_map_list_kernel)
 };
 
 // Per-wave LDS scratch (in 4-byte words), P = pixels per work unit:
@@ -83,7 +86,9 @@ struct RenderParams {
 //   live [P]        compacted pixel slots for phase 2 (fused mode), or
 //   cost [P]        rays traced for the pixel in phase 1 (pass A: the cost estimate that orders pass B; pass A has no phase 2)
 //   cand [P][2]     the leaves the pixel's camera rays can reach, as two queue words (pixel_candidates, rt_device.h), or RTD_CAND_WALK
-// (RTD_WAVE_WORDS(P), RTD_WAVE_WORDS_A(P): rt_launch_consts.h)
+//   map  [2][P] + [2][P]  pass B of an extension by map only, behind pass B's cand: per slot the first item of each pixel of the range,
+//                         then the pixel's next sample less that (run_stream<.., MAP>)
+// (RTD_WAVE_WORDS(P), RTD_WAVE_WORDS_A(P), RTD_WAVE_WORDS_MAP(P): rt_launch_consts.h)
 
 // Wave-private LDS words: adds from many lanes may land on one word (same pixel), so they are ds_add_u32; the owner
 // lane later takes the sum and clears the word in one ds_wrxchg.  One wave's LDS operations execute in order.
@@ -757,7 +762,11 @@ RTD_INLINE void run_rays(const RenderParams &p, const SceneView<LDS> &sc, unsign
 // hands out its items: two accumulator slots alternate, a range is flushed (its sums added to what pass A left in `accum`) when
 // its last path has ended.  There is no dependency between ranges, so no lane waits at a range boundary -- which is what makes
 // small ranges (good load balance across waves) affordable.  Lane states and stage scheduling are Sched's.
-template <bool LDS, bool COUNT, bool TEX, bool FP>
+// MAP (an extension by map, rt_render_extend_map): every pixel of the list has a range of samples of its own, Count .. target-1.  When
+// a range is reserved lane j reads its pixel's Count and target, the counts n2_j = target - Count are prefix-summed across the wave,
+// and the wave's scratch keeps per pixel its first item and (Count - first item); an item finds its pixel by rtm::map_find_pixel
+// (at most six LDS reads, no division) and is sample (Count - first item) + item; flush leaves Count = target.  n1 and n2 are unused.
+template <bool LDS, bool COUNT, bool TEX, bool FP, bool MAP = false>
 RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, RTD_AS3 uint32_t *wv, uint32_t n1, uint32_t n2, Counters &cnt,
                            StageStats &ss, uint64_t &sampleCount) {
     const int lane = threadIdx.x & 63;
@@ -780,11 +789,13 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
             const unsigned long long lp = (unsigned long long) p.live_list[first + (uint32_t) lane];
             const i4 prev = ((const i4 *) p.accum)[lp];
             i4 out;
-            out.x = prev.x + (int) n2;
+            uint32_t add = n2;
+            if constexpr (MAP) add = (uint32_t) (p.ext_targets[lp] - prev.x); // (the list holds only pixels with Count < target)
+            out.x = prev.x + (int) add;
             out.y = prev.y + (int) lds_take(acc + lane * 3 + 0);
             out.z = prev.z + (int) lds_take(acc + lane * 3 + 1);
             out.w = prev.w + (int) lds_take(acc + lane * 3 + 2);
-            sampleCount += (uint64_t) n2;
+            sampleCount += (uint64_t) add;
             ((i4 *) p.accum)[lp] = out;
             if (p.rgb) {
                 p.rgb[lp * 3 + 0] = (uint8_t) (out.y / out.x);
@@ -854,8 +865,29 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                         wv[14u * P + (curSlot * P + lane) * 2u + 1u] = c2;
                         }
                     }
+                    uint32_t total = npx * n2;
+                    if constexpr (MAP) { // the pixels' own ranges: n2_j prefix-summed across the wave
+                        uint32_t have = 0u, add = 0u;
+                        if ((uint32_t) lane < npx) {
+                            const unsigned long long lp = (unsigned long long) p.live_list[first + (uint32_t) lane];
+                            const int c = ((const i4 *) p.accum)[lp].x, t = p.ext_targets[lp];
+                            have = (uint32_t) c;
+                            add = t > c ? (uint32_t) (t - c) : 0u;
+                        }
+                        uint32_t upTo = add; // inclusive
+#pragma unroll
+                        for (int off = 1; off < 64; off <<= 1) {
+                            const uint32_t v = (uint32_t) __shfl_up((int) upTo, off, 64);
+                            if (lane >= off) upTo += v;
+                        }
+                        total = (uint32_t) __builtin_amdgcn_readlane((int) upTo, 63); // <= 64 * 8e6 < 2^32
+                        if ((uint32_t) lane < npx) {
+                            wv[18u * P + curSlot * P + lane] = upTo - add;
+                            wv[20u * P + curSlot * P + lane] = have - (upTo - add);
+                        }
+                    }
                     __builtin_amdgcn_wave_barrier();
-                    curFirst = first; curNpx = npx; curNext = 0u; curTotal = npx * n2; curOut = 0u;
+                    curFirst = first; curNpx = npx; curNext = 0u; curTotal = total; curOut = 0u;
                     RTD_CENSUS(ss.ranges++;)
                 }
             }
@@ -879,8 +911,14 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                 if (L.st == L_IDLE) {
                     if (!L.unpark_lane(rank, nUnL, nUnA, nUnT) && rank - nUn < take) {
                         const uint32_t item = curNext + (rank - nUn);
-                        const uint32_t j = fastDiv ? div_uniform(item, n2, perRcp) : item / n2;
-                        const uint32_t smp = n1 + (item - j * n2);
+                        uint32_t j, smp;
+                        if constexpr (MAP) {
+                            j = rtm::map_find_pixel((const RTD_AS3 uint32_t *) (wv + 18u * P + curSlot * P), curNpx, item);
+                            smp = wv[20u * P + curSlot * P + j] + item;
+                        } else {
+                            j = fastDiv ? div_uniform(item, n2, perRcp) : item / n2;
+                            smp = n1 + (item - j * n2);
+                        }
                         const RTD_AS3 uint32_t *pix = wv + curSlot * SW + 3u * P;
                         const int row = (int) pix[j * 4 + 0], col = (int) pix[j * 4 + 1];
                         const uint64_t pkey = (uint64_t) pix[j * 4 + 2] | ((uint64_t) pix[j * 4 + 3] << 32);
@@ -975,6 +1013,7 @@ RTD_INLINE uint32_t stage_nodes32(const RenderParams &p, unsigned char *smem) {
 // MODE 6 / 7 / 8: MODE 0 / 1 / 2 over a caller's footprint list (rt_render_footprints): pixel i of p.n_rows * p.cols is footprint i of
 //         p.rays ([n][12]: origin, base, du, dv), its stream that of (seed, p.ray_base + i); a sample's ray is footprint_ray's; no pixel
 //         candidates.  Everything else -- units, accumulators, the decision, the compaction, pass B's ordered list -- is the frame's.
+// MODE 9 / 10: MODE 2 / 8 with per-pixel sample ranges (run_stream<.., MAP>): pass B of an extension by map (rt_render_extend_map).
 // Per-pixel cost is heavy-tailed (a pixel on a glass sphere: ~20 rays per sample, 4 ms of one wave), so when a shard has only a few
 // units per wave the fused kernel ends with most waves waiting for a few long units started late; A + sort + B removes that tail.
 // Every mode computes the same integers: which wave traces which sample when has no effect (streams are per item).
@@ -982,8 +1021,9 @@ RTD_INLINE uint32_t stage_nodes32(const RenderParams &p, unsigned char *smem) {
 template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX>
 __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr bool FP = MODE >= 6;             // the pixels are the caller's footprints
-    constexpr int PM = FP ? MODE - 6 : MODE;   // ... and run as this pixel mode
+    constexpr bool MAP = MODE == 9 || MODE == 10; // pass B of an extension by map: of a frame / of a footprint list
+    constexpr bool FP = MODE >= 6 && MODE != 9;   // the pixels are the caller's footprints
+    constexpr int PM = MAP ? 2 : FP ? MODE - 6 : MODE; // ... and run as this pixel mode
     constexpr bool RAYS = MODE == 4 || MODE == 5;
     constexpr bool FUSED = PM == 0 || PM == 3;
     const int lane = threadIdx.x & 63;
@@ -999,7 +1039,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     scv.lds_thr = p.lds_node_thr;
     const SceneView<LDS> &sc = scv;
     const uint32_t P = (uint32_t) p.chunk;
-    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * (RAYS ? 0u : PM == 1 ? RTD_WAVE_WORDS_A(P) : RTD_WAVE_WORDS(P));
+    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * (RAYS ? 0u : PM == 1 ? RTD_WAVE_WORDS_A(P) : MAP ? RTD_WAVE_WORDS_MAP(P) : RTD_WAVE_WORDS(P));
     RTD_AS3 uint32_t *acc = wv;
     RTD_AS3 uint32_t *pix = wv + 6u * P;
     RTD_AS3 uint32_t *live = pix + 4u * P;
@@ -1007,7 +1047,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     unsigned char *pool = p.park_pool + ((size_t) blockIdx.x * (BLOCK / 64) + (size_t) wave) * (size_t) RTD_PARK_ENTRY_BYTES *
                                         (size_t) (p.park + (p.park_l_lds ? 0 : p.park_l) + (TEX ? p.park : 0));
     // the Lambert pools in LDS (if any) follow the waves' scratch
-    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * (RAYS ? 0u : PM == 1 ? RTD_WAVE_WORDS_A(P) : RTD_WAVE_WORDS(P)) * 4u +
+    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * (RAYS ? 0u : PM == 1 ? RTD_WAVE_WORDS_A(P) : MAP ? RTD_WAVE_WORDS_MAP(P) : RTD_WAVE_WORDS(P)) * 4u +
                                      (size_t) wave * (size_t) RTD_PARK_L_LDS_BYTES * (size_t) p.park_l;
 
     const uint64_t nLocal = (uint64_t) p.n_rows * (uint64_t) p.cols;
@@ -1031,7 +1071,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     uint64_t sampleCount = 0; // Scene.traceOnce calls = sum of PixelStats.Count
 
     if constexpr (RAYS) run_rays<LDS, COUNT, TEX, MODE == 5>(p, sc, pool, poolLds, cnt, ss);
-    else if (PM == 2) run_stream<LDS, COUNT, TEX, FP>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
+    else if (PM == 2) run_stream<LDS, COUNT, TEX, FP, MAP>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
     else
     for (;;) {
         uint32_t unit = 0;
@@ -1235,6 +1275,56 @@ __global__ void __launch_bounds__(256) extend_final_rgb_kernel(const int32_t *ac
     for (unsigned long long i = (unsigned long long) blockIdx.x * 256ull + threadIdx.x; i < n; i += stride) {
         const i4 v = ((const i4 *) accum)[i];
         if (v.x != RTD_EARLY_COUNT) continue;
+        rgb[i * 3 + 0] = (uint8_t) (v.y / v.x);
+        rgb[i * 3 + 1] = (uint8_t) (v.z / v.x);
+        rgb[i * 3 + 2] = (uint8_t) (v.w / v.x);
+    }
+}
+
+// ---- extending by map (rt_render_extend_map): the list from the stored Counts AND the caller's per-pixel targets ----
+// extend_list_kernel's shape -- one coalesced 16-byte load of the PixelStats plus one 4-byte load of the target per lane, ballot,
+// lane_rank, one agent-scope atomicAdd per wave -- with the classes of a map: Count == 11 FINAL (whatever the target); Count >= 12 and
+// Count < target <= cap CONTINUED; Count >= 12 and target <= Count LEFT as it is; Count < 11 or target > cap MALFORMED (counted in
+// `foreign`: the seal then continues no pixel).  `cap` >= 12, so a continued pixel has 12 <= Count < target <= cap.
+__global__ void __launch_bounds__(256) extend_map_list_kernel(const int32_t *accum, const int32_t *targets, unsigned long long n, int32_t cap,
+                                                              unsigned int *live_list, unsigned int *live_count, unsigned long long *counters,
+                                                              unsigned int *foreign) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull;
+    const unsigned long long trips = (n + stride - 1ull) / stride; // uniform over the grid: every lane of a wave makes every ballot
+    unsigned long long nFinal = 0ull, nForeign = 0ull;
+    for (unsigned long long t = 0; t < trips; ++t) {
+        const unsigned long long i = t * stride + (unsigned long long) blockIdx.x * 256ull + threadIdx.x;
+        int count = RTD_EARLY_COUNT, target = 0;
+        if (i < n) { count = ((const i4 *) accum)[i].x; target = targets[i]; }
+        const bool fin = i < n && count == RTD_EARLY_COUNT;
+        const bool foreignPx = i < n && !fin && (count < RTD_EARLY_COUNT || target > cap);
+        const bool cont = i < n && !fin && !foreignPx && target > count;
+        const unsigned long long liveMask = __builtin_amdgcn_ballot_w64(cont);
+        const uint32_t nLive = (uint32_t) __popcll(liveMask);
+        if (nLive > 0u) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(live_count, nLive);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (cont) live_list[base + lane_rank(liveMask)] = (unsigned int) i;
+        }
+        nForeign += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(foreignPx));
+        nFinal += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(fin));
+    }
+    if (lane == 0) {
+        if (nFinal != 0ull) atomicAdd(&counters[5], nFinal);
+        if (nForeign != 0ull) atomicAdd(foreign, (unsigned int) nForeign); // (n < 2^32: the sum cannot wrap to 0)
+    }
+}
+// extend_final_rgb_kernel for a map: PixelStats.mean of the FINAL pixels and of those LEFT as they are (Count >= target); pass B writes
+// the continued ones'.  After the seal, before pass B: the Counts read here are the ones the list was built from.
+__global__ void __launch_bounds__(256) extend_map_rest_rgb_kernel(const int32_t *accum, const int32_t *targets, unsigned long long n,
+                                                                  const unsigned int *malformed, uint8_t *rgb) {
+    if (*malformed != 0u) return;
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull;
+    for (unsigned long long i = (unsigned long long) blockIdx.x * 256ull + threadIdx.x; i < n; i += stride) {
+        const i4 v = ((const i4 *) accum)[i];
+        if (v.x != RTD_EARLY_COUNT && targets[i] > v.x) continue;
         rgb[i * 3 + 0] = (uint8_t) (v.y / v.x);
         rgb[i * 3 + 1] = (uint8_t) (v.z / v.x);
         rgb[i * 3 + 2] = (uint8_t) (v.w / v.x);

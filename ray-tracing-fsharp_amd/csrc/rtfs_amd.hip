@@ -200,7 +200,8 @@ static int allow_full_lds(const void *fn) {
 // blocks of 256 and 1024 threads only, and the hit queries (mode 5) shade nothing, so they have no textured variant.  The plan
 // never asks for one of the others; if it did, the launch fails (no kernel is substituted).
 template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX> static render_fn kernel_if_built() {
-    if constexpr ((MODE >= 4 && BLOCK != 256 && BLOCK != 1024) || (MODE == 5 && TEX)) return nullptr; // (the footprint modes 6-8: as the ray lists)
+    if constexpr ((MODE >= 4 && MODE != 9 && BLOCK != 256 && BLOCK != 1024) || (MODE == 5 && TEX)) return nullptr; // (the footprint modes 6-8 and 10: as the ray lists;
+                                                                                                                        // mode 9 runs frames: every block, as mode 2)
     else return render_kernel<LDS, COUNT, BLOCK, MODE, TEX>;
 }
 template <int BLOCK, int MODE, bool TEX> static render_fn pick_variant(bool lds, bool count) {
@@ -223,6 +224,8 @@ static render_fn pick_kernel(const rtp::Pass &q) {
     case 6: return q.tex ? pick_mode<6, true>(q) : pick_mode<6, false>(q);
     case 7: return q.tex ? pick_mode<7, true>(q) : pick_mode<7, false>(q);
     case 8: return q.tex ? pick_mode<8, true>(q) : pick_mode<8, false>(q);
+    case 9: return q.tex ? pick_mode<9, true>(q) : pick_mode<9, false>(q);
+    case 10: return q.tex ? pick_mode<10, true>(q) : pick_mode<10, false>(q);
     default: return nullptr;
     }
 }
@@ -475,6 +478,7 @@ struct Pending {
     uint64_t pixels = 0, waves = 0;
     bool launched = false, keep = false;
     bool extend = false; // an extension: collect_stats reads LaunchScratch::ext_malformed
+    bool map = false;    // ... by map (the message of a malformed buffer)
     std::chrono::steady_clock::time_point t0;
     void release() { // events destroyed, scratch handed back to the stream's pool in stream order
         if (a) (void) hipEventDestroy(a);
@@ -531,8 +535,9 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
         put(r->mode); put((int64_t) r->grid); put((int64_t) r->lds_bytes); put(r->chunk); put(r->park); put(r->park_l); put(r->park_l_lds);
         put(r->lds_node_bytes); put(r->lds_node_thr); put(r->yield_lanes); put(r->leaf_wait); put(r->refill_lanes); put(r->k); put(r->total_waves);
     }
-    put(j.first_sample); // [77]: 0 = a fresh render, else the samples_done of an extension
-    static_assert(1 + 21 + 13 + 3 * 14 + 1 <= RT_LAUNCH_PLAN_WORDS, "rt_dev_last_launch_plan's words");
+    put(j.first_sample); // [77]: 0 = a fresh render, else the samples_done of an extension (by map: RTD_EXTEND_MIN_DONE)
+    put(j.map ? 1 : 0);  // [78]: 1 = an extension by map
+    static_assert(1 + 21 + 13 + 3 * 14 + 2 <= RT_LAUNCH_PLAN_WORDS, "rt_dev_last_launch_plan's words");
     while (n < RT_LAUNCH_PLAN_WORDS) put(0);
 }
 
@@ -584,6 +589,7 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     cl.pixels = plan.pixels;
     cl.waves = plan.waves;
     cl.extend = job.extend();
+    cl.map = job.map;
     if (want_stats) {
         HIP_TRY(hipEventCreate(&cl.a));
         HIP_TRY(hipEventCreate(&cl.b));
@@ -616,10 +622,17 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
             const unsigned long long nLocal = plan.pixels; // (< 2^32: the plan's condition for a list)
             const unsigned long long want = (nLocal + 255ull) / 256ull, most = (unsigned long long) ds->cu_count * 8ull;
             const unsigned listGrid = (unsigned) (want < most ? want : most);
-            hipLaunchKernelGGL(extend_list_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, nLocal, job.first_sample, list, p.live_count,
-                               p.counters, &ls->ext_foreign);
+            if (job.map) // every pixel against its own target (p.spp is the cap); the seal is the same
+                hipLaunchKernelGGL(extend_map_list_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, p.ext_targets, nLocal, p.spp, list,
+                                   p.live_count, p.counters, &ls->ext_foreign);
+            else
+                hipLaunchKernelGGL(extend_list_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, nLocal, job.first_sample, list, p.live_count,
+                                   p.counters, &ls->ext_foreign);
             hipLaunchKernelGGL(extend_seal_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) &ls->ext_foreign, p.live_count, &ls->ext_malformed);
-            if (p.rgb)
+            if (p.rgb && job.map) // the final pixels AND the ones left as they are; pass B writes the continued ones'
+                hipLaunchKernelGGL(extend_map_rest_rgb_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, p.ext_targets, nLocal,
+                                   (const unsigned int *) &ls->ext_malformed, p.rgb);
+            else if (p.rgb)
                 hipLaunchKernelGGL(extend_final_rgb_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, nLocal,
                                    (const unsigned int *) &ls->ext_malformed, p.rgb);
             hipLaunchKernelGGL(fb, dim3((unsigned) plan.b.grid), dim3((unsigned) block), plan.b.lds_bytes, st, p);
@@ -665,7 +678,8 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
 // Enqueues one shard's render on `stream`: the argument checks and the frame's own RenderParams fields, then enqueue().
 static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
                          int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
-                         const rt_render_options *options, bool want_stats, Pending &pd, const RayLog *log = nullptr, int32_t first_sample = 0) {
+                         const rt_render_options *options, bool want_stats, Pending &pd, const RayLog *log = nullptr, int32_t first_sample = 0,
+                         const void *d_targets = nullptr) { // d_targets: an extension by map (first_sample is then RTD_EXTEND_MIN_DONE)
     if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     int rc = check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows);
     if (rc != RT_OK) return rc;
@@ -689,6 +703,8 @@ static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t
     job.n_rows = (uint64_t) n_rows; job.max_w = max_w; job.spp = camera->samples_per_pixel;
     job.ray_log = log != nullptr;
     job.first_sample = first_sample;
+    job.map = d_targets != nullptr;
+    p.ext_targets = (const int32_t *) d_targets;
     return enqueue(scene, device, job, set, flags, stream, p, camera_params(camera, max_w, max_h), want_stats, pd);
 }
 
@@ -715,7 +731,8 @@ static int collect_stats(Pending &pd, rt_stats *stats) {
         HIP_TRY(hipMemcpy(&malformed, pd.scr + offsetof(LaunchScratch, ext_malformed), sizeof(malformed), hipMemcpyDeviceToHost));
         if (malformed) {
             pd.release();
-            return fail(RT_ERR_INVALID_ARGUMENT, "accum is not a buffer of samples_done samples per pixel (a Count that is neither samples_done nor 11); left unchanged");
+            return fail(RT_ERR_INVALID_ARGUMENT, pd.map ? "accum or targets are not what the arguments say (a Count below 11, or a target above the cap); left unchanged"
+                                                        : "accum is not a buffer of samples_done samples per pixel (a Count that is neither samples_done nor 11); left unchanged");
         }
     }
     float ms = 0.f;
@@ -1140,7 +1157,7 @@ static int check_footprints(const rt_scene *scene, size_t n, const void *footpri
 // whose pixel i reads footprint i and owns the stream of (seed, stream_base + i); then enqueue(), as for a frame shard.
 static int launch_footprints(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints, int32_t spp, int32_t bounce_depth,
                              uint64_t seed, uint64_t stream_base, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
-                             const rt_render_options *options, bool want_stats, Pending &pd, int32_t first_sample = 0) {
+                             const rt_render_options *options, bool want_stats, Pending &pd, int32_t first_sample = 0, const void *d_targets = nullptr) {
     RenderParams p{};
     p.spp = spp;
     p.depth = bounce_depth;
@@ -1156,6 +1173,8 @@ static int launch_footprints(const rt_scene *scene, int32_t device, size_t n, co
     job.kind = rtp::Job::FOOTPRINTS;
     job.n = n; job.spp = spp;
     job.first_sample = first_sample;
+    job.map = d_targets != nullptr; // an extension by map (first_sample is then RTD_EXTEND_MIN_DONE)
+    p.ext_targets = (const int32_t *) d_targets;
     return enqueue(scene, device, job, resolve_settings(options), flags, stream, p, CameraParams{}, want_stats, pd); // (no camera: never read in these modes)
 }
 
@@ -1335,6 +1354,140 @@ int rt_render_footprints_extend(const rt_scene *scene, int32_t device, size_t n,
     if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpy(accum, buf + bFp, n * 16u, hipMemcpyDeviceToHost));
     if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bFp + bAcc, n * 3u, hipMemcpyDeviceToHost));
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// extending by map (DESIGN.md "Extending by map"): every pixel from its stored Count to a target of its own.  The cap -- the camera's
+// (footprints: the argument's) samples_per_pixel -- bounds every target.  Planned and launched as the extension 12 -> cap, with the
+// map's list builder and pass B's per-pixel variant (render_kernel MODE 9 / 10).
+// ------------------------------------------------------------------------------------------------------------
+static int check_extend_map(int32_t cap, size_t pixels, const void *targets) {
+    if (cap < RTD_EXTEND_MIN_DONE)
+        return fail(RT_ERR_INVALID_ARGUMENT, "a map's samples_per_pixel (the bound on every target) must be >= 12 (a buffer rendered below cannot be continued)");
+    if (pixels > 0 && !targets) return fail(RT_ERR_INVALID_ARGUMENT, "targets is NULL");
+    return RT_OK;
+}
+// Every argument check of the two frame entry points, made before anything touches a device.
+static int check_extend_map_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t row_first, int32_t row_stride,
+                                  int32_t n_rows, const void *targets, const void *accum, const rt_render_options *options) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    int rc = check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows);
+    if (rc != RT_OK) return rc;
+    if (n_rows > 0 && !accum) return fail(RT_ERR_INVALID_ARGUMENT, "accum is NULL");
+    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
+    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
+    if ((rc = check_extend_map(camera->samples_per_pixel, (size_t) n_rows, targets)) != RT_OK) return rc;
+    if ((uint64_t) n_rows * (uint64_t) (2 * max_w + 1) >= (1ull << 32)) return fail(RT_ERR_INVALID_ARGUMENT, "an extension takes shards of fewer than 2^32 pixels");
+    return RT_OK;
+}
+
+extern "C" {
+
+int rt_render_extend_map_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
+                                int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, const void *d_targets, void *d_accum, void *d_rgb,
+                                void *stream, const rt_render_options *options, rt_stats *stats) {
+    int rc = check_extend_map_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, d_targets, d_accum, options);
+    if (rc != RT_OK) return rc;
+    if (n_rows == 0) { // an empty shard
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    Pending pd;
+    rc = launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d_accum, d_rgb, stream, options, stats != nullptr, pd,
+                       nullptr, RTD_EXTEND_MIN_DONE, d_targets);
+    if (rc != RT_OK || !stats) return rc;
+    return collect_stats(pd, stats);
+}
+
+// The host variant: the buffer and the map copied in, the device variant on the null stream, the outputs copied back -- unless it failed.
+int rt_render_extend_map(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
+                         int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, const int32_t *targets, int32_t *accum, uint8_t *rgb,
+                         rt_stats *stats) {
+    int rc = check_extend_map_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, targets, accum, nullptr);
+    if (rc != RT_OK) return rc;
+    if (n_rows == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
+    const size_t npx = (size_t) n_rows * (size_t) (2 * max_w + 1), bAcc = up16(npx * 16u), bMap = up16(npx * 4u), bRgb = rgb ? up16(npx * 3u) : 0u;
+    unsigned char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **) &buf, bAcc + bMap + bRgb));
+    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
+    HIP_TRY(hipMemcpy(buf, accum, npx * 16u, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(buf + bAcc, targets, npx * 4u, hipMemcpyHostToDevice));
+    rt_stats local; // (always asked for: the malformed-buffer error is reported through it)
+    rc = rt_render_extend_map_device(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, buf + bAcc, buf,
+                                     bRgb ? buf + bAcc + bMap : nullptr, nullptr, nullptr, &local);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpy(accum, buf, npx * 16u, hipMemcpyDeviceToHost));
+    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bAcc + bMap, npx * 3u, hipMemcpyDeviceToHost));
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+int rt_render_footprints_extend_map_device(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints, int32_t samples_per_pixel,
+                                           int32_t bounce_depth, uint64_t seed, uint64_t stream_base, uint32_t flags, const void *d_targets, void *d_accum,
+                                           void *d_rgb, void *stream, const rt_render_options *options, rt_stats *stats) {
+    int rc = check_footprints(scene, n, d_footprints, d_accum, samples_per_pixel, bounce_depth, options);
+    if (rc != RT_OK || (rc = check_extend_map(samples_per_pixel, n, d_targets)) != RT_OK) return rc;
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    Pending pd;
+    rc = launch_footprints(scene, device, n, d_footprints, samples_per_pixel, bounce_depth, seed, stream_base, flags, d_accum, d_rgb, stream, options,
+                           stats != nullptr, pd, RTD_EXTEND_MIN_DONE, d_targets);
+    if (rc != RT_OK || !stats) return rc;
+    return collect_stats(pd, stats);
+}
+
+int rt_render_footprints_extend_map(const rt_scene *scene, int32_t device, size_t n, const double *footprints, int32_t samples_per_pixel, int32_t bounce_depth,
+                                    uint64_t seed, uint64_t stream_base, uint32_t flags, const int32_t *targets, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
+    int rc = check_footprints(scene, n, footprints, accum, samples_per_pixel, bounce_depth, nullptr);
+    if (rc != RT_OK || (rc = check_extend_map(samples_per_pixel, n, targets)) != RT_OK) return rc;
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
+    const size_t bFp = up16(n * 96u), bAcc = up16(n * 16u), bMap = up16(n * 4u), bRgb = rgb ? up16(n * 3u) : 0u;
+    unsigned char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **) &buf, bFp + bAcc + bMap + bRgb));
+    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
+    HIP_TRY(hipMemcpy(buf, footprints, n * 96u, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(buf + bFp, accum, n * 16u, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(buf + bFp + bAcc, targets, n * 4u, hipMemcpyHostToDevice));
+    rt_stats local;
+    rc = rt_render_footprints_extend_map_device(scene, device, n, buf, samples_per_pixel, bounce_depth, seed, stream_base, flags, buf + bFp + bAcc, buf + bFp,
+                                                bRgb ? buf + bFp + bAcc + bMap : nullptr, nullptr, nullptr, &local);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpy(accum, buf + bFp, n * 16u, hipMemcpyDeviceToHost));
+    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bFp + bAcc + bMap, n * 3u, hipMemcpyDeviceToHost));
     if (stats) {
         *stats = local;
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -304,6 +304,32 @@ class Scene {
                                           rgb.data(), &lastStats));
         return rgb;
     }
+    // rt_render_extend_map / rt_render_footprints_extend_map: every pixel of `accum` -- a buffer that began as a render at >= 12 samples --
+    // continued IN PLACE from its own Count to targets[i] (one per pixel, as accum is laid out; at most camera.SamplesPerPixel /
+    // samplesPerPixel).  A pixel whose target is not above its Count is left as it is; one that stopped early (Count 11) is final.
+    // Each pixel is then that pixel of a render at its Count.  Returns PixelStats.mean per pixel.
+    std::vector<uint8_t> extendRowsMap(int maxWidthCoord, int maxHeightCoord, const Camera &camera, std::vector<int32_t> &accum,
+                                       const std::vector<int32_t> &targets, uint64_t seed = 0, int device = 0, int rowFirst = 0, int rowStride = 1) {
+        const size_t cols = (size_t) (2 * maxWidthCoord + 1);
+        if (accum.size() % (cols * 4) != 0 || targets.size() * 4 != accum.size())
+            throw std::invalid_argument("extendRowsMap: accum is not [n_rows][cols][4] or targets not [n_rows][cols]");
+        const int nRows = (int) (accum.size() / (cols * 4));
+        std::vector<uint8_t> rgb((size_t) nRows * cols * 3);
+        rt_camera cam = camera.toAbi();
+        check(rt_render_extend_map(h_, &cam, maxWidthCoord, maxHeightCoord, seed, device, rowFirst, rowStride, nRows, 0u, targets.data(), accum.data(),
+                                   rgb.data(), &lastStats));
+        return rgb;
+    }
+    std::vector<uint8_t> extendFootprintsMap(const std::vector<double> &footprints, int samplesPerPixel, int bounceDepth, std::vector<int32_t> &accum,
+                                             const std::vector<int32_t> &targets, uint64_t seed = 0, uint64_t streamBase = 0, int device = 0) {
+        const size_t n = footprints.size() / 12;
+        if (footprints.size() % 12 != 0 || accum.size() != n * 4 || targets.size() != n)
+            throw std::invalid_argument("extendFootprintsMap: footprints [n][12], accum [n][4], targets [n]");
+        std::vector<uint8_t> rgb(n * 3);
+        check(rt_render_footprints_extend_map(h_, device, n, footprints.data(), samplesPerPixel, bounceDepth, seed, streamBase, 0u, targets.data(),
+                                              accum.data(), rgb.data(), &lastStats));
+        return rgb;
+    }
 
     rt_scene *handle() const { return h_; }
     rt_stats lastStats{};

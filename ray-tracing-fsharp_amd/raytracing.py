@@ -523,6 +523,50 @@ class Scene:
         self.last_stats = st.as_dict()
         return RenderResult(out, rgb, self.last_stats)
 
+    def extend_rows_map(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, accum, targets, *, seed: int = 0,
+                        device: Optional[int] = None, row_first: int = 0, row_stride: int = 1, counters: bool = False, stats: bool = True,
+                        options: Optional[A.rt_render_options] = None) -> RenderResult:
+        """rt_render_extend_map: continues every pixel of `accum` -- the PixelStats of the rows row_first + i*row_stride of a buffer that
+        began as a render at >= 12 samples per pixel -- from its own Count to targets[row, col] (int32 [n_rows, cols]); a pixel whose
+        target is not above its Count is left as it is, one that stopped early (Count 11) is final.  camera.SamplesPerPixel is the upper
+        bound on every target.  Each pixel is then, bit for bit, that pixel of a render at its Count.  Arrays and tensors as for
+        extend_rows: an array is copied, a GPU tensor (with `targets` a tensor on the same device) is extended in place on the
+        current stream."""
+        cols = 2 * maxWidthCoord + 1
+        flags = A.RT_RENDER_COUNTERS if counters else 0
+        cam = camera.to_abi()
+        if _is_torch(accum):
+            torch = _torch()
+            if accum.dtype != torch.int32 or accum.dim() != 3 or tuple(accum.shape[1:]) != (cols, 4) or not accum.is_cuda or not accum.is_contiguous():
+                raise ValueError(f"accum must be a contiguous int32 tensor [n_rows, {cols}, 4] on a GPU")
+            n_rows = accum.shape[0]
+            if (not _is_torch(targets) or targets.dtype != torch.int32 or tuple(targets.shape) != (n_rows, cols) or targets.device != accum.device
+                    or not targets.is_contiguous()):
+                raise ValueError(f"targets must be a contiguous int32 tensor [n_rows, {cols}] on accum's device")
+            dev = _tensor_device(accum, device)
+            rgb = torch.empty((n_rows, cols, 3), dtype=torch.uint8, device=accum.device)
+            st = A.rt_stats() if stats else None
+            check(lib.rt_render_extend_map_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, row_first, row_stride, n_rows, flags,
+                                                  targets.data_ptr(), accum.data_ptr(), rgb.data_ptr(),
+                                                  torch.cuda.current_stream(accum.device).cuda_stream, _ref(options), _ref(st)))
+            self.last_stats = st.as_dict() if st is not None else None
+            return RenderResult(accum, rgb, self.last_stats)
+        if options is not None:
+            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        if not isinstance(accum, np.ndarray) or accum.dtype != np.int32 or accum.ndim != 3 or accum.shape[1:] != (cols, 4):
+            raise ValueError(f"accum must be an int32 array [n_rows, {cols}, 4] or such a tensor on a GPU")
+        out = np.array(accum, dtype=np.int32, order="C")
+        n_rows = out.shape[0]
+        if not isinstance(targets, np.ndarray) or targets.dtype != np.int32 or targets.shape != (n_rows, cols):
+            raise ValueError(f"targets must be an int32 array [n_rows, {cols}]")
+        tg = np.ascontiguousarray(targets)
+        rgb = np.zeros((n_rows, cols, 3), np.uint8)
+        st = A.rt_stats()
+        check(lib.rt_render_extend_map(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, row_first,
+                                       row_stride, n_rows, flags, _i32(tg), _i32(out), _u8(rgb), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return RenderResult(out, rgb, self.last_stats)
+
     def render_frame(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, *, seed: int = 0, devices: Sequence[int] = (0,),
                      gather: int = A.RT_GATHER_AUTO, counters: bool = False, options: Optional[A.rt_render_options] = None) -> RenderResult:
         """rt_render_frame: the whole frame on several GPUs from this one process (rows interleaved over `devices`, one gather);
@@ -614,7 +658,7 @@ class Scene:
 
     def renderFootprints(self, footprints, samplesPerPixel: int, bounceDepth: int, *, seed: int = 0, stream_base: int = 0,
                          device: Optional[int] = None, counters: bool = False, stats: bool = True,
-                         options: Optional[A.rt_render_options] = None, extend=None) -> RenderResult:
+                         options: Optional[A.rt_render_options] = None, extend=None, extend_map=None) -> RenderResult:
         """Scene.renderPixel (Scene.fs:157-194) for caller-defined cameras: footprints [n, 12] float64, per pixel origin, base, du,
         dv.  Sample s of pixel i draws (r1, r2) from the stream keyed (seed, stream_base + i, s) and traces
         Ray.make'(origin, (base + r1*du) + r2*dv) at most bounceDepth+1 hits; the adaptive stop is the reference's, with
@@ -623,7 +667,11 @@ class Scene:
         wait for the device, stats and last_stats are None).
         extend=(accum, samplesDone): rt_render_footprints_extend -- `accum` [n, 4] int32, these footprints' PixelStats at samplesDone
         (>= 12) samples, is continued to samplesPerPixel; bit for bit a render at that count.  An array is copied, a tensor (on the
-        footprints' device) extended in place."""
+        footprints' device) extended in place.
+        extend_map=(accum, targets): rt_render_footprints_extend_map -- every footprint from its own Count to targets[i] (int32 [n]), at
+        most samplesPerPixel; the classes and the array / tensor rules of extend_rows_map."""
+        if extend is not None and extend_map is not None:
+            raise ValueError("extend and extend_map exclude each other")
         flags = A.RT_RENDER_COUNTERS if counters else 0
         if _is_torch(footprints):
             torch = _torch()
@@ -639,6 +687,14 @@ class Scene:
                     raise ValueError("extend=(accum, samplesDone): accum must be a contiguous int32 tensor [n, 4] on the footprints' device")
                 check(lib.rt_render_footprints_extend_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
                                                              done, accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
+            elif extend_map is not None:
+                accum, tg = extend_map
+                if not _is_torch(accum) or accum.dtype != torch.int32 or tuple(accum.shape) != (n, 4) or accum.device != f.device or not accum.is_contiguous():
+                    raise ValueError("extend_map=(accum, targets): accum must be a contiguous int32 tensor [n, 4] on the footprints' device")
+                if not _is_torch(tg) or tg.dtype != torch.int32 or tuple(tg.shape) != (n,) or tg.device != f.device or not tg.is_contiguous():
+                    raise ValueError("extend_map=(accum, targets): targets must be a contiguous int32 tensor [n] on the footprints' device")
+                check(lib.rt_render_footprints_extend_map_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
+                                                                 tg.data_ptr(), accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
             else:
                 accum = torch.empty((n, 4), dtype=torch.int32, device=f.device)
                 check(lib.rt_render_footprints_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
@@ -657,6 +713,16 @@ class Scene:
                 raise ValueError("extend=(accum, samplesDone): accum must be [n, 4] for n footprints")
             check(lib.rt_render_footprints_extend(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed,
                                                   stream_base, flags, extend[1], _i32(accum), _u8(rgb), C.byref(st)))
+        elif extend_map is not None:
+            accum = np.array(_array_arg(extend_map[0], "extend_map's accum", np.int32, 4), order="C")
+            tg = extend_map[1]
+            if accum.shape[0] != n:
+                raise ValueError("extend_map=(accum, targets): accum must be [n, 4] for n footprints")
+            if not isinstance(tg, np.ndarray) or tg.dtype != np.int32 or tg.shape != (n,):
+                raise ValueError("extend_map=(accum, targets): targets must be an int32 array [n]")
+            tg = np.ascontiguousarray(tg)
+            check(lib.rt_render_footprints_extend_map(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed,
+                                                      stream_base, flags, _i32(tg), _i32(accum), _u8(rgb), C.byref(st)))
         else:
             accum = np.zeros((n, 4), np.int32)
             check(lib.rt_render_footprints(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed, stream_base,
