@@ -398,6 +398,10 @@ def test_leaf_queue_of_the_node_loop_under_pressure(rt, orc):
 
 
 def test_reflection_every_style(rt, orc):
+    """Ordinary materials, random rays against unrelated strike points, random generator states.  The edges -- near-normal and grazing
+    incidence, total internal reflection at its threshold (NaN rays included), origins on the surface, the LightSourceCap band, extreme
+    material parameters, chosen generator values, the retry loops, and the timed kernel's own routes to the same arithmetic -- are in
+    tests/test_gpu_reflection.py (cases: tests/reflection_cases.py)."""
     objs, *_ = scenes.all_materials()
     s, o = _scene_pair(rt, orc, objs)
     rng = np.random.default_rng(41)
