@@ -48,12 +48,26 @@ RTD_INLINE V3 vsub(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
 RTD_INLINE V3 vscale(double s, V3 v) { return mk(s * v.x, s * v.y, s * v.z); }
 // Ray.walkAlongRay (Ray.fs:42-43): o + (v * m) per component
 RTD_INLINE V3 walk(V3 o, V3 v, double m) { return mk(o.x + (v.x * m), o.y + (v.y * m), o.z + (v.z * m)); }
+#ifdef RTD_STAGE_CLOCKS
+// Diagnostic builds only: execution counts for the instruction census (scripts/instruction_census.py), summed over every launch since
+// the last rt_diag_census(.., reset).  Words 0-31 are the wave-uniform counts of StageStats (rt_render_kernel.h); the rare events of this
+// file add themselves here, per lane: [32] random_unit retries, [33] lambert_bounce retries, [34] lanes entering the leaf sliver,
+// [35] the same per wave (sliver blocks executed).  Words 36-47: the kernel's own stage counts (rt_render_kernel.h).  Lanes behind the
+// wave-uniform guards (RTD_ANY_LANE below): [48] the Equal arm of sphere_first_intersection, [49] of the leaf pass.
+#define RTD_CENSUS_WORDS 52
+__device__ unsigned long long g_census[RTD_CENSUS_WORDS];
+#define RTD_CENSUS_EVENT(i) atomicAdd(&g_census[i], 1ull)
+#else
+#define RTD_CENSUS_EVENT(i)
+#endif
+
 // Correctly rounded sqrt and reciprocal for operands in the NORMAL range.  The compiler's expansions of sqrt(x) and 1.0/x
 // (v_rsq_f64 / v_rcp_f64 + Newton steps in fma, then one exactly-computed-residual correction -- the sequence that makes the
 // result the correctly rounded one) spend 5 of 18 and 4 of 11 instructions on rescaling denormal / huge operands and on the
-// zero/inf fix-ups.  Every caller below passes a value that has already compared > 1e-8 (or is NaN, which propagates), so the
+// zero/inf fix-ups.  Every caller below uses the result only for a value that has compared > 1e-8 (or is NaN, which propagates), so the
 // rescaling never triggers and the same arithmetic without it returns the same bits; +inf is restored by the caller's one
-// class test.  tests/test_gpu_parity.py::test_normal_range_sqrt_and_reciprocal checks both against the host's sqrt and
+// class test.  (The sphere tests also run it on discriminants below 1e-8, for a result they then discard
+// or that is the NaN they want: sphere_first_intersection.)  tests/test_gpu_parity.py::test_normal_range_sqrt_and_reciprocal checks both against the host's sqrt and
 // division on 40 M operands over [1e-8, 1e300].
 RTD_INLINE double sqrt_core(double x) { // x in [2^-767, 2^1023]: LLVM's f64 sqrt lowering without its input scaling
     const double y = __builtin_amdgcn_rsq(x);
@@ -76,13 +90,22 @@ RTD_INLINE double rcp_core(double s) { // 1.0 / s for s in [2^-511, 2^511]: LLVM
     e = fma(-s, r, 1.0); // numerator 1.0: the quotient estimate IS r; residual computed exactly, one last correction
     return fma(e, r, r);
 }
+// A lane-rare arm behind a wave-uniform guard: `if (RTD_ANY_LANE(cond)) { RTD_RARE_ARM(); if (cond) ... }`.  The ballot of ONE compare is
+// that compare's own lane mask, so the guard is a scalar compare and a scalar branch and the arm's instructions leave the common path
+// (LLVM puts no s_cbranch_execz around blocks this short: without the guard they are issued with an empty mask, every time).  The empty
+// asm keeps the block from being folded back into selects (its text is a comment, which scripts/instruction_census.py finds in the
+// listing).  Never the ballot of a conjunction or of a boolean carried across blocks:
+// that is lowered to a select and a compare per lane (NOTES.md, round 5).
+#define RTD_ANY_LANE(cond) (__builtin_amdgcn_ballot_w64(cond) != 0ull)
+#define RTD_RARE_ARM() asm volatile("; rare arm")
 RTD_INLINE double sqrt_above_tol(double x) { // sqrt(x) for x > 1e-8 or NaN
-    const double g = sqrt_core(x);
-    return __builtin_isinf(x) ? x : g;
+    double g = sqrt_core(x); // NaN for x = +inf (rsq gives 0, inf * 0)
+    if (RTD_ANY_LANE(__builtin_isinf(x))) { RTD_RARE_ARM(); if (__builtin_isinf(x)) g = x; }
+    return g;
 }
 RTD_INLINE double inv_sqrt_above_tol(double x) { // 1.0 / sqrt(x), both roundings as written, for |x| >= 1e-8 or NaN
     const double q = rcp_core(sqrt_core(x));
-    return __builtin_isinf(x) ? 0.0 : q; // sqrt(+inf) = +inf, 1.0 / +inf = +0.0
+    return __builtin_isinf(x) ? 0.0 : q; // sqrt(+inf) = +inf, 1.0 / +inf = +0.0.  A select, not a guarded arm: the guard measured slower (NOTES.md, round 12)
 }
 // Vector.unitise (Point.fs:28-35) == Ray.make' / Ray.overwriteWithMake's direction part (Ray.fs:11-34)
 RTD_INLINE bool unitise(V3 v, V3 &out) {
@@ -92,18 +115,6 @@ RTD_INLINE bool unitise(V3 v, V3 &out) {
     out = vscale(factor, v);
     return true;
 }
-
-#ifdef RTD_STAGE_CLOCKS
-// Diagnostic builds only: execution counts for the instruction census (scripts/instruction_census.py), summed over every launch since
-// the last rt_diag_census(.., reset).  Words 0-31 are the wave-uniform counts of StageStats (rt_render_kernel.h); the rare events of this
-// file add themselves here, per lane: [32] random_unit retries, [33] lambert_bounce retries, [34] lanes entering the leaf sliver,
-// [35] the same per wave (sliver blocks executed).  Words 36-47: the kernel's own stage counts (rt_render_kernel.h).
-#define RTD_CENSUS_WORDS 48
-__device__ unsigned long long g_census[RTD_CENSUS_WORDS];
-#define RTD_CENSUS_EVENT(i) atomicAdd(&g_census[i], 1ull)
-#else
-#define RTD_CENSUS_EVENT(i)
-#endif
 
 // ---- FloatProducer (Float.fs:14-76) ------------------------------------------------------------------------
 struct Rng { uint32_t x, y, z, w; };
@@ -337,18 +348,35 @@ RTD_INLINE bool bbox_hits(double ix, double iy, double iz, V3 o, d2 bx, d2 by, d
 // large that s is absorbed, a multiple of ulp(b) > 1e-8 -- happens only when i1 == i2 exactly (-> i1, the same double).
 // So the result is i2 if i2 > tol, else i1 if i1 > tol, else none; and the closing `Float.positive` of Sphere.fs:382-386 can
 // only reject the Equal branch's -b.  The oracle keeps the reference's literal control flow; tests compare the two.
+// Straight-line code for the Greater / Less case; what only the Equal arm needs runs behind a wave-uniform guard (RTD_ANY_LANE):
+//  * Lanes with disc <= -1e-8 (Less) need no arm of their own: ValueNone is carried as NaN, and the root arithmetic run on them makes
+//    one.  v_rsq_f64 of a negative operand is NaN, so s, i1 and i2 are NaN and fpos(NaN) is false; a NaN discriminant does the same.
+//    Lanes in the Equal band may compute anything there (0 * inf, a denormal's roots): the guard's arm overwrites it.
+//  * i2 is formed as (-b) - s.  Rounding is symmetric, so that is -(b + s) bit for bit except when the sum is zero, where the two
+//    differ in the zero's sign; i2 reaches the result only when it is > 1e-8, so fpos cannot see it.
+//  * INF_FIXUP = false (the kernel's sites) takes the root with sqrt_core alone.  It differs from sqrt_above_tol only for disc = +inf
+//    (|o - c|^2 or r^2 overflowed): there s is NaN instead of +inf, and the result NaN instead of +inf (s - b with b finite) or NaN.
+//    Neither is observable where the result goes: a = t * t is +inf or NaN; `fcmp(a, bestF) == CMP_LT` (unbounded_tests) is false
+//    for both (+inf - bestF is +inf or NaN, +inf < bestF is false), and so is `a < bestF || (a == bestF && prim < best)` (leaf tests):
+//    bestF = +inf only while best = -1, because a hit with t * t = +inf is never accepted in the first place.  The unit hook
+//    (rt_dev_sphere_first_intersection) hands the value itself back and keeps the fix-up.
+template <bool INF_FIXUP>
+RTD_INLINE double sphere_roots(double b, double disc) { // the result of the Greater branch, NaN on Less; unspecified on Equal
+    const double s = INF_FIXUP ? sqrt_above_tol(disc) : sqrt_core(disc);
+    const double i1 = s - b;
+    const double i2 = (-b) - s;
+    return fpos(i2) ? i2 : (fpos(i1) ? i1 : __builtin_nan(""));
+}
+template <bool INF_FIXUP = false>
 RTD_INLINE double sphere_first_intersection(V3 o, V3 d, V3 c, double r2) {
     V3 diff = vsub(o, c);
     double b = dot(d, diff);
     double cc = dot(diff, diff) - r2;
     double disc = (b * b - cc);
-    if (fzero(disc)) { double i = (-b); return fpos(i) ? i : __builtin_nan(""); }
-    double i = __builtin_nan("");
-    if (fgreater0(disc)) { // also taken by a NaN discriminant, which yields NaN roots and so none
-        double s = sqrt_above_tol(disc); // disc > 1e-8 in this branch
-        double i1 = s - b;
-        double i2 = -(b + s);
-        i = fpos(i2) ? i2 : (fpos(i1) ? i1 : i);
+    double i = sphere_roots<INF_FIXUP>(b, disc);
+    if (RTD_ANY_LANE(fzero(disc))) { // Equal: |disc| < 1e-8, a ray within ~2.5e-8 of a tangent
+        RTD_RARE_ARM();
+        if (fzero(disc)) { RTD_CENSUS_EVENT(48); const double m = (-b); i = fpos(m) ? m : __builtin_nan(""); }
     }
     return i;
 }
@@ -837,17 +865,18 @@ RTD_INLINE void leaf_test_object_exact(const SceneView<LDS> &sc, V3 o, V3 d, dou
     const double dd = dot(diff, diff);
     const double cc = dd - g1.y;
     const double disc = (b * b - cc);
-    const bool eq = fzero(disc), gt = fgreater0(disc); // Float.compare disc 0.0: Equal / Greater
-    double t = __builtin_nan("");
-    if (eq) { const double i = (-b); t = fpos(i) ? i : t; }
-    else if (gt) {
-        const double s = sqrt_above_tol(disc);
-        const double i1 = s - b, i2 = -(b + s);
-        t = fpos(i2) ? i2 : (fpos(i1) ? i1 : t);
+    // Roots on every lane, the Equal arm behind its guard, no +inf fix-up: the arguments stand above sphere_first_intersection.
+    const bool eq = fzero(disc); // Float.compare disc 0.0 = Equal
+    double t = sphere_roots<false>(b, disc);
+    if (RTD_ANY_LANE(fzero(disc))) {
+        RTD_RARE_ARM();
+        if (fzero(disc)) { RTD_CENSUS_EVENT(49); const double i = (-b); t = fpos(i) ? i : __builtin_nan(""); }
     }
     const double a = t * t;
     bool cand = a < bestF || (a == bestF && prim < w.best);
-    if (cand && !(implied && gt && dd <= RTD_IMPLIED_DD)) { // the sliver: the leaf's BoundingBox.hits, exactly
+    // A candidate has a t that is not NaN, and outside the Equal band only the Greater branch yields one: under `cand`, !eq IS
+    // `Float.compare disc 0.0 = Greater`, the claim's hypothesis.
+    if (cand && !(implied && !eq && dd <= RTD_IMPLIED_DD)) { // the sliver: the leaf's BoundingBox.hits, exactly
         RTD_CENSUS_EVENT(34);
 #ifdef RTD_STAGE_CLOCKS
         if (__builtin_amdgcn_mbcnt_hi((uint32_t) (__builtin_amdgcn_ballot_w64(true) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) __builtin_amdgcn_ballot_w64(true), 0u)) == 0u) RTD_CENSUS_EVENT(35);

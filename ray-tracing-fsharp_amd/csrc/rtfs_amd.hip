@@ -1809,7 +1809,7 @@ __global__ void k_sphere_isect(int n, const double *rays, const double *sph, dou
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double *r = rays + i * 6, *s = sph + i * 4;
-    t[i] = sphere_first_intersection(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), mk(s[0], s[1], s[2]), s[3] * s[3]);
+    t[i] = sphere_first_intersection<true>(mk(r[0], r[1], r[2]), mk(r[3], r[4], r[5]), mk(s[0], s[1], s[2]), s[3] * s[3]);
 }
 __global__ void k_plane_isect(int n, const double *rays, const double *pl, double *t) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;

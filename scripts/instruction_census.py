@@ -89,6 +89,9 @@ def instructions(path, sym=KERNEL):
         if m:
             out.append((".loc", (int(m.group(1)), int(m.group(2)))))
             continue
+        if re.match(r"\s*; rare arm\b", ln):  # RTD_RARE_ARM (rt_device.h): the head of an arm behind a wave-uniform guard
+            out.append((".rare", None))
+            continue
         m = re.match(r"\s+((?:v|s|ds|global|scratch|buffer|flat)_\w+)\s*(.*?)\s*(;.*)?$", ln)
         if m:
             out.append((m.group(1), m.group(2)))
@@ -127,6 +130,7 @@ class Block:
         self.succ = []  # labels
         self.falls = True
         self.names = []
+        self.rare = False  # part of an arm behind a wave-uniform guard (RTD_ANY_LANE): not on the common path
 
     def valu(self):
         return [o for o in self.ops if o[0].startswith("v_")]
@@ -164,6 +168,9 @@ def blocks(path):
                 cur.label = rest
             cur.names.append(rest)
             continue
+        if op == ".rare":
+            cur.rare = True
+            continue
         if op == ".loc":
             if rest[1] != 0 or loc is None:  # (line 0: compiler-made code, counted with the line before it)
                 loc = (files.get(rest[0], str(rest[0])), rest[1])
@@ -177,6 +184,14 @@ def blocks(path):
             cur = Block(len(out), None)
     if cur.ops:
         out.append(cur)
+    # a guarded arm: the block behind the guard's scalar branch carries the marker; the arm is that block and what it falls or
+    # branches into without a label of its own (the join, and every loop header, has one)
+    for i, b in enumerate(out):
+        if b.rare and not (i and out[i - 1].rare):
+            for nb in out[i + 1:]:
+                if nb.names:
+                    break
+                nb.rare = True
     return out
 
 
@@ -233,6 +248,7 @@ def cmd_blocks(a):
     for b in bl:
         f, fl, ln = b.where()
         n = collections.Counter("s" if op.startswith("s_") else "d" if op.startswith("ds_") else "v" if op.startswith("v_") else "m" for op, _ in b.ops)
+        f = f + " [rare arm]" if b.rare else f
         print(f"{b.idx:5d} {depth[b.idx]:3d}   {(b.label or ''):12s} {n['v']:4d} {fmt_classes(b.by_class())} {b.cost():6.0f} {n['s']:4d} {n['d']:3d} {n['m']:3d}   {f} ({fl}:{ln})")
 
 
@@ -285,6 +301,7 @@ def counts_from(stats, unbounded):
     n = max(1, stats.get("launches", 1))
     out = {k: v / n for k, v in c.items() if not isinstance(v, list)}
     out["zero"] = 0
+    out.setdefault("guarded_arms", 0)  # (executions per frame: census words 48-50 of a diagnostic build, a few thousand lanes)
     out["waves"] = ss["waves"]
     out.setdefault("loop_trips", ss["wave_ticks"] / n)  # (a diagnostic timed launch keeps the node loop's trips there)
     out["shade_stages_x_unbounded_spheres"] = out.get("shade_stages", 0) * unbounded[0]
@@ -309,6 +326,9 @@ def assign(bl):
         if f in ("node_loop_lds32", "pk"):
             after_loop = True
         hit = None
+        if b.rare:
+            out.append(("guarded arms (Equal, +inf): rare", "guarded_arms", stage))
+            continue
         for st, fn, name, key in GROUPS:
             if fn.endswith(":sliver"):
                 if stage == st and f in ("leaf_test_object_exact", "bbox_hits_nf") and any(classify(o) == "f64_other" and o.startswith("v_div") for o, _ in b.valu()):
@@ -324,8 +344,9 @@ def assign(bl):
             hit = ("walk: leaf pass", "leaf_passes")  # everything of the walk stage behind the node loop runs once per leaf pass
         if hit is None:
             # code of helper functions (dot, walk, unitise, math) inherits the group of the block before it inside the same stage
-            if out and out[-1][2] == stage and f not in [m[0] for m in STAGE_MARKERS] and f not in ("run_stream",):
-                hit = out[-1][:2]
+            prev = next((x for x in reversed(out) if x[1] != "guarded_arms"), None)  # (an arm does not hand its group on)
+            if prev and prev[2] == stage and f not in [m[0] for m in STAGE_MARKERS] and f not in ("run_stream",):
+                hit = prev[:2]
             else:
                 hit = STAGE_DEFAULT[stage]
         out.append((hit[0], hit[1], stage))

@@ -44,11 +44,11 @@ rows, cols = 2 * h + 1, 2 * w + 1
 local = torch.zeros((rows, cols, 4), dtype=torch.int32, device="cuda:0")
 if a.census_dump:
     import ctypes
-    cz = (ctypes.c_uint64 * 48)()
+    cz = (ctypes.c_uint64 * 52)()
     if not hasattr(rt.lib, "rt_diag_census"):
         sys.exit("--census-dump needs a -DRTD_STAGE_CLOCKS build (RTFS_LIB): this library has no rt_diag_census")
     rt.lib.rt_diag_census.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32, ctypes.c_int32]
-    rt.lib.rt_diag_census(cz, 48, 1)  # the tuning probe's launches are not the frame's
+    rt.lib.rt_diag_census(cz, 52, 1)  # the tuning probe's launches are not the frame's
 for _ in range(a.launches):
     st = rtd.render_shard_device(scene, cam, w, h, 2024, 0, 0, 1, rows, local, counters=a.counters, want_stats=True)
     print({k: st[k] for k in ("kernel_ms", "rays", "aabb_tests", "prim_tests", "samples")}, flush=True)
@@ -60,7 +60,7 @@ for _ in range(a.launches):
         print(dict(zip(names, list(ss))), flush=True)
         if a.census_dump:
             import json
-            if rt.lib.rt_diag_census(cz, 48, 0) != 0:
+            if rt.lib.rt_diag_census(cz, 52, 0) != 0:
                 sys.exit("rt_diag_census failed")
             cn = ("turns", "lamb_batches", "lamb_lanes", "new_refills", "new_items", "unpark_lambert", "unpark_general", "store_blocks_lambert", "store_lanes_lambert",
                   "store_blocks_general", "light_batches", "light_lanes", "miss_lanes", "ranges", "flushes", "leaf_lanes")
@@ -70,4 +70,7 @@ for _ in range(a.launches):
             d["census"].update(zip(("random_unit_retries", "lambert_bounce_retries", "sliver_lanes", "sliver_blocks"), list(cz)[32:36]))
             d["census"].update(zip(("refill_stages", "walk_entries", "leaf_passes", "shade_stages", "refill_lanes", "shade_lanes", "slow_stages", "slow_lanes", "loop_trips", "loop_lanes",
                                     "unpark_lambert_batches", "unpark_general_batches"), list(cz)[36:48]))
+            # lanes that took an arm behind a wave-uniform guard (rt_device.h, RTD_ANY_LANE); every launch since the reset, not pass B alone
+            d["census"].update(zip(("equal_arm_lanes_unbounded", "equal_arm_lanes_leaf"), list(cz)[48:50]))
+            d["census"]["guarded_arms"] = sum(list(cz)[48:50])
             json.dump(d, open(a.census_dump, "w"), indent=1)
