@@ -374,6 +374,59 @@ int rt_render_footprints_device(const rt_scene *scene, int32_t device, size_t n,
                                 uint32_t flags, void *d_accum, void *d_rgb, void *stream,
                                 const rt_render_options *options, rt_stats *stats);
 
+/* ---- Pixel lists: a caller-chosen list of a FRAME's pixels, bit for bit -------------------------------------------------
+ * pixels[i] is a GLOBAL PIXEL INDEX g = r*cols + c of the frame rt_render renders from (scene, camera, max_width_coord,
+ * max_height_coord, seed): r the image row (0 = top), c the column, cols = 2*max_width_coord+1 (Scene.render's coordinate
+ * mapping, Scene.fs:219,226) -- the index a whole-frame accum uses and the one the streams are keyed by.  Outputs are
+ * COMPACT, in list order: accum[i*4 .. i*4+3] {Count, SumRed, SumGreen, SumBlue} and rgb[i*3 .. i*3+2] (may be NULL)
+ * belong to entry i.
+ *
+ * Entry i IS pixel g of that frame, in every PixelStats word and every rgb byte: Scene.renderPixel (Scene.fs:157-194) with
+ * the frame's streams (seed, g, sample), the frame's camera rays and the adaptive rule with camera->samples_per_pixel --
+ * for any list order, any subset, any launch settings and both kernel variants (DESIGN.md "Pixel lists").  Duplicates are
+ * allowed: each entry is rendered into its own slot, so equal entries give equal results.  A crop, a tile, the pixels a
+ * partial pixel map lacks, a checkerboard or a split of a frame by cost are all lists.
+ *
+ * rt_render_pixels_extend* continue the n compact entries of a buffer a list render made, by rt_render_extend's contract
+ * (below) word for word: samples_done >= 12, the target is camera->samples_per_pixel, Count == samples_done continues,
+ * Count == 11 is final, any other Count makes the buffer MALFORMED and nothing is written; same list, same every other
+ * argument as the call that made the buffer.
+ *
+ * Argument checks come before any device call, nothing is written when one fails: RT_ERR_INVALID_ARGUMENT for everything
+ * rt_render rejects about scene, camera, geometry and options, a NULL pixels or accum with n > 0, n > INT32_MAX, a frame of
+ * more than INT32_MAX pixels, and (extend) samples_done < 12 or a target below it.  n = 0 is a no-op returning RT_OK with
+ * zeroed stats (and so is an extension with target == samples_done).
+ * An entry outside [0, rows*cols) makes the LIST malformed (the check guards meaning, not memory: every store is indexed by
+ * list position).  The host variants find it on the host: RT_ERR_INVALID_ARGUMENT before any device call.  The device variants
+ * find it on the device, in front of the render, on the same stream: NO pixel is rendered, d_accum and d_rgb stay as they
+ * were, and the call returns RT_ERR_INVALID_ARGUMENT when stats is given (it synchronises); with stats == NULL the untouched
+ * buffers are the caller's evidence.
+ *
+ * stats as for a footprint list: pixels = n, samples, pixels_early, kernel_ms, total_ms, the four counters under
+ * RT_RENDER_COUNTERS.  The device variants follow rt_render_device's contract: enqueued on `stream`, scratch is stream-ordered,
+ * any number of calls in flight, with stats == NULL the call returns right after the launch, the caller's current device is
+ * left as it was; the list must not change until the launch has finished.  options: as for a footprint list (a block of 512
+ * or 768 threads runs as 1024; an extension ignores `passes`).
+ * Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */
+int rt_render_pixels(const rt_scene *scene, const rt_camera *camera,
+                     int32_t max_width_coord, int32_t max_height_coord, uint64_t seed,
+                     int32_t device, size_t n, const int32_t *pixels, uint32_t flags,
+                     int32_t *accum, uint8_t *rgb /* may be NULL */, rt_stats *stats);
+int rt_render_pixels_device(const rt_scene *scene, const rt_camera *camera,
+                            int32_t max_width_coord, int32_t max_height_coord, uint64_t seed,
+                            int32_t device, size_t n, const void *d_pixels, uint32_t flags,
+                            void *d_accum, void *d_rgb, void *stream,
+                            const rt_render_options *options, rt_stats *stats);
+int rt_render_pixels_extend(const rt_scene *scene, const rt_camera *camera,
+                            int32_t max_width_coord, int32_t max_height_coord, uint64_t seed,
+                            int32_t device, size_t n, const int32_t *pixels, uint32_t flags, int32_t samples_done,
+                            int32_t *accum /* in, out */, uint8_t *rgb /* out, may be NULL */, rt_stats *stats);
+int rt_render_pixels_extend_device(const rt_scene *scene, const rt_camera *camera,
+                                   int32_t max_width_coord, int32_t max_height_coord, uint64_t seed,
+                                   int32_t device, size_t n, const void *d_pixels, uint32_t flags, int32_t samples_done,
+                                   void *d_accum, void *d_rgb, void *stream,
+                                   const rt_render_options *options, rt_stats *stats);
+
 /* ---- Extending a rendered buffer to a higher sample count --------------------------------------------------------------
  * render at a, then extend a -> b  ==  render at b, for every PixelStats word and every rgb byte, for any 12 <= a <= b
  * (DESIGN.md "Extending a frame"): sample s of a pixel is the same ray tree whenever it is traced, the sums are integers, and
@@ -528,11 +581,12 @@ int rt_set_park(int32_t park_lanes);
  * lanes parked, shader-clock cycles summed over the waves inside the refill / general-reflection / walk / shade stages}. */
 int rt_last_stage_stats(uint64_t out[16]);
 /* Diagnostic: the launch plan (csrc/rt_launch_plan.h) of the calling THREAD's last launch -- a render shard, rt_scene_tune's probe
- * a ray list or a footprint list; of rt_render_frame, its last device's -- as the library gathered its inputs and executed its outputs.  Read-only
+ * a ray list, a footprint list or a pixel list; of rt_render_frame, its last device's -- as the library gathered its inputs and executed its outputs.  Read-only
  * host bookkeeping: no device work, nothing launched depends on it.  Words, under the names tests/c/launch_plan_table.cpp reads
  * and prints:
  *   [0]      1 once this thread has planned a launch (all words are 0 before)
- *   [1..21]  inputs: kind (0 frame shard, 1 traceRays list, 2 hitObject list, 3 footprint list: n pixels) lds_total lds32_total n_nodes n_obj has_tex
+ *   [1..21]  inputs: kind (0 frame shard, 1 traceRays list, 2 hitObject list, 3 footprint list: n pixels,
+ *            4 pixel list: n pixels) lds_total lds32_total n_nodes n_obj has_tex
  *            s_block s_chunk s_bpc s_yield s_refill s_passes s_park (the resolved settings, 0 = "the plan decides") count log
  *            n_rows max_w spp n cu_count per_cu (what the occupancy query answered, before blocks_per_cu)
  *   [22..34] q_lds q_count q_block q_mode q_tex q_lds_bytes two_pass pairs list sort pool waves error
@@ -540,7 +594,7 @@ int rt_last_stage_stats(uint64_t out[16]);
  *            park_l park_l_lds lds_node_bytes lds_node_thr yield leaf_wait refill k total_waves.  F_ is what ran unless two_pass;
  *            A_ and B_ are filled only with two_pass and no error.
  *   [77]     first_sample: 0 for a fresh render; for an extension (rt_render_extend*, rt_render_footprints_extend*) its samples_done.
- *            An extension reports kind 0 or 3, two_pass 1, pairs and sort 0, every A_ word 0 (no pass A is launched) and pass B as
+ *            An extension reports kind 0, 3 or 4 (rt_render_pixels_extend*), two_pass 1, pairs and sort 0, every A_ word 0 (no pass A is launched) and pass B as
  *            the same job gets it with passes = 2.
  *   [78]     1 for an extension by map (rt_render_extend_map*, rt_render_footprints_extend_map*), else 0.  Such a launch reports
  *            first_sample 12 and spp = the cap (it is planned as the extension 12 -> cap) and pass B's mode as 9 (frame) or 10

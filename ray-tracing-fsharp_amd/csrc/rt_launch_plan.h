@@ -37,18 +37,20 @@ struct SceneSize {
 };
 // A frame shard (render_kernel modes 0..3), a caller's ray list (mode 4 paths, mode 5 hit queries) or a caller's footprint list
 // (modes 6..8: planned as a FRAME of n pixels -- chunk widening, fused or two passes, placement, pools -- run by the footprint kernels)
+// or a caller's list of a frame's pixels (modes 11..13, rt_render_pixels: planned exactly as the FOOTPRINTS job of the same n)
 struct Job {
-    enum Kind { FRAME, TRACE, HIT, FOOTPRINTS } kind = FRAME;
+    enum Kind { FRAME, TRACE, HIT, FOOTPRINTS, PIXELS } kind = FRAME;
     uint64_t n_rows = 0; int32_t max_w = 0, spp = 1; // FRAME
     bool ray_log = false;                            // FRAME: rt_scene_tune's probe
-    uint64_t n = 0;                                  // TRACE, HIT: rays; FOOTPRINTS: pixels (with spp)
-    int32_t first_sample = 0;                        // FRAME, FOOTPRINTS: 0 = a fresh render; >= RTD_EXTEND_MIN_DONE: an EXTENSION of a buffer that
+    uint64_t n = 0;                                  // TRACE, HIT: rays; FOOTPRINTS, PIXELS: pixels (with spp)
+    int32_t first_sample = 0;                        // FRAME, FOOTPRINTS, PIXELS: 0 = a fresh render; >= RTD_EXTEND_MIN_DONE: an EXTENSION of a buffer that
                                                      // holds this many samples per continued pixel, to spp (rt_render_extend): pass B alone
     bool map = false;                                // an extension BY MAP (rt_render_extend_map): every pixel from its own Count to its own target <= spp.
                                                      // Planned as the extension RTD_EXTEND_MIN_DONE -> spp (first_sample is that) with the map variant's scratch
     bool extend() const { return first_sample != 0; }
-    bool pixels() const { return kind == FRAME || kind == FOOTPRINTS; } // planned by the pixel rules, not the ray lists'
-    uint64_t pixel_count() const { return kind == FOOTPRINTS ? n : n_rows * (uint64_t) (2 * max_w + 1); }
+    bool list() const { return kind == FOOTPRINTS || kind == PIXELS; }  // n pixels in list order: a frame of one row to the plan
+    bool pixels() const { return kind == FRAME || list(); }             // planned by the pixel rules, not the ray lists'
+    uint64_t pixel_count() const { return list() ? n : n_rows * (uint64_t) (2 * max_w + 1); }
 };
 
 // One kernel launch: which render_kernel<lds, count, block, mode, tex>, its grid and dynamic LDS, and the RenderParams fields the
@@ -141,7 +143,7 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     pl.scene = sc; pl.set = set; pl.job = job; pl.cu_count = cu_count;
     Pass &q = pl.one;
     Settings eff = set; // (a footprint list asked to run at 512 or 768 threads runs at 1024: residency is decided at the block that runs)
-    if (job.kind == Job::FOOTPRINTS && eff.block != 0 && eff.block != 256) eff.block = 1024;
+    if (job.list() && eff.block != 0 && eff.block != 256) eff.block = 1024;
     q.lds = lds_resident(sc, eff, count); // (ray lists too: the render's decision, taken at the block the settings ask for)
     q.count = count;
     q.park = set.park < 0 ? 0 : (set.park ? set.park : RTD_PARK_DEFAULT);
@@ -164,9 +166,9 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     }
     q.block = default_block(set);
     q.mode = job.ray_log ? 3 : 0; // (the ray log of rt_scene_tune's probe: a kernel of its own)
-    if (job.kind == Job::FOOTPRINTS) { // modes 6 / 7 / 8, built for blocks of 256 and 1024 threads only, as the ray lists are
+    if (job.list()) { // modes 6 / 7 / 8 (a pixel list: 11 / 12 / 13), built for blocks of 256 and 1024 threads only, as the ray lists are
         q.block = q.block == 256 ? 256 : 1024;
-        q.mode = 6;
+        q.mode = job.kind == Job::PIXELS ? 11 : 6;
     }
     q.tex = sc.tex;               // otherwise the variant compiled without the texture call: no scratch, no VGPR spills
     const int half = job.spp / 2;
@@ -262,7 +264,7 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     }
     pl.a = pl.b = q;
     pl.a.total_waves = pl.b.total_waves = (uint32_t) (fullGrid * wavesPerBlock);
-    const int fp = pl.job.kind == Job::FOOTPRINTS ? 6 : 0;
+    const int fp = pl.job.kind == Job::FOOTPRINTS ? 6 : pl.job.kind == Job::PIXELS ? 11 : 0;
     pl.a.mode = fp + 1; pl.a.chunk = chunkA;
     pl.b.mode = pl.job.map ? (fp ? 10 : 9) : fp + 2; pl.b.chunk = chunkB; // (9 / 10: pass B with per-pixel ranges)
     place_pass(pl.b, sc, wordsB(chunkB));

@@ -78,6 +78,9 @@ struct RenderParams {
     uint32_t ray_sample;
     // an extension by map (MODE 9 / 10, rt_render_extend_map): read only there and by its list builder
     const int32_t *ext_targets;    // [n_rows*cols]: the Count each pixel is to reach (the classes: extend_map_list_kernel)
+    // a pixel list (MODE 11 / 12 / 13, rt_render_pixels): read only there.  The list's length is ray_n; cols, max_w, max_h and the camera are
+    // the FRAME's, n_rows = 1, row_first = 0, row_stride = 1
+    const int32_t *pixel_list;     // [ray_n]: global pixel indices r * cols + c of the frame; entry i owns accum[i] and rgb[i]
 };
 
 // Per-wave LDS scratch (in 4-byte words), P = pixels per work unit:
@@ -766,7 +769,8 @@ RTD_INLINE void run_rays(const RenderParams &p, const SceneView<LDS> &sc, unsign
 // a range is reserved lane j reads its pixel's Count and target, the counts n2_j = target - Count are prefix-summed across the wave,
 // and the wave's scratch keeps per pixel its first item and (Count - first item); an item finds its pixel by rtm::map_find_pixel
 // (at most six LDS reads, no division) and is sample (Count - first item) + item; flush leaves Count = target.  n1 and n2 are unused.
-template <bool LDS, bool COUNT, bool TEX, bool FP, bool MAP = false>
+// PX (a pixel list, rt_render_pixels): list entry lp is the frame's pixel p.pixel_list[lp]; everything but that look-up is the frame's.
+template <bool LDS, bool COUNT, bool TEX, bool FP, bool MAP = false, bool PX = false>
 RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, RTD_AS3 uint32_t *wv, uint32_t n1, uint32_t n2, Counters &cnt,
                            StageStats &ss, uint64_t &sampleCount) {
     const int lane = threadIdx.x & 63;
@@ -848,6 +852,21 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                             pix[lane * 4 + 1] = 0u;
                             pix[lane * 4 + 2] = (uint32_t) pkey;
                             pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
+                        } else if constexpr (PX) { // the frame's pixel the list names: its (row, col), its stream, its candidates
+                        const uint32_t g = (uint32_t) p.pixel_list[lp];
+                        uint32_t r = g / (uint32_t) p.cols;
+                        uint32_t c = g - r * (uint32_t) p.cols;
+                        uint64_t pkey = pixel_key(p.seed_key, (uint64_t) g); // global pixel index
+                        pix[lane * 4 + 0] = (uint32_t) (p.max_h - (int) r - 1);
+                        pix[lane * 4 + 1] = (uint32_t) ((int) c - p.max_w);
+                        pix[lane * 4 + 2] = (uint32_t) pkey;
+                        pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
+                        const CameraParams *cp = p.cam_ptr;
+                        asm volatile("" : "+s"(cp));
+                        uint32_t c2;
+                        const uint32_t c1 = pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, c2);
+                        wv[14u * P + (curSlot * P + lane) * 2u] = c1;
+                        wv[14u * P + (curSlot * P + lane) * 2u + 1u] = c2;
                         } else {
                         uint32_t lr = (uint32_t) (lp / (unsigned long long) p.cols);
                         uint32_t c = (uint32_t) (lp - (unsigned long long) lr * (unsigned long long) p.cols);
@@ -1014,6 +1033,9 @@ RTD_INLINE uint32_t stage_nodes32(const RenderParams &p, unsigned char *smem) {
 //         p.rays ([n][12]: origin, base, du, dv), its stream that of (seed, p.ray_base + i); a sample's ray is footprint_ray's; no pixel
 //         candidates.  Everything else -- units, accumulators, the decision, the compaction, pass B's ordered list -- is the frame's.
 // MODE 9 / 10: MODE 2 / 8 with per-pixel sample ranges (run_stream<.., MAP>): pass B of an extension by map (rt_render_extend_map).
+// MODE 11 / 12 / 13: MODE 0 / 1 / 2 over a caller's list of the FRAME's pixels (rt_render_pixels): entry i of p.ray_n names the global pixel
+//         index g = p.pixel_list[i]; (row, col) = (g / cols, g % cols), the stream of (seed, g), the frame's camera_ray AND its pixel
+//         candidates -- a frame's pixel in all but where it is stored, which is slot i.  An extension is mode 13 with first_b set.
 // Per-pixel cost is heavy-tailed (a pixel on a glass sphere: ~20 rays per sample, 4 ms of one wave), so when a shard has only a few
 // units per wave the fused kernel ends with most waves waiting for a few long units started late; A + sort + B removes that tail.
 // Every mode computes the same integers: which wave traces which sample when has no effect (streams are per item).
@@ -1022,8 +1044,9 @@ template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX>
 __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool MAP = MODE == 9 || MODE == 10; // pass B of an extension by map: of a frame / of a footprint list
-    constexpr bool FP = MODE >= 6 && MODE != 9;   // the pixels are the caller's footprints
-    constexpr int PM = MAP ? 2 : FP ? MODE - 6 : MODE; // ... and run as this pixel mode
+    constexpr bool PX = MODE >= 11 && MODE <= 13; // the pixels are a caller's list of the frame's
+    constexpr bool FP = MODE >= 6 && MODE != 9 && !PX; // the pixels are the caller's footprints
+    constexpr int PM = MAP ? 2 : PX ? MODE - 11 : FP ? MODE - 6 : MODE; // ... and run as this pixel mode
     constexpr bool RAYS = MODE == 4 || MODE == 5;
     constexpr bool FUSED = PM == 0 || PM == 3;
     const int lane = threadIdx.x & 63;
@@ -1050,7 +1073,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * (RAYS ? 0u : PM == 1 ? RTD_WAVE_WORDS_A(P) : MAP ? RTD_WAVE_WORDS_MAP(P) : RTD_WAVE_WORDS(P)) * 4u +
                                      (size_t) wave * (size_t) RTD_PARK_L_LDS_BYTES * (size_t) p.park_l;
 
-    const uint64_t nLocal = (uint64_t) p.n_rows * (uint64_t) p.cols;
+    const uint64_t nLocal = PX ? p.ray_n : (uint64_t) p.n_rows * (uint64_t) p.cols; // (a pixel list: cols is the frame's)
     const uint32_t k = (uint32_t) p.k;
     const uint32_t n1 = (PM == 2 && p.first_b != 0) ? (uint32_t) p.first_b : 2u * k + 1u; // (pass B of an extension starts where the buffer ends)
     const int n2s = p.spp - (int) n1; // Scene.fs:191
@@ -1071,7 +1094,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     uint64_t sampleCount = 0; // Scene.traceOnce calls = sum of PixelStats.Count
 
     if constexpr (RAYS) run_rays<LDS, COUNT, TEX, MODE == 5>(p, sc, pool, poolLds, cnt, ss);
-    else if (PM == 2) run_stream<LDS, COUNT, TEX, FP, MAP>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
+    else if (PM == 2) run_stream<LDS, COUNT, TEX, FP, MAP, PX>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
     else
     for (;;) {
         uint32_t unit = 0;
@@ -1094,6 +1117,21 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
                 pix[lane * 4 + 1] = 0u;
                 pix[lane * 4 + 2] = (uint32_t) pkey;
                 pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
+            } else if constexpr (PX) { // a pixel list: the frame's pixel the entry names -- its (row, col), its stream, its candidates
+            const uint32_t g = (uint32_t) p.pixel_list[lp];
+            uint32_t r = g / (uint32_t) p.cols;
+            uint32_t c = g - r * (uint32_t) p.cols;
+            uint64_t pkey = pixel_key(p.seed_key, (uint64_t) g); // global pixel index
+            pix[lane * 4 + 0] = (uint32_t) (p.max_h - (int) r - 1);
+            pix[lane * 4 + 1] = (uint32_t) ((int) c - p.max_w);
+            pix[lane * 4 + 2] = (uint32_t) pkey;
+            pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
+            const CameraParams *cp = p.cam_ptr;
+            asm volatile("" : "+s"(cp));
+            uint32_t c2;
+            const uint32_t c1 = pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, c2);
+            cand[lane * 2] = c1;
+            cand[lane * 2 + 1] = c2;
             } else {
             uint32_t lr = (uint32_t) (lp / (unsigned long long) p.cols);
             uint32_t c = (uint32_t) (lp - (unsigned long long) lr * (unsigned long long) p.cols);
@@ -1279,6 +1317,32 @@ __global__ void __launch_bounds__(256) extend_final_rgb_kernel(const int32_t *ac
         rgb[i * 3 + 1] = (uint8_t) (v.z / v.x);
         rgb[i * 3 + 2] = (uint8_t) (v.w / v.x);
     }
+}
+
+// ---- a pixel list (rt_render_pixels): is every entry a pixel of the frame? ----
+// extend_list_kernel's shape: one 4-byte load per lane, a ballot, one agent-scope atomicAdd per wave that saw an entry outside
+// [0, frame_pixels) (frame_pixels <= INT32_MAX, so a negative entry is a large unsigned one).  The check guards MEANING, not memory:
+// every store of a list render is indexed by list position.  For an extension `bad` is LaunchScratch::ext_foreign and the extension's
+// own seal does the rest.
+__global__ void __launch_bounds__(256) pixel_list_check_kernel(const int32_t *list, unsigned long long n, uint32_t frame_pixels, unsigned int *bad) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull;
+    const unsigned long long trips = (n + stride - 1ull) / stride; // uniform over the grid: every lane of a wave makes every ballot
+    unsigned long long nBad = 0ull;
+    for (unsigned long long t = 0; t < trips; ++t) {
+        const unsigned long long i = t * stride + (unsigned long long) blockIdx.x * 256ull + threadIdx.x;
+        uint32_t g = 0u;
+        if (i < n) g = (uint32_t) list[i];
+        nBad += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(i < n && g >= frame_pixels));
+    }
+    if (lane == 0 && nBad != 0ull) atomicAdd(bad, (unsigned int) nBad); // (n < 2^31: the sum cannot wrap to 0)
+}
+// One wave, between the check and a FRESH list render: with even one bad entry the unit counter is poisoned -- unit * chunk is then at
+// or beyond n <= INT32_MAX for every wave that ever asks (the waves of a grid add far less than 2^31 to it), so the fused kernel and
+// pass A start no unit, pass A appends nothing, the sort and pass B see an empty list, and neither accum nor rgb is written --
+// and `malformed` tells collect_stats (RT_ERR_INVALID_ARGUMENT).
+__global__ void pixel_list_seal_kernel(const unsigned int *bad, unsigned int *queue, unsigned int *malformed) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && *bad != 0u) { *queue = 0x80000000u; *malformed = 1u; }
 }
 
 // ---- extending by map (rt_render_extend_map): the list from the stored Counts AND the caller's per-pixel targets ----

@@ -200,7 +200,7 @@ static int allow_full_lds(const void *fn) {
 // blocks of 256 and 1024 threads only, and the hit queries (mode 5) shade nothing, so they have no textured variant.  The plan
 // never asks for one of the others; if it did, the launch fails (no kernel is substituted).
 template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX> static render_fn kernel_if_built() {
-    if constexpr ((MODE >= 4 && MODE != 9 && BLOCK != 256 && BLOCK != 1024) || (MODE == 5 && TEX)) return nullptr; // (the footprint modes 6-8 and 10: as the ray lists;
+    if constexpr ((MODE >= 4 && MODE != 9 && BLOCK != 256 && BLOCK != 1024) || (MODE == 5 && TEX)) return nullptr; // (the footprint modes 6-8 and 10 and the pixel-list modes 11-13: as the ray lists;
                                                                                                                         // mode 9 runs frames: every block, as mode 2)
     else return render_kernel<LDS, COUNT, BLOCK, MODE, TEX>;
 }
@@ -226,6 +226,9 @@ static render_fn pick_kernel(const rtp::Pass &q) {
     case 8: return q.tex ? pick_mode<8, true>(q) : pick_mode<8, false>(q);
     case 9: return q.tex ? pick_mode<9, true>(q) : pick_mode<9, false>(q);
     case 10: return q.tex ? pick_mode<10, true>(q) : pick_mode<10, false>(q);
+    case 11: return q.tex ? pick_mode<11, true>(q) : pick_mode<11, false>(q);
+    case 12: return q.tex ? pick_mode<12, true>(q) : pick_mode<12, false>(q);
+    case 13: return q.tex ? pick_mode<13, true>(q) : pick_mode<13, false>(q);
     default: return nullptr;
     }
 }
@@ -239,6 +242,7 @@ struct LaunchScratch {
     unsigned long long queue_b;      // pass B: next unassigned list entry
     unsigned int live_count;         // pass A -> B: number of pairs / list entries
     unsigned int ext_foreign, ext_malformed, pad1; // an extension: pixels whose Count the arguments do not explain (extend_list_kernel); 1 = nothing was continued (extend_seal_kernel)
+                                                   // a pixel list: ext_foreign also counts entries outside the frame (pixel_list_check_kernel); 1 = nothing was rendered
     unsigned long long stage[12];    // counters[20..31]: slow stages, lanes in them, lanes parked, cycles in refill / slow / walk / shade;
                                      // diagnostic builds (RTD_STAGE_CLOCKS): cycles in loop / leaf / unbounded / new items / lambert
     CameraParams cam;                // RenderParams::cam_ptr
@@ -479,6 +483,7 @@ struct Pending {
     bool launched = false, keep = false;
     bool extend = false; // an extension: collect_stats reads LaunchScratch::ext_malformed
     bool map = false;    // ... by map (the message of a malformed buffer)
+    bool list = false;   // a pixel list: collect_stats reads ext_malformed for a fresh render too (an entry outside the frame)
     std::chrono::steady_clock::time_point t0;
     void release() { // events destroyed, scratch handed back to the stream's pool in stream order
         if (a) (void) hipEventDestroy(a);
@@ -523,7 +528,7 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
     const Settings &s = pl.set;
     const rtp::Job &j = pl.job;
     put(1);
-    put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : (j.kind == rtp::Job::HIT ? 2 : 3)));
+    put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : (j.kind == rtp::Job::HIT ? 2 : (j.kind == rtp::Job::FOOTPRINTS ? 3 : 4))));
     put((int64_t) sc.lds_total); put((int64_t) sc.lds32_total); put(sc.n_nodes); put((int64_t) sc.n_objects); put(sc.tex);
     put(s.block); put(s.chunk); put(s.blocks_per_cu); put(s.yield); put(s.refill); put(s.passes); put(s.park);
     put(pl.one.count); put(j.ray_log); put((int64_t) j.n_rows); put(j.max_w); put(j.spp); put((int64_t) j.n); put(pl.cu_count); put(per_cu);
@@ -590,6 +595,7 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     cl.waves = plan.waves;
     cl.extend = job.extend();
     cl.map = job.map;
+    cl.list = job.kind == rtp::Job::PIXELS;
     if (want_stats) {
         HIP_TRY(hipEventCreate(&cl.a));
         HIP_TRY(hipEventCreate(&cl.b));
@@ -607,6 +613,16 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     }
     if (grid > 0) {
         if (want_stats) HIP_TRY(hipEventRecord(cl.a, st));
+        if (job.kind == rtp::Job::PIXELS) {
+            // in front of everything else: is every entry a pixel of the frame?  An extension's own seal acts on the count; a fresh render
+            // gets a seal that poisons the unit counter, so that nothing is rendered and nothing written (rt_render_kernel.h)
+            LaunchScratch *ls = (LaunchScratch *) scr;
+            const unsigned long long want = (job.n + 255ull) / 256ull, most = (unsigned long long) ds->cu_count * 8ull;
+            hipLaunchKernelGGL(pixel_list_check_kernel, dim3((unsigned) (want < most ? want : most)), dim3(256), 0, st, p.pixel_list, (unsigned long long) job.n,
+                               (uint32_t) p.cols * (uint32_t) (2 * p.max_h + 1), &ls->ext_foreign);
+            if (!job.extend()) hipLaunchKernelGGL(pixel_list_seal_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) &ls->ext_foreign, p.queue, &ls->ext_malformed);
+            HIP_TRY(hipGetLastError());
+        }
         if (job.extend()) {
             // pass B alone, from sample first_sample on: its list comes from the stored Counts (extend_list_kernel) instead of pass A
             // and the sort; the seal between them makes "malformed buffer => nothing written" hold (rt_render_kernel.h)
@@ -726,12 +742,14 @@ static int collect_stats(Pending &pd, rt_stats *stats) {
     g_last_stage_stats[7] = c[15] - (0x4000000000000000ull - c[7]); // first wave start -> last wave end, ticks
     g_last_stage_stats[8] = pd.waves;
     for (int i = 0; i < 7; ++i) g_last_stage_stats[9 + i] = c[16 + i]; // slow stages, lanes in them, lanes parked, cycles in refill / slow / walk / shade
-    if (pd.extend && pd.scr) { // the seal found a Count the arguments do not explain: nothing was continued, nothing written
+    if ((pd.extend || pd.list) && pd.scr) { // the seal found a Count the arguments do not explain (a pixel list: or an entry outside the frame): nothing was continued, nothing written
         unsigned int malformed = 0u;
         HIP_TRY(hipMemcpy(&malformed, pd.scr + offsetof(LaunchScratch, ext_malformed), sizeof(malformed), hipMemcpyDeviceToHost));
         if (malformed) {
             pd.release();
-            return fail(RT_ERR_INVALID_ARGUMENT, pd.map ? "accum or targets are not what the arguments say (a Count below 11, or a target above the cap); left unchanged"
+            return fail(RT_ERR_INVALID_ARGUMENT, pd.list ? (pd.extend ? "the pixel list has an entry outside the frame, or accum is not a buffer of samples_done samples per entry; left unchanged"
+                                                                      : "the pixel list has an entry outside the frame; nothing was rendered")
+                                                 : pd.map ? "accum or targets are not what the arguments say (a Count below 11, or a target above the cap); left unchanged"
                                                         : "accum is not a buffer of samples_done samples per pixel (a Count that is neither samples_done nor 11); left unchanged");
         }
     }
@@ -1488,6 +1506,164 @@ int rt_render_footprints_extend_map(const rt_scene *scene, int32_t device, size_
     if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpy(accum, buf + bFp, n * 16u, hipMemcpyDeviceToHost));
     if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bFp + bAcc + bMap, n * 3u, hipMemcpyDeviceToHost));
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// pixel lists (DESIGN.md "Pixel lists"): Scene.renderPixel (Scene.fs:157-194) over a caller's list of the FRAME's pixels, outputs in list
+// order (render_kernel MODE 11 / 12 / 13)
+// ------------------------------------------------------------------------------------------------------------
+// Every argument check the four entry points share, made before anything touches a device.
+static int check_pixels(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, size_t n, const void *pixels, const void *accum,
+                        const rt_render_options *options) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    int rc = check_geometry(camera, max_w, max_h, 0, 1, 0);
+    if (rc != RT_OK) return rc;
+    if (n > 0 && !pixels) return fail(RT_ERR_INVALID_ARGUMENT, "pixels is NULL");
+    if (n > 0 && !accum) return fail(RT_ERR_INVALID_ARGUMENT, "accum is NULL");
+    if (n > (size_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "more than INT32_MAX list entries");
+    if ((uint64_t) (2 * max_w + 1) * (uint64_t) (2 * max_h + 1) > (uint64_t) INT32_MAX)
+        return fail(RT_ERR_INVALID_ARGUMENT, "a pixel list indexes frames of at most INT32_MAX pixels");
+    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
+    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
+    return RT_OK;
+}
+// The host variants' list check (the device variants' is pixel_list_check_kernel): every entry a global pixel index of the frame.
+static int check_pixel_entries(const int32_t *pixels, size_t n, int32_t max_w, int32_t max_h) {
+    const int32_t frame = (2 * max_w + 1) * (2 * max_h + 1);
+    for (size_t i = 0; i < n; ++i)
+        if (pixels[i] < 0 || pixels[i] >= frame) return fail(RT_ERR_INVALID_ARGUMENT, "the pixel list has an entry outside the frame");
+    return RT_OK;
+}
+
+// Enqueues one list launch on `stream` (n > 0, arguments checked): the frame's own RenderParams fields -- camera, geometry, seed -- and, for
+// the kernel's unit loop, a frame of one row whose pixel i is the frame's pixel d_pixels[i]; then enqueue(), as for a frame shard.
+static int launch_pixels(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                         const void *d_pixels, uint32_t flags, void *d_accum, void *d_rgb, void *stream, const rt_render_options *options,
+                         bool want_stats, Pending &pd, int32_t first_sample = 0) {
+    RenderParams p{};
+    p.max_w = max_w; p.max_h = max_h;
+    p.spp = camera->samples_per_pixel;
+    p.depth = camera->bounce_depth;
+    p.seed_key = mix64(seed + 0x9E3779B97F4A7C15ull); // seed_key(), host side
+    p.cols = 2 * max_w + 1;
+    p.row_first = 0; p.row_stride = 1; p.n_rows = 1;
+    p.accum = (int32_t *) d_accum;
+    p.rgb = (uint8_t *) d_rgb;
+    p.pixel_list = (const int32_t *) d_pixels;
+    p.ray_n = n;
+    rtp::Job job;
+    job.kind = rtp::Job::PIXELS;
+    job.n = n; job.spp = camera->samples_per_pixel;
+    job.first_sample = first_sample;
+    return enqueue(scene, device, job, resolve_settings(options), flags, stream, p, camera_params(camera, max_w, max_h), want_stats, pd);
+}
+
+extern "C" {
+
+int rt_render_pixels_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                            const void *d_pixels, uint32_t flags, void *d_accum, void *d_rgb, void *stream, const rt_render_options *options,
+                            rt_stats *stats) {
+    int rc = check_pixels(scene, camera, max_w, max_h, n, d_pixels, d_accum, options);
+    if (rc != RT_OK) return rc;
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    Pending pd;
+    rc = launch_pixels(scene, camera, max_w, max_h, seed, device, n, d_pixels, flags, d_accum, d_rgb, stream, options, stats != nullptr, pd);
+    if (rc != RT_OK || !stats) return rc;
+    return collect_stats(pd, stats);
+}
+
+// The host variant: the list checked here, one device allocation for the list and the outputs, the device variant on the null stream, the
+// outputs copied back.
+int rt_render_pixels(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                     const int32_t *pixels, uint32_t flags, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
+    int rc = check_pixels(scene, camera, max_w, max_h, n, pixels, accum, nullptr);
+    if (rc != RT_OK || (rc = check_pixel_entries(pixels, n, max_w, max_h)) != RT_OK) return rc;
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
+    const size_t bPx = up16(n * 4u), bAcc = up16(n * 16u), bRgb = rgb ? up16(n * 3u) : 0u;
+    unsigned char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **) &buf, bPx + bAcc + bRgb));
+    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
+    HIP_TRY(hipMemcpy(buf, pixels, n * 4u, hipMemcpyHostToDevice));
+    rt_stats local;
+    rc = rt_render_pixels_device(scene, camera, max_w, max_h, seed, device, n, buf, flags, buf + bPx, bRgb ? buf + bPx + bAcc : nullptr, nullptr, nullptr,
+                                 &local);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpy(accum, buf + bPx, n * 16u, hipMemcpyDeviceToHost));
+    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bPx + bAcc, n * 3u, hipMemcpyDeviceToHost));
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+int rt_render_pixels_extend_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                                   const void *d_pixels, uint32_t flags, int32_t samples_done, void *d_accum, void *d_rgb, void *stream,
+                                   const rt_render_options *options, rt_stats *stats) {
+    int rc = check_pixels(scene, camera, max_w, max_h, n, d_pixels, d_accum, options);
+    if (rc != RT_OK || (rc = check_extend(camera->samples_per_pixel, samples_done)) != RT_OK) return rc;
+    if (n == 0 || camera->samples_per_pixel == samples_done) { // nothing to add
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    Pending pd;
+    rc = launch_pixels(scene, camera, max_w, max_h, seed, device, n, d_pixels, flags, d_accum, d_rgb, stream, options, stats != nullptr, pd, samples_done);
+    if (rc != RT_OK || !stats) return rc;
+    return collect_stats(pd, stats);
+}
+
+// The host variant: the list checked here, list and buffer copied in, the device variant on the null stream, the outputs copied back --
+// unless it failed.
+int rt_render_pixels_extend(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                            const int32_t *pixels, uint32_t flags, int32_t samples_done, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
+    int rc = check_pixels(scene, camera, max_w, max_h, n, pixels, accum, nullptr);
+    if (rc != RT_OK || (rc = check_extend(camera->samples_per_pixel, samples_done)) != RT_OK) return rc;
+    if ((rc = check_pixel_entries(pixels, n, max_w, max_h)) != RT_OK) return rc;
+    if (n == 0 || camera->samples_per_pixel == samples_done) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
+    const size_t bPx = up16(n * 4u), bAcc = up16(n * 16u), bRgb = rgb ? up16(n * 3u) : 0u;
+    unsigned char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **) &buf, bPx + bAcc + bRgb));
+    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
+    HIP_TRY(hipMemcpy(buf, pixels, n * 4u, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(buf + bPx, accum, n * 16u, hipMemcpyHostToDevice));
+    rt_stats local; // (always asked for: the malformed-buffer error is reported through it)
+    rc = rt_render_pixels_extend_device(scene, camera, max_w, max_h, seed, device, n, buf, flags, samples_done, buf + bPx,
+                                        bRgb ? buf + bPx + bAcc : nullptr, nullptr, nullptr, &local);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpy(accum, buf + bPx, n * 16u, hipMemcpyDeviceToHost));
+    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bPx + bAcc, n * 3u, hipMemcpyDeviceToHost));
     if (stats) {
         *stats = local;
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

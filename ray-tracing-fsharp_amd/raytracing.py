@@ -402,7 +402,7 @@ class Scene:
 
     @property
     def last_stats(self) -> Optional[dict]:
-        """The statistics of the calling THREAD's last render_rows / hitObject / traceRays / renderFootprints on this scene (None before its first,
+        """The statistics of the calling THREAD's last render_rows / hitObject / traceRays / renderFootprints / renderPixels on this scene (None before its first,
         or after a device call with stats=False).  Per thread, like rt_last_error: a scene may be used from many threads at once."""
         return getattr(self._local, "stats", None)
 
@@ -727,6 +727,70 @@ class Scene:
             accum = np.zeros((n, 4), np.int32)
             check(lib.rt_render_footprints(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed, stream_base,
                                            flags, _i32(accum), _u8(rgb), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return RenderResult(accum, rgb, self.last_stats)
+
+    def renderPixels(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, pixels, *, seed: int = 0, device: Optional[int] = None,
+                     counters: bool = False, stats: bool = True, options: Optional[A.rt_render_options] = None, extend=None) -> RenderResult:
+        """Scene.renderPixel (Scene.fs:157-194) for a caller-chosen list of the FRAME's pixels: pixels [n] int32, each a global pixel
+        index row * (2*maxWidthCoord+1) + col (row 0 = top) -> RenderResult(accum [n, 4] int32, rgb [n, 3] uint8, stats), in list
+        order.  Entry i is, bit for bit, that pixel of render_rows of the whole frame with the same camera, geometry and seed, for any
+        order or subset; duplicates are allowed.  numpy arrays / torch tensors as for renderFootprints: a tensor goes through
+        rt_render_pixels_device on torch.cuda.current_stream() and the results are tensors (stats=False: no wait for the device, stats
+        and last_stats are None; a list with an entry outside the frame then goes unreported and renders nothing).
+        extend=(accum, samplesDone): rt_render_pixels_extend -- `accum` [n, 4] int32, this list's PixelStats at samplesDone (>= 12)
+        samples, is continued to camera.SamplesPerPixel; bit for bit a list render at that count.  An array is copied, a tensor (on the
+        list's device) extended in place."""
+        flags = A.RT_RENDER_COUNTERS if counters else 0
+        cam = camera.to_abi()
+        if _is_torch(pixels):
+            torch = _torch()
+            if pixels.dtype != torch.int32:
+                raise TypeError(f"pixels must have dtype torch.int32, not {pixels.dtype}")
+            if pixels.dim() != 1:
+                raise ValueError(f"pixels must have shape [n], not {list(pixels.shape)}")
+            if not pixels.is_cuda:
+                raise ValueError("pixels must be on a GPU (a numpy array takes the host entry point)")
+            px = pixels.contiguous()
+            dev = _tensor_device(px, device)
+            n = px.shape[0]
+            rgb = torch.empty((n, 3), dtype=torch.uint8, device=px.device)
+            st = A.rt_stats() if stats else None
+            stream = torch.cuda.current_stream(px.device).cuda_stream
+            if extend is not None:
+                accum, done = extend
+                if not _is_torch(accum) or accum.dtype != torch.int32 or tuple(accum.shape) != (n, 4) or accum.device != px.device or not accum.is_contiguous():
+                    raise ValueError("extend=(accum, samplesDone): accum must be a contiguous int32 tensor [n, 4] on the list's device")
+                check(lib.rt_render_pixels_extend_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, n, px.data_ptr(), flags, done,
+                                                         accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
+            else:
+                accum = torch.empty((n, 4), dtype=torch.int32, device=px.device)
+                check(lib.rt_render_pixels_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, n, px.data_ptr(), flags,
+                                                  accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
+            self.last_stats = st.as_dict() if st is not None else None
+            return RenderResult(accum, rgb, self.last_stats)
+        if options is not None:
+            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        if not isinstance(pixels, np.ndarray):
+            raise TypeError(f"pixels must be a numpy array or a torch tensor on a GPU, not {type(pixels).__name__}")
+        if pixels.dtype != np.int32:
+            raise TypeError(f"pixels must have dtype int32, not {pixels.dtype}")
+        if pixels.ndim != 1:
+            raise ValueError(f"pixels must have shape [n], not {list(pixels.shape)}")
+        px = np.ascontiguousarray(pixels)
+        n = px.shape[0]
+        rgb = np.zeros((n, 3), np.uint8)
+        st = A.rt_stats()
+        if extend is not None:
+            accum = np.array(_array_arg(extend[0], "extend's accum", np.int32, 4), order="C")
+            if accum.shape[0] != n:
+                raise ValueError("extend=(accum, samplesDone): accum must be [n, 4] for n list entries")
+            check(lib.rt_render_pixels_extend(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, n, _i32(px),
+                                              flags, extend[1], _i32(accum), _u8(rgb), C.byref(st)))
+        else:
+            accum = np.zeros((n, 4), np.int32)
+            check(lib.rt_render_pixels(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, n, _i32(px), flags,
+                                       _i32(accum), _u8(rgb), C.byref(st)))
         self.last_stats = st.as_dict()
         return RenderResult(accum, rgb, self.last_stats)
 
