@@ -427,6 +427,48 @@ int rt_render_pixels_extend_device(const rt_scene *scene, const rt_camera *camer
                                    void *d_accum, void *d_rgb, void *stream,
                                    const rt_render_options *options, rt_stats *stats);
 
+/* ---- Camera hits: the object each pixel sample's camera ray strikes first ------------------------------------------------
+ * A frame is (scene, camera, max_width_coord, max_height_coord, seed), as for rt_render.  For list entry i -- the GLOBAL PIXEL INDEX
+ * g = r*cols + c of rt_render_pixels (pixels == NULL: entry i is pixel i, n <= rows*cols) -- and sample s in
+ * [sample_first, sample_first + n_samples):
+ *   rand = the stream keyed (seed, g, s); (r1, r2) = rand.GetTwo(); the ray is Scene.traceOnce's (Scene.fs:129-143) with
+ *   row = max_height_coord - r - 1 and col = c - max_width_coord; the answer is Scene.hitObject scene ray (Scene.fs:62-91).
+ * It is the very ray sample s of pixel g starts with in rt_render and rt_render_pixels: an object-id or depth buffer, a per-sample
+ * coverage mask, "all pixels that show sphere 17" (the list rt_render_pixels and the targets rt_render_extend_map want next).
+ *
+ * Outputs are in list order, samples innermost: slot i*n_samples + (s - sample_first) holds entry i, sample s.  hit_index and strike
+ * are rt_hit_objects': hit_index is an index into rt_scene_create's array, -1 ValueNone, -2 Ray.make' gave ValueNone; strike
+ * (may be NULL) is Ray.walkAlong ray bestLength, NaN where hit_index < 0.  rays_out (may be NULL) is the ray itself, origin then
+ * unit direction, all six NaN at -2: depth is |strike - origin|, and the rays can be fed to rt_trace_rays.  Duplicates are
+ * allowed: every store is indexed by slot, never by an entry's value.  camera->samples_per_pixel and bounce_depth must pass
+ * rt_render's checks and are not otherwise used.
+ *
+ * Argument checks come before any device call, nothing is written when one fails: RT_ERR_INVALID_ARGUMENT for everything
+ * rt_render_pixels rejects about scene, camera, geometry and options, sample_first < 0, n_samples < 1,
+ * sample_first + n_samples > 8000000, n * n_samples > INT32_MAX, a NULL hit_index with n > 0, and pixels == NULL with
+ * n > rows*cols.  n = 0 is a no-op returning RT_OK with zeroed stats.  An entry outside [0, rows*cols) makes the LIST malformed, as
+ * for rt_render_pixels: the host variant refuses it on the host; the device variant finds it on the device, in front of the launch
+ * and on the same stream, writes NO output and returns RT_ERR_INVALID_ARGUMENT when stats is given.
+ *
+ * stats: pixels = n, samples = n*n_samples, kernel_ms, total_ms; under RT_RENDER_COUNTERS the counting variant runs and fills
+ * rays (the slots whose ray was made), aabb_tests and prim_tests; reflections is 0.  The timed variant starts a camera ray from its
+ * pixel's candidates exactly as a frame does, the counting variant walks from the root: results never depend on which.  The device
+ * variant follows rt_render_device's contract: enqueued on `stream`, scratch is stream-ordered, any number of calls in flight, with
+ * stats == NULL the call returns right after the launch, the caller's current device is left as it was; the list must not change
+ * until the launch has finished.  options: chunk_pixels counts list entries per work unit; a block of 512 or 768 threads runs as
+ * 1024; passes and park_lanes are checked and not used.
+ * Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */
+int rt_camera_hits(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                   uint64_t seed, int32_t device, size_t n, const int32_t *pixels /* NULL: entry i is pixel i, n <= rows*cols */,
+                   int32_t sample_first, int32_t n_samples, uint32_t flags,
+                   int32_t *hit_index /* n*n_samples */, double *strike /* n*n_samples*3, may be NULL */,
+                   double *rays_out /* n*n_samples*6, may be NULL */, rt_stats *stats);
+int rt_camera_hits_device(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                          uint64_t seed, int32_t device, size_t n, const void *d_pixels /* may be NULL */,
+                          int32_t sample_first, int32_t n_samples, uint32_t flags,
+                          void *d_hit_index, void *d_strike /* may be NULL */, void *d_rays_out /* may be NULL */,
+                          void *stream, const rt_render_options *options, rt_stats *stats);
+
 /* ---- Extending a rendered buffer to a higher sample count --------------------------------------------------------------
  * render at a, then extend a -> b  ==  render at b, for every PixelStats word and every rgb byte, for any 12 <= a <= b
  * (DESIGN.md "Extending a frame"): sample s of a pixel is the same ray tree whenever it is traced, the sums are integers, and
@@ -581,19 +623,20 @@ int rt_set_park(int32_t park_lanes);
  * lanes parked, shader-clock cycles summed over the waves inside the refill / general-reflection / walk / shade stages}. */
 int rt_last_stage_stats(uint64_t out[16]);
 /* Diagnostic: the launch plan (csrc/rt_launch_plan.h) of the calling THREAD's last launch -- a render shard, rt_scene_tune's probe
- * a ray list, a footprint list or a pixel list; of rt_render_frame, its last device's -- as the library gathered its inputs and executed its outputs.  Read-only
+ * a ray list, a footprint list, a pixel list or a camera-hit list; of rt_render_frame, its last device's -- as the library gathered its inputs and executed its outputs.  Read-only
  * host bookkeeping: no device work, nothing launched depends on it.  Words, under the names tests/c/launch_plan_table.cpp reads
  * and prints:
  *   [0]      1 once this thread has planned a launch (all words are 0 before)
  *   [1..21]  inputs: kind (0 frame shard, 1 traceRays list, 2 hitObject list, 3 footprint list: n pixels,
- *            4 pixel list: n pixels) lds_total lds32_total n_nodes n_obj has_tex
+ *            4 pixel list: n pixels, 5 camera hits: n list entries, spp = n_samples) lds_total lds32_total n_nodes n_obj has_tex
  *            s_block s_chunk s_bpc s_yield s_refill s_passes s_park (the resolved settings, 0 = "the plan decides") count log
  *            n_rows max_w spp n cu_count per_cu (what the occupancy query answered, before blocks_per_cu)
  *   [22..34] q_lds q_count q_block q_mode q_tex q_lds_bytes two_pass pairs list sort pool waves error
  *   [35..48] the fused or ray-list kernel (F_), [49..62] pass A (A_), [63..76] pass B (B_), each: mode grid lds_bytes chunk park
  *            park_l park_l_lds lds_node_bytes lds_node_thr yield leaf_wait refill k total_waves.  F_ is what ran unless two_pass;
  *            A_ and B_ are filled only with two_pass and no error.
- *   [77]     first_sample: 0 for a fresh render; for an extension (rt_render_extend*, rt_render_footprints_extend*) its samples_done.
+ *   [77]     first_sample: 0 for a fresh render; for an extension (rt_render_extend*, rt_render_footprints_extend*) its samples_done;
+ *            for camera hits (kind 5, mode 14, planned as a ray list of n * n_samples rays with units of F_chunk entries) sample_first.
  *            An extension reports kind 0, 3 or 4 (rt_render_pixels_extend*), two_pass 1, pairs and sort 0, every A_ word 0 (no pass A is launched) and pass B as
  *            the same job gets it with passes = 2.
  *   [78]     1 for an extension by map (rt_render_extend_map*, rt_render_footprints_extend_map*), else 0.  Such a launch reports

@@ -15,6 +15,7 @@
 #define RTD_WAVE_WORDS(P) (18u * (uint32_t) (P)) /* fused: 13 P used; pass B: two slots of {acc [P][3], pix [P][4]}, then cand [2][P][2] */
 #define RTD_WAVE_WORDS_A(P) (13u * (uint32_t) (P)) /* pass A: acc, pix, cost, cand [P][2] -- a tighter footprint, so its units can be wider */
 #define RTD_WAVE_WORDS_MAP(P) (22u * (uint32_t) (P)) /* pass B of an extension by map: pass B's 18 P, then per slot first item [P] and sample base [P] */
+#define RTD_WAVE_WORDS_CAM(P) (6u * (uint32_t) (P)) /* camera hits: pix [P][4] and cand [P][2] of the unit being handed out; nothing is accumulated */
 
 // ---- the lane scheduler's thresholds (rt_render_kernel.h, Sched) ----
 #define RTD_YIELD_DEFAULT 50

@@ -38,16 +38,20 @@ struct SceneSize {
 // A frame shard (render_kernel modes 0..3), a caller's ray list (mode 4 paths, mode 5 hit queries) or a caller's footprint list
 // (modes 6..8: planned as a FRAME of n pixels -- chunk widening, fused or two passes, placement, pools -- run by the footprint kernels)
 // or a caller's list of a frame's pixels (modes 11..13, rt_render_pixels: planned exactly as the FOOTPRINTS job of the same n)
+// or the camera hits of such a list (mode 14, rt_camera_hits: n entries x spp samples, planned by the ray lists' rules over n * spp rays,
+// with units of chunk ENTRIES and the wave scratch their pix and candidate words need)
 struct Job {
-    enum Kind { FRAME, TRACE, HIT, FOOTPRINTS, PIXELS } kind = FRAME;
+    enum Kind { FRAME, TRACE, HIT, FOOTPRINTS, PIXELS, CAMERA_HITS } kind = FRAME;
     uint64_t n_rows = 0; int32_t max_w = 0, spp = 1; // FRAME
     bool ray_log = false;                            // FRAME: rt_scene_tune's probe
-    uint64_t n = 0;                                  // TRACE, HIT: rays; FOOTPRINTS, PIXELS: pixels (with spp)
+    uint64_t n = 0;                                  // TRACE, HIT: rays; FOOTPRINTS, PIXELS: pixels (with spp); CAMERA_HITS: list entries (spp: n_samples)
     int32_t first_sample = 0;                        // FRAME, FOOTPRINTS, PIXELS: 0 = a fresh render; >= RTD_EXTEND_MIN_DONE: an EXTENSION of a buffer that
                                                      // holds this many samples per continued pixel, to spp (rt_render_extend): pass B alone
+                                                     // CAMERA_HITS: sample_first, any value >= 0 (nothing is extended)
     bool map = false;                                // an extension BY MAP (rt_render_extend_map): every pixel from its own Count to its own target <= spp.
                                                      // Planned as the extension RTD_EXTEND_MIN_DONE -> spp (first_sample is that) with the map variant's scratch
-    bool extend() const { return first_sample != 0; }
+    bool extend() const { return kind != CAMERA_HITS && first_sample != 0; }
+    uint64_t ray_count() const { return kind == CAMERA_HITS ? n * (uint64_t) spp : n; } // TRACE, HIT, CAMERA_HITS: what the grid is sized by
     bool list() const { return kind == FOOTPRINTS || kind == PIXELS; }  // n pixels in list order: a frame of one row to the plan
     bool pixels() const { return kind == FRAME || list(); }             // planned by the pixel rules, not the ray lists'
     uint64_t pixel_count() const { return list() ? n : n_rows * (uint64_t) (2 * max_w + 1); }
@@ -157,10 +161,19 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
         // 24 instantiations: blocks of 256 or 1024 threads only (a launch asking for 512 or 768 runs at 1024: the block size never
         // changes a result); the hit queries shade nothing, so they have no textured variant and park nothing.
         q.block = default_block(set) == 256 ? 256 : 1024;
-        q.mode = job.kind == Job::HIT ? 5 : 4;
+        q.mode = job.kind == Job::HIT ? 5 : job.kind == Job::CAMERA_HITS ? 14 : 4;
         q.tex = job.kind == Job::TRACE && sc.tex;
         q.chunk = set.chunk ? set.chunk : RTD_MAX_CHUNK; // rays per run of the queue (a wave takes as many runs at once as it has idle lanes)
-        if (job.kind == Job::HIT) q.park = 0;
+        if (job.kind != Job::TRACE) q.park = 0;
+        if (job.kind == Job::CAMERA_HITS) {
+            // a unit is chunk list ENTRIES, each spp items: about a wave's worth of items per unit unless the caller says otherwise (a
+            // unit is set up once and handed out without draining, so small units cost one atomic each and balance the waves best)
+            if (!set.chunk) q.chunk = job.spp >= RTD_MAX_CHUNK ? 1 : (RTD_MAX_CHUNK + job.spp - 1) / job.spp;
+            // (6 P words are fewer than the 18 P residency was decided with, at the caller's chunk or at 16; a wider default gives way)
+            while (q.lds && q.chunk > 1 && lds_need(sc, true, count, q.block, RTD_WAVE_WORDS_CAM(q.chunk)) > RT_LDS_BYTES) q.chunk /= 2;
+            place_pass(q, sc, RTD_WAVE_WORDS_CAM(q.chunk));
+            return pl;
+        }
         place_pass(q, sc, 0u); // no per-wave scratch in these modes
         return pl;
     }
@@ -202,7 +215,7 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     const uint64_t fullGrid = (uint64_t) pl.cu_count * (uint64_t) per_cu;
     const uint64_t wavesPerBlock = (uint64_t) q.block / 64u;
     if (!pl.job.pixels()) {
-        const uint64_t wavesWanted = (pl.job.n + 63u) / 64u; // a wave's worth of rays each, at least
+        const uint64_t wavesWanted = (pl.job.ray_count() + 63u) / 64u; // a wave's worth of rays each, at least
         const uint64_t needBlocks = (wavesWanted + wavesPerBlock - 1) / wavesPerBlock;
         q.grid = fullGrid > needBlocks ? needBlocks : fullGrid;
         pl.pool_bytes = park_pool_bytes(q.grid, q);

@@ -81,6 +81,10 @@ struct RenderParams {
     // a pixel list (MODE 11 / 12 / 13, rt_render_pixels): read only there.  The list's length is ray_n; cols, max_w, max_h and the camera are
     // the FRAME's, n_rows = 1, row_first = 0, row_stride = 1
     const int32_t *pixel_list;     // [ray_n]: global pixel indices r * cols + c of the frame; entry i owns accum[i] and rgb[i]
+    // camera hits (MODE 14, rt_camera_hits): read only there.  ray_n entries, each the frame's pixel pixel_list[i] (null: pixel i); the
+    // answers go to ray_hit / ray_strike (as MODE 5's) and cam_rays_out, at slot i * cam_n_samples + (sample - cam_sample_first)
+    double *cam_rays_out;          // [ray_n * cam_n_samples][6]: the camera ray itself, origin then unit direction; or null
+    int32_t cam_sample_first, cam_n_samples;
 };
 
 // Per-wave LDS scratch (in 4-byte words), P = pixels per work unit:
@@ -760,6 +764,114 @@ RTD_INLINE void run_rays(const RenderParams &p, const SceneView<LDS> &sc, unsign
     }
 }
 
+// Camera hits (MODE 14, rt_camera_hits): Scene.hitObject (Scene.fs:62-91) of the ray Scene.traceOnce (Scene.fs:129-143) gives sample s
+// of a frame's pixel, for samples [cam_sample_first, cam_sample_first + cam_n_samples) of the caller's list entries [0, p.ray_n) -- the
+// pixel modes' unit set-up feeding MODE 5's tail.  A wave takes a unit of p.chunk entries from the global queue and writes, once per
+// entry, its pix words (row, col, stream key) and its two candidate words to the wave's scratch -- the frame's own set-up code, with
+// g = pixel_list ? pixel_list[lp] : lp -- then hands the unit's npx * cam_n_samples items to idle lanes through Sched::start_item,
+// the item's output slot in slotOff.  A started item has copied what it needs of the scratch, so the next unit is taken as soon as the
+// last item is handed out: nothing drains at a unit's end.  There is no shading, so no park pool and no stage but the walk; a lane
+// whose walk is done runs the unbounded tests and stores (hit, strike, ray).  In the timed variant a camera ray starts from its
+// pixel's candidates exactly as a frame's does; the counting variant walks from the root.
+template <bool LDS, bool COUNT>
+RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, RTD_AS3 uint32_t *wv, Counters &cnt,
+                                StageStats &ss) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t P = (uint32_t) p.chunk;
+    const uint32_t per = (uint32_t) p.cam_n_samples;
+    RTD_AS3 uint32_t *pix = wv;           // [P][4]
+    RTD_AS3 uint32_t *cand = wv + 4u * P; // [P][2]
+    Sched<LDS, COUNT, false, false> L(p, sc, cnt, ss, pool, poolLds);
+    // wave-uniform: items [next, total) of the current unit are not handed out yet; the unit's first item has output slot slot0
+    uint32_t next = 0, total = 0, slot0 = 0;
+    bool exhausted = false;
+    const bool fastDiv = (uint64_t) P * (uint64_t) per < (1ull << 22) && per < (1u << 23); // a unit holds at most P * per items; see div_uniform
+    const float perRcp = 1.0f / (float) per;
+    // a query's answer, at its slot (n * n_samples <= INT32_MAX: every index below fits 64-bit arithmetic on a 32-bit slot)
+    auto emit = [&](bool made) {
+        const uint64_t i = (uint64_t) L.slotOff;
+        const double nanv = __builtin_nan("");
+        const bool none = !made || L.w.best < 0;
+        p.ray_hit[i] = !made ? -2 : (L.w.best < 0 ? -1 : p.obj_to_orig[L.w.best]);
+        if (p.ray_strike) {
+            const V3 sp = walk(L.o, L.d, L.w.bestLen); // Ray.walkAlong ray bestLength (Scene.fs:91)
+            p.ray_strike[i * 3 + 0] = none ? nanv : sp.x;
+            p.ray_strike[i * 3 + 1] = none ? nanv : sp.y;
+            p.ray_strike[i * 3 + 2] = none ? nanv : sp.z;
+        }
+        if (p.cam_rays_out) {
+            double *r = p.cam_rays_out + i * 6;
+            r[0] = made ? L.o.x : nanv; r[1] = made ? L.o.y : nanv; r[2] = made ? L.o.z : nanv;
+            r[3] = made ? L.d.x : nanv; r[4] = made ? L.d.y : nanv; r[5] = made ? L.d.z : nanv;
+        }
+    };
+    for (;;) {
+        const unsigned long long t0 = (COUNT || RTD_CLK) ? __builtin_amdgcn_s_memtime() : 0ull;
+        // ---- refill: idle lanes take the next items of the unit; a new unit is taken when the current one is handed out ----
+        const unsigned long long idle = __builtin_amdgcn_ballot_w64(L.st == L_IDLE);
+        const uint32_t nIdle = (uint32_t) __popcll(idle);
+        if (nIdle != 0u && (next < total || !exhausted) && ((int) nIdle >= p.refill_lanes || nIdle == 64u)) {
+            if (next >= total && !exhausted) {
+                uint32_t unit = 0;
+                if (lane == 0) unit = atomicAdd(p.queue, 1u);
+                unit = __builtin_amdgcn_readfirstlane(unit);
+                const unsigned long long first = (unsigned long long) unit * P;
+                if (first >= p.ray_n) exhausted = true;
+                else {
+                    const uint32_t npx = (uint32_t) ((p.ray_n - first < (unsigned long long) P) ? (p.ray_n - first) : (unsigned long long) P);
+                    __builtin_amdgcn_wave_barrier(); // (the last unit's words have all been read)
+                    if ((uint32_t) lane < npx) { // a busy lane too: nothing of its path's state is touched
+                        const unsigned long long lp = first + (uint32_t) lane;
+                        const uint32_t g = p.pixel_list ? (uint32_t) p.pixel_list[lp] : (uint32_t) lp;
+                        uint32_t r = g / (uint32_t) p.cols;
+                        uint32_t c = g - r * (uint32_t) p.cols;
+                        uint64_t pkey = pixel_key(p.seed_key, (uint64_t) g); // global pixel index
+                        pix[lane * 4 + 0] = (uint32_t) (p.max_h - (int) r - 1);
+                        pix[lane * 4 + 1] = (uint32_t) ((int) c - p.max_w);
+                        pix[lane * 4 + 2] = (uint32_t) pkey;
+                        pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
+                        const CameraParams *cp = p.cam_ptr;
+                        asm volatile("" : "+s"(cp));
+                        uint32_t c2;
+                        const uint32_t c1 = pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, c2);
+                        cand[lane * 2] = c1;
+                        cand[lane * 2 + 1] = c2;
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    next = 0u; total = npx * per; slot0 = (uint32_t) first * per;
+                }
+            }
+            const uint32_t avail = total - next;
+            const uint32_t take = nIdle < avail ? nIdle : avail;
+            const uint32_t rank = lane_rank(idle);
+            if (COUNT || RTD_CLK) { ss.refill++; ss.refillLanes += nIdle; }
+            if (L.st == L_IDLE && rank < take) {
+                const uint32_t item = next + rank;
+                const uint32_t j = fastDiv ? div_uniform(item, per, perRcp) : item / per;
+                const uint32_t s = (uint32_t) p.cam_sample_first + (item - j * per);
+                const int row = (int) pix[j * 4 + 0], col = (int) pix[j * 4 + 1];
+                const uint64_t pkey = (uint64_t) pix[j * 4 + 2] | ((uint64_t) pix[j * 4 + 3] << 32);
+                if (!L.start_item(pkey, s, row, col, slot0 + item, cand[j * 2], cand[j * 2 + 1])) emit(false); // ValueNone: no walk; -2
+            }
+            next += take;
+        }
+        if (__builtin_amdgcn_ballot_w64(L.st != L_IDLE) == 0ull) {
+            if (next >= total && exhausted) break;
+            continue;
+        }
+        const unsigned long long t1 = (COUNT || RTD_CLK) ? __builtin_amdgcn_s_memtime() : 0ull;
+        L.stage_walk();
+        const unsigned long long t2 = (COUNT || RTD_CLK) ? __builtin_amdgcn_s_memtime() : 0ull;
+        // the rest of Scene.hitObject (Scene.fs:77-91): the unbounded objects, then the answer
+        if (__builtin_amdgcn_ballot_w64(L.st == L_DONE) != 0ull && L.st == L_DONE) {
+            unbounded_tests<LDS, COUNT>(sc, L.o, L.d, L.w, cnt);
+            emit(true);
+            L.st = L_IDLE; L.w.off = L.end;
+        }
+        if (COUNT || RTD_CLK) { const unsigned long long t3 = __builtin_amdgcn_s_memtime(); ss.tRefill += t1 - t0; ss.tWalk += t2 - t1; ss.tShade += t3 - t2; }
+    }
+}
+
 // Pass B (MODE 2): phase 2 for the pixels of the cost-ordered list, STREAMED.  A wave reserves a run of list entries ("range"),
 // hands out its npx*n2 items, and while the last paths of that range are still in flight it already reserves the next range and
 // hands out its items: two accumulator slots alternate, a range is flushed (its sums added to what pass A left in `accum`) when
@@ -1036,6 +1148,8 @@ RTD_INLINE uint32_t stage_nodes32(const RenderParams &p, unsigned char *smem) {
 // MODE 11 / 12 / 13: MODE 0 / 1 / 2 over a caller's list of the FRAME's pixels (rt_render_pixels): entry i of p.ray_n names the global pixel
 //         index g = p.pixel_list[i]; (row, col) = (g / cols, g % cols), the stream of (seed, g), the frame's camera_ray AND its pixel
 //         candidates -- a frame's pixel in all but where it is stored, which is slot i.  An extension is mode 13 with first_b set.
+// MODE 14: camera hits (rt_camera_hits, run_camera_hits): the first object that sample s of a listed pixel's camera ray strikes -- the pixel
+//         modes' unit set-up (pix and candidate words, 6 P words of scratch per wave) feeding MODE 5's tail; nothing is shaded.
 // Per-pixel cost is heavy-tailed (a pixel on a glass sphere: ~20 rays per sample, 4 ms of one wave), so when a shard has only a few
 // units per wave the fused kernel ends with most waves waiting for a few long units started late; A + sort + B removes that tail.
 // Every mode computes the same integers: which wave traces which sample when has no effect (streams are per item).
@@ -1045,7 +1159,8 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr bool MAP = MODE == 9 || MODE == 10; // pass B of an extension by map: of a frame / of a footprint list
     constexpr bool PX = MODE >= 11 && MODE <= 13; // the pixels are a caller's list of the frame's
-    constexpr bool FP = MODE >= 6 && MODE != 9 && !PX; // the pixels are the caller's footprints
+    constexpr bool CAM = MODE == 14;              // camera hits: a list of the frame's pixels, answered as MODE 5 answers rays
+    constexpr bool FP = MODE >= 6 && MODE != 9 && !PX && !CAM; // the pixels are the caller's footprints
     constexpr int PM = MAP ? 2 : PX ? MODE - 11 : FP ? MODE - 6 : MODE; // ... and run as this pixel mode
     constexpr bool RAYS = MODE == 4 || MODE == 5;
     constexpr bool FUSED = PM == 0 || PM == 3;
@@ -1062,7 +1177,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     scv.lds_thr = p.lds_node_thr;
     const SceneView<LDS> &sc = scv;
     const uint32_t P = (uint32_t) p.chunk;
-    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * (RAYS ? 0u : PM == 1 ? RTD_WAVE_WORDS_A(P) : MAP ? RTD_WAVE_WORDS_MAP(P) : RTD_WAVE_WORDS(P));
+    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * (RAYS ? 0u : CAM ? RTD_WAVE_WORDS_CAM(P) : PM == 1 ? RTD_WAVE_WORDS_A(P) : MAP ? RTD_WAVE_WORDS_MAP(P) : RTD_WAVE_WORDS(P));
     RTD_AS3 uint32_t *acc = wv;
     RTD_AS3 uint32_t *pix = wv + 6u * P;
     RTD_AS3 uint32_t *live = pix + 4u * P;
@@ -1070,7 +1185,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     unsigned char *pool = p.park_pool + ((size_t) blockIdx.x * (BLOCK / 64) + (size_t) wave) * (size_t) RTD_PARK_ENTRY_BYTES *
                                         (size_t) (p.park + (p.park_l_lds ? 0 : p.park_l) + (TEX ? p.park : 0));
     // the Lambert pools in LDS (if any) follow the waves' scratch
-    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * (RAYS ? 0u : PM == 1 ? RTD_WAVE_WORDS_A(P) : MAP ? RTD_WAVE_WORDS_MAP(P) : RTD_WAVE_WORDS(P)) * 4u +
+    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * (RAYS ? 0u : CAM ? RTD_WAVE_WORDS_CAM(P) : PM == 1 ? RTD_WAVE_WORDS_A(P) : MAP ? RTD_WAVE_WORDS_MAP(P) : RTD_WAVE_WORDS(P)) * 4u +
                                      (size_t) wave * (size_t) RTD_PARK_L_LDS_BYTES * (size_t) p.park_l;
 
     const uint64_t nLocal = PX ? p.ray_n : (uint64_t) p.n_rows * (uint64_t) p.cols; // (a pixel list: cols is the frame's)
@@ -1094,6 +1209,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     uint64_t sampleCount = 0; // Scene.traceOnce calls = sum of PixelStats.Count
 
     if constexpr (RAYS) run_rays<LDS, COUNT, TEX, MODE == 5>(p, sc, pool, poolLds, cnt, ss);
+    else if constexpr (CAM) run_camera_hits<LDS, COUNT>(p, sc, pool, poolLds, wv, cnt, ss);
     else if (PM == 2) run_stream<LDS, COUNT, TEX, FP, MAP, PX>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
     else
     for (;;) {

@@ -200,8 +200,8 @@ static int allow_full_lds(const void *fn) {
 // blocks of 256 and 1024 threads only, and the hit queries (mode 5) shade nothing, so they have no textured variant.  The plan
 // never asks for one of the others; if it did, the launch fails (no kernel is substituted).
 template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX> static render_fn kernel_if_built() {
-    if constexpr ((MODE >= 4 && MODE != 9 && BLOCK != 256 && BLOCK != 1024) || (MODE == 5 && TEX)) return nullptr; // (the footprint modes 6-8 and 10 and the pixel-list modes 11-13: as the ray lists;
-                                                                                                                        // mode 9 runs frames: every block, as mode 2)
+    if constexpr ((MODE >= 4 && MODE != 9 && BLOCK != 256 && BLOCK != 1024) || ((MODE == 5 || MODE == 14) && TEX)) return nullptr; // (the footprint modes 6-8 and 10, the pixel-list modes 11-13 and the
+                                                                                                                        // camera hits, mode 14 (untextured, as mode 5): as the ray lists; mode 9 runs frames: every block, as mode 2)
     else return render_kernel<LDS, COUNT, BLOCK, MODE, TEX>;
 }
 template <int BLOCK, int MODE, bool TEX> static render_fn pick_variant(bool lds, bool count) {
@@ -229,6 +229,7 @@ static render_fn pick_kernel(const rtp::Pass &q) {
     case 11: return q.tex ? pick_mode<11, true>(q) : pick_mode<11, false>(q);
     case 12: return q.tex ? pick_mode<12, true>(q) : pick_mode<12, false>(q);
     case 13: return q.tex ? pick_mode<13, true>(q) : pick_mode<13, false>(q);
+    case 14: return q.tex ? nullptr : pick_mode<14, false>(q);
     default: return nullptr;
     }
 }
@@ -483,7 +484,7 @@ struct Pending {
     bool launched = false, keep = false;
     bool extend = false; // an extension: collect_stats reads LaunchScratch::ext_malformed
     bool map = false;    // ... by map (the message of a malformed buffer)
-    bool list = false;   // a pixel list: collect_stats reads ext_malformed for a fresh render too (an entry outside the frame)
+    bool list = false;   // a pixel list (of a render, or of camera hits): collect_stats reads ext_malformed for a fresh render too (an entry outside the frame)
     std::chrono::steady_clock::time_point t0;
     void release() { // events destroyed, scratch handed back to the stream's pool in stream order
         if (a) (void) hipEventDestroy(a);
@@ -528,7 +529,7 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
     const Settings &s = pl.set;
     const rtp::Job &j = pl.job;
     put(1);
-    put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : (j.kind == rtp::Job::HIT ? 2 : (j.kind == rtp::Job::FOOTPRINTS ? 3 : 4))));
+    put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : (j.kind == rtp::Job::HIT ? 2 : (j.kind == rtp::Job::FOOTPRINTS ? 3 : (j.kind == rtp::Job::PIXELS ? 4 : 5)))));
     put((int64_t) sc.lds_total); put((int64_t) sc.lds32_total); put(sc.n_nodes); put((int64_t) sc.n_objects); put(sc.tex);
     put(s.block); put(s.chunk); put(s.blocks_per_cu); put(s.yield); put(s.refill); put(s.passes); put(s.park);
     put(pl.one.count); put(j.ray_log); put((int64_t) j.n_rows); put(j.max_w); put(j.spp); put((int64_t) j.n); put(pl.cu_count); put(per_cu);
@@ -540,7 +541,7 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
         put(r->mode); put((int64_t) r->grid); put((int64_t) r->lds_bytes); put(r->chunk); put(r->park); put(r->park_l); put(r->park_l_lds);
         put(r->lds_node_bytes); put(r->lds_node_thr); put(r->yield_lanes); put(r->leaf_wait); put(r->refill_lanes); put(r->k); put(r->total_waves);
     }
-    put(j.first_sample); // [77]: 0 = a fresh render, else the samples_done of an extension (by map: RTD_EXTEND_MIN_DONE)
+    put(j.first_sample); // [77]: 0 = a fresh render, else the samples_done of an extension (by map: RTD_EXTEND_MIN_DONE); camera hits: sample_first
     put(j.map ? 1 : 0);  // [78]: 1 = an extension by map
     static_assert(1 + 21 + 13 + 3 * 14 + 2 <= RT_LAUNCH_PLAN_WORDS, "rt_dev_last_launch_plan's words");
     while (n < RT_LAUNCH_PLAN_WORDS) put(0);
@@ -595,7 +596,8 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     cl.waves = plan.waves;
     cl.extend = job.extend();
     cl.map = job.map;
-    cl.list = job.kind == rtp::Job::PIXELS;
+    const bool checked_list = job.kind == rtp::Job::PIXELS || (job.kind == rtp::Job::CAMERA_HITS && p.pixel_list != nullptr);
+    cl.list = checked_list;
     if (want_stats) {
         HIP_TRY(hipEventCreate(&cl.a));
         HIP_TRY(hipEventCreate(&cl.b));
@@ -613,9 +615,9 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     }
     if (grid > 0) {
         if (want_stats) HIP_TRY(hipEventRecord(cl.a, st));
-        if (job.kind == rtp::Job::PIXELS) {
+        if (checked_list) {
             // in front of everything else: is every entry a pixel of the frame?  An extension's own seal acts on the count; a fresh render
-            // gets a seal that poisons the unit counter, so that nothing is rendered and nothing written (rt_render_kernel.h)
+            // (and camera hits) gets a seal that poisons the unit counter, so that nothing is rendered and nothing written (rt_render_kernel.h)
             LaunchScratch *ls = (LaunchScratch *) scr;
             const unsigned long long want = (job.n + 255ull) / 256ull, most = (unsigned long long) ds->cu_count * 8ull;
             hipLaunchKernelGGL(pixel_list_check_kernel, dim3((unsigned) (want < most ? want : most)), dim3(256), 0, st, p.pixel_list, (unsigned long long) job.n,
@@ -1664,6 +1666,120 @@ int rt_render_pixels_extend(const rt_scene *scene, const rt_camera *camera, int3
     if (rc != RT_OK) return rc;
     HIP_TRY(hipMemcpy(accum, buf + bPx, n * 16u, hipMemcpyDeviceToHost));
     if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bPx + bAcc, n * 3u, hipMemcpyDeviceToHost));
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// camera hits (DESIGN.md "Camera hits"): Scene.hitObject (Scene.fs:62-91) of the ray sample s of a frame's pixel starts with
+// (Scene.traceOnce, Scene.fs:129-143), for a caller's list of pixels and a range of samples (render_kernel MODE 14)
+// ------------------------------------------------------------------------------------------------------------
+#define RT_CAMERA_HITS_MAX_SAMPLE 8000000 /* sample_first + n_samples at most: the cap of the map calls (check_geometry's samples_per_pixel) */
+// Every argument check the two entry points share, made before anything touches a device.
+static int check_camera_hits(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, size_t n, const void *pixels, int32_t sample_first,
+                             int32_t n_samples, const void *hit_index, const rt_render_options *options) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    int rc = check_geometry(camera, max_w, max_h, 0, 1, 0);
+    if (rc != RT_OK) return rc;
+    const uint64_t frame = (uint64_t) (2 * max_w + 1) * (uint64_t) (2 * max_h + 1);
+    if (frame > (uint64_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "a pixel list indexes frames of at most INT32_MAX pixels");
+    if (sample_first < 0) return fail(RT_ERR_INVALID_ARGUMENT, "sample_first must be >= 0");
+    if (n_samples < 1) return fail(RT_ERR_INVALID_ARGUMENT, "n_samples must be >= 1");
+    if ((int64_t) sample_first + (int64_t) n_samples > (int64_t) RT_CAMERA_HITS_MAX_SAMPLE) return fail(RT_ERR_INVALID_ARGUMENT, "sample_first + n_samples exceeds 8000000");
+    if (n > (size_t) INT32_MAX || (uint64_t) n * (uint64_t) n_samples > (uint64_t) INT32_MAX)
+        return fail(RT_ERR_INVALID_ARGUMENT, "more than INT32_MAX output slots (n * n_samples)");
+    if (n > 0 && !hit_index) return fail(RT_ERR_INVALID_ARGUMENT, "hit_index is NULL");
+    if (!pixels && (uint64_t) n > frame) return fail(RT_ERR_INVALID_ARGUMENT, "pixels is NULL and n exceeds the frame's pixels");
+    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
+    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
+    return RT_OK;
+}
+
+// Enqueues the one launch on `stream` (n > 0, arguments checked): the frame's camera, geometry and seed, the list (or none), the sample
+// range and the outputs, as MODE 5's where they are MODE 5's; then enqueue(), which checks a device list in front of the launch.
+static int launch_camera_hits(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                              const void *d_pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, void *d_hit_index, void *d_strike,
+                              void *d_rays_out, void *stream, const rt_render_options *options, bool want_stats, Pending &pd) {
+    RenderParams p{};
+    p.max_w = max_w; p.max_h = max_h;
+    p.spp = camera->samples_per_pixel;
+    p.depth = camera->bounce_depth;
+    p.seed_key = mix64(seed + 0x9E3779B97F4A7C15ull); // seed_key(), host side
+    p.cols = 2 * max_w + 1;
+    p.row_first = 0; p.row_stride = 1; p.n_rows = 1;
+    p.pixel_list = (const int32_t *) d_pixels;
+    p.ray_n = n;
+    p.ray_hit = (int32_t *) d_hit_index;
+    p.ray_strike = (double *) d_strike;
+    p.cam_rays_out = (double *) d_rays_out;
+    p.cam_sample_first = sample_first; p.cam_n_samples = n_samples;
+    rtp::Job job;
+    job.kind = rtp::Job::CAMERA_HITS;
+    job.n = n; job.spp = n_samples; job.first_sample = sample_first;
+    return enqueue(scene, device, job, resolve_settings(options), flags, stream, p, camera_params(camera, max_w, max_h), want_stats, pd);
+}
+
+extern "C" {
+
+int rt_camera_hits_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                          const void *d_pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, void *d_hit_index, void *d_strike,
+                          void *d_rays_out, void *stream, const rt_render_options *options, rt_stats *stats) {
+    int rc = check_camera_hits(scene, camera, max_w, max_h, n, d_pixels, sample_first, n_samples, d_hit_index, options);
+    if (rc != RT_OK) return rc;
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    Pending pd;
+    rc = launch_camera_hits(scene, camera, max_w, max_h, seed, device, n, d_pixels, sample_first, n_samples, flags, d_hit_index, d_strike, d_rays_out, stream,
+                            options, stats != nullptr, pd);
+    if (rc != RT_OK || !stats) return rc;
+    rc = collect_stats(pd, stats);
+    if (rc != RT_OK) return rc;
+    stats->pixels = (uint64_t) n;                          // list entries; nothing is shaded, so `reflections` stays 0
+    stats->samples = (uint64_t) n * (uint64_t) n_samples;  // output slots (`rays`, under RT_RENDER_COUNTERS: those whose ray was made)
+    return RT_OK;
+}
+
+// The host variant: the list checked here, one device allocation for the list and the outputs, the device variant on the null stream, the
+// outputs copied back.
+int rt_camera_hits(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                   const int32_t *pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, int32_t *hit_index, double *strike, double *rays_out,
+                   rt_stats *stats) {
+    int rc = check_camera_hits(scene, camera, max_w, max_h, n, pixels, sample_first, n_samples, hit_index, nullptr);
+    if (rc != RT_OK) return rc;
+    if (pixels && (rc = check_pixel_entries(pixels, n, max_w, max_h)) != RT_OK) return rc;
+    if (n == 0) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    rc = guard.enter(device);
+    if (rc != RT_OK) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
+    const size_t slots = n * (size_t) n_samples;
+    const size_t bPx = pixels ? up16(n * 4u) : 0u, bHit = up16(slots * 4u), bStrike = strike ? up16(slots * 24u) : 0u, bRays = rays_out ? up16(slots * 48u) : 0u;
+    unsigned char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **) &buf, bPx + bHit + bStrike + bRays));
+    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
+    if (pixels) HIP_TRY(hipMemcpy(buf, pixels, n * 4u, hipMemcpyHostToDevice));
+    unsigned char *dHit = buf + bPx, *dStrike = bStrike ? dHit + bHit : nullptr, *dRays = bRays ? dHit + bHit + bStrike : nullptr;
+    rt_stats local;
+    rc = rt_camera_hits_device(scene, camera, max_w, max_h, seed, device, n, pixels ? buf : nullptr, sample_first, n_samples, flags, dHit, dStrike, dRays,
+                               nullptr, nullptr, &local);
+    if (rc != RT_OK) return rc;
+    HIP_TRY(hipMemcpy(hit_index, dHit, slots * 4u, hipMemcpyDeviceToHost));
+    if (strike) HIP_TRY(hipMemcpy(strike, dStrike, slots * 24u, hipMemcpyDeviceToHost));
+    if (rays_out) HIP_TRY(hipMemcpy(rays_out, dRays, slots * 48u, hipMemcpyDeviceToHost));
     if (stats) {
         *stats = local;
         stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

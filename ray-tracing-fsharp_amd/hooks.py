@@ -161,5 +161,6 @@ def last_launch_plan():
             out.update({f"{name}_{k}": v for k, v in zip(PLAN_PASS, w[at:at + len(PLAN_PASS)])})
         at += len(PLAN_PASS)
     inp["first_sample"] = w[at]  # word 77: 0 = a fresh render, else the samples_done of an extension (pass B alone: A_ words 0)
+                                 # (camera hits, kind 5: sample_first)
     inp["map"] = w[at + 1]       # word 78: 1 = an extension by map (first_sample is then 12, spp the cap, B_mode 9 or 10)
     return {"in": inp, "out": out}

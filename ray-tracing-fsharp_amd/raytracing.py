@@ -394,6 +394,13 @@ class RenderResult(NamedTuple):
     stats: dict
 
 
+class CameraHits(NamedTuple):
+    hit_index: np.ndarray  # [n, n_samples] int32: index into Scene.make's objects, -1 none, -2 where Ray.make' gave ValueNone
+    strike: Optional[np.ndarray]  # [n, n_samples, 3] float64, NaN where hit_index < 0; None if not asked for
+    rays: Optional[np.ndarray]    # [n, n_samples, 6] float64: the camera ray, origin then unit direction, NaN at -2; None if not asked for
+    stats: Optional[dict]
+
+
 class Scene:
     def __init__(self, handle: int, keep):
         self._h = C.c_void_p(handle)
@@ -402,7 +409,7 @@ class Scene:
 
     @property
     def last_stats(self) -> Optional[dict]:
-        """The statistics of the calling THREAD's last render_rows / hitObject / traceRays / renderFootprints / renderPixels on this scene (None before its first,
+        """The statistics of the calling THREAD's last render_rows / hitObject / traceRays / renderFootprints / renderPixels / cameraHits on this scene (None before its first,
         or after a device call with stats=False).  Per thread, like rt_last_error: a scene may be used from many threads at once."""
         return getattr(self._local, "stats", None)
 
@@ -793,6 +800,77 @@ class Scene:
                                        _i32(accum), _u8(rgb), C.byref(st)))
         self.last_stats = st.as_dict()
         return RenderResult(accum, rgb, self.last_stats)
+
+    def cameraHits(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, pixels=None, *, sample_first: int = 0, n_samples: int = 1,
+                   seed: int = 0, n: Optional[int] = None, strike: bool = True, rays: bool = True, tensors: bool = False, device: Optional[int] = None,
+                   counters: bool = False, stats: bool = True, options: Optional[A.rt_render_options] = None) -> CameraHits:
+        """What each pixel sample's camera ray strikes first: Scene.hitObject (Scene.fs:62-91) of the ray Scene.traceOnce
+        (Scene.fs:129-143) builds for samples sample_first .. sample_first + n_samples - 1 of the FRAME's pixels in `pixels` ([n] int32
+        global pixel indices row * (2*maxWidthCoord+1) + col, as for renderPixels; None: pixels 0 .. n-1, n defaulting to the whole
+        frame) -> CameraHits(hit_index [n, n_samples], strike [n, n_samples, 3], rays [n, n_samples, 6], stats), in list order.  It is the
+        very ray that sample starts with in render_rows and renderPixels with the same camera, geometry and seed; duplicates are
+        allowed.  strike=False / rays=False: that output is not computed (None).  numpy arrays / torch tensors as for renderPixels: a
+        tensor goes through rt_camera_hits_device on torch.cuda.current_stream() and the results are tensors (stats=False: no wait for
+        the device; a list with an entry outside the frame then goes unreported and nothing is written); with pixels=None,
+        tensors=True does the same on `device` (default: torch's current one)."""
+        flags = A.RT_RENDER_COUNTERS if counters else 0
+        cam = camera.to_abi()
+        frame = (2 * maxWidthCoord + 1) * (2 * maxHeightCoord + 1)
+        if not isinstance(n_samples, int) or not isinstance(sample_first, int):
+            raise TypeError("sample_first and n_samples must be ints")
+        if pixels is not None and n is not None:
+            raise ValueError("n applies to pixels=None")
+        if _is_torch(pixels) or (pixels is None and tensors):
+            torch = _torch()
+            if pixels is None:
+                tdev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+                dev, count, ptr = tdev.index, frame if n is None else int(n), None
+            else:
+                if pixels.dtype != torch.int32:
+                    raise TypeError(f"pixels must have dtype torch.int32, not {pixels.dtype}")
+                if pixels.dim() != 1:
+                    raise ValueError(f"pixels must have shape [n], not {list(pixels.shape)}")
+                if not pixels.is_cuda:
+                    raise ValueError("pixels must be on a GPU (a numpy array takes the host entry point)")
+                px = pixels.contiguous()
+                tdev, dev, count, ptr = px.device, _tensor_device(px, device), px.shape[0], px.data_ptr()
+            per = max(n_samples, 0)
+            hit = torch.empty((count, per), dtype=torch.int32, device=tdev)
+            sk = torch.empty((count, per, 3), dtype=torch.float64, device=tdev) if strike else None
+            ry = torch.empty((count, per, 6), dtype=torch.float64, device=tdev) if rays else None
+            st = A.rt_stats() if stats else None
+            check(lib.rt_camera_hits_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, count, ptr, sample_first, n_samples, flags,
+                                            hit.data_ptr(), sk.data_ptr() if strike else None, ry.data_ptr() if rays else None,
+                                            torch.cuda.current_stream(tdev).cuda_stream, _ref(options), _ref(st)))
+            self.last_stats = st.as_dict() if st is not None else None
+            return CameraHits(hit, sk, ry, self.last_stats)
+        if options is not None:
+            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config for arrays")
+        if pixels is None:
+            px, count = None, frame if n is None else int(n)
+        else:
+            if not isinstance(pixels, np.ndarray):
+                raise TypeError(f"pixels must be a numpy array or a torch tensor on a GPU, not {type(pixels).__name__}")
+            if pixels.dtype != np.int32:
+                raise TypeError(f"pixels must have dtype int32, not {pixels.dtype}")
+            if pixels.ndim != 1:
+                raise ValueError(f"pixels must have shape [n], not {list(pixels.shape)}")
+            px = np.ascontiguousarray(pixels)
+            count = px.shape[0]
+        if count < 0:
+            raise ValueError("n must be >= 0")
+        per = max(n_samples, 0)
+        big = count * per > 2**31 - 1  # (refused by the library: no buffers are made for it)
+        shape = (0, 0) if big else (count, per)
+        hit = np.zeros(shape, np.int32)
+        sk = np.zeros(shape + (3,), np.float64) if strike else None
+        ry = np.zeros(shape + (6,), np.float64) if rays else None
+        st = A.rt_stats()
+        check(lib.rt_camera_hits(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, count,
+                                 _i32(px) if px is not None else None, sample_first, n_samples, flags, _i32(hit), _f64(sk) if strike else None,
+                                 _f64(ry) if rays else None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return CameraHits(hit, sk, ry, self.last_stats)
 
     @staticmethod
     def render(progressIncrement: Callable[[float], None], log: Callable[[str], None], maxWidthCoord: int, maxHeightCoord: int,
