@@ -15,6 +15,7 @@
 #include <chrono>
 #include <cstddef>
 #include <cstdio>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -40,6 +41,11 @@ static int fail(int code, const std::string &msg) noexcept {
     do {                                                                                                                \
         hipError_t e_ = (expr);                                                                                         \
         if (e_ != hipSuccess) return fail(RT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));               \
+    } while (0)
+#define RT_TRY(expr) /* a step that has already called fail(): its code is the caller's */                              \
+    do {                                                                                                                \
+        const int rc_ = (expr);                                                                                         \
+        if (rc_ != RT_OK) return rc_;                                                                                   \
     } while (0)
 
 // No exception crosses the C boundary: an entry point that fills host containers or starts threads runs its body through
@@ -455,18 +461,55 @@ int rt_scene_get_filter_tree(const rt_scene *s, float *boxes, int32_t *links) {
     return RT_OK;
 }
 
+// The argument checks more than one family of entry points makes, each stated once.  The first fault found decides the code and the
+// text of rt_last_error(), so every check_* function below lists its pieces in the order its entry points have always tested them.
+static int check_options(const rt_render_options *options) { // (null: the rt_set_* defaults, which are checked as well)
+    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
+    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
+    return RT_OK;
+}
+static int check_spp(int32_t spp) {
+    if (spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel must be >= 1");
+    if (spp > 8000000) return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel too large for int32 sums (255*spp)");
+    return RT_OK;
+}
+static int check_depth(int32_t bounce_depth) {
+    if (bounce_depth < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth must be >= 0");
+    if (bounce_depth > 0xFFFFFF) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth too large");
+    return RT_OK;
+}
+static int check_count(size_t n, const char *what) { // a list of `what`: "rays", "footprints", "list entries"
+    if (n > (size_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, std::string("more than INT32_MAX ") + what);
+    return RT_OK;
+}
+static int check_list_frame(int32_t max_w, int32_t max_h) { // a pixel list's entries are int32 indices into the frame
+    if ((uint64_t) (2 * max_w + 1) * (uint64_t) (2 * max_h + 1) > (uint64_t) INT32_MAX)
+        return fail(RT_ERR_INVALID_ARGUMENT, "a pixel list indexes frames of at most INT32_MAX pixels");
+    return RT_OK;
+}
+static int check_extend_shard(int32_t max_w, int32_t n_rows) { // the extension's list of continued pixels holds uint32 indices
+    if ((uint64_t) n_rows * (uint64_t) (2 * max_w + 1) >= (1ull << 32)) return fail(RT_ERR_INVALID_ARGUMENT, "an extension takes shards of fewer than 2^32 pixels");
+    return RT_OK;
+}
+
 static int check_geometry(const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t row_first, int32_t row_stride, int32_t n_rows) {
     if (!camera) return fail(RT_ERR_INVALID_ARGUMENT, "camera is NULL");
     if (max_w <= 0 || max_h <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "max_width_coord and max_height_coord must be positive");
     if (max_w > (1 << 20) || max_h > (1 << 20)) return fail(RT_ERR_INVALID_ARGUMENT, "image too large");
-    if (camera->samples_per_pixel < 1) return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel must be >= 1");
-    if (camera->samples_per_pixel > 8000000) return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel too large for int32 sums (255*spp)");
-    if (camera->bounce_depth < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth must be >= 0");
-    if (camera->bounce_depth > 0xFFFFFF) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth too large");
+    RT_TRY(check_spp(camera->samples_per_pixel));
+    RT_TRY(check_depth(camera->bounce_depth));
     const int rows = 2 * max_h + 1;
     if (row_stride <= 0 || row_first < 0 || n_rows < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bad row shard");
     if (n_rows > 0 && (int64_t) row_first + (int64_t) (n_rows - 1) * row_stride >= rows) return fail(RT_ERR_INVALID_ARGUMENT, "row shard exceeds the image");
     return RT_OK;
+}
+// A frame shard's checks: rt_render_device(_ex) and the frame extensions (`no_accum`: their texts for a missing buffer differ).
+static int check_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t row_first, int32_t row_stride, int32_t n_rows,
+                       const void *accum, const char *no_accum, const rt_render_options *options) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    RT_TRY(check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows));
+    if (n_rows > 0 && !accum) return fail(RT_ERR_INVALID_ARGUMENT, no_accum);
+    return check_options(options);
 }
 
 } // extern "C"
@@ -693,19 +736,12 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     return RT_OK;
 }
 
-// Enqueues one shard's render on `stream`: the argument checks and the frame's own RenderParams fields, then enqueue().
+// Enqueues one shard's render on `stream` (arguments checked by the caller, check_frame; n_rows may be 0: an empty shard of a fresh
+// render still goes to the device, which the later entry points' no-op does not): the frame's own RenderParams fields, then enqueue().
 static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
                          int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
                          const rt_render_options *options, bool want_stats, Pending &pd, const RayLog *log = nullptr, int32_t first_sample = 0,
                          const void *d_targets = nullptr) { // d_targets: an extension by map (first_sample is then RTD_EXTEND_MIN_DONE)
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    int rc = check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows);
-    if (rc != RT_OK) return rc;
-    if (n_rows > 0 && !d_accum) return fail(RT_ERR_INVALID_ARGUMENT, "d_accum is NULL");
-    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
-    const Settings set = resolve_settings(options);
-    if (const char *m = check_settings(set)) return fail(RT_ERR_INVALID_ARGUMENT, m);
-
     RenderParams p{};
     p.max_w = max_w; p.max_h = max_h;
     p.spp = camera->samples_per_pixel;
@@ -723,7 +759,7 @@ static int launch_render(const rt_scene *scene, const rt_camera *camera, int32_t
     job.first_sample = first_sample;
     job.map = d_targets != nullptr;
     p.ext_targets = (const int32_t *) d_targets;
-    return enqueue(scene, device, job, set, flags, stream, p, camera_params(camera, max_w, max_h), want_stats, pd);
+    return enqueue(scene, device, job, resolve_settings(options), flags, stream, p, camera_params(camera, max_w, max_h), want_stats, pd);
 }
 
 // Waits for the launch's stream and reads its counters (the device of the launch must be current).
@@ -767,6 +803,86 @@ static int collect_stats(Pending &pd, rt_stats *stats) {
     return RT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// the two shapes of a launching entry point: the device variant (the caller's device buffers, on its stream) and the host variant (host
+// buffers staged through one device allocation, on the null stream).  Each is its argument checks, its no-op condition and ONE call of
+// run_device or run_host around the same launch_* function.
+// ------------------------------------------------------------------------------------------------------------
+static int nothing_to_do(rt_stats *stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    return RT_OK;
+}
+
+// The device variants' tail.  `launch(want_stats, pd)` is the entry point's launch_* call over its (checked) arguments.
+template <class Launch> static int run_device(int32_t device, rt_stats *stats, bool nothing, Launch &&launch) {
+    if (nothing) return nothing_to_do(stats);
+    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
+    RT_TRY(guard.enter(device));
+    Pending pd;
+    const int rc = launch(stats != nullptr, pd);
+    if (rc != RT_OK || !stats) return rc;
+    return collect_stats(pd, stats);
+}
+
+namespace { // (host-side helpers with member functions: kept out of the library's dynamic symbols)
+
+// One buffer of a host variant: where it is on the host (null: an optional buffer the caller left out, which takes no space), its
+// size and which way it is copied.
+enum { SEG_IN = 1, SEG_OUT = 2, SEG_INOUT = SEG_IN | SEG_OUT };
+struct Segment { const void *host; size_t bytes; int use; };
+// A host variant's device memory: its segments, in list order, at 16-byte-aligned offsets of ONE allocation that every exit path frees.
+struct Staging {
+    enum { MAX_SEGMENTS = 5 };
+    Segment seg[MAX_SEGMENTS];
+    void *dev[MAX_SEGMENTS] = {}; // segment i on the device; null for an absent one
+    int n = 0;
+    unsigned char *buf = nullptr;
+    ~Staging() { if (buf) (void) hipFree(buf); }
+    int in(std::initializer_list<Segment> segments) { // the allocation (none for zero bytes), then the inputs, in list order
+        size_t off[MAX_SEGMENTS], total = 0;
+        for (const Segment &s : segments) {
+            seg[n] = s; off[n++] = total;
+            if (s.host) total += (s.bytes + 15u) & ~(size_t) 15u;
+        }
+        if (total) HIP_TRY(hipMalloc((void **) &buf, total));
+        for (int i = 0; i < n; ++i) {
+            if (!buf || !seg[i].host) continue;
+            dev[i] = buf + off[i];
+            if ((seg[i].use & SEG_IN) && seg[i].bytes) HIP_TRY(hipMemcpy(dev[i], seg[i].host, seg[i].bytes, hipMemcpyHostToDevice));
+        }
+        return RT_OK;
+    }
+    int out() { // the outputs, in list order
+        for (int i = 0; i < n; ++i)
+            if (dev[i] && (seg[i].use & SEG_OUT) && seg[i].bytes) HIP_TRY(hipMemcpy(const_cast<void *>(seg[i].host), dev[i], seg[i].bytes, hipMemcpyDeviceToHost));
+        return RT_OK;
+    }
+};
+
+} // namespace
+
+// The host variants' body.  `launch(dev, want_stats, pd)` is the device variant's launch_* call over dev[i], segment i on the device,
+// with a null stream and null options.  The statistics are ALWAYS asked for, whether or not the caller wants them: what only the
+// device can refuse -- a buffer that is not what the arguments say, a list entry outside the frame -- is reported through
+// collect_stats, and after such a refusal nothing is copied back.
+template <class Launch>
+static int run_host(int32_t device, rt_stats *stats, bool nothing, std::initializer_list<Segment> segments, Launch &&launch) {
+    if (nothing) return nothing_to_do(stats);
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    const auto t0 = std::chrono::steady_clock::now();
+    Staging st;
+    RT_TRY(st.in(segments));
+    rt_stats local;
+    RT_TRY(run_device(device, &local, false, [&](bool want_stats, Pending &pd) { return launch(st.dev, want_stats, pd); }));
+    RT_TRY(st.out());
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
 #ifdef RTD_STAGE_CLOCKS
 // Diagnostic builds only (not in include/rtfs_amd.h, not part of the ABI): the instruction census' execution counts of the current
 // device, g_census (rt_device.h), summed over pass B's timed launches since the last reset.
@@ -786,13 +902,13 @@ extern "C" {
 int rt_render_device_ex(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
                         int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
                         const rt_render_options *options, rt_stats *stats) {
-    DeviceGuard guard; // entered again inside launch_render (a no-op then); kept here so that collect_stats runs on the device too
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    Pending pd;
-    rc = launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d_accum, d_rgb, stream, options, stats != nullptr, pd);
-    if (rc != RT_OK || !stats) return rc;
-    return collect_stats(pd, stats);
+    // The oldest entry points -- this one, rt_render_device and rt_render -- differ from all later ones in two ways that are kept as
+    // they are and not fixed here: they test their arguments (rt_render: the scene and the settings) only after entering the device,
+    // so a missing device or a bad device index is what they report first; and an empty shard (n_rows == 0) still goes to the device.
+    return run_device(device, stats, false, [&](bool want_stats, Pending &pd) {
+        RT_TRY(check_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, d_accum, "d_accum is NULL", options));
+        return launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d_accum, d_rgb, stream, options, want_stats, pd);
+    });
 }
 
 int rt_render_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
@@ -970,37 +1086,14 @@ int rt_scene_tune_rays(rt_scene *scene, const double *rays, size_t n_rays, rt_tu
 
 int rt_render(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
               int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, int32_t *accum_host, uint8_t *rgb_host, rt_stats *stats) {
-    int rc = check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows);
-    if (rc != RT_OK) return rc;
+    RT_TRY(check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows));
     if (n_rows > 0 && !accum_host) return fail(RT_ERR_INVALID_ARGUMENT, "accum_host is NULL");
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
     const size_t npx = (size_t) n_rows * (size_t) (2 * max_w + 1);
-    int32_t *d_accum = nullptr;
-    uint8_t *d_rgb = nullptr;
-    if (npx > 0) {
-        HIP_TRY(hipMalloc((void **) &d_accum, npx * 16u));
-        if (rgb_host) {
-            hipError_t e = hipMalloc((void **) &d_rgb, npx * 3u);
-            if (e != hipSuccess) { (void) hipFree(d_accum); return fail(RT_ERR_HIP, std::string("hipMalloc rgb: ") + hipGetErrorString(e)); }
-        }
-    }
-    rt_stats local;
-    rc = rt_render_device(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d_accum, d_rgb, nullptr, &local);
-    if (rc == RT_OK && npx > 0) {
-        hipError_t e = hipMemcpy(accum_host, d_accum, npx * 16u, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rgb_host) e = hipMemcpy(rgb_host, d_rgb, npx * 3u, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void) hipFree(d_accum);
-    (void) hipFree(d_rgb);
-    if (rc == RT_OK && stats) {
-        *stats = local;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return rc;
+    return run_host(device, stats, false, {{accum_host, npx * 16u, SEG_OUT}, {rgb_host, npx * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
+        if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL"); // (tested here, on the device: see rt_render_device_ex)
+        RT_TRY(check_options(nullptr));
+        return launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d[0], d[1], nullptr, nullptr, want_stats, pd);
+    });
 }
 
 } // extern "C"
@@ -1026,12 +1119,9 @@ static int check_rays(const rt_scene *scene, size_t n, const void *rays, const v
     if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     if (n > 0 && !rays) return fail(RT_ERR_INVALID_ARGUMENT, "rays is NULL");
     if (n > 0 && !out) return fail(RT_ERR_INVALID_ARGUMENT, "output is NULL");
-    if (n > (size_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "more than INT32_MAX rays");
-    if (bounce_depth < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth must be >= 0");
-    if (bounce_depth > 0xFFFFFF) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth too large");
-    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
-    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
-    return RT_OK;
+    RT_TRY(check_count(n, "rays"));
+    RT_TRY(check_depth(bounce_depth));
+    return check_options(options);
 }
 
 // Enqueues one ray-list launch on `stream` (n > 0, arguments checked by check_rays): the list's own RenderParams fields, then
@@ -1057,56 +1147,20 @@ static int launch_rays(const rt_scene *scene, int32_t device, const RayJob &job,
 
 static int run_rays_device(const rt_scene *scene, int32_t device, const RayJob &job, uint32_t flags, void *stream,
                            const rt_render_options *options, rt_stats *stats) {
-    if (job.n == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard; // (launch_rays enters it again: a no-op then) so that collect_stats runs on the device too
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    Pending pd;
-    rc = launch_rays(scene, device, job, flags, stream, options, stats != nullptr, pd);
-    if (rc != RT_OK || !stats) return rc;
-    return collect_stats(pd, stats);
+    return run_device(device, stats, job.n == 0, [&](bool want_stats, Pending &pd) { return launch_rays(scene, device, job, flags, stream, options, want_stats, pd); });
 }
 
-// The host variants: one device allocation for inputs and outputs, the device variant on the null stream, the outputs copied back.
-static int run_rays_host(const rt_scene *scene, int32_t device, RayJob job, uint32_t flags, rt_stats *stats) {
-    if (job.n == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    int rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
+// The host variants.  A job has the buffers of its own mode only (hit_job, trace_job); the colours come before the generator states
+// because that is the order the two have always been copied back in.
+static int run_rays_host(const rt_scene *scene, int32_t device, const RayJob &job, uint32_t flags, rt_stats *stats) {
     const size_t n = job.n;
-    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
-    const size_t bRays = up16(n * 48u), bRng = job.rng ? up16(n * 16u) : 0u, bCol = job.hit ? 0u : up16(n * 3u),
-                 bHit = job.hit ? up16(n * 4u) : 0u, bStrike = (job.hit && job.strike) ? up16(n * 24u) : 0u;
-    unsigned char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **) &buf, bRays + bRng + bCol + bHit + bStrike));
-    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
-    const RayJob host = job;
-    job.rays = buf;
-    job.rng = bRng ? buf + bRays : nullptr;
-    job.colour = bCol ? buf + bRays + bRng : nullptr;
-    job.hit_index = bHit ? buf + bRays + bRng + bCol : nullptr;
-    job.strike = bStrike ? buf + bRays + bRng + bCol + bHit : nullptr;
-    HIP_TRY(hipMemcpy(buf, host.rays, n * 48u, hipMemcpyHostToDevice));
-    if (job.rng) HIP_TRY(hipMemcpy(job.rng, host.rng, n * 16u, hipMemcpyHostToDevice));
-    rt_stats local;
-    rc = run_rays_device(scene, device, job, flags, nullptr, nullptr, &local);
-    if (rc != RT_OK) return rc;
-    if (job.colour) HIP_TRY(hipMemcpy(host.colour, job.colour, n * 3u, hipMemcpyDeviceToHost));
-    if (job.rng) HIP_TRY(hipMemcpy(host.rng, job.rng, n * 16u, hipMemcpyDeviceToHost));
-    if (job.hit_index) HIP_TRY(hipMemcpy(host.hit_index, job.hit_index, n * 4u, hipMemcpyDeviceToHost));
-    if (job.strike) HIP_TRY(hipMemcpy(host.strike, job.strike, n * 24u, hipMemcpyDeviceToHost));
-    if (stats) {
-        *stats = local;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return RT_OK;
+    return run_host(device, stats, n == 0,
+                    {{job.rays, n * 48u, SEG_IN}, {job.colour, n * 3u, SEG_OUT}, {job.rng, n * 16u, SEG_INOUT}, {job.hit_index, n * 4u, SEG_OUT}, {job.strike, n * 24u, SEG_OUT}},
+                    [&](void *const *d, bool want_stats, Pending &pd) {
+                        RayJob dev = job;
+                        dev.rays = d[0]; dev.colour = d[1]; dev.rng = d[2]; dev.hit_index = d[3]; dev.strike = d[4];
+                        return launch_rays(scene, device, dev, flags, nullptr, nullptr, want_stats, pd);
+                    });
 }
 
 static RayJob hit_job(size_t n, const void *rays, void *hit_index, void *strike) {
@@ -1125,30 +1179,26 @@ extern "C" {
 
 int rt_hit_objects(const rt_scene *scene, int32_t device, size_t n, const double *rays, uint32_t flags, int32_t *hit_index, double *strike,
                    rt_stats *stats) {
-    const int rc = check_rays(scene, n, rays, hit_index, 0, nullptr);
-    if (rc != RT_OK) return rc;
+    RT_TRY(check_rays(scene, n, rays, hit_index, 0, nullptr));
     return run_rays_host(scene, device, hit_job(n, rays, hit_index, strike), flags, stats);
 }
 
 int rt_hit_objects_device(const rt_scene *scene, int32_t device, size_t n, const void *d_rays, uint32_t flags, void *d_hit_index, void *d_strike,
                           void *stream, const rt_render_options *options, rt_stats *stats) {
-    const int rc = check_rays(scene, n, d_rays, d_hit_index, 0, options);
-    if (rc != RT_OK) return rc;
+    RT_TRY(check_rays(scene, n, d_rays, d_hit_index, 0, options));
     return run_rays_device(scene, device, hit_job(n, d_rays, d_hit_index, d_strike), flags, stream, options, stats);
 }
 
 int rt_trace_rays(const rt_scene *scene, int32_t device, size_t n, const double *rays, uint32_t *rng, uint64_t seed, uint64_t stream_base,
                   uint32_t sample, int32_t bounce_depth, uint32_t flags, uint8_t *colour, rt_stats *stats) {
-    const int rc = check_rays(scene, n, rays, colour, bounce_depth, nullptr);
-    if (rc != RT_OK) return rc;
+    RT_TRY(check_rays(scene, n, rays, colour, bounce_depth, nullptr));
     return run_rays_host(scene, device, trace_job(n, rays, rng, seed, stream_base, sample, bounce_depth, colour), flags, stats);
 }
 
 int rt_trace_rays_device(const rt_scene *scene, int32_t device, size_t n, const void *d_rays, void *d_rng, uint64_t seed, uint64_t stream_base,
                          uint32_t sample, int32_t bounce_depth, uint32_t flags, void *d_colour, void *stream, const rt_render_options *options,
                          rt_stats *stats) {
-    const int rc = check_rays(scene, n, d_rays, d_colour, bounce_depth, options);
-    if (rc != RT_OK) return rc;
+    RT_TRY(check_rays(scene, n, d_rays, d_colour, bounce_depth, options));
     return run_rays_device(scene, device, trace_job(n, d_rays, d_rng, seed, stream_base, sample, bounce_depth, d_colour), flags, stream, options, stats);
 }
 
@@ -1163,14 +1213,10 @@ static int check_footprints(const rt_scene *scene, size_t n, const void *footpri
     if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
     if (n > 0 && !footprints) return fail(RT_ERR_INVALID_ARGUMENT, "footprints is NULL");
     if (n > 0 && !accum) return fail(RT_ERR_INVALID_ARGUMENT, "accum is NULL");
-    if (n > (size_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "more than INT32_MAX footprints");
-    if (spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel must be >= 1");
-    if (spp > 8000000) return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel too large for int32 sums (255*spp)");
-    if (bounce_depth < 0) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth must be >= 0");
-    if (bounce_depth > 0xFFFFFF) return fail(RT_ERR_INVALID_ARGUMENT, "bounce_depth too large");
-    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
-    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
-    return RT_OK;
+    RT_TRY(check_count(n, "footprints"));
+    RT_TRY(check_spp(spp));
+    RT_TRY(check_depth(bounce_depth));
+    return check_options(options);
 }
 
 // Enqueues one footprint launch on `stream` (n > 0, arguments checked): to the kernel the list is a frame of one row and n columns
@@ -1203,52 +1249,18 @@ extern "C" {
 int rt_render_footprints_device(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints, int32_t samples_per_pixel,
                                 int32_t bounce_depth, uint64_t seed, uint64_t stream_base, uint32_t flags, void *d_accum, void *d_rgb, void *stream,
                                 const rt_render_options *options, rt_stats *stats) {
-    int rc = check_footprints(scene, n, d_footprints, d_accum, samples_per_pixel, bounce_depth, options);
-    if (rc != RT_OK) return rc;
-    if (n == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    Pending pd;
-    rc = launch_footprints(scene, device, n, d_footprints, samples_per_pixel, bounce_depth, seed, stream_base, flags, d_accum, d_rgb, stream, options,
-                           stats != nullptr, pd);
-    if (rc != RT_OK || !stats) return rc;
-    return collect_stats(pd, stats);
+    RT_TRY(check_footprints(scene, n, d_footprints, d_accum, samples_per_pixel, bounce_depth, options));
+    return run_device(device, stats, n == 0, [&](bool want_stats, Pending &pd) {
+        return launch_footprints(scene, device, n, d_footprints, samples_per_pixel, bounce_depth, seed, stream_base, flags, d_accum, d_rgb, stream, options, want_stats, pd);
+    });
 }
 
-// The host variant: one device allocation for the footprints and the outputs, the device variant on the null stream, the outputs copied back.
 int rt_render_footprints(const rt_scene *scene, int32_t device, size_t n, const double *footprints, int32_t samples_per_pixel, int32_t bounce_depth,
                          uint64_t seed, uint64_t stream_base, uint32_t flags, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
-    int rc = check_footprints(scene, n, footprints, accum, samples_per_pixel, bounce_depth, nullptr);
-    if (rc != RT_OK) return rc;
-    if (n == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
-    const size_t bFp = up16(n * 96u), bAcc = up16(n * 16u), bRgb = rgb ? up16(n * 3u) : 0u;
-    unsigned char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **) &buf, bFp + bAcc + bRgb));
-    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
-    HIP_TRY(hipMemcpy(buf, footprints, n * 96u, hipMemcpyHostToDevice));
-    rt_stats local;
-    rc = rt_render_footprints_device(scene, device, n, buf, samples_per_pixel, bounce_depth, seed, stream_base, flags, buf + bFp,
-                                     bRgb ? buf + bFp + bAcc : nullptr, nullptr, nullptr, &local);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpy(accum, buf + bFp, n * 16u, hipMemcpyDeviceToHost));
-    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bFp + bAcc, n * 3u, hipMemcpyDeviceToHost));
-    if (stats) {
-        *stats = local;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return RT_OK;
+    RT_TRY(check_footprints(scene, n, footprints, accum, samples_per_pixel, bounce_depth, nullptr));
+    return run_host(device, stats, n == 0, {{footprints, n * 96u, SEG_IN}, {accum, n * 16u, SEG_OUT}, {rgb, n * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_footprints(scene, device, n, d[0], samples_per_pixel, bounce_depth, seed, stream_base, flags, d[1], d[2], nullptr, nullptr, want_stats, pd);
+    });
 }
 
 } // extern "C"
@@ -1265,15 +1277,9 @@ static int check_extend(int32_t target, int32_t samples_done) {
 // Every argument check of the two frame entry points, made before anything touches a device.
 static int check_extend_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t row_first, int32_t row_stride,
                               int32_t n_rows, const void *accum, const rt_render_options *options, int32_t samples_done) {
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    int rc = check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows);
-    if (rc != RT_OK) return rc;
-    if (n_rows > 0 && !accum) return fail(RT_ERR_INVALID_ARGUMENT, "accum is NULL");
-    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
-    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
-    if ((rc = check_extend(camera->samples_per_pixel, samples_done)) != RT_OK) return rc;
-    if ((uint64_t) n_rows * (uint64_t) (2 * max_w + 1) >= (1ull << 32)) return fail(RT_ERR_INVALID_ARGUMENT, "an extension takes shards of fewer than 2^32 pixels");
-    return RT_OK;
+    RT_TRY(check_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, accum, "accum is NULL", options)); // (the options BEFORE the counts)
+    RT_TRY(check_extend(camera->samples_per_pixel, samples_done));
+    return check_extend_shard(max_w, n_rows);
 }
 
 extern "C" {
@@ -1281,104 +1287,42 @@ extern "C" {
 int rt_render_extend_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
                             int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, int32_t samples_done, void *d_accum, void *d_rgb,
                             void *stream, const rt_render_options *options, rt_stats *stats) {
-    int rc = check_extend_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, d_accum, options, samples_done);
-    if (rc != RT_OK) return rc;
-    if (n_rows == 0 || camera->samples_per_pixel == samples_done) { // nothing to add
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    Pending pd;
-    rc = launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d_accum, d_rgb, stream, options, stats != nullptr, pd,
-                       nullptr, samples_done);
-    if (rc != RT_OK || !stats) return rc;
-    return collect_stats(pd, stats);
+    RT_TRY(check_extend_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, d_accum, options, samples_done));
+    const bool nothing = n_rows == 0 || camera->samples_per_pixel == samples_done; // nothing to add
+    return run_device(device, stats, nothing, [&](bool want_stats, Pending &pd) {
+        return launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d_accum, d_rgb, stream, options, want_stats, pd, nullptr, samples_done);
+    });
 }
 
-// The host variant: the buffer copied in, the device variant on the null stream, the outputs copied back -- unless it failed.
 int rt_render_extend(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
                      int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, int32_t samples_done, int32_t *accum, uint8_t *rgb,
                      rt_stats *stats) {
-    int rc = check_extend_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, accum, nullptr, samples_done);
-    if (rc != RT_OK) return rc;
-    if (n_rows == 0 || camera->samples_per_pixel == samples_done) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
-    const size_t npx = (size_t) n_rows * (size_t) (2 * max_w + 1), bAcc = up16(npx * 16u), bRgb = rgb ? up16(npx * 3u) : 0u;
-    unsigned char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **) &buf, bAcc + bRgb));
-    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
-    HIP_TRY(hipMemcpy(buf, accum, npx * 16u, hipMemcpyHostToDevice));
-    rt_stats local; // (always asked for: the malformed-buffer error is reported through it)
-    rc = rt_render_extend_device(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, samples_done, buf,
-                                 bRgb ? buf + bAcc : nullptr, nullptr, nullptr, &local);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpy(accum, buf, npx * 16u, hipMemcpyDeviceToHost));
-    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bAcc, npx * 3u, hipMemcpyDeviceToHost));
-    if (stats) {
-        *stats = local;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return RT_OK;
+    RT_TRY(check_extend_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, accum, nullptr, samples_done));
+    const bool nothing = n_rows == 0 || camera->samples_per_pixel == samples_done;
+    const size_t npx = (size_t) n_rows * (size_t) (2 * max_w + 1);
+    return run_host(device, stats, nothing, {{accum, npx * 16u, SEG_INOUT}, {rgb, npx * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d[0], d[1], nullptr, nullptr, want_stats, pd, nullptr, samples_done);
+    });
 }
 
 int rt_render_footprints_extend_device(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints, int32_t samples_per_pixel,
                                        int32_t bounce_depth, uint64_t seed, uint64_t stream_base, uint32_t flags, int32_t samples_done, void *d_accum,
                                        void *d_rgb, void *stream, const rt_render_options *options, rt_stats *stats) {
-    int rc = check_footprints(scene, n, d_footprints, d_accum, samples_per_pixel, bounce_depth, options);
-    if (rc != RT_OK || (rc = check_extend(samples_per_pixel, samples_done)) != RT_OK) return rc;
-    if (n == 0 || samples_per_pixel == samples_done) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    Pending pd;
-    rc = launch_footprints(scene, device, n, d_footprints, samples_per_pixel, bounce_depth, seed, stream_base, flags, d_accum, d_rgb, stream, options,
-                           stats != nullptr, pd, samples_done);
-    if (rc != RT_OK || !stats) return rc;
-    return collect_stats(pd, stats);
+    RT_TRY(check_footprints(scene, n, d_footprints, d_accum, samples_per_pixel, bounce_depth, options));
+    RT_TRY(check_extend(samples_per_pixel, samples_done));
+    return run_device(device, stats, n == 0 || samples_per_pixel == samples_done, [&](bool want_stats, Pending &pd) {
+        return launch_footprints(scene, device, n, d_footprints, samples_per_pixel, bounce_depth, seed, stream_base, flags, d_accum, d_rgb, stream, options, want_stats, pd, samples_done);
+    });
 }
 
 int rt_render_footprints_extend(const rt_scene *scene, int32_t device, size_t n, const double *footprints, int32_t samples_per_pixel, int32_t bounce_depth,
                                 uint64_t seed, uint64_t stream_base, uint32_t flags, int32_t samples_done, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
-    int rc = check_footprints(scene, n, footprints, accum, samples_per_pixel, bounce_depth, nullptr);
-    if (rc != RT_OK || (rc = check_extend(samples_per_pixel, samples_done)) != RT_OK) return rc;
-    if (n == 0 || samples_per_pixel == samples_done) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
-    const size_t bFp = up16(n * 96u), bAcc = up16(n * 16u), bRgb = rgb ? up16(n * 3u) : 0u;
-    unsigned char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **) &buf, bFp + bAcc + bRgb));
-    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
-    HIP_TRY(hipMemcpy(buf, footprints, n * 96u, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(buf + bFp, accum, n * 16u, hipMemcpyHostToDevice));
-    rt_stats local;
-    rc = rt_render_footprints_extend_device(scene, device, n, buf, samples_per_pixel, bounce_depth, seed, stream_base, flags, samples_done, buf + bFp,
-                                            bRgb ? buf + bFp + bAcc : nullptr, nullptr, nullptr, &local);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpy(accum, buf + bFp, n * 16u, hipMemcpyDeviceToHost));
-    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bFp + bAcc, n * 3u, hipMemcpyDeviceToHost));
-    if (stats) {
-        *stats = local;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return RT_OK;
+    RT_TRY(check_footprints(scene, n, footprints, accum, samples_per_pixel, bounce_depth, nullptr));
+    RT_TRY(check_extend(samples_per_pixel, samples_done));
+    return run_host(device, stats, n == 0 || samples_per_pixel == samples_done,
+                    {{footprints, n * 96u, SEG_IN}, {accum, n * 16u, SEG_INOUT}, {rgb, n * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_footprints(scene, device, n, d[0], samples_per_pixel, bounce_depth, seed, stream_base, flags, d[1], d[2], nullptr, nullptr, want_stats, pd, samples_done);
+    });
 }
 
 } // extern "C"
@@ -1397,15 +1341,9 @@ static int check_extend_map(int32_t cap, size_t pixels, const void *targets) {
 // Every argument check of the two frame entry points, made before anything touches a device.
 static int check_extend_map_frame(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, int32_t row_first, int32_t row_stride,
                                   int32_t n_rows, const void *targets, const void *accum, const rt_render_options *options) {
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    int rc = check_geometry(camera, max_w, max_h, row_first, row_stride, n_rows);
-    if (rc != RT_OK) return rc;
-    if (n_rows > 0 && !accum) return fail(RT_ERR_INVALID_ARGUMENT, "accum is NULL");
-    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
-    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
-    if ((rc = check_extend_map(camera->samples_per_pixel, (size_t) n_rows, targets)) != RT_OK) return rc;
-    if ((uint64_t) n_rows * (uint64_t) (2 * max_w + 1) >= (1ull << 32)) return fail(RT_ERR_INVALID_ARGUMENT, "an extension takes shards of fewer than 2^32 pixels");
-    return RT_OK;
+    RT_TRY(check_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, accum, "accum is NULL", options)); // (the options BEFORE the map)
+    RT_TRY(check_extend_map(camera->samples_per_pixel, (size_t) n_rows, targets));
+    return check_extend_shard(max_w, n_rows);
 }
 
 extern "C" {
@@ -1413,106 +1351,40 @@ extern "C" {
 int rt_render_extend_map_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
                                 int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, const void *d_targets, void *d_accum, void *d_rgb,
                                 void *stream, const rt_render_options *options, rt_stats *stats) {
-    int rc = check_extend_map_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, d_targets, d_accum, options);
-    if (rc != RT_OK) return rc;
-    if (n_rows == 0) { // an empty shard
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    Pending pd;
-    rc = launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d_accum, d_rgb, stream, options, stats != nullptr, pd,
-                       nullptr, RTD_EXTEND_MIN_DONE, d_targets);
-    if (rc != RT_OK || !stats) return rc;
-    return collect_stats(pd, stats);
+    RT_TRY(check_extend_map_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, d_targets, d_accum, options));
+    return run_device(device, stats, n_rows == 0, [&](bool want_stats, Pending &pd) { // (an empty shard; a map whose every target is reached still goes to the device)
+        return launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d_accum, d_rgb, stream, options, want_stats, pd, nullptr, RTD_EXTEND_MIN_DONE, d_targets);
+    });
 }
 
-// The host variant: the buffer and the map copied in, the device variant on the null stream, the outputs copied back -- unless it failed.
 int rt_render_extend_map(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
                          int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, const int32_t *targets, int32_t *accum, uint8_t *rgb,
                          rt_stats *stats) {
-    int rc = check_extend_map_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, targets, accum, nullptr);
-    if (rc != RT_OK) return rc;
-    if (n_rows == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
-    const size_t npx = (size_t) n_rows * (size_t) (2 * max_w + 1), bAcc = up16(npx * 16u), bMap = up16(npx * 4u), bRgb = rgb ? up16(npx * 3u) : 0u;
-    unsigned char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **) &buf, bAcc + bMap + bRgb));
-    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
-    HIP_TRY(hipMemcpy(buf, accum, npx * 16u, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(buf + bAcc, targets, npx * 4u, hipMemcpyHostToDevice));
-    rt_stats local; // (always asked for: the malformed-buffer error is reported through it)
-    rc = rt_render_extend_map_device(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, buf + bAcc, buf,
-                                     bRgb ? buf + bAcc + bMap : nullptr, nullptr, nullptr, &local);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpy(accum, buf, npx * 16u, hipMemcpyDeviceToHost));
-    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bAcc + bMap, npx * 3u, hipMemcpyDeviceToHost));
-    if (stats) {
-        *stats = local;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return RT_OK;
+    RT_TRY(check_extend_map_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, targets, accum, nullptr));
+    const size_t npx = (size_t) n_rows * (size_t) (2 * max_w + 1);
+    return run_host(device, stats, n_rows == 0, {{accum, npx * 16u, SEG_INOUT}, {targets, npx * 4u, SEG_IN}, {rgb, npx * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_render(scene, camera, max_w, max_h, seed, device, row_first, row_stride, n_rows, flags, d[0], d[2], nullptr, nullptr, want_stats, pd, nullptr, RTD_EXTEND_MIN_DONE, d[1]);
+    });
 }
 
 int rt_render_footprints_extend_map_device(const rt_scene *scene, int32_t device, size_t n, const void *d_footprints, int32_t samples_per_pixel,
                                            int32_t bounce_depth, uint64_t seed, uint64_t stream_base, uint32_t flags, const void *d_targets, void *d_accum,
                                            void *d_rgb, void *stream, const rt_render_options *options, rt_stats *stats) {
-    int rc = check_footprints(scene, n, d_footprints, d_accum, samples_per_pixel, bounce_depth, options);
-    if (rc != RT_OK || (rc = check_extend_map(samples_per_pixel, n, d_targets)) != RT_OK) return rc;
-    if (n == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    Pending pd;
-    rc = launch_footprints(scene, device, n, d_footprints, samples_per_pixel, bounce_depth, seed, stream_base, flags, d_accum, d_rgb, stream, options,
-                           stats != nullptr, pd, RTD_EXTEND_MIN_DONE, d_targets);
-    if (rc != RT_OK || !stats) return rc;
-    return collect_stats(pd, stats);
+    RT_TRY(check_footprints(scene, n, d_footprints, d_accum, samples_per_pixel, bounce_depth, options));
+    RT_TRY(check_extend_map(samples_per_pixel, n, d_targets));
+    return run_device(device, stats, n == 0, [&](bool want_stats, Pending &pd) {
+        return launch_footprints(scene, device, n, d_footprints, samples_per_pixel, bounce_depth, seed, stream_base, flags, d_accum, d_rgb, stream, options, want_stats, pd, RTD_EXTEND_MIN_DONE, d_targets);
+    });
 }
 
 int rt_render_footprints_extend_map(const rt_scene *scene, int32_t device, size_t n, const double *footprints, int32_t samples_per_pixel, int32_t bounce_depth,
                                     uint64_t seed, uint64_t stream_base, uint32_t flags, const int32_t *targets, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
-    int rc = check_footprints(scene, n, footprints, accum, samples_per_pixel, bounce_depth, nullptr);
-    if (rc != RT_OK || (rc = check_extend_map(samples_per_pixel, n, targets)) != RT_OK) return rc;
-    if (n == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
-    const size_t bFp = up16(n * 96u), bAcc = up16(n * 16u), bMap = up16(n * 4u), bRgb = rgb ? up16(n * 3u) : 0u;
-    unsigned char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **) &buf, bFp + bAcc + bMap + bRgb));
-    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
-    HIP_TRY(hipMemcpy(buf, footprints, n * 96u, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(buf + bFp, accum, n * 16u, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(buf + bFp + bAcc, targets, n * 4u, hipMemcpyHostToDevice));
-    rt_stats local;
-    rc = rt_render_footprints_extend_map_device(scene, device, n, buf, samples_per_pixel, bounce_depth, seed, stream_base, flags, buf + bFp + bAcc, buf + bFp,
-                                                bRgb ? buf + bFp + bAcc + bMap : nullptr, nullptr, nullptr, &local);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpy(accum, buf + bFp, n * 16u, hipMemcpyDeviceToHost));
-    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bFp + bAcc + bMap, n * 3u, hipMemcpyDeviceToHost));
-    if (stats) {
-        *stats = local;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return RT_OK;
+    RT_TRY(check_footprints(scene, n, footprints, accum, samples_per_pixel, bounce_depth, nullptr));
+    RT_TRY(check_extend_map(samples_per_pixel, n, targets));
+    return run_host(device, stats, n == 0, {{footprints, n * 96u, SEG_IN}, {accum, n * 16u, SEG_INOUT}, {targets, n * 4u, SEG_IN}, {rgb, n * 3u, SEG_OUT}},
+                    [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_footprints(scene, device, n, d[0], samples_per_pixel, bounce_depth, seed, stream_base, flags, d[1], d[3], nullptr, nullptr, want_stats, pd, RTD_EXTEND_MIN_DONE, d[2]);
+    });
 }
 
 } // extern "C"
@@ -1525,16 +1397,12 @@ int rt_render_footprints_extend_map(const rt_scene *scene, int32_t device, size_
 static int check_pixels(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, size_t n, const void *pixels, const void *accum,
                         const rt_render_options *options) {
     if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    int rc = check_geometry(camera, max_w, max_h, 0, 1, 0);
-    if (rc != RT_OK) return rc;
+    RT_TRY(check_geometry(camera, max_w, max_h, 0, 1, 0));
     if (n > 0 && !pixels) return fail(RT_ERR_INVALID_ARGUMENT, "pixels is NULL");
     if (n > 0 && !accum) return fail(RT_ERR_INVALID_ARGUMENT, "accum is NULL");
-    if (n > (size_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "more than INT32_MAX list entries");
-    if ((uint64_t) (2 * max_w + 1) * (uint64_t) (2 * max_h + 1) > (uint64_t) INT32_MAX)
-        return fail(RT_ERR_INVALID_ARGUMENT, "a pixel list indexes frames of at most INT32_MAX pixels");
-    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
-    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
-    return RT_OK;
+    RT_TRY(check_count(n, "list entries"));
+    RT_TRY(check_list_frame(max_w, max_h));
+    return check_options(options);
 }
 // The host variants' list check (the device variants' is pixel_list_check_kernel): every entry a global pixel index of the frame.
 static int check_pixel_entries(const int32_t *pixels, size_t n, int32_t max_w, int32_t max_h) {
@@ -1572,105 +1440,41 @@ extern "C" {
 int rt_render_pixels_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
                             const void *d_pixels, uint32_t flags, void *d_accum, void *d_rgb, void *stream, const rt_render_options *options,
                             rt_stats *stats) {
-    int rc = check_pixels(scene, camera, max_w, max_h, n, d_pixels, d_accum, options);
-    if (rc != RT_OK) return rc;
-    if (n == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    Pending pd;
-    rc = launch_pixels(scene, camera, max_w, max_h, seed, device, n, d_pixels, flags, d_accum, d_rgb, stream, options, stats != nullptr, pd);
-    if (rc != RT_OK || !stats) return rc;
-    return collect_stats(pd, stats);
+    RT_TRY(check_pixels(scene, camera, max_w, max_h, n, d_pixels, d_accum, options));
+    return run_device(device, stats, n == 0, [&](bool want_stats, Pending &pd) {
+        return launch_pixels(scene, camera, max_w, max_h, seed, device, n, d_pixels, flags, d_accum, d_rgb, stream, options, want_stats, pd);
+    });
 }
 
-// The host variant: the list checked here, one device allocation for the list and the outputs, the device variant on the null stream, the
-// outputs copied back.
+// The host variants check the list here, before anything touches a device (the device variants: pixel_list_check_kernel).
 int rt_render_pixels(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
                      const int32_t *pixels, uint32_t flags, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
-    int rc = check_pixels(scene, camera, max_w, max_h, n, pixels, accum, nullptr);
-    if (rc != RT_OK || (rc = check_pixel_entries(pixels, n, max_w, max_h)) != RT_OK) return rc;
-    if (n == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
-    const size_t bPx = up16(n * 4u), bAcc = up16(n * 16u), bRgb = rgb ? up16(n * 3u) : 0u;
-    unsigned char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **) &buf, bPx + bAcc + bRgb));
-    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
-    HIP_TRY(hipMemcpy(buf, pixels, n * 4u, hipMemcpyHostToDevice));
-    rt_stats local;
-    rc = rt_render_pixels_device(scene, camera, max_w, max_h, seed, device, n, buf, flags, buf + bPx, bRgb ? buf + bPx + bAcc : nullptr, nullptr, nullptr,
-                                 &local);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpy(accum, buf + bPx, n * 16u, hipMemcpyDeviceToHost));
-    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bPx + bAcc, n * 3u, hipMemcpyDeviceToHost));
-    if (stats) {
-        *stats = local;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return RT_OK;
+    RT_TRY(check_pixels(scene, camera, max_w, max_h, n, pixels, accum, nullptr));
+    RT_TRY(check_pixel_entries(pixels, n, max_w, max_h));
+    return run_host(device, stats, n == 0, {{pixels, n * 4u, SEG_IN}, {accum, n * 16u, SEG_OUT}, {rgb, n * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_pixels(scene, camera, max_w, max_h, seed, device, n, d[0], flags, d[1], d[2], nullptr, nullptr, want_stats, pd);
+    });
 }
 
 int rt_render_pixels_extend_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
                                    const void *d_pixels, uint32_t flags, int32_t samples_done, void *d_accum, void *d_rgb, void *stream,
                                    const rt_render_options *options, rt_stats *stats) {
-    int rc = check_pixels(scene, camera, max_w, max_h, n, d_pixels, d_accum, options);
-    if (rc != RT_OK || (rc = check_extend(camera->samples_per_pixel, samples_done)) != RT_OK) return rc;
-    if (n == 0 || camera->samples_per_pixel == samples_done) { // nothing to add
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    Pending pd;
-    rc = launch_pixels(scene, camera, max_w, max_h, seed, device, n, d_pixels, flags, d_accum, d_rgb, stream, options, stats != nullptr, pd, samples_done);
-    if (rc != RT_OK || !stats) return rc;
-    return collect_stats(pd, stats);
+    RT_TRY(check_pixels(scene, camera, max_w, max_h, n, d_pixels, d_accum, options));
+    RT_TRY(check_extend(camera->samples_per_pixel, samples_done));
+    return run_device(device, stats, n == 0 || camera->samples_per_pixel == samples_done, [&](bool want_stats, Pending &pd) { // nothing to add
+        return launch_pixels(scene, camera, max_w, max_h, seed, device, n, d_pixels, flags, d_accum, d_rgb, stream, options, want_stats, pd, samples_done);
+    });
 }
 
-// The host variant: the list checked here, list and buffer copied in, the device variant on the null stream, the outputs copied back --
-// unless it failed.
 int rt_render_pixels_extend(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
                             const int32_t *pixels, uint32_t flags, int32_t samples_done, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
-    int rc = check_pixels(scene, camera, max_w, max_h, n, pixels, accum, nullptr);
-    if (rc != RT_OK || (rc = check_extend(camera->samples_per_pixel, samples_done)) != RT_OK) return rc;
-    if ((rc = check_pixel_entries(pixels, n, max_w, max_h)) != RT_OK) return rc;
-    if (n == 0 || camera->samples_per_pixel == samples_done) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
-    const size_t bPx = up16(n * 4u), bAcc = up16(n * 16u), bRgb = rgb ? up16(n * 3u) : 0u;
-    unsigned char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **) &buf, bPx + bAcc + bRgb));
-    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
-    HIP_TRY(hipMemcpy(buf, pixels, n * 4u, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(buf + bPx, accum, n * 16u, hipMemcpyHostToDevice));
-    rt_stats local; // (always asked for: the malformed-buffer error is reported through it)
-    rc = rt_render_pixels_extend_device(scene, camera, max_w, max_h, seed, device, n, buf, flags, samples_done, buf + bPx,
-                                        bRgb ? buf + bPx + bAcc : nullptr, nullptr, nullptr, &local);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpy(accum, buf + bPx, n * 16u, hipMemcpyDeviceToHost));
-    if (rgb) HIP_TRY(hipMemcpy(rgb, buf + bPx + bAcc, n * 3u, hipMemcpyDeviceToHost));
-    if (stats) {
-        *stats = local;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return RT_OK;
+    RT_TRY(check_pixels(scene, camera, max_w, max_h, n, pixels, accum, nullptr));
+    RT_TRY(check_extend(camera->samples_per_pixel, samples_done));
+    RT_TRY(check_pixel_entries(pixels, n, max_w, max_h));
+    return run_host(device, stats, n == 0 || camera->samples_per_pixel == samples_done,
+                    {{pixels, n * 4u, SEG_IN}, {accum, n * 16u, SEG_INOUT}, {rgb, n * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_pixels(scene, camera, max_w, max_h, seed, device, n, d[0], flags, d[1], d[2], nullptr, nullptr, want_stats, pd, samples_done);
+    });
 }
 
 } // extern "C"
@@ -1684,10 +1488,9 @@ int rt_render_pixels_extend(const rt_scene *scene, const rt_camera *camera, int3
 static int check_camera_hits(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, size_t n, const void *pixels, int32_t sample_first,
                              int32_t n_samples, const void *hit_index, const rt_render_options *options) {
     if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
-    int rc = check_geometry(camera, max_w, max_h, 0, 1, 0);
-    if (rc != RT_OK) return rc;
+    RT_TRY(check_geometry(camera, max_w, max_h, 0, 1, 0));
+    RT_TRY(check_list_frame(max_w, max_h));
     const uint64_t frame = (uint64_t) (2 * max_w + 1) * (uint64_t) (2 * max_h + 1);
-    if (frame > (uint64_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "a pixel list indexes frames of at most INT32_MAX pixels");
     if (sample_first < 0) return fail(RT_ERR_INVALID_ARGUMENT, "sample_first must be >= 0");
     if (n_samples < 1) return fail(RT_ERR_INVALID_ARGUMENT, "n_samples must be >= 1");
     if ((int64_t) sample_first + (int64_t) n_samples > (int64_t) RT_CAMERA_HITS_MAX_SAMPLE) return fail(RT_ERR_INVALID_ARGUMENT, "sample_first + n_samples exceeds 8000000");
@@ -1695,9 +1498,7 @@ static int check_camera_hits(const rt_scene *scene, const rt_camera *camera, int
         return fail(RT_ERR_INVALID_ARGUMENT, "more than INT32_MAX output slots (n * n_samples)");
     if (n > 0 && !hit_index) return fail(RT_ERR_INVALID_ARGUMENT, "hit_index is NULL");
     if (!pixels && (uint64_t) n > frame) return fail(RT_ERR_INVALID_ARGUMENT, "pixels is NULL and n exceeds the frame's pixels");
-    if (options && options->struct_size < sizeof(uint32_t)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_options.struct_size is not set");
-    if (const char *m = check_settings(resolve_settings(options))) return fail(RT_ERR_INVALID_ARGUMENT, m);
-    return RT_OK;
+    return check_options(options);
 }
 
 // Enqueues the one launch on `stream` (n > 0, arguments checked): the frame's camera, geometry and seed, the list (or none), the sample
@@ -1724,66 +1525,38 @@ static int launch_camera_hits(const rt_scene *scene, const rt_camera *camera, in
     return enqueue(scene, device, job, resolve_settings(options), flags, stream, p, camera_params(camera, max_w, max_h), want_stats, pd);
 }
 
+// What the statistics of camera hits count (collect_stats has filled in the rest).
+static void camera_hits_counts(rt_stats *stats, size_t n, int32_t n_samples) {
+    if (!stats) return;
+    stats->pixels = (uint64_t) n;                          // list entries; nothing is shaded, so `reflections` stays 0
+    stats->samples = (uint64_t) n * (uint64_t) n_samples;  // output slots (`rays`, under RT_RENDER_COUNTERS: those whose ray was made)
+}
+
 extern "C" {
 
 int rt_camera_hits_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
                           const void *d_pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, void *d_hit_index, void *d_strike,
                           void *d_rays_out, void *stream, const rt_render_options *options, rt_stats *stats) {
-    int rc = check_camera_hits(scene, camera, max_w, max_h, n, d_pixels, sample_first, n_samples, d_hit_index, options);
-    if (rc != RT_OK) return rc;
-    if (n == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard; // (enqueue enters it again: a no-op then) so that collect_stats runs on the device too
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    Pending pd;
-    rc = launch_camera_hits(scene, camera, max_w, max_h, seed, device, n, d_pixels, sample_first, n_samples, flags, d_hit_index, d_strike, d_rays_out, stream,
-                            options, stats != nullptr, pd);
-    if (rc != RT_OK || !stats) return rc;
-    rc = collect_stats(pd, stats);
-    if (rc != RT_OK) return rc;
-    stats->pixels = (uint64_t) n;                          // list entries; nothing is shaded, so `reflections` stays 0
-    stats->samples = (uint64_t) n * (uint64_t) n_samples;  // output slots (`rays`, under RT_RENDER_COUNTERS: those whose ray was made)
+    RT_TRY(check_camera_hits(scene, camera, max_w, max_h, n, d_pixels, sample_first, n_samples, d_hit_index, options));
+    RT_TRY(run_device(device, stats, n == 0, [&](bool want_stats, Pending &pd) {
+        return launch_camera_hits(scene, camera, max_w, max_h, seed, device, n, d_pixels, sample_first, n_samples, flags, d_hit_index, d_strike, d_rays_out, stream, options, want_stats, pd);
+    }));
+    camera_hits_counts(stats, n, n_samples);
     return RT_OK;
 }
 
-// The host variant: the list checked here, one device allocation for the list and the outputs, the device variant on the null stream, the
-// outputs copied back.
+// The host variant checks a list here, before anything touches a device.
 int rt_camera_hits(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
                    const int32_t *pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, int32_t *hit_index, double *strike, double *rays_out,
                    rt_stats *stats) {
-    int rc = check_camera_hits(scene, camera, max_w, max_h, n, pixels, sample_first, n_samples, hit_index, nullptr);
-    if (rc != RT_OK) return rc;
-    if (pixels && (rc = check_pixel_entries(pixels, n, max_w, max_h)) != RT_OK) return rc;
-    if (n == 0) {
-        if (stats) memset(stats, 0, sizeof(*stats));
-        return RT_OK;
-    }
-    DeviceGuard guard;
-    rc = guard.enter(device);
-    if (rc != RT_OK) return rc;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto up16 = [](size_t b) { return (b + 15u) & ~(size_t) 15u; };
+    RT_TRY(check_camera_hits(scene, camera, max_w, max_h, n, pixels, sample_first, n_samples, hit_index, nullptr));
+    if (pixels) RT_TRY(check_pixel_entries(pixels, n, max_w, max_h));
     const size_t slots = n * (size_t) n_samples;
-    const size_t bPx = pixels ? up16(n * 4u) : 0u, bHit = up16(slots * 4u), bStrike = strike ? up16(slots * 24u) : 0u, bRays = rays_out ? up16(slots * 48u) : 0u;
-    unsigned char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **) &buf, bPx + bHit + bStrike + bRays));
-    struct Free { unsigned char *b; ~Free() { (void) hipFree(b); } } release{buf};
-    if (pixels) HIP_TRY(hipMemcpy(buf, pixels, n * 4u, hipMemcpyHostToDevice));
-    unsigned char *dHit = buf + bPx, *dStrike = bStrike ? dHit + bHit : nullptr, *dRays = bRays ? dHit + bHit + bStrike : nullptr;
-    rt_stats local;
-    rc = rt_camera_hits_device(scene, camera, max_w, max_h, seed, device, n, pixels ? buf : nullptr, sample_first, n_samples, flags, dHit, dStrike, dRays,
-                               nullptr, nullptr, &local);
-    if (rc != RT_OK) return rc;
-    HIP_TRY(hipMemcpy(hit_index, dHit, slots * 4u, hipMemcpyDeviceToHost));
-    if (strike) HIP_TRY(hipMemcpy(strike, dStrike, slots * 24u, hipMemcpyDeviceToHost));
-    if (rays_out) HIP_TRY(hipMemcpy(rays_out, dRays, slots * 48u, hipMemcpyDeviceToHost));
-    if (stats) {
-        *stats = local;
-        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
+    RT_TRY(run_host(device, stats, n == 0, {{pixels, n * 4u, SEG_IN}, {hit_index, slots * 4u, SEG_OUT}, {strike, slots * 24u, SEG_OUT}, {rays_out, slots * 48u, SEG_OUT}},
+                    [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_camera_hits(scene, camera, max_w, max_h, seed, device, n, d[0], sample_first, n_samples, flags, d[1], d[2], d[3], nullptr, nullptr, want_stats, pd);
+    }));
+    camera_hits_counts(stats, n, n_samples);
     return RT_OK;
 }
 
@@ -1915,6 +1688,7 @@ static int render_frame(const rt_scene *scene, const rt_camera *camera, int32_t 
         if (f.n_rows < 0) f.n_rows = 0;
         HIP_TRY(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
         if (f.n_rows > 0) HIP_TRY(hipMalloc((void **) &f.accum, (size_t) f.n_rows * rowBytes));
+        RT_TRY(check_options(options)); // (the one argument not tested above; here, where launch_render used to test it)
         rc = launch_render(scene, camera, max_w, max_h, seed, devices[i], i, n_devices, f.n_rows, flags, f.accum, nullptr, f.stream, options,
                            stats != nullptr, f.pd);
         if (rc != RT_OK) return rc;

@@ -517,8 +517,7 @@ class Scene:
                                               _ref(options), _ref(st)))
             self.last_stats = st.as_dict() if st is not None else None
             return RenderResult(accum, rgb, self.last_stats)
-        if options is not None:
-            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        _no_options(options)
         if not isinstance(accum, np.ndarray) or accum.dtype != np.int32 or accum.ndim != 3 or accum.shape[1:] != (cols, 4):
             raise ValueError(f"accum must be an int32 array [n_rows, {cols}, 4] or such a tensor on a GPU")
         out = np.array(accum, dtype=np.int32, order="C")
@@ -558,8 +557,7 @@ class Scene:
                                                   torch.cuda.current_stream(accum.device).cuda_stream, _ref(options), _ref(st)))
             self.last_stats = st.as_dict() if st is not None else None
             return RenderResult(accum, rgb, self.last_stats)
-        if options is not None:
-            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        _no_options(options)
         if not isinstance(accum, np.ndarray) or accum.dtype != np.int32 or accum.ndim != 3 or accum.shape[1:] != (cols, 4):
             raise ValueError(f"accum must be an int32 array [n_rows, {cols}, 4] or such a tensor on a GPU")
         out = np.array(accum, dtype=np.int32, order="C")
@@ -609,8 +607,7 @@ class Scene:
                                             torch.cuda.current_stream(r.device).cuda_stream, _ref(options), _ref(st)))
             self.last_stats = st.as_dict() if st is not None else None
             return hit, strike
-        if options is not None:
-            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        _no_options(options)
         r = _array_arg(rays, "rays", np.float64, 6)
         n = r.shape[0]
         hit = np.zeros(n, np.int32)
@@ -647,8 +644,7 @@ class Scene:
                                            _ref(options), _ref(st)))
             self.last_stats = st.as_dict() if st is not None else None
             return colour, g
-        if options is not None:
-            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        _no_options(options)
         r = _array_arg(rays, "rays", np.float64, 6)
         n = r.shape[0]
         g = None
@@ -690,14 +686,12 @@ class Scene:
             stream = torch.cuda.current_stream(f.device).cuda_stream
             if extend is not None:
                 accum, done = extend
-                if not _is_torch(accum) or accum.dtype != torch.int32 or tuple(accum.shape) != (n, 4) or accum.device != f.device or not accum.is_contiguous():
-                    raise ValueError("extend=(accum, samplesDone): accum must be a contiguous int32 tensor [n, 4] on the footprints' device")
+                _accum_tensor(accum, n, f.device, "extend=(accum, samplesDone)", "the footprints' device")
                 check(lib.rt_render_footprints_extend_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
                                                              done, accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
             elif extend_map is not None:
                 accum, tg = extend_map
-                if not _is_torch(accum) or accum.dtype != torch.int32 or tuple(accum.shape) != (n, 4) or accum.device != f.device or not accum.is_contiguous():
-                    raise ValueError("extend_map=(accum, targets): accum must be a contiguous int32 tensor [n, 4] on the footprints' device")
+                _accum_tensor(accum, n, f.device, "extend_map=(accum, targets)", "the footprints' device")
                 if not _is_torch(tg) or tg.dtype != torch.int32 or tuple(tg.shape) != (n,) or tg.device != f.device or not tg.is_contiguous():
                     raise ValueError("extend_map=(accum, targets): targets must be a contiguous int32 tensor [n] on the footprints' device")
                 check(lib.rt_render_footprints_extend_map_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
@@ -708,8 +702,7 @@ class Scene:
                                                       accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
             self.last_stats = st.as_dict() if st is not None else None
             return RenderResult(accum, rgb, self.last_stats)
-        if options is not None:
-            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
+        _no_options(options)
         f = _array_arg(footprints, "footprints", np.float64, 12)
         n = f.shape[0]
         rgb = np.zeros((n, 3), np.uint8)
@@ -752,13 +745,7 @@ class Scene:
         cam = camera.to_abi()
         if _is_torch(pixels):
             torch = _torch()
-            if pixels.dtype != torch.int32:
-                raise TypeError(f"pixels must have dtype torch.int32, not {pixels.dtype}")
-            if pixels.dim() != 1:
-                raise ValueError(f"pixels must have shape [n], not {list(pixels.shape)}")
-            if not pixels.is_cuda:
-                raise ValueError("pixels must be on a GPU (a numpy array takes the host entry point)")
-            px = pixels.contiguous()
+            px = _list_tensor(pixels)
             dev = _tensor_device(px, device)
             n = px.shape[0]
             rgb = torch.empty((n, 3), dtype=torch.uint8, device=px.device)
@@ -766,8 +753,7 @@ class Scene:
             stream = torch.cuda.current_stream(px.device).cuda_stream
             if extend is not None:
                 accum, done = extend
-                if not _is_torch(accum) or accum.dtype != torch.int32 or tuple(accum.shape) != (n, 4) or accum.device != px.device or not accum.is_contiguous():
-                    raise ValueError("extend=(accum, samplesDone): accum must be a contiguous int32 tensor [n, 4] on the list's device")
+                _accum_tensor(accum, n, px.device, "extend=(accum, samplesDone)", "the list's device")
                 check(lib.rt_render_pixels_extend_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, n, px.data_ptr(), flags, done,
                                                          accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
             else:
@@ -776,15 +762,8 @@ class Scene:
                                                   accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
             self.last_stats = st.as_dict() if st is not None else None
             return RenderResult(accum, rgb, self.last_stats)
-        if options is not None:
-            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config / set_park for arrays")
-        if not isinstance(pixels, np.ndarray):
-            raise TypeError(f"pixels must be a numpy array or a torch tensor on a GPU, not {type(pixels).__name__}")
-        if pixels.dtype != np.int32:
-            raise TypeError(f"pixels must have dtype int32, not {pixels.dtype}")
-        if pixels.ndim != 1:
-            raise ValueError(f"pixels must have shape [n], not {list(pixels.shape)}")
-        px = np.ascontiguousarray(pixels)
+        _no_options(options)
+        px = _list_array(pixels)
         n = px.shape[0]
         rgb = np.zeros((n, 3), np.uint8)
         st = A.rt_stats()
@@ -826,13 +805,7 @@ class Scene:
                 tdev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
                 dev, count, ptr = tdev.index, frame if n is None else int(n), None
             else:
-                if pixels.dtype != torch.int32:
-                    raise TypeError(f"pixels must have dtype torch.int32, not {pixels.dtype}")
-                if pixels.dim() != 1:
-                    raise ValueError(f"pixels must have shape [n], not {list(pixels.shape)}")
-                if not pixels.is_cuda:
-                    raise ValueError("pixels must be on a GPU (a numpy array takes the host entry point)")
-                px = pixels.contiguous()
+                px = _list_tensor(pixels)
                 tdev, dev, count, ptr = px.device, _tensor_device(px, device), px.shape[0], px.data_ptr()
             per = max(n_samples, 0)
             hit = torch.empty((count, per), dtype=torch.int32, device=tdev)
@@ -844,18 +817,11 @@ class Scene:
                                             torch.cuda.current_stream(tdev).cuda_stream, _ref(options), _ref(st)))
             self.last_stats = st.as_dict() if st is not None else None
             return CameraHits(hit, sk, ry, self.last_stats)
-        if options is not None:
-            raise ValueError("options apply to the device entry point (torch tensors); use set_launch_config for arrays")
+        _no_options(options, "set_launch_config")
         if pixels is None:
             px, count = None, frame if n is None else int(n)
         else:
-            if not isinstance(pixels, np.ndarray):
-                raise TypeError(f"pixels must be a numpy array or a torch tensor on a GPU, not {type(pixels).__name__}")
-            if pixels.dtype != np.int32:
-                raise TypeError(f"pixels must have dtype int32, not {pixels.dtype}")
-            if pixels.ndim != 1:
-                raise ValueError(f"pixels must have shape [n], not {list(pixels.shape)}")
-            px = np.ascontiguousarray(pixels)
+            px = _list_array(pixels)
             count = px.shape[0]
         if count < 0:
             raise ValueError("n must be >= 0")
@@ -1006,6 +972,39 @@ def _tensor_arg(t, name: str, dtypes, width: int):
     if not t.is_cuda:
         raise ValueError(f"{name} must be on a GPU (a numpy array takes the host entry point)")
     return t.contiguous()
+
+
+def _list_array(a) -> np.ndarray:
+    """A pixel list [n] int32 for the host entry points."""
+    if not isinstance(a, np.ndarray):
+        raise TypeError(f"pixels must be a numpy array or a torch tensor on a GPU, not {type(a).__name__}")
+    if a.dtype != np.int32:
+        raise TypeError(f"pixels must have dtype int32, not {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"pixels must have shape [n], not {list(a.shape)}")
+    return np.ascontiguousarray(a)
+
+
+def _list_tensor(t):
+    """A pixel list [n] int32 for the device entry points."""
+    if t.dtype != _torch().int32:
+        raise TypeError(f"pixels must have dtype torch.int32, not {t.dtype}")
+    if t.dim() != 1:
+        raise ValueError(f"pixels must have shape [n], not {list(t.shape)}")
+    if not t.is_cuda:
+        raise ValueError("pixels must be on a GPU (a numpy array takes the host entry point)")
+    return t.contiguous()
+
+
+def _accum_tensor(accum, n: int, device, what: str, where: str) -> None:
+    """The buffer an extension of n list entries continues in place: `what` names the argument, `where` the device it must be on."""
+    if not _is_torch(accum) or accum.dtype != _torch().int32 or tuple(accum.shape) != (n, 4) or accum.device != device or not accum.is_contiguous():
+        raise ValueError(f"{what}: accum must be a contiguous int32 tensor [n, 4] on {where}")
+
+
+def _no_options(options, instead: str = "set_launch_config / set_park") -> None:
+    if options is not None:
+        raise ValueError(f"options apply to the device entry point (torch tensors); use {instead} for arrays")
 
 
 def _tensor_device(t, device: Optional[int]) -> int:

@@ -374,3 +374,47 @@ def test_c_program_continues_a_frame_by_map(rt, orc, tmp_path):
     acc, rgb = np.where(cont[..., None], acc24, acc12), np.where(cont[..., None], rgb24, rgb12)
     assert int(line[0].split()[-1], 16) == _digest(acc, rgb)
     assert f"{int((acc12[..., 0] == EARLY).sum())} final, {int(cont.sum())} continued" in line[0]
+
+
+def test_host_variants_without_rgb_equal_the_oracle(rt, orc):
+    """The host variants lay their buffers out in one device allocation, and an optional buffer that is absent takes no room in it: so
+    every host variant that takes `rgb`, called with rgb == NULL and with one (the wrapper always passes one), against the oracle's
+    frame at 12, at 40 and at the per-pixel targets, and footprint_cases.compose for a list of 65 footprints (one wave and one)."""
+    name = "all_materials"
+    _, _, w, h = _frame(name)
+    L, S = rt.lib, _scene(rt, name).handle
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+    cam = lambda spp: C.byref(_cam(name, spp).to_abi())     # noqa: E731
+    rows, cols = 2 * h + 1, 2 * w + 1
+    targets = _targets(rows * cols).reshape(rows, cols)
+    want12, want40, want_map = _oracle(orc, name, 12), _oracle(orc, name, 40), _frame_expect(orc, name, targets)
+    n = 65
+    px = np.ascontiguousarray(np.arange(rows * cols, dtype=np.int32)[::-1][3::rows * cols // n][:n])  # back to front, duplicates none
+    fs, fp = _fp_scene(rt, name).handle, np.ascontiguousarray(_case(name)[1][:n])
+    tg = np.ascontiguousarray(_targets(len(_case(name)[1]))[:n])
+    fp12, fp40 = _fp_expected(orc, name, 12), _fp_expected(orc, name, 40)
+    fp_map = _fp_expect(orc, name, _targets(len(_case(name)[1])))
+    assert len(px) == n == len(fp)
+    for with_rgb in (False, True):
+        def run(call, shape, accum, want_acc, want_rgb, what):
+            rgb = np.full(shape + (3,), 0xA5, np.uint8) if with_rgb else None
+            assert call(i32(accum), rgb.ctypes.data_as(C.POINTER(C.c_uint8)) if with_rgb else None) == rt._abi.RT_OK, (what, rt.lib.rt_last_error())
+            assert np.array_equal(accum, want_acc.reshape(accum.shape)), (what, with_rgb)
+            assert rgb is None or np.array_equal(rgb, want_rgb.reshape(rgb.shape)), what
+            return accum
+
+        frame = (rows, cols)
+        base = run(lambda a, r: L.rt_render(S, cam(12), w, h, SEED, 0, 0, 1, rows, 0, a, r, None), frame, np.zeros(frame + (4,), np.int32), *want12[:2], "rt_render")
+        run(lambda a, r: L.rt_render_extend(S, cam(40), w, h, SEED, 0, 0, 1, rows, 0, 12, a, r, None), frame, base.copy(), *want40[:2], "rt_render_extend")
+        run(lambda a, r: L.rt_render_extend_map(S, cam(CAP), w, h, SEED, 0, 0, 1, rows, 0, i32(targets), a, r, None), frame, base.copy(), *want_map[:2],
+            "rt_render_extend_map")
+        flat12, flat40 = [x.reshape(rows * cols, -1)[px] for x in want12[:2]], [x.reshape(rows * cols, -1)[px] for x in want40[:2]]
+        lst = run(lambda a, r: L.rt_render_pixels(S, cam(12), w, h, SEED, 0, n, i32(px), 0, a, r, None), (n,), np.zeros((n, 4), np.int32), *flat12, "rt_render_pixels")
+        run(lambda a, r: L.rt_render_pixels_extend(S, cam(40), w, h, SEED, 0, n, i32(px), 0, 12, a, r, None), (n,), lst.copy(), *flat40, "rt_render_pixels_extend")
+        f64 = fp.ctypes.data_as(C.POINTER(C.c_double))
+        fb = run(lambda a, r: L.rt_render_footprints(fs, 0, n, f64, 12, DEPTH, SEED, 0, 0, a, r, None), (n,), np.zeros((n, 4), np.int32), fp12.accum[:n], fp12.rgb[:n],
+                 "rt_render_footprints")
+        run(lambda a, r: L.rt_render_footprints_extend(fs, 0, n, f64, 40, DEPTH, SEED, 0, 0, 12, a, r, None), (n,), fb.copy(), fp40.accum[:n], fp40.rgb[:n],
+            "rt_render_footprints_extend")
+        run(lambda a, r: L.rt_render_footprints_extend_map(fs, 0, n, f64, CAP, DEPTH, SEED, 0, 0, i32(tg), a, r, None), (n,), fb.copy(), fp_map[0][:n], fp_map[1][:n],
+            "rt_render_footprints_extend_map")

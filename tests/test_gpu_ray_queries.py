@@ -1,6 +1,7 @@
 """Scene.hitObject and Scene.traceRays -- the render kernel's ray-list modes -- against the CPU oracle, bit for bit.  The oracle is
 given orc.ray_make(origin, vector) of the same inputs; the product the raw inputs, with vectors scaled by random factors from 1e-3
 to 1e3, so that Ray.make' on the device is checked too."""
+import ctypes as C
 import subprocess
 
 import numpy as np
@@ -104,6 +105,10 @@ def test_hit_objects_equal_the_oracle(rt, orc):
             assert np.array_equal(h1, h2) and _same_f64(s1, s2), (name, tuned)
             assert np.array_equal(h0, h2) and _same_f64(s0, s2), (name, tuned)
             assert (h2 == -2).sum() == 40 and 0.02 < np.mean(h2 >= 0), name
+            if not tuned:  # the host variant without its optional output (the wrapper always passes one): 65 rays, one wave and one
+                few, h3 = np.ascontiguousarray(raw[:65]), np.full(65, -9, np.int32)
+                assert rt.lib.rt_hit_objects(s.handle, 0, 65, few.ctypes.data_as(C.POINTER(C.c_double)), 0, h3.ctypes.data_as(C.POINTER(C.c_int32)), None, None) == 0
+                assert np.array_equal(h3, h2[:65]), name
     assert seen_placements == {0, 1}
 
 
