@@ -585,6 +585,55 @@ int64_t rt_format_pixel_map(const uint8_t *rgb, int32_t rows, int32_t cols, uint
  * (may be NULL); a truncated tail is ignored as in the reference.  Returns the pixel count, or a negative status. */
 int64_t rt_parse_pixel_map(const uint8_t *data, size_t n, int32_t rows, int32_t cols, uint8_t *rgb_out, uint8_t *present_out);
 
+/* ---- Output side, on the device: the same bytes from an image that is already there (DESIGN.md "Output on the device") ----
+ * d_rgb is rows*cols*3 uint8 on `device` (rt_render_device's d_rgb, a torch tensor's data_ptr()); d_rgb and d_out may have any byte
+ * alignment.  Everything is enqueued on `stream` (NULL = the null stream) with stream-ordered scratch: any number of calls may be
+ * in flight, no call synchronises unless its contract says so, and the caller's current device is left as it was.
+ * Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */
+
+/* Upper bound on rt_format_ppm's length: strlen(header) + 12*rows*cols - 1 (every channel three digits; reached exactly by an image
+ * whose every byte is >= 100 after gamma).  Pure host arithmetic; negative status on rows/cols <= 0 or more than INT32_MAX pixels. */
+int64_t rt_ppm_max_bytes(int32_t rows, int32_t cols);
+/* EXACT length of rt_format_pixel_map's output, in closed form (no image needed: lengths depend on (row, col) alone,
+ * ImageOutput.fs:115-161).  Negative status as rt_ppm_max_bytes. */
+int64_t rt_pixel_map_bytes(int32_t rows, int32_t cols);
+
+/* PixelOutput.correct (ImageOutput.fs:11-18) over n bytes on the device; d_out may equal d_in.  RT_ERR_INVALID_ARGUMENT for a NULL
+ * pointer with n > 0; n = 0 is a no-op. */
+int rt_gamma_correct_device(int32_t device, size_t n, const void *d_in, void *d_out, void *stream);
+
+/* rt_format_ppm's bytes (ImageOutput.fs:163-197, PixelOutput.toPpm :20-30; no NUL) and rt_format_pixel_map's bytes
+ * (ImageOutput.fs:115-161) from a device image into a device buffer.
+ * Argument checks come before any device call, nothing is written when one fails: RT_ERR_INVALID_ARGUMENT for a NULL d_rgb, rows or
+ * cols <= 0, more than INT32_MAX pixels, or a non-NULL d_out with out_capacity == 0; then RT_ERR_NO_DEVICE without a device.
+ * The needed length is always stored to d_length (an int64 on the device) when it is given; when `length` is non-NULL the call
+ * synchronises the stream and stores it there too.  d_out == NULL: only the lengths are computed.
+ * A capacity below the needed length is found ON THE DEVICE, in front of the writing kernel: NO byte of d_out is written, and the
+ * call returns RT_ERR_INVALID_ARGUMENT when `length` is given; with length == NULL it returns RT_OK, and d_length > out_capacity and
+ * the untouched buffer are the caller's evidence (the pattern of a malformed device pixel list).  Bytes at and beyond the needed
+ * length are never written, whatever the capacity. */
+int rt_format_ppm_device(int32_t device, const void *d_rgb, int32_t rows, int32_t cols, int32_t gamma_correct,
+                         void *d_out /* may be NULL: length only */, size_t out_capacity,
+                         void *d_length /* int64 on the device, may be NULL */, void *stream,
+                         int64_t *length /* host; may be NULL */);
+int rt_format_pixel_map_device(int32_t device, const void *d_rgb, int32_t rows, int32_t cols,
+                               void *d_out, size_t out_capacity, void *d_length, void *stream, int64_t *length);
+
+/* ImageOutput.writePpm (ImageOutput.fs:163-197) from a device image: format on the device, ONE device-to-host copy of exactly the
+ * text, write.  Synchronises.  Arguments are checked (as above, and a NULL path), then the file is opened -- RT_ERR_IO before any
+ * device work when that fails -- then the device runs; a short write is RT_ERR_IO, as in rt_write_ppm. */
+int rt_write_ppm_device(const char *path, int32_t device, const void *d_rgb, int32_t rows, int32_t cols,
+                        int32_t gamma_correct, void *stream);
+
+/* Scene.render |> ImageOutput.writePpm (Scene.fs:196-236, ImageOutput.fs:163-197): the whole frame rendered, formatted and written;
+ * its pixels never visit the host as rgb.  The file is byte for byte rt_format_ppm of rt_render's rgb for the same arguments.
+ * Rejects what rt_render rejects about scene, camera, geometry and options (the same check list), and a NULL path; then opens the
+ * file (RT_ERR_IO before any device work), renders on the null stream, formats, copies the text out and writes it.
+ * stats (may be NULL) as rt_render fills them: kernel_ms = the render kernel; total_ms = the whole call, file included. */
+int rt_render_ppm(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                  uint64_t seed, int32_t device, uint32_t flags, int32_t gamma_correct, const char *path,
+                  const rt_render_options *options, rt_stats *stats);
+
 /* ---- Runtime ------------------------------------------------------------------------------------- */
 int rt_device_count(void);         /* 0 when no HIP device is visible (never an error) */
 const char *rt_last_error(void);   /* thread-local message of the last failing call */

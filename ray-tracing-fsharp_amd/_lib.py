@@ -135,6 +135,16 @@ SIGNATURES = {
     "rt_format_ppm": (C.c_int64, [_u8p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
     "rt_format_pixel_map": (C.c_int64, [_u8p, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
     "rt_parse_pixel_map": (C.c_int64, [C.c_char_p, C.c_size_t, C.c_int32, C.c_int32, _u8p, _u8p]),
+    "rt_ppm_max_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rt_pixel_map_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rt_gamma_correct_device": (C.c_int, [C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_format_ppm_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                       _P(C.c_int64)]),
+    "rt_format_pixel_map_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                             _P(C.c_int64)]),
+    "rt_write_ppm_device": (C.c_int, [C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "rt_render_ppm": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32, C.c_char_p,
+                                _P(A.rt_render_options), _P(A.rt_stats)]),
     "rt_dev_float_producer": (C.c_int, [C.c_int32, _u32p, C.c_int32, _dp]),
     "rt_dev_stream_state": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32, _u64p, _u32p, _u32p]),
     "rt_dev_bbox_hits": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _i32p]),

@@ -36,6 +36,15 @@
 // ---- scene image (rt_device.h) ----
 #define RTD_NODE32_BYTES 64 /* a single-precision filter record of the timed node loop */
 
+// ---- the output stage (rt_output.h; DESIGN.md "Output on the device") ----
+#define RTO_BLOCK 256           /* threads of a tile's workgroup */
+#define RTO_THREAD_PIXELS 4     /* consecutive pixels per thread: 12 colour bytes */
+#define RTO_TILE_PIXELS (RTO_BLOCK * RTO_THREAD_PIXELS) /* 1024 pixels: 3 KiB of colour in, at most 12 KiB of P3 text (25 KiB of pixel map) staged in LDS */
+#define RTO_PPM_PIXEL_BYTES 12  /* "255 255 255" and one separator */
+#define RTO_MAP_PIXEL_BYTES 25  /* ten digits, ',', ten digits, '\n', three colour bytes */
+#define RTO_SCAN_THREADS 1024   /* tile sums per trip of the one scanning workgroup: trips begin at RTO_SCAN_THREADS * RTO_TILE_PIXELS = 2^20 pixels */
+#define RTO_SCRATCH_HEAD 16     /* struct FormatScratch; one uint64 per tile follows */
+
 // ---- host side ----
 // LDS budget: 160 KiB per CU (MI355X_MICROARCH.md); the LDS part of the scene image plus every wave's scratch must fit one workgroup.
 #define RT_LDS_BYTES 163840u

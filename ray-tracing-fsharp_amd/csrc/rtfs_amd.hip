@@ -4,6 +4,7 @@
 #include "../../include/rtfs_amd.h"
 #include "rt_device.h"
 #include "rt_launch_plan.h"
+#include "rt_output.h"
 #include "rt_render_kernel.h"
 #include "rt_scene.h"
 
@@ -1822,6 +1823,230 @@ int rt_write_ppm(const char *path, const uint8_t *rgb, int32_t rows, int32_t col
         const size_t w = fwrite(s.data(), 1, s.size(), f);
         const int c = fclose(f);
         if (w != s.size() || c != 0) return fail(RT_ERR_IO, std::string("short write to ") + path);
+        return (int) RT_OK;
+    });
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// output on the device (rt_output.h): the same bytes as rth::format_ppm / rth::format_pixel_map, from an image that is already there
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct FormatJob {
+    int fmt; // rto::FMT_PPM or rto::FMT_MAP
+    const void *d_rgb;
+    int32_t rows, cols;
+    bool gamma;
+    void *d_out;
+    size_t capacity;
+    void *d_length;
+};
+// A format call's stream-ordered scratch (rto::FormatScratch, then one uint64 per tile): given back to the stream's pool on every exit path.
+struct FormatPending {
+    unsigned char *scr = nullptr;
+    hipStream_t st = nullptr;
+    ~FormatPending() { if (scr) (void) hipFreeAsync(scr, st); }
+};
+// Stream-ordered device memory of the calls that own their buffers (rt_write_ppm_device, rt_render_ppm).
+struct StreamBuf {
+    unsigned char *p = nullptr;
+    hipStream_t st = nullptr;
+    ~StreamBuf() { if (p) (void) hipFreeAsync(p, st); }
+};
+struct FileCloser {
+    FILE *f = nullptr;
+    ~FileCloser() { if (f) (void) fclose(f); }
+};
+
+} // namespace
+
+static int check_image_size(int32_t rows, int32_t cols) {
+    if (rows <= 0 || cols <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "rows and cols must be positive");
+    if ((uint64_t) rows * (uint64_t) cols > (uint64_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "an image of more than INT32_MAX pixels");
+    return RT_OK;
+}
+static int check_format(const void *d_rgb, int32_t rows, int32_t cols, const void *d_out, size_t out_capacity) {
+    if (!d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "d_rgb is NULL");
+    RT_TRY(check_image_size(rows, cols));
+    if (d_out && out_capacity == 0) return fail(RT_ERR_INVALID_ARGUMENT, "d_out is given but out_capacity is 0");
+    return RT_OK;
+}
+static rto::PpmHeader ppm_header(int32_t rows, int32_t cols) { // "P3\n<cols> <rows>\n255\n" (ImageOutput.fs:166-176)
+    rto::PpmHeader h{};
+    h.len = (uint32_t) snprintf((char *) h.text, sizeof(h.text), "P3\n%d %d\n255\n", cols, rows);
+    return h;
+}
+static rto::GammaTable gamma_table(bool gamma) { // the ONE definition, rth::gamma_correct, tabulated; the identity when gamma is off
+    rto::GammaTable t;
+    for (int i = 0; i < 256; ++i) t.v[i] = gamma ? rth::gamma_correct((uint8_t) i) : (uint8_t) i;
+    return t;
+}
+static int64_t ascii_int_digits_below(int64_t n) { // sum of writeAsciiInt's digit counts over 0 .. n-1 (0 has none): sum over k of max(0, n - 10^k)
+    int64_t sum = 0;
+    for (int64_t p = 1; p < n; p *= 10) sum += n - p;
+    return sum;
+}
+
+// Enqueues one format on `stream` (arguments checked, the device current): sums, scan and -- when there is a buffer -- the scatter.
+// Never waits for the device.
+static int enqueue_format(const FormatJob &j, void *stream, FormatPending &fp) {
+    hipStream_t st = (hipStream_t) stream;
+    const uint32_t npx = (uint32_t) ((uint64_t) j.rows * (uint64_t) j.cols);
+    const uint32_t n_tiles = (npx + (uint32_t) RTO_TILE_PIXELS - 1u) / (uint32_t) RTO_TILE_PIXELS;
+    HIP_TRY(hipMallocAsync((void **) &fp.scr, RTO_SCRATCH_HEAD + (size_t) n_tiles * sizeof(unsigned long long), st));
+    fp.st = st;
+    rto::FormatScratch *head = (rto::FormatScratch *) fp.scr;
+    unsigned long long *tiles = (unsigned long long *) (fp.scr + RTO_SCRATCH_HEAD);
+    const unsigned char *rgb = (const unsigned char *) j.d_rgb;
+    const rto::GammaTable g = gamma_table(j.gamma);
+    const rto::PpmHeader hdr = j.fmt == rto::FMT_PPM ? ppm_header(j.rows, j.cols) : rto::PpmHeader{};
+    if (j.fmt == rto::FMT_PPM) hipLaunchKernelGGL(rto::format_sums_kernel<rto::FMT_PPM>, dim3(n_tiles), dim3(RTO_BLOCK), 0, st, rgb, npx, (uint32_t) j.cols, g, tiles);
+    else hipLaunchKernelGGL(rto::format_sums_kernel<rto::FMT_MAP>, dim3(n_tiles), dim3(RTO_BLOCK), 0, st, rgb, npx, (uint32_t) j.cols, g, tiles);
+    hipLaunchKernelGGL(rto::format_scan_kernel, dim3(1), dim3(RTO_SCAN_THREADS), 0, st, tiles, n_tiles, (unsigned long long) hdr.len, head, (long long *) j.d_length,
+                       (unsigned long long) j.capacity, j.d_out ? 1 : 0);
+    if (j.d_out) {
+#ifdef RTO_PLAIN_STORES
+        constexpr bool staged = false;
+#else
+        constexpr bool staged = true;
+#endif
+        if (j.fmt == rto::FMT_PPM)
+            hipLaunchKernelGGL((rto::format_scatter_kernel<rto::FMT_PPM, staged>), dim3(n_tiles), dim3(RTO_BLOCK), 0, st, rgb, npx, (uint32_t) j.cols, g, hdr,
+                               (const unsigned long long *) tiles, (const rto::FormatScratch *) head, (unsigned char *) j.d_out);
+        else
+            hipLaunchKernelGGL((rto::format_scatter_kernel<rto::FMT_MAP, staged>), dim3(n_tiles), dim3(RTO_BLOCK), 0, st, rgb, npx, (uint32_t) j.cols, g, hdr,
+                               (const unsigned long long *) tiles, (const rto::FormatScratch *) head, (unsigned char *) j.d_out);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+// Waits for the stream, reads the needed length and reports a buffer the device found too small (it wrote none of it).
+static int finish_format(FormatPending &fp, const FormatJob &j, int64_t *length) {
+    long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, fp.scr + offsetof(rto::FormatScratch, total), sizeof(total), hipMemcpyDeviceToHost, fp.st));
+    HIP_TRY(hipStreamSynchronize(fp.st));
+    *length = (int64_t) total;
+    if (j.d_out && (unsigned long long) total > (unsigned long long) j.capacity)
+        return fail(RT_ERR_INVALID_ARGUMENT, "out_capacity " + std::to_string(j.capacity) + " below the " + std::to_string(total) + " bytes needed");
+    return RT_OK;
+}
+static int run_format(int32_t device, const FormatJob &j, void *stream, int64_t *length) {
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    FormatPending fp;
+    RT_TRY(enqueue_format(j, stream, fp));
+    return length ? finish_format(fp, j, length) : RT_OK;
+}
+// The P3 text of a device image in host memory (the device current): a device buffer of rt_ppm_max_bytes from the stream's pool, the
+// format, and ONE device-to-host copy of exactly the text.  Waits for the stream.
+static int ppm_to_host(const void *d_rgb, int32_t rows, int32_t cols, bool gamma, hipStream_t st, unsigned char *d_text, size_t capacity,
+                       std::unique_ptr<char[]> &text, int64_t &len) {
+    const FormatJob j{rto::FMT_PPM, d_rgb, rows, cols, gamma, d_text, capacity, nullptr};
+    FormatPending fp;
+    RT_TRY(enqueue_format(j, st, fp));
+    RT_TRY(finish_format(fp, j, &len));
+    text.reset(new char[(size_t) len]);
+    HIP_TRY(hipMemcpyAsync(text.get(), d_text, (size_t) len, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RT_OK;
+}
+static int write_all(FileCloser &file, const char *path, const char *text, int64_t len) {
+    const size_t w = fwrite(text, 1, (size_t) len, file.f);
+    const int c = fclose(file.f);
+    file.f = nullptr;
+    if (w != (size_t) len || c != 0) return fail(RT_ERR_IO, std::string("short write to ") + path);
+    return RT_OK;
+}
+
+extern "C" {
+
+int64_t rt_ppm_max_bytes(int32_t rows, int32_t cols) {
+    if (check_image_size(rows, cols) != RT_OK) return -RT_ERR_INVALID_ARGUMENT;
+    return (int64_t) ppm_header(rows, cols).len + (int64_t) RTO_PPM_PIXEL_BYTES * (int64_t) rows * (int64_t) cols - 1;
+}
+
+int64_t rt_pixel_map_bytes(int32_t rows, int32_t cols) {
+    if (check_image_size(rows, cols) != RT_OK) return -RT_ERR_INVALID_ARGUMENT;
+    return (int64_t) cols * ascii_int_digits_below(rows) + (int64_t) rows * ascii_int_digits_below(cols) + 5 * (int64_t) rows * (int64_t) cols;
+}
+
+int rt_gamma_correct_device(int32_t device, size_t n, const void *d_in, void *d_out, void *stream) {
+    if (n > 0 && !d_in) return fail(RT_ERR_INVALID_ARGUMENT, "d_in is NULL");
+    if (n > 0 && !d_out) return fail(RT_ERR_INVALID_ARGUMENT, "d_out is NULL");
+    if (n == 0) return RT_OK;
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    const size_t want = (n / 4u + RTO_BLOCK - 1u) / RTO_BLOCK + 1u;
+    hipLaunchKernelGGL(rto::gamma_kernel, dim3((unsigned) (want < 4096u ? want : 4096u)), dim3(RTO_BLOCK), 0, (hipStream_t) stream, (const unsigned char *) d_in,
+                       (unsigned char *) d_out, (unsigned long long) n, gamma_table(true));
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+int rt_format_ppm_device(int32_t device, const void *d_rgb, int32_t rows, int32_t cols, int32_t gamma_correct, void *d_out, size_t out_capacity,
+                         void *d_length, void *stream, int64_t *length) {
+    RT_TRY(check_format(d_rgb, rows, cols, d_out, out_capacity));
+    return run_format(device, FormatJob{rto::FMT_PPM, d_rgb, rows, cols, gamma_correct != 0, d_out, out_capacity, d_length}, stream, length);
+}
+
+int rt_format_pixel_map_device(int32_t device, const void *d_rgb, int32_t rows, int32_t cols, void *d_out, size_t out_capacity, void *d_length,
+                               void *stream, int64_t *length) {
+    RT_TRY(check_format(d_rgb, rows, cols, d_out, out_capacity));
+    return run_format(device, FormatJob{rto::FMT_MAP, d_rgb, rows, cols, false, d_out, out_capacity, d_length}, stream, length);
+}
+
+int rt_write_ppm_device(const char *path, int32_t device, const void *d_rgb, int32_t rows, int32_t cols, int32_t gamma_correct, void *stream) {
+    if (!path) return fail(RT_ERR_INVALID_ARGUMENT, "path is NULL");
+    RT_TRY(check_format(d_rgb, rows, cols, nullptr, 0));
+    return guarded("rt_write_ppm_device", [&]() {
+        FileCloser file;
+        if (!(file.f = fopen(path, "wb"))) return fail(RT_ERR_IO, std::string("cannot open ") + path);
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        const size_t capacity = (size_t) rt_ppm_max_bytes(rows, cols);
+        StreamBuf d_text;
+        d_text.st = (hipStream_t) stream;
+        HIP_TRY(hipMallocAsync((void **) &d_text.p, capacity, d_text.st));
+        std::unique_ptr<char[]> text;
+        int64_t len = 0;
+        RT_TRY(ppm_to_host(d_rgb, rows, cols, gamma_correct != 0, d_text.st, d_text.p, capacity, text, len));
+        return write_all(file, path, text.get(), len);
+    });
+}
+
+int rt_render_ppm(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, uint32_t flags,
+                  int32_t gamma_correct, const char *path, const rt_render_options *options, rt_stats *stats) {
+    const int32_t rows = (max_h > 0 && max_h <= (1 << 20)) ? 2 * max_h + 1 : 0, cols = (max_w > 0 && max_w <= (1 << 20)) ? 2 * max_w + 1 : 0;
+    RT_TRY(check_frame(scene, camera, max_w, max_h, 0, 1, rows, scene, "", options)); // rt_render's check list (the buffers are this call's own)
+    if (!path) return fail(RT_ERR_INVALID_ARGUMENT, "path is NULL");
+    RT_TRY(check_image_size(rows, cols));
+    return guarded("rt_render_ppm", [&]() {
+        const auto t0 = std::chrono::steady_clock::now();
+        FileCloser file;
+        if (!(file.f = fopen(path, "wb"))) return fail(RT_ERR_IO, std::string("cannot open ") + path);
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        // accum, rgb and the text in ONE allocation from the null stream's pool; the pixels never visit the host as rgb
+        const size_t npx = (size_t) rows * (size_t) cols, capacity = (size_t) rt_ppm_max_bytes(rows, cols), rgb_at = npx * 16u,
+                     text_at = rgb_at + ((npx * 3u + 15u) & ~(size_t) 15u);
+        StreamBuf buf;
+        HIP_TRY(hipMallocAsync((void **) &buf.p, text_at + capacity, buf.st));
+        rt_stats local;
+        {
+            Pending pd;
+            RT_TRY(launch_render(scene, camera, max_w, max_h, seed, device, 0, 1, rows, flags, buf.p, buf.p + rgb_at, nullptr, options, true, pd));
+            RT_TRY(collect_stats(pd, &local));
+        }
+        std::unique_ptr<char[]> text;
+        int64_t len = 0;
+        RT_TRY(ppm_to_host(buf.p + rgb_at, rows, cols, gamma_correct != 0, buf.st, buf.p + text_at, capacity, text, len));
+        RT_TRY(write_all(file, path, text.get(), len));
+        if (stats) {
+            *stats = local;
+            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
         return (int) RT_OK;
     });
 }

@@ -2,6 +2,7 @@
 // Differences that follow from the scope: the output is the gamma-corrected P3 PPM of ImageOutput.writePpm
 // (the reference writes the same pixels as PNG through SkiaSharp), and the randomness comes from --seed.
 // Options: --seed N  --spp N  --depth N  --scale K (divide maxWidthCoord/maxHeightCoord by K)  --device D  --no-gamma  --list
+//          --host-output (format the file on the host: Scene::render, then ImageOutput::writePpm; the default formats it on the device)
 #include "SampleImages.hpp"
 
 #include <cstdio>
@@ -15,7 +16,7 @@ int main(int argc, char **argv) {
         std::vector<std::string> pos;
         uint64_t seed = 2024;
         int spp = 0, depth = -1, scale = 1, device = 0;
-        bool gamma = true, info = false;
+        bool gamma = true, info = false, hostOutput = false;
         for (int i = 1; i < argc; ++i) {
             const std::string a = argv[i];
             auto val = [&]() -> std::string { if (i + 1 >= argc) throw std::runtime_error("missing value for " + a); return argv[++i]; };
@@ -26,6 +27,7 @@ int main(int argc, char **argv) {
             else if (a == "--scale") scale = std::stoi(val());
             else if (a == "--device") device = std::stoi(val());
             else if (a == "--no-gamma") gamma = false;
+            else if (a == "--host-output") hostOutput = true; // the same bytes by the old route, for A/B measurement
             else if (a == "--info") info = true; // print the flattened scene's shape and a hash of its tree, do not render
             else pos.push_back(a);
         }
@@ -66,11 +68,16 @@ int main(int argc, char **argv) {
             if (ti.tuned) std::fprintf(stderr, "walk tree tuned: %.1f -> %.1f box tests per probe ray, %d -> %d nodes, %.0f ms\n", ti.box_tests_before,
                                        ti.box_tests_after, ti.nodes_before, ti.nodes_after, ti.probe_ms + ti.build_ms);
         }
-        auto res = Scene::render(tick, [](const std::string &) {}, def.maxWidthCoord, def.maxHeightCoord, def.camera, scene, seed, device);
-        Image &image = res.second;
-        const std::vector<uint8_t> &rows = image.render(); // forces the render on the GPU
-        ImageOutput::writePpm(gamma, tick, rows, image.RowCount, image.ColCount, output);
-        std::fprintf(stderr, "%dx%d px, %llu samples, kernel %.2f ms\n", image.ColCount, image.RowCount, (unsigned long long) scene->lastStats.samples,
+        const int colCount = 2 * def.maxWidthCoord + 1, rowCount = 2 * def.maxHeightCoord + 1;
+        if (hostOutput) {
+            auto res = Scene::render(tick, [](const std::string &) {}, def.maxWidthCoord, def.maxHeightCoord, def.camera, scene, seed, device);
+            Image &image = res.second;
+            const std::vector<uint8_t> &rows = image.render(); // forces the render on the GPU
+            ImageOutput::writePpm(gamma, tick, rows, image.RowCount, image.ColCount, output);
+        } else { // rendered, formatted and written in one call: the pixels never visit the host as rgb
+            scene->renderPpm(tick, def.maxWidthCoord, def.maxHeightCoord, def.camera, gamma, output, seed, device);
+        }
+        std::fprintf(stderr, "%dx%d px, %llu samples, kernel %.2f ms\n", colCount, rowCount, (unsigned long long) scene->lastStats.samples,
                      scene->lastStats.kernel_ms);
         std::cout << output << "\n"; // printfn "%s" pngOutput.FullName (Program.fs:56)
         return 0;

@@ -269,6 +269,15 @@ class Scene {
         return {(double) rowsIter, Image(rowsIter, colsIter, force)};
     }
 
+    // Scene.render |> ImageOutput.writePpm in one call (rt_render_ppm): the frame rendered, formatted as P3 text on the device and written
+    // to `output`; byte for byte writePpm of render's pixels, which never visit the host as rgb.  Progress ticks once per row.
+    void renderPpm(const std::function<void(double)> &progressIncrement, int maxWidthCoord, int maxHeightCoord, const Camera &camera, bool gammaCorrect,
+                   const std::string &output, uint64_t seed = 0, int device = 0) {
+        rt_camera cam = camera.toAbi();
+        check(rt_render_ppm(h_, &cam, maxWidthCoord, maxHeightCoord, seed, device, 0u, gammaCorrect ? 1 : 0, output.c_str(), nullptr, &lastStats));
+        for (int r = 0; r < 2 * maxHeightCoord + 1; ++r) progressIncrement(1.0);
+    }
+
     // rt_scene_tune (no counterpart in the reference): the walk tree rebuilt from the rays of a small probe render with this camera;
     // same pixels, about a third fewer box tests per ray, ~12 % off the frame time.  Costs ~20 ms: worth it from a scene's second frame on, or
     // for a first frame of more than about 0.15 s.

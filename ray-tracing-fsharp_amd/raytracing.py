@@ -493,6 +493,17 @@ class Scene:
         self.last_stats = st.as_dict()
         return RenderResult(accum, rgb, self.last_stats)
 
+    def renderPpm(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, path: str, *, gammaCorrect: bool = True, seed: int = 0,
+                  device: int = 0, counters: bool = False) -> dict:
+        """rt_render_ppm: Scene.render |> ImageOutput.writePpm in one call -- the frame rendered, formatted as P3 text on the device and
+        written to `path`; byte for byte ImageOutput.writePpm of render_rows' rgb.  Returns the statistics (total_ms covers the file)."""
+        st = A.rt_stats()
+        cam = camera.to_abi()
+        check(lib.rt_render_ppm(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, device, A.RT_RENDER_COUNTERS if counters else 0,
+                                int(bool(gammaCorrect)), str(path).encode(), None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return self.last_stats
+
     def extend_rows(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, accum, samplesDone: int, *, seed: int = 0,
                     device: Optional[int] = None, row_first: int = 0, row_stride: int = 1, counters: bool = False, stats: bool = True,
                     options: Optional[A.rt_render_options] = None) -> RenderResult:
@@ -868,10 +879,27 @@ class PixelOutput:
     def correct(b: int) -> int:  # ImageOutput.fs:11-18
         return int(lib.rt_gamma_correct(int(b)))
 
+    @staticmethod
+    def correctImage(pixels):
+        """PixelOutput.correct over every byte of `pixels` (uint8, any shape); a new array.  A torch tensor on a GPU goes through
+        rt_gamma_correct_device on torch.cuda.current_stream() (no wait for the device), a numpy array through a table of rt_gamma_correct."""
+        if _is_torch(pixels):
+            t = _bytes_tensor(pixels)
+            out = _torch().empty_like(t)
+            check(lib.rt_gamma_correct_device(t.device.index, t.numel(), t.data_ptr(), out.data_ptr(), _torch().cuda.current_stream(t.device).cuda_stream))
+            return out
+        lut = np.array([lib.rt_gamma_correct(b) for b in range(256)], np.uint8)
+        return lut[np.ascontiguousarray(pixels, dtype=np.uint8)]
+
 
 class ImageOutput:
     @staticmethod
-    def formatPpm(gammaCorrect: bool, pixels: np.ndarray) -> bytes:
+    def formatPpm(gammaCorrect: bool, pixels) -> bytes:
+        """ImageOutput.writePpm's bytes.  A numpy array takes rt_format_ppm on the host; a contiguous uint8 torch tensor [rows, cols, 3] on a
+        GPU is formatted there (formatPpmDevice) and only the text is copied back."""
+        if _is_torch(pixels):
+            text, length = ImageOutput.formatPpmDevice(gammaCorrect, pixels)
+            return text[: int(length)].cpu().numpy().tobytes()
         px = np.ascontiguousarray(pixels, dtype=np.uint8)
         rows, cols = px.shape[0], px.shape[1]
         n = lib.rt_format_ppm(_u8(px), rows, cols, int(bool(gammaCorrect)), None, 0)
@@ -879,6 +907,46 @@ class ImageOutput:
             check(int(-n))
         buf = C.create_string_buffer(int(n) + 1)
         lib.rt_format_ppm(_u8(px), rows, cols, int(bool(gammaCorrect)), buf, int(n) + 1)
+        return buf.raw[: int(n)]
+
+    @staticmethod
+    def formatPpmDevice(gammaCorrect: bool, pixels):
+        """rt_format_ppm_device on torch.cuda.current_stream(), without waiting for the device: (text, length) -- a uint8 tensor of
+        rt_ppm_max_bytes(rows, cols) bytes whose first `length` (an int64 tensor) are ImageOutput.writePpm's; the rest is not written."""
+        t = _image_tensor(pixels)
+        torch = _torch()
+        rows, cols = int(t.shape[0]), int(t.shape[1])
+        cap = lib.rt_ppm_max_bytes(rows, cols)
+        if cap < 0:
+            check(int(-cap))
+        text = torch.empty(int(cap), dtype=torch.uint8, device=t.device)
+        length = torch.empty((), dtype=torch.int64, device=t.device)
+        check(lib.rt_format_ppm_device(t.device.index, t.data_ptr(), rows, cols, int(bool(gammaCorrect)), text.data_ptr(), int(cap), length.data_ptr(),
+                                       torch.cuda.current_stream(t.device).cuda_stream, None))
+        return text, length
+
+    @staticmethod
+    def formatPixelMap(pixels) -> bytes:
+        """The pixel-map bytes of ImageOutput.resume / toPpm (ImageOutput.fs:115-161): per pixel `<row>,<col>\n` (0 as NO digits) and the
+        three raw colour bytes.  numpy: rt_format_pixel_map on the host; a torch tensor on a GPU: rt_format_pixel_map_device."""
+        if _is_torch(pixels):
+            t = _image_tensor(pixels)
+            torch = _torch()
+            rows, cols = int(t.shape[0]), int(t.shape[1])
+            cap = lib.rt_pixel_map_bytes(rows, cols)
+            if cap < 0:
+                check(int(-cap))
+            out = torch.empty(int(cap), dtype=torch.uint8, device=t.device)
+            n = C.c_int64(0)
+            check(lib.rt_format_pixel_map_device(t.device.index, t.data_ptr(), rows, cols, out.data_ptr(), int(cap), None,
+                                                 torch.cuda.current_stream(t.device).cuda_stream, C.byref(n)))
+            return out[: n.value].cpu().numpy().tobytes()
+        px = np.ascontiguousarray(pixels, dtype=np.uint8)
+        n = lib.rt_format_pixel_map(_u8(px), px.shape[0], px.shape[1], None, 0)
+        if n < 0:
+            check(int(-n))
+        buf = C.create_string_buffer(int(n))
+        lib.rt_format_pixel_map(_u8(px), px.shape[0], px.shape[1], buf, int(n))
         return buf.raw[: int(n)]
 
     @staticmethod
@@ -916,8 +984,16 @@ class ImageOutput:
         return rgb
 
     @staticmethod
-    def writePpm(gammaCorrect: bool, incrementProgress: Callable[[float], None], pixels: np.ndarray, output: str) -> None:
-        """ImageOutput.writePpm (ImageOutput.fs:163-197)."""
+    def writePpm(gammaCorrect: bool, incrementProgress: Callable[[float], None], pixels, output: str) -> None:
+        """ImageOutput.writePpm (ImageOutput.fs:163-197).  A torch tensor on a GPU is formatted there (rt_write_ppm_device, on
+        torch.cuda.current_stream()); a numpy array takes rt_write_ppm."""
+        if _is_torch(pixels):
+            t = _image_tensor(pixels)
+            check(lib.rt_write_ppm_device(str(output).encode(), t.device.index, t.data_ptr(), int(t.shape[0]), int(t.shape[1]), int(bool(gammaCorrect)),
+                                          _torch().cuda.current_stream(t.device).cuda_stream))
+            for _ in range(int(t.shape[0]) * int(t.shape[1])):
+                incrementProgress(1.0)
+            return
         px = np.ascontiguousarray(pixels, dtype=np.uint8)
         check(lib.rt_write_ppm(str(output).encode(), _u8(px), px.shape[0], px.shape[1], int(bool(gammaCorrect))))
         for _ in range(px.shape[0] * px.shape[1]):
@@ -972,6 +1048,22 @@ def _tensor_arg(t, name: str, dtypes, width: int):
     if not t.is_cuda:
         raise ValueError(f"{name} must be on a GPU (a numpy array takes the host entry point)")
     return t.contiguous()
+
+
+def _bytes_tensor(t):
+    """Bytes on a GPU, any shape (PixelOutput.correctImage)."""
+    if t.dtype != _torch().uint8:
+        raise TypeError(f"pixels must have dtype torch.uint8, not {t.dtype}")
+    if not t.is_cuda:
+        raise ValueError("pixels must be on a GPU (a numpy array takes the host route)")
+    return t.contiguous()
+
+
+def _image_tensor(t):
+    """An image [rows, cols, 3] uint8 for the device output entry points."""
+    if t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f"pixels must have shape [rows, cols, 3], not {list(t.shape)}")
+    return _bytes_tensor(t)
 
 
 def _list_array(a) -> np.ndarray:
