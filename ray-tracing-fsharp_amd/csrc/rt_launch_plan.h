@@ -10,6 +10,7 @@
 // Both passes of a two-pass launch use the grid the FUSED kernel's occupancy gives: kept as measured, not queried per pass.
 #pragma once
 #include "rt_launch_consts.h"
+#include "rt_modes.h"
 
 #include <cstddef>
 #include <cstdint>
@@ -35,11 +36,11 @@ struct SceneSize {
     uint64_t n_objects = 0;
     bool tex = false;                        // has parameterised textures
 };
-// A frame shard (render_kernel modes 0..3), a caller's ray list (mode 4 paths, mode 5 hit queries) or a caller's footprint list
-// (modes 6..8: planned as a FRAME of n pixels -- chunk widening, fused or two passes, placement, pools -- run by the footprint kernels)
-// or a caller's list of a frame's pixels (modes 11..13, rt_render_pixels: planned exactly as the FOOTPRINTS job of the same n)
-// or the camera hits of such a list (mode 14, rt_camera_hits: n entries x spp samples, planned by the ray lists' rules over n * spp rays,
-// with units of chunk ENTRIES and the wave scratch their pix and candidate words need)
+// A frame shard (rtmode::FRAME_* [0..3, 9]), a caller's ray list (RAYS_TRACE [4] paths, RAYS_HIT [5] hit queries) or a caller's footprint
+// list (FOOTPRINTS_* [6..8, 10]: planned as a FRAME of n pixels -- chunk widening, fused or two passes, placement, pools -- run by the
+// footprint kernels) or a caller's list of a frame's pixels (PIXELS_* [11..13], rt_render_pixels: planned exactly as the FOOTPRINTS job of
+// the same n) or the camera hits of such a list (CAMERA_HITS [14], rt_camera_hits: n entries x spp samples, planned by the ray lists' rules
+// over n * spp rays, with units of chunk ENTRIES and the wave scratch their pix and candidate words need)
 struct Job {
     enum Kind { FRAME, TRACE, HIT, FOOTPRINTS, PIXELS, CAMERA_HITS } kind = FRAME;
     uint64_t n_rows = 0; int32_t max_w = 0, spp = 1; // FRAME
@@ -55,13 +56,16 @@ struct Job {
     bool list() const { return kind == FOOTPRINTS || kind == PIXELS; }  // n pixels in list order: a frame of one row to the plan
     bool pixels() const { return kind == FRAME || list(); }             // planned by the pixel rules, not the ray lists'
     uint64_t pixel_count() const { return list() ? n : n_rows * (uint64_t) (2 * max_w + 1); }
+    rtmode::Pixels source() const { // where the job's kernels find their pixels
+        return kind == FRAME ? rtmode::Pixels::FRAME : kind == FOOTPRINTS ? rtmode::Pixels::FOOTPRINTS : (kind == PIXELS || kind == CAMERA_HITS) ? rtmode::Pixels::LIST : rtmode::Pixels::NONE;
+    }
 };
 
-// One kernel launch: which render_kernel<lds, count, block, mode, tex>, its grid and dynamic LDS, and the RenderParams fields the
+// One kernel launch: which render_kernel<lds, count, block, mode, tex> (mode: an rtmode::Mode), its grid and dynamic LDS, and the RenderParams fields the
 // plan owns.
 struct Pass {
     bool lds = false, count = false, tex = false;
-    int block = 1024, mode = 0;
+    int block = 1024, mode = rtmode::FRAME_FUSED;
     uint64_t grid = 0;
     size_t lds_bytes = 0;
     int32_t chunk = 16, park = 0, park_l = 0, park_l_lds = 0, lds_node_bytes = 0, lds_node_thr = 0;
@@ -72,7 +76,7 @@ struct LaunchPlan {
     SceneSize scene; Settings set{}; Job job; int cu_count = 0; // (the inputs, kept for plan_finish)
     bool two_pass = false;
     Pass one;  // the fused kernel or the ray-list kernel; with two_pass only its (kernel, block, lds_bytes) were used, for the occupancy
-    Pass a, b; // two_pass: pass A (mode 1) and pass B (mode 2); the three sort kernels run between them
+    Pass a, b; // two_pass: pass A and pass B of the job's pixels (rtmode::Pass::A, ::B); the three sort kernels run between them
                // (an extension: two_pass with pass B only -- a.grid = 0, its list comes from the list-building kernel, unordered)
     size_t pairs_bytes = 0, list_bytes = 0, sort_bytes = 0, pool_bytes = 0; // workspace sections behind the launch's scratch, in this order
     uint64_t pixels = 0, waves = 0;                                         // what the statistics report
@@ -80,7 +84,7 @@ struct LaunchPlan {
 };
 
 // `count`: the counting kernel variant stages the exact double-precision node records (112 B), the timed one the single-precision
-// filter records (64 B).  wave_words: a wave's LDS scratch, RTD_WAVE_WORDS(chunk) / RTD_WAVE_WORDS_A(chunk); ray lists use none.
+// filter records (64 B).  wave_words: a wave's LDS scratch, rtmode::wave_words(mode, chunk); ray lists use none.
 static inline size_t lds_need(const SceneSize &sc, bool lds, bool count, int block, uint32_t wave_words) {
     return (lds ? (size_t) (count ? sc.lds_total : sc.lds32_total) : 0u) + (size_t) (block / 64) * wave_words * 4u;
 }
@@ -116,11 +120,11 @@ static inline uint32_t hybrid_node_bytes(const SceneSize &sc, size_t &ldsBytes, 
     ldsBytes += room;
     return (uint32_t) room;
 }
-// Places one pass in LDS -- the scene image (if resident) and the waves' scratch, then the top of the filter tree (hybrid), then the
+// Places one pass in LDS -- the scene image (if resident) and the waves' scratch (its mode's, at its unit size), then the top of the filter tree (hybrid), then the
 // Lambert pool if at least 32 entries fit -- and fills the fields that follow from it.  The Lambert pool rides with the general one
 // ("never park", park = 0, switches both off); where it does not fit the LDS it keeps its default size in global memory.
-static inline void place_pass(Pass &q, const SceneSize &sc, uint32_t wave_words) {
-    size_t bytes = lds_need(sc, q.lds, q.count, q.block, wave_words);
+static inline void place_pass(Pass &q, const SceneSize &sc) {
+    size_t bytes = lds_need(sc, q.lds, q.count, q.block, rtmode::wave_words(q.mode, (uint32_t) q.chunk));
     q.lds_node_bytes = (int32_t) hybrid_node_bytes(sc, bytes, q.lds, q.count, q.block, q.park > 0);
     q.lds_node_thr = RTD_HYBRID_LANES;
     q.park_l = q.park > 0 ? RTD_PARK_L_DEFAULT : 0;
@@ -138,7 +142,7 @@ static inline int default_block(const Settings &s) { return s.block ? s.block : 
 // per SIMD -- 899 spheres, tuned: 25.1 ms against 12.3 ms for the global-memory variant at 1024 threads.)
 // (an LDS-resident scene has far fewer than the 16384 objects the node loop's 14-bit queue entries can name: 48 B each of 160 KiB)
 static inline bool lds_resident(const SceneSize &sc, const Settings &s, bool count) {
-    return sc.n_objects < 16384u && lds_need(sc, true, count, default_block(s), RTD_WAVE_WORDS(s.chunk ? s.chunk : 16)) <= RT_LDS_BYTES;
+    return sc.n_objects < 16384u && lds_need(sc, true, count, default_block(s), rtmode::wave_words(rtmode::FRAME_FUSED, s.chunk ? s.chunk : 16)) <= RT_LDS_BYTES;
 }
 
 // Step one.  `count`: the counting kernel variant (RT_RENDER_COUNTERS).
@@ -161,7 +165,7 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
         // 24 instantiations: blocks of 256 or 1024 threads only (a launch asking for 512 or 768 runs at 1024: the block size never
         // changes a result); the hit queries shade nothing, so they have no textured variant and park nothing.
         q.block = default_block(set) == 256 ? 256 : 1024;
-        q.mode = job.kind == Job::HIT ? 5 : job.kind == Job::CAMERA_HITS ? 14 : 4;
+        q.mode = rtmode::mode_of({job.source(), job.kind == Job::CAMERA_HITS ? rtmode::Pass::CAMERA_HITS : rtmode::Pass::RAY_LIST, false, false, job.kind != Job::TRACE});
         q.tex = job.kind == Job::TRACE && sc.tex;
         q.chunk = set.chunk ? set.chunk : RTD_MAX_CHUNK; // rays per run of the queue (a wave takes as many runs at once as it has idle lanes)
         if (job.kind != Job::TRACE) q.park = 0;
@@ -170,19 +174,15 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
             // unit is set up once and handed out without draining, so small units cost one atomic each and balance the waves best)
             if (!set.chunk) q.chunk = job.spp >= RTD_MAX_CHUNK ? 1 : (RTD_MAX_CHUNK + job.spp - 1) / job.spp;
             // (6 P words are fewer than the 18 P residency was decided with, at the caller's chunk or at 16; a wider default gives way)
-            while (q.lds && q.chunk > 1 && lds_need(sc, true, count, q.block, RTD_WAVE_WORDS_CAM(q.chunk)) > RT_LDS_BYTES) q.chunk /= 2;
-            place_pass(q, sc, RTD_WAVE_WORDS_CAM(q.chunk));
-            return pl;
+            while (q.lds && q.chunk > 1 && lds_need(sc, true, count, q.block, rtmode::wave_words(q.mode, q.chunk)) > RT_LDS_BYTES) q.chunk /= 2;
         }
-        place_pass(q, sc, 0u); // no per-wave scratch in these modes
+        place_pass(q, sc); // (the ray lists: no per-wave scratch)
         return pl;
     }
     q.block = default_block(set);
-    q.mode = job.ray_log ? 3 : 0; // (the ray log of rt_scene_tune's probe: a kernel of its own)
-    if (job.list()) { // modes 6 / 7 / 8 (a pixel list: 11 / 12 / 13), built for blocks of 256 and 1024 threads only, as the ray lists are
-        q.block = q.block == 256 ? 256 : 1024;
-        q.mode = job.kind == Job::PIXELS ? 11 : 6;
-    }
+    // (the ray log of rt_scene_tune's probe: a kernel of its own, of frames only)
+    q.mode = rtmode::mode_of({job.source(), rtmode::Pass::FUSED, false, job.ray_log && !job.list()});
+    if (!rtmode::built_for_every_block(q.mode)) q.block = q.block == 256 ? 256 : 1024; // (a list: as the ray lists)
     q.tex = sc.tex;               // otherwise the variant compiled without the texture call: no scratch, no VGPR spills
     const int half = job.spp / 2;
     q.k = half < 5 ? half : 5; // min 5 (spp / 2), Scene.fs:172
@@ -195,9 +195,9 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     if (!set.chunk && set.passes != 2 && !job.extend() && job.spp <= 74) { // (below the two-pass rule's 64 samples in phase 2)
         const uint64_t px = job.pixel_count(), waves = (uint64_t) cu_count * (uint64_t) (q.block / 64);
         for (int c = 64; c > q.chunk; c /= 2)
-            if (px >= 7ull * (uint64_t) c * waves && (!q.lds || lds_need(sc, true, count, q.block, RTD_WAVE_WORDS(c)) <= RT_LDS_BYTES)) { q.chunk = c; break; }
+            if (px >= 7ull * (uint64_t) c * waves && (!q.lds || lds_need(sc, true, count, q.block, rtmode::wave_words(q.mode, c)) <= RT_LDS_BYTES)) { q.chunk = c; break; }
     }
-    place_pass(q, sc, RTD_WAVE_WORDS(q.chunk));
+    place_pass(q, sc);
     return pl;
 }
 
@@ -236,7 +236,10 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     const bool ext = pl.job.extend(); // pass B alone, from sample first_sample on: planned as this job with two passes forced
     int n2 = pl.job.spp - (ext ? pl.job.first_sample : 2 * q.k + 1);
     if (pl.job.map && n2 < 1) n2 = 1; // (a map with cap == 12 continues nothing, but still classifies every pixel and writes rgb)
-    const auto wordsB = [&](int c) { return pl.job.map ? RTD_WAVE_WORDS_MAP(c) : RTD_WAVE_WORDS(c); }; // pass B's scratch per wave
+    // (a PIXELS job by map, which no entry point makes and the table has no mode for, keeps the plan it always had: the footprints' pass B)
+    const rtmode::Pixels srcB = pl.job.map && pl.job.kind == Job::PIXELS ? rtmode::Pixels::FOOTPRINTS : pl.job.source();
+    const int modeA = rtmode::mode_of({pl.job.source(), rtmode::Pass::A}), modeB = rtmode::mode_of({srcB, rtmode::Pass::B, pl.job.map});
+    const auto wordsB = [&](int c) { return rtmode::wave_words(modeB, (uint32_t) c); }; // pass B's scratch per wave (a map's is larger)
     pl.two_pass = n2 > 0 && nLocal > 0 && nLocal < (1ull << 32) &&
                   (set.passes == 2 || ext || (set.passes == 0 && (n2 >= 128 || (n2 >= 64 && nLocal >= (1ull << 21))) && units < 64ull * fullGrid * wavesPerBlock));
     // (frames of 2 Mpx and more pay for the second launch from ~75 spp: 2401x1601 at 100 spp 23.1 Gray/s fused, 26.9 in two passes; 1201x801: 19.6 / 19.8)
@@ -264,7 +267,7 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     }
     // both passes must fit the LDS beside the scene image, decided BEFORE anything is launched (a misfit found after
     // pass A would leave a half-rendered buffer);
-    auto needA = [&](int c) { return lds_need(sc, true, q.count, q.block, RTD_WAVE_WORDS_A(c)); };
+    auto needA = [&](int c) { return lds_need(sc, true, q.count, q.block, rtmode::wave_words(modeA, (uint32_t) c)); };
     while (q.lds && chunkA > 1 && needA(chunkA) > RT_LDS_BYTES) chunkA /= 2;
     while (q.lds && chunkB > 1 && lds_need(sc, true, q.count, q.block, wordsB(chunkB)) > RT_LDS_BYTES) chunkB /= 2;
     if (q.lds && q.park > 0 && !set.chunk) { // ... and not so wide that the Lambert pool no longer fits beside them
@@ -277,13 +280,12 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     }
     pl.a = pl.b = q;
     pl.a.total_waves = pl.b.total_waves = (uint32_t) (fullGrid * wavesPerBlock);
-    const int fp = pl.job.kind == Job::FOOTPRINTS ? 6 : pl.job.kind == Job::PIXELS ? 11 : 0;
-    pl.a.mode = fp + 1; pl.a.chunk = chunkA;
-    pl.b.mode = pl.job.map ? (fp ? 10 : 9) : fp + 2; pl.b.chunk = chunkB; // (9 / 10: pass B with per-pixel ranges)
-    place_pass(pl.b, sc, wordsB(chunkB));
+    pl.a.mode = modeA; pl.a.chunk = chunkA;
+    pl.b.mode = modeB; pl.b.chunk = chunkB;
+    place_pass(pl.b, sc);
     pl.b.grid = fullGrid;                            // pass B always launches the full grid (its units shrink along the list)
     if (ext) { pl.a = Pass{}; pl.a.chunk = 0; return; } // no pass A: nothing of it is launched or reported
-    place_pass(pl.a, sc, RTD_WAVE_WORDS_A(chunkA));
+    place_pass(pl.a, sc);
     const uint64_t unitsA = (nLocal + (uint64_t) chunkA - 1) / (uint64_t) chunkA;
     const uint64_t gridA = (unitsA + wavesPerBlock - 1) / wavesPerBlock;
     pl.a.grid = gridA > fullGrid ? fullGrid : gridA; // pass A's grid is capped by its own unit count

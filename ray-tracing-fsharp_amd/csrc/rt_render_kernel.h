@@ -20,6 +20,7 @@
 #pragma once
 #include "rt_device.h"
 #include "rt_extend_map.h"
+#include "rt_modes.h"
 
 namespace rtd {
 
@@ -66,23 +67,23 @@ struct RenderParams {
     double *ray_log;               // [ray_log_cap][6]: origin, direction; null outside a probe
     unsigned int *ray_log_count;   // rays that wanted a slot (may exceed the capacity: the probe is then repeated more thinly)
     uint32_t ray_log_cap, ray_log_mask;
-    // the ray-list modes (MODE 4 / 5, run_rays; rt_trace_rays / rt_hit_objects): read only there -- and, `rays` and `ray_base`, in the
-    // footprint modes (MODE 6 / 7 / 8), where the pixels are cols = n, n_rows = 1, row_first = 0, row_stride = 1
+    // the ray-list modes (rtmode::RAYS_TRACE [4] / RAYS_HIT [5], run_rays; rt_trace_rays / rt_hit_objects): read only there -- and, `rays` and
+    // `ray_base`, in the footprint modes (FOOTPRINTS_* [6, 7, 8, 10]), where the pixels are cols = n, n_rows = 1, row_first = 0, row_stride = 1
     const double *rays;            // [ray_n][6]: origin, vector (Ray.make' is applied on the device); footprints: [n][12] origin, base, du, dv
     uint32_t *ray_rng;             // [ray_n][4]: xorshift128 states, read and written back; null: stream (seed, ray_base + i, ray_sample)
-    uint8_t *ray_colour;           // [ray_n][3] (MODE 4)
-    int32_t *ray_hit;              // [ray_n] (MODE 5): index into rt_scene_create's array, -1 none, -2 Ray.make' failed
-    double *ray_strike;            // [ray_n][3] or null (MODE 5)
-    const int32_t *obj_to_orig;    // object-table index -> index into rt_scene_create's array (MODE 5)
+    uint8_t *ray_colour;           // [ray_n][3] (RAYS_TRACE)
+    int32_t *ray_hit;              // [ray_n] (RAYS_HIT): index into rt_scene_create's array, -1 none, -2 Ray.make' failed
+    double *ray_strike;            // [ray_n][3] or null (RAYS_HIT)
+    const int32_t *obj_to_orig;    // object-table index -> index into rt_scene_create's array (RAYS_HIT)
     uint64_t ray_n, ray_base;      // (footprints: ray_base is stream_base)
     uint32_t ray_sample;
-    // an extension by map (MODE 9 / 10, rt_render_extend_map): read only there and by its list builder
+    // an extension by map (FRAME_PASS_B_MAP [9] / FOOTPRINTS_PASS_B_MAP [10], rt_render_extend_map): read only there and by its list builder
     const int32_t *ext_targets;    // [n_rows*cols]: the Count each pixel is to reach (the classes: extend_map_list_kernel)
-    // a pixel list (MODE 11 / 12 / 13, rt_render_pixels): read only there.  The list's length is ray_n; cols, max_w, max_h and the camera are
+    // a pixel list (PIXELS_* [11, 12, 13], rt_render_pixels): read only there.  The list's length is ray_n; cols, max_w, max_h and the camera are
     // the FRAME's, n_rows = 1, row_first = 0, row_stride = 1
     const int32_t *pixel_list;     // [ray_n]: global pixel indices r * cols + c of the frame; entry i owns accum[i] and rgb[i]
-    // camera hits (MODE 14, rt_camera_hits): read only there.  ray_n entries, each the frame's pixel pixel_list[i] (null: pixel i); the
-    // answers go to ray_hit / ray_strike (as MODE 5's) and cam_rays_out, at slot i * cam_n_samples + (sample - cam_sample_first)
+    // camera hits (CAMERA_HITS [14], rt_camera_hits): read only there.  ray_n entries, each the frame's pixel pixel_list[i] (null: pixel i); the
+    // answers go to ray_hit / ray_strike (as RAYS_HIT's) and cam_rays_out, at slot i * cam_n_samples + (sample - cam_sample_first)
     double *cam_rays_out;          // [ray_n * cam_n_samples][6]: the camera ray itself, origin then unit direction; or null
     int32_t cam_sample_first, cam_n_samples;
 };
@@ -95,7 +96,7 @@ struct RenderParams {
 //   cand [P][2]     the leaves the pixel's camera rays can reach, as two queue words (pixel_candidates, rt_device.h), or RTD_CAND_WALK
 //   map  [2][P] + [2][P]  pass B of an extension by map only, behind pass B's cand: per slot the first item of each pixel of the range,
 //                         then the pixel's next sample less that (run_stream<.., MAP>)
-// (RTD_WAVE_WORDS(P), RTD_WAVE_WORDS_A(P), RTD_WAVE_WORDS_MAP(P): rt_launch_consts.h)
+// (rtmode::wave_words(mode, P), rt_modes.h; the values RTD_WAVE_WORDS(P), _A, _MAP, _CAM: rt_launch_consts.h)
 
 // Wave-private LDS words: adds from many lanes may land on one word (same pixel), so they are ds_add_u32; the owner
 // lane later takes the sum and clears the word in one ds_wrxchg.  One wave's LDS operations execute in order.
@@ -111,53 +112,28 @@ RTD_INLINE uint32_t lane_rank(unsigned long long mask) { // number of set bits o
     return __builtin_amdgcn_mbcnt_hi((uint32_t) (mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) mask, 0u));
 }
 
-// F32: the LDS copy is the timed variant's -- geo | meta | node32 (stage_scene<.., true>), walked by node_loop_lds32
-template <bool LDS, bool F32 = false> RTD_INLINE SceneView<LDS> make_view(const RenderParams &p, const unsigned char *lds_base);
-template <> RTD_INLINE SceneView<true> make_view<true, false>(const RenderParams &p, const unsigned char *lds_base) {
-    SceneView<true> v;
-    const RTD_AS3 unsigned char *b = (const RTD_AS3 unsigned char *) lds_base;
-    v.node = (Ptrs<true>::bp) (b + p.off.node);
-    v.geo = (Ptrs<true>::d2p) (b + p.off.geo);
-    v.meta = (Ptrs<true>::i2p) (b + p.off.meta);
+// F32: the records are the timed variant's single-precision ones -- in LDS the copy geo | meta | node32 (stage_scene<.., true>), walked
+// by node_loop_lds32; in global memory the image's node32 section, whose links are byte offsets from its start (node_loop_glb32)
+template <bool LDS, bool F32 = false> RTD_INLINE SceneView<LDS> make_view(const RenderParams &p, const unsigned char *lds_base) {
+    SceneView<LDS> v;
+    const uint32_t nodeOff = F32 ? p.off.node32 : p.off.node;
+    if constexpr (LDS) {
+        const RTD_AS3 unsigned char *b = (const RTD_AS3 unsigned char *) lds_base;
+        if constexpr (F32) b -= p.off.geo; // the copy starts at the image's `geo` section
+        v.node = (Ptrs<true>::bp) (b + nodeOff);
+        v.geo = (Ptrs<true>::d2p) (b + p.off.geo);
+        v.meta = (Ptrs<true>::i2p) (b + p.off.meta);
+    } else {
+        const unsigned char *b = p.scene_image;
+        v.node = b + nodeOff;
+        v.geo = (const d2 *) (b + p.off.geo);
+        v.meta = (const i2 *) (b + p.off.meta);
+    }
     v.mat = (const double *) (p.scene_image + p.off.mat);
     v.n_nodes = p.off.n_nodes; v.n_bounded = p.off.n_bounded; v.n_unbounded = p.off.n_unbounded;
-    v.first = (int) (uint32_t) (uintptr_t) v.node; v.end = v.first + v.n_nodes * RTD_NODE_BYTES; // links were made absolute at staging
-    v.tex = p.tex; v.texels = p.texels; v.lds_lim = 0; v.lds_thr = 65; v.narrow = (v.n_bounded + v.n_unbounded) < 16384 ? 1 : 0;
-    return v;
-}
-template <> RTD_INLINE SceneView<true> make_view<true, true>(const RenderParams &p, const unsigned char *lds_base) {
-    SceneView<true> v;
-    const RTD_AS3 unsigned char *b = (const RTD_AS3 unsigned char *) lds_base - p.off.geo; // the copy starts at the image's `geo` section
-    v.node = (Ptrs<true>::bp) (b + p.off.node32);
-    v.geo = (Ptrs<true>::d2p) (b + p.off.geo);
-    v.meta = (Ptrs<true>::i2p) (b + p.off.meta);
-    v.mat = (const double *) (p.scene_image + p.off.mat);
-    v.n_nodes = p.off.n_nodes; v.n_bounded = p.off.n_bounded; v.n_unbounded = p.off.n_unbounded;
-    v.first = (int) (uint32_t) (uintptr_t) v.node; v.end = v.first + v.n_nodes * RTD_NODE32_BYTES;
-    v.tex = p.tex; v.texels = p.texels; v.lds_lim = 0; v.lds_thr = 65; v.narrow = (v.n_bounded + v.n_unbounded) < 16384 ? 1 : 0;
-    return v;
-}
-template <> RTD_INLINE SceneView<false> make_view<false, true>(const RenderParams &p, const unsigned char *) { // the timed variant over global memory
-    SceneView<false> v;
-    const unsigned char *b = p.scene_image;
-    v.node = b + p.off.node32; // links are byte offsets from here (node_loop_glb32)
-    v.geo = (const d2 *) (b + p.off.geo);
-    v.meta = (const i2 *) (b + p.off.meta);
-    v.mat = (const double *) (b + p.off.mat);
-    v.n_nodes = p.off.n_nodes; v.n_bounded = p.off.n_bounded; v.n_unbounded = p.off.n_unbounded;
-    v.first = 0; v.end = v.n_nodes * RTD_NODE32_BYTES;
-    v.tex = p.tex; v.texels = p.texels; v.lds_lim = 0; v.lds_thr = 65; v.narrow = (v.n_bounded + v.n_unbounded) < 16384 ? 1 : 0;
-    return v;
-}
-template <> RTD_INLINE SceneView<false> make_view<false, false>(const RenderParams &p, const unsigned char *) {
-    SceneView<false> v;
-    const unsigned char *b = p.scene_image;
-    v.node = b + p.off.node;
-    v.geo = (const d2 *) (b + p.off.geo);
-    v.meta = (const i2 *) (b + p.off.meta);
-    v.mat = (const double *) (b + p.off.mat);
-    v.n_nodes = p.off.n_nodes; v.n_bounded = p.off.n_bounded; v.n_unbounded = p.off.n_unbounded;
-    v.first = 0; v.end = v.n_nodes * RTD_NODE_BYTES;
+    if constexpr (LDS) v.first = (int) (uint32_t) (uintptr_t) v.node; // links were made absolute at staging
+    else v.first = 0;                                                 // links are byte offsets from v.node
+    v.end = v.first + v.n_nodes * (F32 ? RTD_NODE32_BYTES : RTD_NODE_BYTES);
     v.tex = p.tex; v.texels = p.texels; v.lds_lim = 0; v.lds_thr = 65; v.narrow = (v.n_bounded + v.n_unbounded) < 16384 ? 1 : 0;
     return v;
 }
@@ -208,7 +184,7 @@ enum { L_IDLE = 0, L_WALK = 1, L_DONE = 2, L_SLOW = 3, L_LAMB = 4, L_TEX = 5 };
 
 // LOG: the kernel may be asked to log rays (rt_scene_tune's probe): only the fused mode's instantiations carry that code -- the
 // log's four kernel arguments otherwise sit in scalar registers across the whole loop of the two-pass kernels, which have none to spare
-// FP: the pixels are the caller's footprints (MODE 6 / 7 / 8): a sample's ray comes from footprint_ray instead of camera_ray
+// FP: the pixels are the caller's footprints (rtmode::Pixels::FOOTPRINTS): a sample's ray comes from footprint_ray instead of camera_ray
 template <bool LDS, bool COUNT, bool TEX, bool LOG, bool FP = false>
 struct Sched {
     const RenderParams &p;
@@ -654,13 +630,13 @@ RTD_INLINE void run_items(const RenderParams &p, const SceneView<LDS> &sc, unsig
     }
 }
 
-// The ray-list modes: MODE 4 is Scene.traceRay (Scene.fs:93-114), MODE 5 Scene.hitObject (Scene.fs:62-91), for the caller's rays
+// The ray-list modes: rtmode::RAYS_TRACE is Scene.traceRay (Scene.fs:93-114), RAYS_HIT Scene.hitObject (Scene.fs:62-91), for the caller's rays
 // [0, p.ray_n).  A wave takes runs of p.chunk ray indices from the global queue -- as many runs at once as it has idle lanes for --
 // and a lane's new item is ray i: Ray.make' of the caller's (origin, vector), its rng state (the caller's, or the stream keyed
 // (seed, ray_base + i, ray_sample), as a render keys (pixel, sample)), colour White.  The walk starts at the root (no pixel
 // candidates: those are a camera's), and every stage is Sched's, so parked paths carry the ray index in slotOff as they carry a
 // pixel's accumulator word in a render.  Where a render adds an ended path's colour to its pixel, the ray's colour and final rng
-// state are stored; MODE 5 instead stores (hit, strike) once the walk and the unbounded tests are done, and shades nothing.
+// state are stored; RAYS_HIT instead stores (hit, strike) once the walk and the unbounded tests are done, and shades nothing.
 template <bool LDS, bool COUNT, bool TEX, bool HIT>
 RTD_INLINE void run_rays(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, Counters &cnt, StageStats &ss) {
     const int lane = threadIdx.x & 63;
@@ -764,9 +740,58 @@ RTD_INLINE void run_rays(const RenderParams &p, const SceneView<LDS> &sc, unsign
     }
 }
 
-// Camera hits (MODE 14, rt_camera_hits): Scene.hitObject (Scene.fs:62-91) of the ray Scene.traceOnce (Scene.fs:129-143) gives sample s
+// The set-up of a unit's pixel by lane `lane`: writes the four words pix[lane * 4 ..] (row, col, stream key lo, hi) of local pixel
+// `local` and answers, as pixel_candidates (rt_device.h) does, the pixel's two candidate words -- the first returned, the second in
+// `second` -- which the caller stores where it keeps them (pass B behind its two slots, the others at cand[lane * 2]).  The sources
+// differ only in how the global pixel g and its (r, c) are found:
+//   Pixels::FRAME       lp counts the shard's pixels row by row: image row row_first + (lp / cols) * row_stride
+//   Pixels::LIST        g = pixel_list[lp]; OPTIONAL_LIST (camera hits): a null list is every pixel of the frame, g = lp
+// (A footprint has no frame and no candidates: footprint_setup below.)
+// Three things about the form keep the callers' code as it is when the lines stand in the caller, and are to be kept: `local` comes in
+// the caller's width (pass B's list entries are 32-bit and are widened HERE, so that the division is still narrowed to 32 bits); the
+// second word lives in the caller, as pixel_candidates' own does (so a footprint, which has none, has a function of its own); each
+// store's address is formed at the store (pix and lane, not pix + lane * 4).  (profiles/r17/device_code.txt)
+template <bool LDS, bool COUNT, rtmode::Pixels SRC, bool OPTIONAL_LIST = false, typename LP>
+RTD_INLINE uint32_t pixel_setup(const RenderParams &p, const SceneView<LDS> &sc, LP local, RTD_AS3 uint32_t *pix, int lane, uint32_t &second) {
+    static_assert(SRC == rtmode::Pixels::FRAME || SRC == rtmode::Pixels::LIST, "a pixel of the frame");
+    const unsigned long long lp = (unsigned long long) local;
+    uint32_t r, c;
+    uint64_t g; // global pixel index
+    if constexpr (SRC == rtmode::Pixels::LIST) {
+        const uint32_t gl = (!OPTIONAL_LIST || p.pixel_list) ? (uint32_t) p.pixel_list[lp] : (uint32_t) lp;
+        r = gl / (uint32_t) p.cols;
+        c = gl - r * (uint32_t) p.cols;
+        g = (uint64_t) gl;
+    } else {
+        const uint32_t lr = (uint32_t) (lp / (unsigned long long) p.cols);
+        c = (uint32_t) (lp - (unsigned long long) lr * (unsigned long long) p.cols);
+        r = (uint32_t) p.row_first + lr * (uint32_t) p.row_stride;
+        g = (uint64_t) r * (uint64_t) p.cols + c;
+    }
+    const uint64_t pkey = pixel_key(p.seed_key, g);
+    pix[lane * 4 + 0] = (uint32_t) (p.max_h - (int) r - 1); // the row flipped, the column centred (Scene.fs:219,226)
+    pix[lane * 4 + 1] = (uint32_t) ((int) c - p.max_w);
+    pix[lane * 4 + 2] = (uint32_t) pkey;
+    pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
+    const CameraParams *cp = p.cam_ptr;
+    asm volatile("" : "+s"(cp)); // read the camera here: its words must not sit in SGPRs across the caller's loop
+    return pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, second);
+}
+
+// ... and of a footprint: the list index where a frame keeps (row, col), the stream of (seed, stream_base + index), and no candidates --
+// a footprint's camera rays walk the tree from the root (run_items)
+template <typename LP> RTD_INLINE void footprint_setup(const RenderParams &p, LP local, RTD_AS3 uint32_t *pix, int lane) {
+    const unsigned long long lp = (unsigned long long) local;
+    const uint64_t pkey = pixel_key(p.seed_key, p.ray_base + lp);
+    pix[lane * 4 + 0] = (uint32_t) lp;
+    pix[lane * 4 + 1] = 0u;
+    pix[lane * 4 + 2] = (uint32_t) pkey;
+    pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
+}
+
+// Camera hits (rtmode::CAMERA_HITS [14], rt_camera_hits): Scene.hitObject (Scene.fs:62-91) of the ray Scene.traceOnce (Scene.fs:129-143) gives sample s
 // of a frame's pixel, for samples [cam_sample_first, cam_sample_first + cam_n_samples) of the caller's list entries [0, p.ray_n) -- the
-// pixel modes' unit set-up feeding MODE 5's tail.  A wave takes a unit of p.chunk entries from the global queue and writes, once per
+// pixel modes' unit set-up (pixel_setup) feeding RAYS_HIT's tail.  A wave takes a unit of p.chunk entries from the global queue and writes, once per
 // entry, its pix words (row, col, stream key) and its two candidate words to the wave's scratch -- the frame's own set-up code, with
 // g = pixel_list ? pixel_list[lp] : lp -- then hands the unit's npx * cam_n_samples items to idle lanes through Sched::start_item,
 // the item's output slot in slotOff.  A started item has copied what it needs of the scratch, so the next unit is taken as soon as the
@@ -822,18 +847,8 @@ RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc,
                     __builtin_amdgcn_wave_barrier(); // (the last unit's words have all been read)
                     if ((uint32_t) lane < npx) { // a busy lane too: nothing of its path's state is touched
                         const unsigned long long lp = first + (uint32_t) lane;
-                        const uint32_t g = p.pixel_list ? (uint32_t) p.pixel_list[lp] : (uint32_t) lp;
-                        uint32_t r = g / (uint32_t) p.cols;
-                        uint32_t c = g - r * (uint32_t) p.cols;
-                        uint64_t pkey = pixel_key(p.seed_key, (uint64_t) g); // global pixel index
-                        pix[lane * 4 + 0] = (uint32_t) (p.max_h - (int) r - 1);
-                        pix[lane * 4 + 1] = (uint32_t) ((int) c - p.max_w);
-                        pix[lane * 4 + 2] = (uint32_t) pkey;
-                        pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
-                        const CameraParams *cp = p.cam_ptr;
-                        asm volatile("" : "+s"(cp));
                         uint32_t c2;
-                        const uint32_t c1 = pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, c2);
+                        const uint32_t c1 = pixel_setup<LDS, COUNT, rtmode::Pixels::LIST, true>(p, sc, lp, pix, lane, c2);
                         cand[lane * 2] = c1;
                         cand[lane * 2 + 1] = c2;
                     }
@@ -872,7 +887,7 @@ RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc,
     }
 }
 
-// Pass B (MODE 2): phase 2 for the pixels of the cost-ordered list, STREAMED.  A wave reserves a run of list entries ("range"),
+// Pass B (rtmode::Pass::B): phase 2 for the pixels of the cost-ordered list, STREAMED.  A wave reserves a run of list entries ("range"),
 // hands out its npx*n2 items, and while the last paths of that range are still in flight it already reserves the next range and
 // hands out its items: two accumulator slots alternate, a range is flushed (its sums added to what pass A left in `accum`) when
 // its last path has ended.  There is no dependency between ranges, so no lane waits at a range boundary -- which is what makes
@@ -957,43 +972,12 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                     RTD_AS3 uint32_t *pix = acc + 3u * P;
                     for (uint32_t i = (uint32_t) lane; i < 3u * P; i += 64u) acc[i] = 0u;
                     if ((uint32_t) lane < npx) {
-                        const unsigned long long lp = (unsigned long long) p.live_list[first + (uint32_t) lane];
-                        if constexpr (FP) { // the list index where a frame keeps (row, col); the stream of (seed, stream_base + index)
-                            const uint64_t pkey = pixel_key(p.seed_key, p.ray_base + lp);
-                            pix[lane * 4 + 0] = (uint32_t) lp;
-                            pix[lane * 4 + 1] = 0u;
-                            pix[lane * 4 + 2] = (uint32_t) pkey;
-                            pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
-                        } else if constexpr (PX) { // the frame's pixel the list names: its (row, col), its stream, its candidates
-                        const uint32_t g = (uint32_t) p.pixel_list[lp];
-                        uint32_t r = g / (uint32_t) p.cols;
-                        uint32_t c = g - r * (uint32_t) p.cols;
-                        uint64_t pkey = pixel_key(p.seed_key, (uint64_t) g); // global pixel index
-                        pix[lane * 4 + 0] = (uint32_t) (p.max_h - (int) r - 1);
-                        pix[lane * 4 + 1] = (uint32_t) ((int) c - p.max_w);
-                        pix[lane * 4 + 2] = (uint32_t) pkey;
-                        pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
-                        const CameraParams *cp = p.cam_ptr;
-                        asm volatile("" : "+s"(cp));
-                        uint32_t c2;
-                        const uint32_t c1 = pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, c2);
-                        wv[14u * P + (curSlot * P + lane) * 2u] = c1;
-                        wv[14u * P + (curSlot * P + lane) * 2u + 1u] = c2;
-                        } else {
-                        uint32_t lr = (uint32_t) (lp / (unsigned long long) p.cols);
-                        uint32_t c = (uint32_t) (lp - (unsigned long long) lr * (unsigned long long) p.cols);
-                        uint32_t r = (uint32_t) p.row_first + lr * (uint32_t) p.row_stride;
-                        uint64_t pkey = pixel_key(p.seed_key, (uint64_t) r * (uint64_t) p.cols + c); // global pixel index
-                        pix[lane * 4 + 0] = (uint32_t) (p.max_h - (int) r - 1);
-                        pix[lane * 4 + 1] = (uint32_t) ((int) c - p.max_w);
-                        pix[lane * 4 + 2] = (uint32_t) pkey;
-                        pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
-                        const CameraParams *cp = p.cam_ptr;
-                        asm volatile("" : "+s"(cp));
-                        uint32_t c2;
-                        const uint32_t c1 = pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, c2);
-                        wv[14u * P + (curSlot * P + lane) * 2u] = c1;
-                        wv[14u * P + (curSlot * P + lane) * 2u + 1u] = c2;
+                        if constexpr (FP) footprint_setup(p, p.live_list[first + (uint32_t) lane], pix, lane);
+                        else {
+                            uint32_t c2;
+                            const uint32_t c1 = pixel_setup<LDS, COUNT, PX ? rtmode::Pixels::LIST : rtmode::Pixels::FRAME>(p, sc, p.live_list[first + (uint32_t) lane], pix, lane, c2);
+                            wv[14u * P + (curSlot * P + lane) * 2u] = c1;
+                            wv[14u * P + (curSlot * P + lane) * 2u + 1u] = c2;
                         }
                     }
                     uint32_t total = npx * n2;
@@ -1132,38 +1116,18 @@ RTD_INLINE uint32_t stage_nodes32(const RenderParams &p, unsigned char *smem) {
     return bytes;
 }
 
-// MODE 0: fused -- a unit's pixels go through phase 1, the adaptive decision and phase 2 on one wave.
-// MODE 1: pass A -- phase 1 and the decision for every pixel; pixels that continue are appended to `pairs` with the number of
-//         rays their 2k+1 samples took (a cost estimate), the others are final.
-// MODE 2: pass B -- phase 2 for the pixels of `live_list`, which the host-side launch sequence has ordered by decreasing cost
-//         (longest job first); run_stream.
-// MODE 3: MODE 0 with the ray log of rt_scene_tune's probe compiled in (a dozen more scalar values live across the loop: kept out
-//         of the kernels that render frames).
-// MODE 4: the caller's rays through Scene.traceRay; MODE 5: the caller's rays through Scene.hitObject (run_rays).  No pixels, so no
-//         per-wave LDS scratch: the LDS holds the scene (or the top of its tree) and the Lambert pools only.
-// MODE 6 / 7 / 8: MODE 0 / 1 / 2 over a caller's footprint list (rt_render_footprints): pixel i of p.n_rows * p.cols is footprint i of
-//         p.rays ([n][12]: origin, base, du, dv), its stream that of (seed, p.ray_base + i); a sample's ray is footprint_ray's; no pixel
-//         candidates.  Everything else -- units, accumulators, the decision, the compaction, pass B's ordered list -- is the frame's.
-// MODE 9 / 10: MODE 2 / 8 with per-pixel sample ranges (run_stream<.., MAP>): pass B of an extension by map (rt_render_extend_map).
-// MODE 11 / 12 / 13: MODE 0 / 1 / 2 over a caller's list of the FRAME's pixels (rt_render_pixels): entry i of p.ray_n names the global pixel
-//         index g = p.pixel_list[i]; (row, col) = (g / cols, g % cols), the stream of (seed, g), the frame's camera_ray AND its pixel
-//         candidates -- a frame's pixel in all but where it is stored, which is slot i.  An extension is mode 13 with first_b set.
-// MODE 14: camera hits (rt_camera_hits, run_camera_hits): the first object that sample s of a listed pixel's camera ray strikes -- the pixel
-//         modes' unit set-up (pix and candidate words, 6 P words of scratch per wave) feeding MODE 5's tail; nothing is shaded.
-// Per-pixel cost is heavy-tailed (a pixel on a glass sphere: ~20 rays per sample, 4 ms of one wave), so when a shard has only a few
-// units per wave the fused kernel ends with most waves waiting for a few long units started late; A + sort + B removes that tail.
-// Every mode computes the same integers: which wave traces which sample when has no effect (streams are per item).
+// MODE: one of rtmode::Mode (rt_modes.h: the table of the fifteen modes, what each does and what follows from it).  The parameter stays
+// an int so that every kernel keeps its symbol; everything the kernel asks of it is read from the mode's description D.
 // TEX: the scene has parameterised textures (see `reflection`).
 template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX>
 __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr bool MAP = MODE == 9 || MODE == 10; // pass B of an extension by map: of a frame / of a footprint list
-    constexpr bool PX = MODE >= 11 && MODE <= 13; // the pixels are a caller's list of the frame's
-    constexpr bool CAM = MODE == 14;              // camera hits: a list of the frame's pixels, answered as MODE 5 answers rays
-    constexpr bool FP = MODE >= 6 && MODE != 9 && !PX && !CAM; // the pixels are the caller's footprints
-    constexpr int PM = MAP ? 2 : PX ? MODE - 11 : FP ? MODE - 6 : MODE; // ... and run as this pixel mode
-    constexpr bool RAYS = MODE == 4 || MODE == 5;
-    constexpr bool FUSED = PM == 0 || PM == 3;
+    constexpr rtmode::ModeDesc D = rtmode::mode_desc(MODE);
+    constexpr bool FUSED = D.pass == rtmode::Pass::FUSED, PASS_A = D.pass == rtmode::Pass::A, PASS_B = D.pass == rtmode::Pass::B;
+    constexpr bool RAYS = D.pass == rtmode::Pass::RAY_LIST, CAM = D.pass == rtmode::Pass::CAMERA_HITS;
+    constexpr bool MAP = D.map, LOG = D.ray_log;
+    constexpr bool FP = D.pixels == rtmode::Pixels::FOOTPRINTS;  // the pixels are the caller's footprints
+    constexpr bool PX = D.pixels == rtmode::Pixels::LIST && !CAM; // the pixels are a caller's list of the frame's, rendered as the frame's are
     const int lane = threadIdx.x & 63;
     // the wave's index as a SCALAR: everything derived from it (the wave's LDS scratch, its park pools) then has a scalar base, and the
     // pools' field addresses are scalar base + 32-bit lane offset instead of 64-bit vector arithmetic kept alive across the loop
@@ -1177,7 +1141,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     scv.lds_thr = p.lds_node_thr;
     const SceneView<LDS> &sc = scv;
     const uint32_t P = (uint32_t) p.chunk;
-    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * (RAYS ? 0u : CAM ? RTD_WAVE_WORDS_CAM(P) : PM == 1 ? RTD_WAVE_WORDS_A(P) : MAP ? RTD_WAVE_WORDS_MAP(P) : RTD_WAVE_WORDS(P));
+    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * rtmode::wave_words(MODE, P);
     RTD_AS3 uint32_t *acc = wv;
     RTD_AS3 uint32_t *pix = wv + 6u * P;
     RTD_AS3 uint32_t *live = pix + 4u * P;
@@ -1185,12 +1149,12 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     unsigned char *pool = p.park_pool + ((size_t) blockIdx.x * (BLOCK / 64) + (size_t) wave) * (size_t) RTD_PARK_ENTRY_BYTES *
                                         (size_t) (p.park + (p.park_l_lds ? 0 : p.park_l) + (TEX ? p.park : 0));
     // the Lambert pools in LDS (if any) follow the waves' scratch
-    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * (RAYS ? 0u : CAM ? RTD_WAVE_WORDS_CAM(P) : PM == 1 ? RTD_WAVE_WORDS_A(P) : MAP ? RTD_WAVE_WORDS_MAP(P) : RTD_WAVE_WORDS(P)) * 4u +
+    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * rtmode::wave_words(MODE, P) * 4u +
                                      (size_t) wave * (size_t) RTD_PARK_L_LDS_BYTES * (size_t) p.park_l;
 
     const uint64_t nLocal = PX ? p.ray_n : (uint64_t) p.n_rows * (uint64_t) p.cols; // (a pixel list: cols is the frame's)
     const uint32_t k = (uint32_t) p.k;
-    const uint32_t n1 = (PM == 2 && p.first_b != 0) ? (uint32_t) p.first_b : 2u * k + 1u; // (pass B of an extension starts where the buffer ends)
+    const uint32_t n1 = (PASS_B && p.first_b != 0) ? (uint32_t) p.first_b : 2u * k + 1u; // (pass B of an extension starts where the buffer ends)
     const int n2s = p.spp - (int) n1; // Scene.fs:191
     const uint32_t n2 = n2s > 0 ? (uint32_t) n2s : 0u;
 
@@ -1208,9 +1172,9 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
     uint32_t earlyCount = 0;
     uint64_t sampleCount = 0; // Scene.traceOnce calls = sum of PixelStats.Count
 
-    if constexpr (RAYS) run_rays<LDS, COUNT, TEX, MODE == 5>(p, sc, pool, poolLds, cnt, ss);
+    if constexpr (RAYS) run_rays<LDS, COUNT, TEX, D.hits>(p, sc, pool, poolLds, cnt, ss);
     else if constexpr (CAM) run_camera_hits<LDS, COUNT>(p, sc, pool, poolLds, wv, cnt, ss);
-    else if (PM == 2) run_stream<LDS, COUNT, TEX, FP, MAP, PX>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
+    else if (PASS_B) run_stream<LDS, COUNT, TEX, FP, MAP, PX>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
     else
     for (;;) {
         uint32_t unit = 0;
@@ -1222,53 +1186,22 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
 
         // per-pixel coordinates (Scene.fs:219,226) and stream key; clear the accumulators
         for (uint32_t i = (uint32_t) lane; i < 6u * P; i += 64u) acc[i] = 0u;
-        if (PM == 1 && (uint32_t) lane < P) acc[10u * P + lane] = 0u;
+        if (PASS_A && (uint32_t) lane < P) acc[10u * P + lane] = 0u;
         unsigned long long lp = 0; // local pixel of lane j < npx
         if ((uint32_t) lane < npx) {
             lp = first + (uint32_t) lane;
-            if constexpr (FP) { // a footprint list (a frame of one row): the list index where a frame keeps (row, col), the stream of
-                                // (seed, stream_base + index), and no pixel candidates -- its camera rays walk the tree (run_items)
-                const uint64_t pkey = pixel_key(p.seed_key, p.ray_base + lp);
-                pix[lane * 4 + 0] = (uint32_t) lp;
-                pix[lane * 4 + 1] = 0u;
-                pix[lane * 4 + 2] = (uint32_t) pkey;
-                pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
-            } else if constexpr (PX) { // a pixel list: the frame's pixel the entry names -- its (row, col), its stream, its candidates
-            const uint32_t g = (uint32_t) p.pixel_list[lp];
-            uint32_t r = g / (uint32_t) p.cols;
-            uint32_t c = g - r * (uint32_t) p.cols;
-            uint64_t pkey = pixel_key(p.seed_key, (uint64_t) g); // global pixel index
-            pix[lane * 4 + 0] = (uint32_t) (p.max_h - (int) r - 1);
-            pix[lane * 4 + 1] = (uint32_t) ((int) c - p.max_w);
-            pix[lane * 4 + 2] = (uint32_t) pkey;
-            pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
-            const CameraParams *cp = p.cam_ptr;
-            asm volatile("" : "+s"(cp));
-            uint32_t c2;
-            const uint32_t c1 = pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, c2);
-            cand[lane * 2] = c1;
-            cand[lane * 2 + 1] = c2;
-            } else {
-            uint32_t lr = (uint32_t) (lp / (unsigned long long) p.cols);
-            uint32_t c = (uint32_t) (lp - (unsigned long long) lr * (unsigned long long) p.cols);
-            uint32_t r = (uint32_t) p.row_first + lr * (uint32_t) p.row_stride;
-            uint64_t pkey = pixel_key(p.seed_key, (uint64_t) r * (uint64_t) p.cols + c); // global pixel index
-            pix[lane * 4 + 0] = (uint32_t) (p.max_h - (int) r - 1);
-            pix[lane * 4 + 1] = (uint32_t) ((int) c - p.max_w);
-            pix[lane * 4 + 2] = (uint32_t) pkey;
-            pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
-            const CameraParams *cp = p.cam_ptr;
-            asm volatile("" : "+s"(cp));
-            uint32_t c2;
-            const uint32_t c1 = pixel_candidates<LDS, !COUNT>(sc, *cp, p.max_h - (int) r - 1, (int) c - p.max_w, c2);
-            cand[lane * 2] = c1;
-            cand[lane * 2 + 1] = c2;
+            if constexpr (FP) footprint_setup(p, lp, pix, lane);
+            else {
+                uint32_t c2;
+                const uint32_t c1 = pixel_setup<LDS, COUNT, D.pixels>(p, sc, lp, pix, lane, c2);
+                cand[lane * 2] = c1;
+                cand[lane * 2 + 1] = c2;
             }
         }
         __builtin_amdgcn_wave_barrier();
 
         // ---- phase 1: 2k+1 samples per pixel, sums split after sample k (Scene.fs:172-182) ----
-        run_items<LDS, COUNT, PM == 1, TEX, PM == 3, FP>(p, sc, pool, poolLds, acc, pix, cand, live, false, npx * n1, n1, 0u, k + 1u, cnt, ss);
+        run_items<LDS, COUNT, PASS_A, TEX, LOG, FP>(p, sc, pool, poolLds, acc, pix, cand, live, false, npx * n1, n1, 0u, k + 1u, cnt, ss);
         __builtin_amdgcn_wave_barrier();
 
         // ---- decide (Scene.fs:177-188) and compact the pixels that continue ----
@@ -1303,7 +1236,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
 
         // ---- phase 2: the remaining spp-2k-1 samples of the surviving pixels (Scene.fs:191-192) ----
         if (FUSED && nLive > 0u) {
-            run_items<LDS, COUNT, false, TEX, PM == 3, FP>(p, sc, pool, poolLds, acc, pix, cand, live, true, nLive * n2, n2, n1, 0xFFFFFFFFu, cnt, ss);
+            run_items<LDS, COUNT, false, TEX, LOG, FP>(p, sc, pool, poolLds, acc, pix, cand, live, true, nLive * n2, n2, n1, 0xFFFFFFFFu, cnt, ss);
             __builtin_amdgcn_wave_barrier();
         }
 
@@ -1364,7 +1297,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
             atomicAdd(&p.counters[31], ss.tLamb);
             if (!COUNT) { atomicAdd(&p.counters[14], ss.loopTrips); atomicAdd(&p.counters[15], ss.loopLanes); } // (the counting variant keeps its wave lifetimes there)
 #ifdef RTD_STAGE_CLOCKS
-            if (!COUNT && PM == 2) { // the census describes pass B's timed kernel
+            if (!COUNT && PASS_B) { // the census describes pass B's timed kernel
                 const uint32_t cz[16] = {ss.turns, ss.lambBatches, ss.lambLanes, ss.newRefills, ss.newItems, ss.unparkL, ss.unparkA, ss.storeBlocksL, ss.storeLanesL,
                                          ss.storeBlocksA, ss.lightBatches, ss.lightLanes, ss.missLanes, ss.ranges, ss.flushes, ss.leafLanes};
                 for (int i = 0; i < 16; ++i) atomicAdd(&g_census[i], (unsigned long long) cz[i]);

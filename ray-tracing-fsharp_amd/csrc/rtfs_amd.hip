@@ -203,13 +203,11 @@ static int allow_full_lds(const void *fn) {
     try { done.insert({fn, device}); } catch (const std::bad_alloc &) {} // (set again next time)
     return RT_OK;
 }
-// The SET of instantiated render_kernel<...> is part of the build (compile time, code size): the ray-list modes 4 and 5 exist for
-// blocks of 256 and 1024 threads only, and the hit queries (mode 5) shade nothing, so they have no textured variant.  The plan
-// never asks for one of the others; if it did, the launch fails (no kernel is substituted).
+// The SET of instantiated render_kernel<...> is part of the build (compile time, code size): rtmode::is_built (rt_modes.h) says which
+// (mode, block, tex) exist.  The plan never asks for one of the others; if it did, the launch fails (no kernel is substituted).
 template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX> static render_fn kernel_if_built() {
-    if constexpr ((MODE >= 4 && MODE != 9 && BLOCK != 256 && BLOCK != 1024) || ((MODE == 5 || MODE == 14) && TEX)) return nullptr; // (the footprint modes 6-8 and 10, the pixel-list modes 11-13 and the
-                                                                                                                        // camera hits, mode 14 (untextured, as mode 5): as the ray lists; mode 9 runs frames: every block, as mode 2)
-    else return render_kernel<LDS, COUNT, BLOCK, MODE, TEX>;
+    if constexpr (rtmode::is_built(MODE, BLOCK, TEX)) return render_kernel<LDS, COUNT, BLOCK, MODE, TEX>;
+    else return nullptr;
 }
 template <int BLOCK, int MODE, bool TEX> static render_fn pick_variant(bool lds, bool count) {
     if (lds) return count ? kernel_if_built<true, true, BLOCK, MODE, TEX>() : kernel_if_built<true, false, BLOCK, MODE, TEX>();
@@ -219,26 +217,11 @@ template <int MODE, bool TEX> static render_fn pick_mode(const rtp::Pass &q) {
     return q.block == 1024 ? pick_variant<1024, MODE, TEX>(q.lds, q.count) : q.block == 768 ? pick_variant<768, MODE, TEX>(q.lds, q.count) :
            q.block == 512  ? pick_variant<512, MODE, TEX>(q.lds, q.count)  : pick_variant<256, MODE, TEX>(q.lds, q.count);
 }
-// tex: the scene has parameterised textures (otherwise the variant compiled without the texture call: no scratch, no VGPR spills)
-static render_fn pick_kernel(const rtp::Pass &q) {
-    switch (q.mode) {
-    case 0: return q.tex ? pick_mode<0, true>(q) : pick_mode<0, false>(q);
-    case 1: return q.tex ? pick_mode<1, true>(q) : pick_mode<1, false>(q);
-    case 2: return q.tex ? pick_mode<2, true>(q) : pick_mode<2, false>(q);
-    case 3: return q.tex ? pick_mode<3, true>(q) : pick_mode<3, false>(q);
-    case 4: return q.tex ? pick_mode<4, true>(q) : pick_mode<4, false>(q);
-    case 5: return q.tex ? nullptr : pick_mode<5, false>(q);
-    case 6: return q.tex ? pick_mode<6, true>(q) : pick_mode<6, false>(q);
-    case 7: return q.tex ? pick_mode<7, true>(q) : pick_mode<7, false>(q);
-    case 8: return q.tex ? pick_mode<8, true>(q) : pick_mode<8, false>(q);
-    case 9: return q.tex ? pick_mode<9, true>(q) : pick_mode<9, false>(q);
-    case 10: return q.tex ? pick_mode<10, true>(q) : pick_mode<10, false>(q);
-    case 11: return q.tex ? pick_mode<11, true>(q) : pick_mode<11, false>(q);
-    case 12: return q.tex ? pick_mode<12, true>(q) : pick_mode<12, false>(q);
-    case 13: return q.tex ? pick_mode<13, true>(q) : pick_mode<13, false>(q);
-    case 14: return q.tex ? nullptr : pick_mode<14, false>(q);
-    default: return nullptr;
-    }
+// q.mode against every mode of the table in turn.  tex: the scene has parameterised textures (otherwise the variant compiled without
+// the texture call: no scratch, no VGPR spills)
+template <int MODE = rtmode::FRAME_FUSED> static render_fn pick_kernel(const rtp::Pass &q) {
+    if constexpr (MODE < rtmode::MODE_COUNT) return q.mode == MODE ? (q.tex ? pick_mode<MODE, true>(q) : pick_mode<MODE, false>(q)) : pick_kernel<MODE + 1>(q);
+    else return nullptr;
 }
 
 // Per-launch scratch, stream-ordered (hipMallocAsync on the launch stream), RT_SCRATCH_BYTES of it; the launch's workspace (pass B's
@@ -1100,16 +1083,16 @@ int rt_render(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int
 } // extern "C"
 
 // ------------------------------------------------------------------------------------------------------------
-// ray lists: the caller's rays through Scene.traceRay / Scene.hitObject (render_kernel MODE 4 / MODE 5, run_rays)
+// ray lists: the caller's rays through Scene.traceRay / Scene.hitObject (rtmode::RAYS_TRACE [4] / RAYS_HIT [5], run_rays)
 // ------------------------------------------------------------------------------------------------------------
 struct RayJob {
-    bool hit;            // MODE 5 (hit queries) or MODE 4 (paths)
+    bool hit;            // RAYS_HIT (hit queries) or RAYS_TRACE (paths)
     size_t n;
     const void *rays;    // [n][6] doubles
-    void *rng;           // [n][4] uint32 or null (MODE 4)
-    void *colour;        // [n][3] uint8 (MODE 4)
-    void *hit_index;     // [n] int32 (MODE 5)
-    void *strike;        // [n][3] doubles or null (MODE 5)
+    void *rng;           // [n][4] uint32 or null (RAYS_TRACE)
+    void *colour;        // [n][3] uint8 (RAYS_TRACE)
+    void *hit_index;     // [n] int32 (RAYS_HIT)
+    void *strike;        // [n][3] doubles or null (RAYS_HIT)
     uint64_t seed = 0, stream_base = 0;
     uint32_t sample = 0;
     int32_t depth = 0;
@@ -1206,7 +1189,7 @@ int rt_trace_rays_device(const rt_scene *scene, int32_t device, size_t n, const 
 } // extern "C"
 
 // ------------------------------------------------------------------------------------------------------------
-// footprints: Scene.renderPixel over the caller's pixels, each with a camera of its own (render_kernel MODE 6 / 7 / 8)
+// footprints: Scene.renderPixel over the caller's pixels, each with a camera of its own (rtmode::FOOTPRINTS_* [6, 7, 8])
 // ------------------------------------------------------------------------------------------------------------
 // Every argument check of the two footprint entry points, made before anything touches a device.
 static int check_footprints(const rt_scene *scene, size_t n, const void *footprints, const void *accum, int32_t spp, int32_t bounce_depth,
@@ -1331,7 +1314,7 @@ int rt_render_footprints_extend(const rt_scene *scene, int32_t device, size_t n,
 // ------------------------------------------------------------------------------------------------------------
 // extending by map (DESIGN.md "Extending by map"): every pixel from its stored Count to a target of its own.  The cap -- the camera's
 // (footprints: the argument's) samples_per_pixel -- bounds every target.  Planned and launched as the extension 12 -> cap, with the
-// map's list builder and pass B's per-pixel variant (render_kernel MODE 9 / 10).
+// map's list builder and pass B's per-pixel variant (rtmode::FRAME_PASS_B_MAP [9] / FOOTPRINTS_PASS_B_MAP [10]).
 // ------------------------------------------------------------------------------------------------------------
 static int check_extend_map(int32_t cap, size_t pixels, const void *targets) {
     if (cap < RTD_EXTEND_MIN_DONE)
@@ -1392,7 +1375,7 @@ int rt_render_footprints_extend_map(const rt_scene *scene, int32_t device, size_
 
 // ------------------------------------------------------------------------------------------------------------
 // pixel lists (DESIGN.md "Pixel lists"): Scene.renderPixel (Scene.fs:157-194) over a caller's list of the FRAME's pixels, outputs in list
-// order (render_kernel MODE 11 / 12 / 13)
+// order (rtmode::PIXELS_* [11, 12, 13])
 // ------------------------------------------------------------------------------------------------------------
 // Every argument check the four entry points share, made before anything touches a device.
 static int check_pixels(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, size_t n, const void *pixels, const void *accum,
@@ -1482,7 +1465,7 @@ int rt_render_pixels_extend(const rt_scene *scene, const rt_camera *camera, int3
 
 // ------------------------------------------------------------------------------------------------------------
 // camera hits (DESIGN.md "Camera hits"): Scene.hitObject (Scene.fs:62-91) of the ray sample s of a frame's pixel starts with
-// (Scene.traceOnce, Scene.fs:129-143), for a caller's list of pixels and a range of samples (render_kernel MODE 14)
+// (Scene.traceOnce, Scene.fs:129-143), for a caller's list of pixels and a range of samples (rtmode::CAMERA_HITS [14])
 // ------------------------------------------------------------------------------------------------------------
 #define RT_CAMERA_HITS_MAX_SAMPLE 8000000 /* sample_first + n_samples at most: the cap of the map calls (check_geometry's samples_per_pixel) */
 // Every argument check the two entry points share, made before anything touches a device.
@@ -1503,7 +1486,7 @@ static int check_camera_hits(const rt_scene *scene, const rt_camera *camera, int
 }
 
 // Enqueues the one launch on `stream` (n > 0, arguments checked): the frame's camera, geometry and seed, the list (or none), the sample
-// range and the outputs, as MODE 5's where they are MODE 5's; then enqueue(), which checks a device list in front of the launch.
+// range and the outputs, as RAYS_HIT's where they are RAYS_HIT's; then enqueue(), which checks a device list in front of the launch.
 static int launch_camera_hits(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
                               const void *d_pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, void *d_hit_index, void *d_strike,
                               void *d_rays_out, void *stream, const rt_render_options *options, bool want_stats, Pending &pd) {

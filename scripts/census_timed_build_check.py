@@ -17,7 +17,7 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import instruction_census as ic  # noqa: E402
 
-HEADERS = ("rt_device.h", "rt_render_kernel.h", "rt_launch_consts.h", "rt_scene.h", "rt_trig.h", "rt_trig_tables.h")
+HEADERS = ("rt_device.h", "rt_render_kernel.h", "rt_launch_consts.h", "rt_modes.h", "rt_extend_map.h", "rt_scene.h", "rt_trig.h", "rt_trig_tables.h")
 
 
 def strip_diag(text):

@@ -321,8 +321,9 @@ def assign(bl):
                 if st != stage:
                     after_loop = False
                 stage = st
-        if f in ("run_stream", "lds_take", "lds_add", "add_result") and stage not in ("prologue", "refill", "epilogue"):
-            stage = "loop"  # (run_stream's own lines inside the refill are the item arithmetic: they stay with the refill)
+        if f in ("run_stream", "pixel_setup", "footprint_setup", "lds_take", "lds_add", "add_result") and stage not in ("prologue", "refill", "epilogue"):
+            stage = "loop"  # (run_stream's own lines inside the refill are the item arithmetic: they stay with the refill;
+                            #  pixel_setup's and footprint_setup's lines were run_stream's until they became functions, and are counted as they were)
         if f in ("node_loop_lds32", "pk"):
             after_loop = True
         hit = None
@@ -345,7 +346,7 @@ def assign(bl):
         if hit is None:
             # code of helper functions (dot, walk, unitise, math) inherits the group of the block before it inside the same stage
             prev = next((x for x in reversed(out) if x[1] != "guarded_arms"), None)  # (an arm does not hand its group on)
-            if prev and prev[2] == stage and f not in [m[0] for m in STAGE_MARKERS] and f not in ("run_stream",):
+            if prev and prev[2] == stage and f not in [m[0] for m in STAGE_MARKERS] and f not in ("run_stream", "pixel_setup", "footprint_setup"):
                 hit = prev[:2]
             else:
                 hit = STAGE_DEFAULT[stage]

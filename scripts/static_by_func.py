@@ -9,12 +9,15 @@ root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ray-traci
 src = {f: open(os.path.join(root, f)).read().splitlines() for f in ("rt_device.h", "rt_render_kernel.h")}
 
 
+SAME_GROUP = {"pixel_setup": "run_stream", "footprint_setup": "run_stream"}  # a unit's pixel set-up: pass B's own lines until they became functions
+
+
 def func_of(f, l):
     L = src[f]
     for i in range(l - 1, -1, -1):
         m = re.match(r"^\s{0,4}(?:template.*>\s*)?(?:RTD_INLINE|__device__|__global__|__host__)[^;]*?(\w+)\(", L[i])
         if m:
-            return m.group(1)
+            return SAME_GROUP.get(m.group(1), m.group(1))
     return "?"
 
 
