@@ -585,6 +585,19 @@ int64_t rt_format_pixel_map(const uint8_t *rgb, int32_t rows, int32_t cols, uint
  * (may be NULL); a truncated tail is ignored as in the reference.  Returns the pixel count, or a negative status. */
 int64_t rt_parse_pixel_map(const uint8_t *data, size_t n, int32_t rows, int32_t cols, uint8_t *rgb_out, uint8_t *present_out);
 
+/* Png.write gammaCorrect pixels file (ImageOutput.fs:214-251; Program.fs:50 is its caller): the reference hands PixelOutput.toSkia
+ * colours (ImageOutput.fs:32-39: R, G, B after PixelOutput.correct or as they are, alpha 255) to Skia's PNG encoder.  Those encoded
+ * bytes cannot be reproduced; PNG is lossless, so the PIXELS are pinned -- any conforming decoder returns exactly those colours -- and
+ * the container bytes are defined here (csrc/rt_png.h): colour type 2 (8-bit RGB, no alpha channel: a decoder reports the image as
+ * opaque), every row Sub-filtered, ONE IDAT of run-length deflate blocks of rt_png_tile_bytes() filtered bytes each.
+ * RT_ERR_INVALID_ARGUMENT as rt_write_ppm; RT_ERR_UNSUPPORTED for an image whose worst-case IDAT would not fit a 31-bit chunk length. */
+int rt_write_png(const char *path, const uint8_t *rgb, int32_t rows, int32_t cols, int32_t gamma_correct);
+/* Same bytes into a caller buffer; returns the length, or a negative status.  out == NULL: the length only.  A capacity below the
+ * length: -RT_ERR_INVALID_ARGUMENT and nothing written.  Works without a GPU. */
+int64_t rt_format_png(const uint8_t *rgb, int32_t rows, int32_t cols, int32_t gamma_correct, uint8_t *out, size_t out_capacity);
+/* Filtered bytes per tile = per deflate block (RTO_PNG_TILE_BYTES). */
+int32_t rt_png_tile_bytes(void);
+
 /* ---- Output side, on the device: the same bytes from an image that is already there (DESIGN.md "Output on the device") ----
  * d_rgb is rows*cols*3 uint8 on `device` (rt_render_device's d_rgb, a torch tensor's data_ptr()); d_rgb and d_out may have any byte
  * alignment.  Everything is enqueued on `stream` (NULL = the null stream) with stream-ordered scratch: any number of calls may be
@@ -597,6 +610,10 @@ int64_t rt_ppm_max_bytes(int32_t rows, int32_t cols);
 /* EXACT length of rt_format_pixel_map's output, in closed form (no image needed: lengths depend on (row, col) alone,
  * ImageOutput.fs:115-161).  Negative status as rt_ppm_max_bytes. */
 int64_t rt_pixel_map_bytes(int32_t rows, int32_t cols);
+/* Upper bound on rt_format_png's length, in closed form: the file of an image whose every tile is a stored block,
+ * 68 + rows*(1+3*cols) + 5*ceil(rows*(1+3*cols) / rt_png_tile_bytes()); reached exactly by such an image.  Negative status as
+ * rt_ppm_max_bytes, and -RT_ERR_UNSUPPORTED where rt_format_png says so. */
+int64_t rt_png_max_bytes(int32_t rows, int32_t cols);
 
 /* PixelOutput.correct (ImageOutput.fs:11-18) over n bytes on the device; d_out may equal d_in.  RT_ERR_INVALID_ARGUMENT for a NULL
  * pointer with n > 0; n = 0 is a no-op. */
@@ -619,10 +636,22 @@ int rt_format_ppm_device(int32_t device, const void *d_rgb, int32_t rows, int32_
 int rt_format_pixel_map_device(int32_t device, const void *d_rgb, int32_t rows, int32_t cols,
                                void *d_out, size_t out_capacity, void *d_length, void *stream, int64_t *length);
 
+/* rt_format_png's bytes (Png.write, ImageOutput.fs:32-39,214-251) from a device image into a device buffer: exactly the contract of
+ * rt_format_ppm_device above -- alignment, d_length, length, d_out == NULL, the capacity found on the device -- and RT_ERR_UNSUPPORTED
+ * as rt_format_png, after the argument checks.  Four launches on `stream` (csrc/rt_png_kernels.h). */
+int rt_format_png_device(int32_t device, const void *d_rgb, int32_t rows, int32_t cols, int32_t gamma_correct,
+                         void *d_out /* may be NULL: length only */, size_t out_capacity,
+                         void *d_length /* int64 on the device, may be NULL */, void *stream,
+                         int64_t *length /* host; may be NULL */);
+
 /* ImageOutput.writePpm (ImageOutput.fs:163-197) from a device image: format on the device, ONE device-to-host copy of exactly the
  * text, write.  Synchronises.  Arguments are checked (as above, and a NULL path), then the file is opened -- RT_ERR_IO before any
  * device work when that fails -- then the device runs; a short write is RT_ERR_IO, as in rt_write_ppm. */
 int rt_write_ppm_device(const char *path, int32_t device, const void *d_rgb, int32_t rows, int32_t cols,
+                        int32_t gamma_correct, void *stream);
+/* Png.write (ImageOutput.fs:214-251) from a device image: rt_write_ppm_device with rt_format_png_device's bytes -- the same checks in the
+ * same order, the file opened before any device work, a device buffer of rt_png_max_bytes, ONE device-to-host copy of exactly the file. */
+int rt_write_png_device(const char *path, int32_t device, const void *d_rgb, int32_t rows, int32_t cols,
                         int32_t gamma_correct, void *stream);
 
 /* Scene.render |> ImageOutput.writePpm (Scene.fs:196-236, ImageOutput.fs:163-197): the whole frame rendered, formatted and written;
@@ -631,6 +660,11 @@ int rt_write_ppm_device(const char *path, int32_t device, const void *d_rgb, int
  * file (RT_ERR_IO before any device work), renders on the null stream, formats, copies the text out and writes it.
  * stats (may be NULL) as rt_render fills them: kernel_ms = the render kernel; total_ms = the whole call, file included. */
 int rt_render_ppm(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                  uint64_t seed, int32_t device, uint32_t flags, int32_t gamma_correct, const char *path,
+                  const rt_render_options *options, rt_stats *stats);
+/* Scene.render |> Png.write (Program.fs:47-50, ImageOutput.fs:214-251): rt_render_ppm with the PNG; the file is byte for byte
+ * rt_format_png of rt_render's rgb for the same arguments. */
+int rt_render_png(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
                   uint64_t seed, int32_t device, uint32_t flags, int32_t gamma_correct, const char *path,
                   const rt_render_options *options, rt_stats *stats);
 

@@ -44,6 +44,7 @@
 #define RTO_MAP_PIXEL_BYTES 25  /* ten digits, ',', ten digits, '\n', three colour bytes */
 #define RTO_SCAN_THREADS 1024   /* tile sums per trip of the one scanning workgroup: trips begin at RTO_SCAN_THREADS * RTO_TILE_PIXELS = 2^20 pixels */
 #define RTO_SCRATCH_HEAD 16     /* struct FormatScratch; one uint64 per tile follows */
+#define RTO_PNG_TILE_BYTES 16384 /* filtered bytes of a PNG tile = one deflate block (rt_png.h): 64 per thread; 16 KiB staged in, at most 16 KiB + 5 out */
 
 // ---- host side ----
 // LDS budget: 160 KiB per CU (MI355X_MICROARCH.md); the LDS part of the scene image plus every wave's scratch must fit one workgroup.

@@ -5,6 +5,7 @@
 #include "rt_device.h"
 #include "rt_launch_plan.h"
 #include "rt_output.h"
+#include "rt_png_kernels.h"
 #include "rt_render_kernel.h"
 #include "rt_scene.h"
 
@@ -1812,13 +1813,66 @@ int rt_write_ppm(const char *path, const uint8_t *rgb, int32_t rows, int32_t col
 
 } // extern "C"
 
+static int check_image_size(int32_t rows, int32_t cols);
+static int check_png_size(int32_t rows, int32_t cols) { // after check_image_size
+    if (!rtp::supported((uint64_t) rows, (uint64_t) cols)) return fail(RT_ERR_UNSUPPORTED, "an image whose PNG data may pass 2^31 - 1 bytes");
+    return RT_OK;
+}
+static void fill_gamma(uint8_t *t, bool gamma) { // the ONE definition, rth::gamma_correct, tabulated; the identity when gamma is off
+    for (int i = 0; i < 256; ++i) t[i] = gamma ? rth::gamma_correct((uint8_t) i) : (uint8_t) i;
+}
+// Png.write's file (rt_png.h) of a host image
+static std::vector<uint8_t> host_png(const uint8_t *rgb, int32_t rows, int32_t cols, bool gamma) {
+    uint8_t table[256];
+    fill_gamma(table, gamma);
+    std::vector<uint8_t> file((size_t) rtp::max_bytes((uint64_t) rows, (uint64_t) cols));
+    file.resize((size_t) rtp::format_png(rgb, (uint32_t) rows, (uint32_t) cols, table, file.data()));
+    return file;
+}
+
+extern "C" {
+
+int64_t rt_format_png(const uint8_t *rgb, int32_t rows, int32_t cols, int32_t gamma_correct, uint8_t *out, size_t out_capacity) {
+    if (!rgb) { fail(RT_ERR_INVALID_ARGUMENT, "bad image"); return -RT_ERR_INVALID_ARGUMENT; }
+    if (check_image_size(rows, cols) != RT_OK) return -RT_ERR_INVALID_ARGUMENT;
+    if (check_png_size(rows, cols) != RT_OK) return -RT_ERR_UNSUPPORTED;
+    return guarded<int64_t>("rt_format_png", [&]() {
+        const std::vector<uint8_t> file = host_png(rgb, rows, cols, gamma_correct != 0);
+        if (out && out_capacity < file.size()) { // nothing is written
+            fail(RT_ERR_INVALID_ARGUMENT, "out_capacity " + std::to_string(out_capacity) + " below the " + std::to_string(file.size()) + " bytes needed");
+            return (int64_t) -RT_ERR_INVALID_ARGUMENT;
+        }
+        if (out) memcpy(out, file.data(), file.size());
+        return (int64_t) file.size();
+    }, -RT_ERR_HOST);
+}
+
+int rt_write_png(const char *path, const uint8_t *rgb, int32_t rows, int32_t cols, int32_t gamma_correct) {
+    if (!path || !rgb) return fail(RT_ERR_INVALID_ARGUMENT, "bad image or path");
+    RT_TRY(check_image_size(rows, cols));
+    RT_TRY(check_png_size(rows, cols));
+    return guarded("rt_write_png", [&]() {
+        const std::vector<uint8_t> file = host_png(rgb, rows, cols, gamma_correct != 0);
+        FILE *f = fopen(path, "wb");
+        if (!f) return fail(RT_ERR_IO, std::string("cannot open ") + path);
+        const size_t w = fwrite(file.data(), 1, file.size(), f);
+        const int c = fclose(f);
+        if (w != file.size() || c != 0) return fail(RT_ERR_IO, std::string("short write to ") + path);
+        return (int) RT_OK;
+    });
+}
+
+int32_t rt_png_tile_bytes(void) { return RTO_PNG_TILE_BYTES; }
+
+} // extern "C"
+
 // ------------------------------------------------------------------------------------------------------------
 // output on the device (rt_output.h): the same bytes as rth::format_ppm / rth::format_pixel_map, from an image that is already there
 // ------------------------------------------------------------------------------------------------------------
 namespace {
 
 struct FormatJob {
-    int fmt; // rto::FMT_PPM or rto::FMT_MAP
+    int fmt; // rto::FMT_PPM, rto::FMT_MAP or rto::FMT_PNG
     const void *d_rgb;
     int32_t rows, cols;
     bool gamma;
@@ -1861,9 +1915,9 @@ static rto::PpmHeader ppm_header(int32_t rows, int32_t cols) { // "P3\n<cols> <r
     h.len = (uint32_t) snprintf((char *) h.text, sizeof(h.text), "P3\n%d %d\n255\n", cols, rows);
     return h;
 }
-static rto::GammaTable gamma_table(bool gamma) { // the ONE definition, rth::gamma_correct, tabulated; the identity when gamma is off
+static rto::GammaTable gamma_table(bool gamma) {
     rto::GammaTable t;
-    for (int i = 0; i < 256; ++i) t.v[i] = gamma ? rth::gamma_correct((uint8_t) i) : (uint8_t) i;
+    fill_gamma(t.v, gamma);
     return t;
 }
 static int64_t ascii_int_digits_below(int64_t n) { // sum of writeAsciiInt's digit counts over 0 .. n-1 (0 has none): sum over k of max(0, n - 10^k)
@@ -1872,10 +1926,36 @@ static int64_t ascii_int_digits_below(int64_t n) { // sum of writeAsciiInt's dig
     return sum;
 }
 
+// The PNG of rt_png.h (rt_png_kernels.h): sums, the same scan over the tiles and the file's tail, and -- when there is a buffer -- scatter
+// and finish.  Scratch: the head, one uint64 per tile and one for the tail, one PngPartial per tile.
+static int enqueue_png(const FormatJob &j, hipStream_t st, FormatPending &fp) {
+    const uint32_t N = (uint32_t) rtp::filtered_bytes((uint64_t) j.rows, (uint64_t) j.cols), n_tiles = (uint32_t) rtp::tile_count((uint64_t) j.rows, (uint64_t) j.cols);
+    const size_t parts_at = RTO_SCRATCH_HEAD + ((size_t) n_tiles + 1u) * sizeof(unsigned long long);
+    HIP_TRY(hipMallocAsync((void **) &fp.scr, parts_at + (size_t) n_tiles * sizeof(rto::PngPartial), st));
+    fp.st = st;
+    rto::FormatScratch *head = (rto::FormatScratch *) fp.scr;
+    unsigned long long *tiles = (unsigned long long *) (fp.scr + RTO_SCRATCH_HEAD);
+    rto::PngPartial *parts = (rto::PngPartial *) (fp.scr + parts_at);
+    const unsigned char *rgb = (const unsigned char *) j.d_rgb;
+    const rto::GammaTable g = gamma_table(j.gamma);
+    hipLaunchKernelGGL(rto::png_sums_kernel, dim3(n_tiles), dim3(RTO_BLOCK), 0, st, rgb, N, (uint32_t) j.cols, g, tiles, n_tiles);
+    hipLaunchKernelGGL(rto::format_scan_kernel, dim3(1), dim3(RTO_SCAN_THREADS), 0, st, tiles, n_tiles + 1u, (unsigned long long) rtp::HEAD_BYTES, head,
+                       (long long *) j.d_length, (unsigned long long) j.capacity, j.d_out ? 1 : 0);
+    if (j.d_out) {
+        hipLaunchKernelGGL(rto::png_scatter_kernel, dim3(n_tiles), dim3(RTO_BLOCK), 0, st, rgb, N, (uint32_t) j.cols, g, (const unsigned long long *) tiles,
+                           (const rto::FormatScratch *) head, parts, (unsigned char *) j.d_out);
+        hipLaunchKernelGGL(rto::png_finish_kernel, dim3(1), dim3(RTO_BLOCK), 0, st, (uint32_t) j.rows, (uint32_t) j.cols, N, (const unsigned long long *) tiles, n_tiles,
+                           (const rto::FormatScratch *) head, (const rto::PngPartial *) parts, (unsigned char *) j.d_out);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
 // Enqueues one format on `stream` (arguments checked, the device current): sums, scan and -- when there is a buffer -- the scatter.
 // Never waits for the device.
 static int enqueue_format(const FormatJob &j, void *stream, FormatPending &fp) {
     hipStream_t st = (hipStream_t) stream;
+    if (j.fmt == rto::FMT_PNG) return enqueue_png(j, st, fp);
     const uint32_t npx = (uint32_t) ((uint64_t) j.rows * (uint64_t) j.cols);
     const uint32_t n_tiles = (npx + (uint32_t) RTO_TILE_PIXELS - 1u) / (uint32_t) RTO_TILE_PIXELS;
     HIP_TRY(hipMallocAsync((void **) &fp.scr, RTO_SCRATCH_HEAD + (size_t) n_tiles * sizeof(unsigned long long), st));
@@ -1922,11 +2002,11 @@ static int run_format(int32_t device, const FormatJob &j, void *stream, int64_t 
     RT_TRY(enqueue_format(j, stream, fp));
     return length ? finish_format(fp, j, length) : RT_OK;
 }
-// The P3 text of a device image in host memory (the device current): a device buffer of rt_ppm_max_bytes from the stream's pool, the
-// format, and ONE device-to-host copy of exactly the text.  Waits for the stream.
-static int ppm_to_host(const void *d_rgb, int32_t rows, int32_t cols, bool gamma, hipStream_t st, unsigned char *d_text, size_t capacity,
-                       std::unique_ptr<char[]> &text, int64_t &len) {
-    const FormatJob j{rto::FMT_PPM, d_rgb, rows, cols, gamma, d_text, capacity, nullptr};
+// The P3 text or the PNG of a device image in host memory (the device current): a device buffer of rt_ppm_max_bytes / rt_png_max_bytes from
+// the stream's pool, the format, and ONE device-to-host copy of exactly the file.  Waits for the stream.
+static int file_to_host(int fmt, const void *d_rgb, int32_t rows, int32_t cols, bool gamma, hipStream_t st, unsigned char *d_text, size_t capacity,
+                        std::unique_ptr<char[]> &text, int64_t &len) {
+    const FormatJob j{fmt, d_rgb, rows, cols, gamma, d_text, capacity, nullptr};
     FormatPending fp;
     RT_TRY(enqueue_format(j, st, fp));
     RT_TRY(finish_format(fp, j, &len));
@@ -1943,11 +2023,78 @@ static int write_all(FileCloser &file, const char *path, const char *text, int64
     return RT_OK;
 }
 
+static int64_t file_max_bytes(int fmt, int32_t rows, int32_t cols); // rt_ppm_max_bytes / rt_png_max_bytes
+
+// rt_write_ppm_device / rt_write_png_device: one body, so that the two keep one check list and one order of events.
+static int write_file_device(const char *name, int fmt, const char *path, int32_t device, const void *d_rgb, int32_t rows, int32_t cols, int32_t gamma_correct,
+                             void *stream) {
+    if (!path) return fail(RT_ERR_INVALID_ARGUMENT, "path is NULL");
+    RT_TRY(check_format(d_rgb, rows, cols, nullptr, 0));
+    if (fmt == rto::FMT_PNG) RT_TRY(check_png_size(rows, cols));
+    return guarded(name, [&]() {
+        FileCloser file;
+        if (!(file.f = fopen(path, "wb"))) return fail(RT_ERR_IO, std::string("cannot open ") + path);
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        const size_t capacity = (size_t) file_max_bytes(fmt, rows, cols);
+        StreamBuf d_text;
+        d_text.st = (hipStream_t) stream;
+        HIP_TRY(hipMallocAsync((void **) &d_text.p, capacity, d_text.st));
+        std::unique_ptr<char[]> text;
+        int64_t len = 0;
+        RT_TRY(file_to_host(fmt, d_rgb, rows, cols, gamma_correct != 0, d_text.st, d_text.p, capacity, text, len));
+        return write_all(file, path, text.get(), len);
+    });
+}
+
+// rt_render_ppm / rt_render_png
+static int render_file(const char *name, int fmt, const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
+                       uint32_t flags, int32_t gamma_correct, const char *path, const rt_render_options *options, rt_stats *stats) {
+    const int32_t rows = (max_h > 0 && max_h <= (1 << 20)) ? 2 * max_h + 1 : 0, cols = (max_w > 0 && max_w <= (1 << 20)) ? 2 * max_w + 1 : 0;
+    RT_TRY(check_frame(scene, camera, max_w, max_h, 0, 1, rows, scene, "", options)); // rt_render's check list (the buffers are this call's own)
+    if (!path) return fail(RT_ERR_INVALID_ARGUMENT, "path is NULL");
+    RT_TRY(check_image_size(rows, cols));
+    if (fmt == rto::FMT_PNG) RT_TRY(check_png_size(rows, cols));
+    return guarded(name, [&]() {
+        const auto t0 = std::chrono::steady_clock::now();
+        FileCloser file;
+        if (!(file.f = fopen(path, "wb"))) return fail(RT_ERR_IO, std::string("cannot open ") + path);
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        // accum, rgb and the file in ONE allocation from the null stream's pool; the pixels never visit the host as rgb
+        const size_t npx = (size_t) rows * (size_t) cols, capacity = (size_t) file_max_bytes(fmt, rows, cols), rgb_at = npx * 16u,
+                     text_at = rgb_at + ((npx * 3u + 15u) & ~(size_t) 15u);
+        StreamBuf buf;
+        HIP_TRY(hipMallocAsync((void **) &buf.p, text_at + capacity, buf.st));
+        rt_stats local;
+        {
+            Pending pd;
+            RT_TRY(launch_render(scene, camera, max_w, max_h, seed, device, 0, 1, rows, flags, buf.p, buf.p + rgb_at, nullptr, options, true, pd));
+            RT_TRY(collect_stats(pd, &local));
+        }
+        std::unique_ptr<char[]> text;
+        int64_t len = 0;
+        RT_TRY(file_to_host(fmt, buf.p + rgb_at, rows, cols, gamma_correct != 0, buf.st, buf.p + text_at, capacity, text, len));
+        RT_TRY(write_all(file, path, text.get(), len));
+        if (stats) {
+            *stats = local;
+            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return (int) RT_OK;
+    });
+}
+
 extern "C" {
 
 int64_t rt_ppm_max_bytes(int32_t rows, int32_t cols) {
     if (check_image_size(rows, cols) != RT_OK) return -RT_ERR_INVALID_ARGUMENT;
     return (int64_t) ppm_header(rows, cols).len + (int64_t) RTO_PPM_PIXEL_BYTES * (int64_t) rows * (int64_t) cols - 1;
+}
+
+int64_t rt_png_max_bytes(int32_t rows, int32_t cols) {
+    if (check_image_size(rows, cols) != RT_OK) return -RT_ERR_INVALID_ARGUMENT;
+    if (check_png_size(rows, cols) != RT_OK) return -RT_ERR_UNSUPPORTED;
+    return (int64_t) rtp::max_bytes((uint64_t) rows, (uint64_t) cols);
 }
 
 int64_t rt_pixel_map_bytes(int32_t rows, int32_t cols) {
@@ -1980,61 +2127,32 @@ int rt_format_pixel_map_device(int32_t device, const void *d_rgb, int32_t rows, 
     return run_format(device, FormatJob{rto::FMT_MAP, d_rgb, rows, cols, false, d_out, out_capacity, d_length}, stream, length);
 }
 
+int rt_format_png_device(int32_t device, const void *d_rgb, int32_t rows, int32_t cols, int32_t gamma_correct, void *d_out, size_t out_capacity,
+                         void *d_length, void *stream, int64_t *length) {
+    RT_TRY(check_format(d_rgb, rows, cols, d_out, out_capacity));
+    RT_TRY(check_png_size(rows, cols));
+    return run_format(device, FormatJob{rto::FMT_PNG, d_rgb, rows, cols, gamma_correct != 0, d_out, out_capacity, d_length}, stream, length);
+}
+
 int rt_write_ppm_device(const char *path, int32_t device, const void *d_rgb, int32_t rows, int32_t cols, int32_t gamma_correct, void *stream) {
-    if (!path) return fail(RT_ERR_INVALID_ARGUMENT, "path is NULL");
-    RT_TRY(check_format(d_rgb, rows, cols, nullptr, 0));
-    return guarded("rt_write_ppm_device", [&]() {
-        FileCloser file;
-        if (!(file.f = fopen(path, "wb"))) return fail(RT_ERR_IO, std::string("cannot open ") + path);
-        DeviceGuard guard;
-        RT_TRY(guard.enter(device));
-        const size_t capacity = (size_t) rt_ppm_max_bytes(rows, cols);
-        StreamBuf d_text;
-        d_text.st = (hipStream_t) stream;
-        HIP_TRY(hipMallocAsync((void **) &d_text.p, capacity, d_text.st));
-        std::unique_ptr<char[]> text;
-        int64_t len = 0;
-        RT_TRY(ppm_to_host(d_rgb, rows, cols, gamma_correct != 0, d_text.st, d_text.p, capacity, text, len));
-        return write_all(file, path, text.get(), len);
-    });
+    return write_file_device("rt_write_ppm_device", rto::FMT_PPM, path, device, d_rgb, rows, cols, gamma_correct, stream);
+}
+int rt_write_png_device(const char *path, int32_t device, const void *d_rgb, int32_t rows, int32_t cols, int32_t gamma_correct, void *stream) {
+    return write_file_device("rt_write_png_device", rto::FMT_PNG, path, device, d_rgb, rows, cols, gamma_correct, stream);
 }
 
 int rt_render_ppm(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, uint32_t flags,
                   int32_t gamma_correct, const char *path, const rt_render_options *options, rt_stats *stats) {
-    const int32_t rows = (max_h > 0 && max_h <= (1 << 20)) ? 2 * max_h + 1 : 0, cols = (max_w > 0 && max_w <= (1 << 20)) ? 2 * max_w + 1 : 0;
-    RT_TRY(check_frame(scene, camera, max_w, max_h, 0, 1, rows, scene, "", options)); // rt_render's check list (the buffers are this call's own)
-    if (!path) return fail(RT_ERR_INVALID_ARGUMENT, "path is NULL");
-    RT_TRY(check_image_size(rows, cols));
-    return guarded("rt_render_ppm", [&]() {
-        const auto t0 = std::chrono::steady_clock::now();
-        FileCloser file;
-        if (!(file.f = fopen(path, "wb"))) return fail(RT_ERR_IO, std::string("cannot open ") + path);
-        DeviceGuard guard;
-        RT_TRY(guard.enter(device));
-        // accum, rgb and the text in ONE allocation from the null stream's pool; the pixels never visit the host as rgb
-        const size_t npx = (size_t) rows * (size_t) cols, capacity = (size_t) rt_ppm_max_bytes(rows, cols), rgb_at = npx * 16u,
-                     text_at = rgb_at + ((npx * 3u + 15u) & ~(size_t) 15u);
-        StreamBuf buf;
-        HIP_TRY(hipMallocAsync((void **) &buf.p, text_at + capacity, buf.st));
-        rt_stats local;
-        {
-            Pending pd;
-            RT_TRY(launch_render(scene, camera, max_w, max_h, seed, device, 0, 1, rows, flags, buf.p, buf.p + rgb_at, nullptr, options, true, pd));
-            RT_TRY(collect_stats(pd, &local));
-        }
-        std::unique_ptr<char[]> text;
-        int64_t len = 0;
-        RT_TRY(ppm_to_host(buf.p + rgb_at, rows, cols, gamma_correct != 0, buf.st, buf.p + text_at, capacity, text, len));
-        RT_TRY(write_all(file, path, text.get(), len));
-        if (stats) {
-            *stats = local;
-            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        }
-        return (int) RT_OK;
-    });
+    return render_file("rt_render_ppm", rto::FMT_PPM, scene, camera, max_w, max_h, seed, device, flags, gamma_correct, path, options, stats);
+}
+int rt_render_png(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, uint32_t flags,
+                  int32_t gamma_correct, const char *path, const rt_render_options *options, rt_stats *stats) {
+    return render_file("rt_render_png", rto::FMT_PNG, scene, camera, max_w, max_h, seed, device, flags, gamma_correct, path, options, stats);
 }
 
 } // extern "C"
+
+static int64_t file_max_bytes(int fmt, int32_t rows, int32_t cols) { return fmt == rto::FMT_PNG ? rt_png_max_bytes(rows, cols) : rt_ppm_max_bytes(rows, cols); }
 
 // ============================================================================================================
 // Device unit hooks: tiny kernels that call the SAME inlined device functions the render kernel uses.

@@ -504,6 +504,17 @@ class Scene:
         self.last_stats = st.as_dict()
         return self.last_stats
 
+    def renderPng(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, path: str, *, gammaCorrect: bool = True, seed: int = 0,
+                  device: int = 0, counters: bool = False) -> dict:
+        """rt_render_png: Scene.render |> Png.write (Program.fs:47-50) in one call -- the frame rendered, encoded as a PNG on the device and
+        written to `path`; byte for byte Png.format of render_rows' rgb.  Returns the statistics (total_ms covers the file)."""
+        st = A.rt_stats()
+        cam = camera.to_abi()
+        check(lib.rt_render_png(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, device, A.RT_RENDER_COUNTERS if counters else 0,
+                                int(bool(gammaCorrect)), str(path).encode(), None, C.byref(st)))
+        self.last_stats = st.as_dict()
+        return self.last_stats
+
     def extend_rows(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, accum, samplesDone: int, *, seed: int = 0,
                     device: Optional[int] = None, row_first: int = 0, row_stride: int = 1, counters: bool = False, stats: bool = True,
                     options: Optional[A.rt_render_options] = None) -> RenderResult:
@@ -997,6 +1008,63 @@ class ImageOutput:
         px = np.ascontiguousarray(pixels, dtype=np.uint8)
         check(lib.rt_write_ppm(str(output).encode(), _u8(px), px.shape[0], px.shape[1], int(bool(gammaCorrect))))
         for _ in range(px.shape[0] * px.shape[1]):
+            incrementProgress(1.0)
+
+
+class Png:
+    """Png.write (ImageOutput.fs:214-251).  The reference's file comes out of Skia's encoder; here the PIXELS are the reference's
+    (PixelOutput.toSkia, ImageOutput.fs:32-39: R, G, B after PixelOutput.correct or as they are, alpha 255 -- written as 8-bit RGB without an
+    alpha channel, which a decoder reports as opaque) and the container bytes are this library's own (csrc/rt_png.h)."""
+
+    @staticmethod
+    def format(gammaCorrect: bool, pixels) -> bytes:
+        """The file's bytes.  A numpy array takes rt_format_png on the host; a contiguous uint8 torch tensor [rows, cols, 3] on a GPU is
+        encoded there (formatDevice) and only the file is copied back."""
+        if _is_torch(pixels):
+            data, length = Png.formatDevice(gammaCorrect, pixels)
+            return data[: int(length)].cpu().numpy().tobytes()
+        px = np.ascontiguousarray(pixels, dtype=np.uint8)
+        rows, cols = px.shape[0], px.shape[1]
+        cap = lib.rt_png_max_bytes(rows, cols)
+        if cap < 0:
+            check(int(-cap))
+        buf = np.empty(int(cap), np.uint8)
+        n = lib.rt_format_png(_u8(px), rows, cols, int(bool(gammaCorrect)), buf.ctypes.data, int(cap))
+        if n < 0:
+            check(int(-n))
+        return buf[: int(n)].tobytes()
+
+    @staticmethod
+    def formatDevice(gammaCorrect: bool, pixels):
+        """rt_format_png_device on torch.cuda.current_stream(), without waiting for the device: (data, length) -- a uint8 tensor of
+        rt_png_max_bytes(rows, cols) bytes whose first `length` (an int64 tensor) are the file; the rest is not written."""
+        t = _image_tensor(pixels)
+        torch = _torch()
+        rows, cols = int(t.shape[0]), int(t.shape[1])
+        cap = lib.rt_png_max_bytes(rows, cols)
+        if cap < 0:
+            check(int(-cap))
+        data = torch.empty(int(cap), dtype=torch.uint8, device=t.device)
+        length = torch.empty((), dtype=torch.int64, device=t.device)
+        check(lib.rt_format_png_device(t.device.index, t.data_ptr(), rows, cols, int(bool(gammaCorrect)), data.data_ptr(), int(cap), length.data_ptr(),
+                                       torch.cuda.current_stream(t.device).cuda_stream, None))
+        return data, length
+
+    @staticmethod
+    def write(gammaCorrect: bool, incrementProgress: Callable[[float], None], pixels, output: str) -> None:
+        """Png.write (ImageOutput.fs:216-251).  A torch tensor on a GPU is encoded there (rt_write_png_device, on
+        torch.cuda.current_stream()); a numpy array takes rt_write_png.  Progress as the reference counts it: once per pixel but a row's
+        last (ImageOutput.fs:230-233), once per row but the last (:239-241) -- rows * cols - 1 in all."""
+        if _is_torch(pixels):
+            t = _image_tensor(pixels)
+            rows, cols = int(t.shape[0]), int(t.shape[1])
+            check(lib.rt_write_png_device(str(output).encode(), t.device.index, t.data_ptr(), rows, cols, int(bool(gammaCorrect)),
+                                          _torch().cuda.current_stream(t.device).cuda_stream))
+        else:
+            px = np.ascontiguousarray(pixels, dtype=np.uint8)
+            rows, cols = px.shape[0], px.shape[1]
+            check(lib.rt_write_png(str(output).encode(), _u8(px), rows, cols, int(bool(gammaCorrect))))
+        for _ in range(rows * cols - 1):
             incrementProgress(1.0)
 
 
