@@ -469,6 +469,76 @@ int rt_camera_hits_device(const rt_scene *scene, const rt_camera *camera, int32_
                           void *d_hit_index, void *d_strike /* may be NULL */, void *d_rays_out /* may be NULL */,
                           void *stream, const rt_render_options *options, rt_stats *stats);
 
+/* ---- Path records: the vertices of each sample's path ---------------------------------------------------------------------
+ * A SLOT is one path: follow Scene.traceRay maxCount scene &ray (Scene.fs:93-114) from {Ray = ray; Colour = White}.  Every loop
+ * iteration in which hitObject answers ValueSome (object, strikePoint) is VERTEX j = 0, 1, ... of the path.  Per vertex:
+ *   hit_index     the object's index in rt_scene_create's array (as rt_hit_objects')
+ *   strike        Ray.walkAlong ray bestLength (Scene.fs:91)
+ *   colour_after  object.Reflection (&ray, strikePoint) gave ValueNone: ray.Colour after the call; ValueSome c: c
+ *   ray_after     ValueNone: ray.Ray after the call (origin, unit direction); ValueSome: six NaN
+ * Per slot: n_vertices, the number of vertices the path has (NOT capped by what is stored); colour, traceRay's result; end:
+ *   RT_PATH_MISS          hitObject gave ValueNone; the result is Black
+ *   RT_PATH_STOPPED       Reflection gave ValueSome
+ *   RT_PATH_BOUNCE_LIMIT  bounces > maxCount; the result is HotPink and n_vertices = maxCount + 1
+ *   RT_PATH_NO_RAY        Ray.make' gave ValueNone: Black, 0 vertices, nothing drawn beyond what made the ray (as rt_trace_rays)
+ * Only the first max_vertices (K) vertices of a slot are stored, at record slot*K + j; the unused records of a slot are written
+ * too: hit_index -1, strike and ray_after NaN, colour_after 0.  Every element of every non-NULL output is written by every
+ * successful call, and every store is indexed by slot, never by a list entry's value.  K == 0 ignores the per-record pointers.
+ *
+ * Camera paths (rt_camera_paths): the list, the frame, the sample range and the slot numbering i*n_samples + (s - sample_first) are
+ * rt_camera_hits'.  The stream is (seed, g, s); GetTwo makes Scene.traceOnce's ray (Scene.fs:129-143) and the SAME generator then
+ * feeds the path, maxCount = camera->bounce_depth: the very path sample s of pixel g follows in rt_render and rt_render_pixels.
+ * first_ray (6 doubles per slot) is that camera ray, as rt_camera_hits' rays_out.  summary: RT_PATH_SUMMARY_WORDS int32 per list
+ * ENTRY, reduced over the entry's n_samples slots (integer sums and one max, so no order can matter):
+ *   [0] slots  [1] sum of n_vertices  [2] max n_vertices  [3..6] slots ending MISS, STOPPED, BOUNCE_LIMIT, NO_RAY
+ *   [7] slots with >= 1 vertex  [8..10] sums of R, G, B of colour_after at vertex 0 over those (first-hit albedo)  [11] 0
+ *   [12..15] {Count, SumRed, SumGreen, SumBlue} of colour over the slots: PixelStats over these samples -- for a pixel that took all
+ *   spp samples and the range [0, spp) the render's accum words.  Duplicated list entries each get their own 16 words.
+ * Ray paths (rt_trace_paths): slot i is ray i; rays, rng (given: read, then written back advanced; NULL: the stream keyed
+ * (seed, stream_base + i, sample)) and bounce_depth are exactly rt_trace_rays', and colour and the returned states equal its.
+ *
+ * The contract is rt_camera_hits' for the camera variants and rt_trace_rays' for the ray variants (argument checks before any device
+ * call and nothing written when one fails, n = 0 a no-op with zeroed stats, an entry outside the frame makes the list malformed --
+ * found on the host by the host variant, on the device in front of the launch by the device variant --, stream-ordered scratch, any
+ * number of calls in flight, stats == NULL returns after the launch, the caller's device is left as it was).  Refused as well: out
+ * NULL or of another struct_size, every output NULL, max_vertices < 0, slots * max(K, 1) > INT32_MAX,
+ * n_samples * (bounce_depth + 1) > INT32_MAX when summary is given, first_ray or summary given to a ray-path call.
+ * flags: RT_RENDER_COUNTERS runs the counting variant and fills rays (hitObject calls), aabb_tests, prim_tests and reflections
+ * (= the sum of n_vertices).  stats: pixels = n and samples = slots, always.  options: block_threads (512 and 768 run as 1024),
+ * chunk_pixels (slots per run of the queue, default 64) and blocks_per_cu are honoured; the others are checked and not used.
+ * Added symbols and one added struct only -- RT_ABI_VERSION stays 7. */
+enum rt_path_end { RT_PATH_MISS = 0, RT_PATH_STOPPED = 1, RT_PATH_BOUNCE_LIMIT = 2, RT_PATH_NO_RAY = 3 };
+#define RT_PATH_SUMMARY_WORDS 16
+typedef struct rt_path_outputs { /* host pointers in the host variants, device pointers in the _device variants; any may be NULL */
+    uint32_t struct_size;        /* sizeof(rt_path_outputs) */
+    int32_t max_vertices;        /* K >= 0 */
+    int32_t *n_vertices;         /* per slot: 1 */
+    int32_t *end;                /* per slot: 1 (enum rt_path_end) */
+    uint8_t *colour;             /* per slot: 3 */
+    double *first_ray;           /* per slot: 6 (camera paths only) */
+    int32_t *hit_index;          /* per record slot*K + j: 1 */
+    double *strike;              /* per record: 3 */
+    uint8_t *colour_after;       /* per record: 3 */
+    double *ray_after;           /* per record: 6 */
+    int32_t *summary;            /* per list entry: RT_PATH_SUMMARY_WORDS (camera paths only) */
+} rt_path_outputs;
+int rt_camera_paths(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                    uint64_t seed, int32_t device, size_t n, const int32_t *pixels /* NULL: entry i is pixel i, n <= rows*cols */,
+                    int32_t sample_first, int32_t n_samples, uint32_t flags, const rt_path_outputs *out, rt_stats *stats);
+int rt_camera_paths_device(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                           uint64_t seed, int32_t device, size_t n, const void *d_pixels /* may be NULL */,
+                           int32_t sample_first, int32_t n_samples, uint32_t flags, const rt_path_outputs *out,
+                           void *stream, const rt_render_options *options, rt_stats *stats);
+int rt_trace_paths(const rt_scene *scene, int32_t device, size_t n, const double *rays, uint32_t *rng /* n*4, may be NULL */,
+                   uint64_t seed, uint64_t stream_base, uint32_t sample, int32_t bounce_depth, uint32_t flags,
+                   const rt_path_outputs *out, rt_stats *stats);
+int rt_trace_paths_device(const rt_scene *scene, int32_t device, size_t n, const void *d_rays, void *d_rng /* may be NULL */,
+                          uint64_t seed, uint64_t stream_base, uint32_t sample, int32_t bounce_depth, uint32_t flags,
+                          const rt_path_outputs *out, void *stream, const rt_render_options *options, rt_stats *stats);
+/* Diagnostic: the plan (csrc/rt_paths_plan.h) of the calling THREAD's last path launch: block, grid, chunk, lds_bytes,
+ * lds_resident (1: the filter loop over the scene in LDS ran), counting, textured, slots.  All 0 before the first launch. */
+int rt_dev_last_paths_plan(int64_t out[8]);
+
 /* ---- Extending a rendered buffer to a higher sample count --------------------------------------------------------------
  * render at a, then extend a -> b  ==  render at b, for every PixelStats word and every rgb byte, for any 12 <= a <= b
  * (DESIGN.md "Extending a frame"): sample s of a pixel is the same ray tree whenever it is traced, the sums are integers, and

@@ -103,5 +103,22 @@ class rt_tune_info(C.Structure):
         super().__init__(struct_size=C.sizeof(rt_tune_info))
 
 
+class rt_path_outputs(C.Structure):
+    """The outputs of rt_camera_paths / rt_trace_paths: host pointers in the host variants, device pointers in the _device ones."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("max_vertices", C.c_int32),
+        ("n_vertices", C.c_void_p), ("end", C.c_void_p), ("colour", C.c_void_p), ("first_ray", C.c_void_p),
+        ("hit_index", C.c_void_p), ("strike", C.c_void_p), ("colour_after", C.c_void_p), ("ray_after", C.c_void_p),
+        ("summary", C.c_void_p),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__(struct_size=C.sizeof(rt_path_outputs), **kw)
+
+
+RT_PATH_MISS, RT_PATH_STOPPED, RT_PATH_BOUNCE_LIMIT, RT_PATH_NO_RAY = 0, 1, 2, 3  # enum rt_path_end
+RT_PATH_SUMMARY_WORDS = 16
+
 # numbering of rt_abi_sizeof / rt_abi_offsetof
 ABI_STRUCTS = (rt_hittable, rt_texture, rt_camera, rt_scene_info, rt_stats, rt_render_options, rt_scene_options, rt_tune_info)
+ABI_STRUCT_PATH_OUTPUTS = 9  # rt_path_outputs (8 stays unused: the C smoke test probes it as "no such struct")

@@ -5,6 +5,8 @@
 #include "rt_device.h"
 #include "rt_launch_plan.h"
 #include "rt_output.h"
+#include "rt_paths_kernels.h"
+#include "rt_paths_plan.h"
 #include "rt_png_kernels.h"
 #include "rt_render_kernel.h"
 #include "rt_scene.h"
@@ -17,6 +19,8 @@
 #include <chrono>
 #include <cstddef>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <initializer_list>
 #include <map>
 #include <memory>
@@ -117,6 +121,7 @@ static std::atomic<int> g_park_lanes{0};
 static std::atomic<int> g_walk_tree{RT_WALK_TREE_SAH};
 static thread_local unsigned long long g_last_stage_stats[16] = {0};
 static thread_local int64_t g_last_launch_plan[RT_LAUNCH_PLAN_WORDS] = {0};
+static thread_local int64_t g_last_paths_plan[8] = {0};
 
 static int device_scene(rt_scene *s, int device, DeviceScene **out) {
     std::lock_guard<std::mutex> lock(s->mu);
@@ -268,6 +273,7 @@ size_t rt_abi_sizeof(int which) {
     case 5: return sizeof(rt_render_options);
     case 6: return sizeof(rt_scene_options);
     case 7: return sizeof(rt_tune_info);
+    case 9: return sizeof(rt_path_outputs); // (8 stays unused: bindings probe it as "no such struct")
     default: return 0;
     }
 }
@@ -297,6 +303,9 @@ size_t rt_abi_offsetof(int which, int field) {
     case 7: RT_OFFS(rt_tune_info, F(rt_tune_info, struct_size), F(rt_tune_info, tuned), F(rt_tune_info, probe_rows), F(rt_tune_info, probe_rays),
                     F(rt_tune_info, nodes_before), F(rt_tune_info, nodes_after), F(rt_tune_info, box_tests_before), F(rt_tune_info, box_tests_after),
                     F(rt_tune_info, probe_ms), F(rt_tune_info, build_ms))
+    case 9: RT_OFFS(rt_path_outputs, F(rt_path_outputs, struct_size), F(rt_path_outputs, max_vertices), F(rt_path_outputs, n_vertices), F(rt_path_outputs, end),
+                    F(rt_path_outputs, colour), F(rt_path_outputs, first_ray), F(rt_path_outputs, hit_index), F(rt_path_outputs, strike),
+                    F(rt_path_outputs, colour_after), F(rt_path_outputs, ray_after), F(rt_path_outputs, summary))
     default: return (size_t) -1;
     }
 #undef F
@@ -817,7 +826,7 @@ enum { SEG_IN = 1, SEG_OUT = 2, SEG_INOUT = SEG_IN | SEG_OUT };
 struct Segment { const void *host; size_t bytes; int use; };
 // A host variant's device memory: its segments, in list order, at 16-byte-aligned offsets of ONE allocation that every exit path frees.
 struct Staging {
-    enum { MAX_SEGMENTS = 5 };
+    enum { MAX_SEGMENTS = 12 }; // (the most a call lists: the path records' two inputs and nine outputs)
     Segment seg[MAX_SEGMENTS];
     void *dev[MAX_SEGMENTS] = {}; // segment i on the device; null for an absent one
     int n = 0;
@@ -1542,6 +1551,251 @@ int rt_camera_hits(const rt_scene *scene, const rt_camera *camera, int32_t max_w
         return launch_camera_hits(scene, camera, max_w, max_h, seed, device, n, d[0], sample_first, n_samples, flags, d[1], d[2], d[3], nullptr, nullptr, want_stats, pd);
     }));
     camera_hits_counts(stats, n, n_samples);
+    return RT_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// path records (DESIGN.md "Path records"): Scene.traceRay (Scene.fs:93-114) with every vertex written down, for the samples of a
+// frame's pixels (rt_camera_paths: rt_camera_hits' list, frame and slots) or a caller's rays (rt_trace_paths: rt_trace_rays' rays,
+// states and keys).  A kernel of its own (rt_paths_kernels.h) with a plan of its own (rt_paths_plan.h), on the launch wrapper, the
+// staging helper and the check list of every other entry point.
+// ------------------------------------------------------------------------------------------------------------
+typedef void (*paths_fn)(const RenderParams, const PathParams);
+template <bool TEX, int BLOCK> static paths_fn pick_paths_variant(bool lds, bool count) {
+    if (count) return paths_kernel<false, true, TEX, BLOCK>;
+    return lds ? paths_kernel<true, false, TEX, BLOCK> : paths_kernel<false, false, TEX, BLOCK>;
+}
+static paths_fn pick_paths_kernel(const rtpp::PathsPlan &pl) { // blocks of 256 and 1024 only; TEX only where the scene has parameterised textures
+    if (pl.block == 256) return pl.tex ? pick_paths_variant<true, 256>(pl.lds, pl.count) : pick_paths_variant<false, 256>(pl.lds, pl.count);
+    return pl.tex ? pick_paths_variant<true, 1024>(pl.lds, pl.count) : pick_paths_variant<false, 1024>(pl.lds, pl.count);
+}
+
+// What both families refuse about `out`, made before anything touches a device.  `camera`: first_ray and summary belong to camera paths.
+static int check_path_outputs(const rt_path_outputs *out, bool camera) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (out->struct_size != sizeof(rt_path_outputs)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_path_outputs.struct_size is not sizeof(rt_path_outputs)");
+    if (out->max_vertices < 0) return fail(RT_ERR_INVALID_ARGUMENT, "max_vertices must be >= 0");
+    if (!camera && (out->first_ray || out->summary)) return fail(RT_ERR_INVALID_ARGUMENT, "first_ray and summary belong to camera paths");
+    const bool records = out->max_vertices > 0 && (out->hit_index || out->strike || out->colour_after || out->ray_after);
+    if (!out->n_vertices && !out->end && !out->colour && !out->first_ray && !out->summary && !records)
+        return fail(RT_ERR_INVALID_ARGUMENT, "every output is NULL");
+    return RT_OK;
+}
+static int check_path_sizes(uint64_t slots, const rt_path_outputs *out, int32_t n_samples, int32_t bounce_depth) {
+    const uint64_t k = out->max_vertices > 0 ? (uint64_t) out->max_vertices : 1u;
+    if (slots > (uint64_t) INT32_MAX || slots * k > (uint64_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "more than INT32_MAX records (slots * max(max_vertices, 1))");
+    if (out->summary && (uint64_t) n_samples * ((uint64_t) bounce_depth + 1u) > (uint64_t) INT32_MAX)
+        return fail(RT_ERR_INVALID_ARGUMENT, "n_samples * (bounce_depth + 1) exceeds INT32_MAX: the summary's sum of n_vertices is an int32");
+    return RT_OK;
+}
+static int check_camera_paths(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, size_t n, const void *pixels, int32_t sample_first,
+                              int32_t n_samples, const rt_path_outputs *out, const rt_render_options *options) {
+    RT_TRY(check_path_outputs(out, true));
+    RT_TRY(check_camera_hits(scene, camera, max_w, max_h, n, pixels, sample_first, n_samples, out, options)); // (`out` stands for its one required output)
+    return check_path_sizes((uint64_t) n * (uint64_t) n_samples, out, n_samples, camera->bounce_depth);
+}
+static int check_trace_paths(const rt_scene *scene, size_t n, const void *rays, int32_t bounce_depth, const rt_path_outputs *out, const rt_render_options *options) {
+    RT_TRY(check_path_outputs(out, false));
+    RT_TRY(check_rays(scene, n, rays, out, bounce_depth, options));
+    return check_path_sizes((uint64_t) n, out, 1, bounce_depth);
+}
+
+// The outputs as the kernel reads them: K == 0 ignores the per-record pointers.
+static void path_outputs_to_params(const rt_path_outputs &o, PathParams &q) {
+    const bool rec = o.max_vertices > 0;
+    q.max_vertices = o.max_vertices;
+    q.n_vertices = o.n_vertices; q.end = o.end; q.colour = o.colour; q.first_ray = o.first_ray;
+    q.hit_index = rec ? o.hit_index : nullptr; q.strike = rec ? o.strike : nullptr;
+    q.colour_after = rec ? o.colour_after : nullptr; q.ray_after = rec ? o.ray_after : nullptr;
+    q.summary = o.summary;
+}
+
+// Enqueues one path launch on `stream` (slots > 0, arguments checked): the scene's RenderParams fields, the plan, the launch's scratch
+// from the stream's pool, then -- all on `stream`, nothing waits for the device -- the scratch's set-up, a device list's check and seal
+// (pixel_list_check_kernel; the seal poisons the run counter, so nothing is traced and nothing written), the summary's zeroing behind
+// that seal, and the kernel.  `entries`: list entries (camera paths) or rays.
+static int enqueue_paths(const rt_scene *scene, int32_t device, PathParams q, uint64_t entries, const CameraParams &cam, const Settings &set, uint32_t flags,
+                         void *stream, bool want_stats, Pending &pd) {
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceScene *ds = nullptr;
+    RT_TRY(device_scene(const_cast<rt_scene *>(scene), device, &ds));
+    const rth::HostScene &h = scene->host;
+    hipStream_t st = (hipStream_t) stream;
+    RenderParams p{}; // the scene's part only: what stage_scene and make_view read
+    p.off = h.off;
+    p.scene_image = ds->image;
+    p.tex = ds->tex;
+    p.texels = ds->texels;
+    q.obj_to_orig = ds->obj_to_orig;
+
+    // RTFS_PATHS_ROUTE=global: a measurement's switch (scripts/paths_measure.py times the two routes of one scene); results cannot depend on it
+    const char *route = getenv("RTFS_PATHS_ROUTE");
+    rtpp::PathsPlan plan = rtpp::plan_begin(scene_size(h), set, (flags & RT_RENDER_COUNTERS) != 0, q.slots, !(route && strcmp(route, "global") == 0));
+    paths_fn fn = pick_paths_kernel(plan);
+    RT_TRY(allow_full_lds((const void *) fn));
+    int perCu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *) fn, plan.block, plan.lds_bytes));
+    if (perCu < 1) return fail(RT_ERR_HIP, "path kernel does not fit on a CU (occupancy 0)");
+    rtpp::plan_finish(plan, ds->cu_count, perCu);
+    {
+        int64_t *o = g_last_paths_plan;
+        o[0] = plan.block; o[1] = (int64_t) plan.grid; o[2] = plan.chunk; o[3] = (int64_t) plan.lds_bytes; o[4] = plan.lds ? 1 : 0;
+        o[5] = plan.count ? 1 : 0; o[6] = plan.tex ? 1 : 0; o[7] = (int64_t) plan.slots;
+    }
+    q.chunk = plan.chunk;
+
+    unsigned char *scr = nullptr;
+    HIP_TRY(hipMallocAsync((void **) &scr, RT_SCRATCH_BYTES, st));
+    pd.scr = scr; pd.st = st; pd.device = device; pd.t0 = t0; // on every exit path pd's destructor (or collect_stats) gives the scratch back
+    pd.pixels = entries;
+    pd.waves = plan.grid * (uint64_t) (plan.block / 64);
+    pd.list = q.pixel_list != nullptr;
+    if (want_stats) {
+        HIP_TRY(hipEventCreate(&pd.a));
+        HIP_TRY(hipEventCreate(&pd.b));
+    }
+    LaunchScratch *ls = (LaunchScratch *) scr;
+    q.counters = ls->counters;
+    q.queue = &ls->queue;
+    q.cam = &ls->cam;
+    hipLaunchKernelGGL(launch_init_kernel, dim3(1), dim3(64), 0, st, scr, cam);
+    HIP_TRY(hipGetLastError());
+    if (want_stats) HIP_TRY(hipEventRecord(pd.a, st));
+    const unsigned long long most = (unsigned long long) ds->cu_count * 8ull;
+    if (pd.list) {
+        const unsigned long long want = ((unsigned long long) entries + 255ull) / 256ull;
+        hipLaunchKernelGGL(pixel_list_check_kernel, dim3((unsigned) (want < most ? want : most)), dim3(256), 0, st, q.pixel_list, (unsigned long long) entries,
+                           (uint32_t) q.cols * (uint32_t) (2 * q.max_h + 1), &ls->ext_foreign);
+        hipLaunchKernelGGL(pixel_list_seal_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) &ls->ext_foreign, q.queue, &ls->ext_malformed);
+        HIP_TRY(hipGetLastError());
+    }
+    if (q.summary) {
+        const unsigned long long words = (unsigned long long) entries * RT_PATH_SUMMARY_WORDS, want = (words + 255ull) / 256ull;
+        hipLaunchKernelGGL(paths_summary_zero_kernel, dim3((unsigned) (want < most ? want : most)), dim3(256), 0, st, q.summary, words,
+                           pd.list ? (const unsigned int *) &ls->ext_malformed : (const unsigned int *) nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(fn, dim3((unsigned) plan.grid), dim3((unsigned) plan.block), plan.lds_bytes, st, p, q);
+    HIP_TRY(hipGetLastError());
+    if (want_stats) HIP_TRY(hipEventRecord(pd.b, st));
+    pd.launched = true;
+    if (!want_stats) pd.release();
+    return RT_OK;
+}
+
+static int launch_camera_paths(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                               const void *d_pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, const rt_path_outputs &out, void *stream,
+                               const rt_render_options *options, bool want_stats, Pending &pd) {
+    PathParams q{};
+    q.pixel_list = (const int32_t *) d_pixels;
+    q.seed_key = mix64(seed + 0x9E3779B97F4A7C15ull); // seed_key(), host side
+    q.sample_first = sample_first; q.n_samples = n_samples;
+    q.cols = 2 * max_w + 1; q.max_w = max_w; q.max_h = max_h;
+    q.depth = camera->bounce_depth;
+    q.slots = (uint64_t) n * (uint64_t) n_samples;
+    path_outputs_to_params(out, q);
+    return enqueue_paths(scene, device, q, (uint64_t) n, camera_params(camera, max_w, max_h), resolve_settings(options), flags, stream, want_stats, pd);
+}
+static int launch_trace_paths(const rt_scene *scene, int32_t device, size_t n, const void *d_rays, void *d_rng, uint64_t seed, uint64_t stream_base, uint32_t sample,
+                              int32_t bounce_depth, uint32_t flags, const rt_path_outputs &out, void *stream, const rt_render_options *options, bool want_stats,
+                              Pending &pd) {
+    PathParams q{};
+    q.rays = (const double *) d_rays;
+    q.rng = (uint32_t *) d_rng;
+    q.seed_key = mix64(seed + 0x9E3779B97F4A7C15ull); // seed_key(), host side: rt_trace_rays' keying
+    q.ray_base = stream_base; q.ray_sample = sample;
+    q.n_samples = 1;
+    q.depth = bounce_depth;
+    q.slots = (uint64_t) n;
+    path_outputs_to_params(out, q);
+    q.first_ray = nullptr; q.summary = nullptr;
+    return enqueue_paths(scene, device, q, (uint64_t) n, CameraParams{}, resolve_settings(options), flags, stream, want_stats, pd); // (no camera: never read)
+}
+
+// What the statistics of a path call count (collect_stats has filled in the rest).
+static void paths_counts(rt_stats *stats, size_t n, uint64_t slots) {
+    if (!stats) return;
+    stats->pixels = (uint64_t) n; // list entries or rays
+    stats->samples = slots;
+}
+
+// The host variants' segments behind their inputs: the nine outputs, in rt_path_outputs' order (an absent one takes no space).
+#define RT_PATH_SEGMENTS(o, slots, recs, entries)                                                                                                       \
+    {(o).n_vertices, (slots) * 4u, SEG_OUT}, {(o).end, (slots) * 4u, SEG_OUT}, {(o).colour, (slots) * 3u, SEG_OUT}, {(o).first_ray, (slots) * 48u, SEG_OUT},  \
+    {(o).hit_index, (recs) * 4u, SEG_OUT}, {(o).strike, (recs) * 24u, SEG_OUT}, {(o).colour_after, (recs) * 3u, SEG_OUT}, {(o).ray_after, (recs) * 48u, SEG_OUT}, \
+    {(o).summary, (entries) * (size_t) RT_PATH_SUMMARY_WORDS * 4u, SEG_OUT}
+static rt_path_outputs staged_path_outputs(const rt_path_outputs &host, void *const *d) { // d: the nine segments above, on the device
+    rt_path_outputs o = host;
+    o.n_vertices = (int32_t *) d[0]; o.end = (int32_t *) d[1]; o.colour = (uint8_t *) d[2]; o.first_ray = (double *) d[3];
+    o.hit_index = (int32_t *) d[4]; o.strike = (double *) d[5]; o.colour_after = (uint8_t *) d[6]; o.ray_after = (double *) d[7];
+    o.summary = (int32_t *) d[8];
+    return o;
+}
+static rt_path_outputs host_path_outputs(const rt_path_outputs &out) { // K == 0: the per-record pointers are not the caller's to be written
+    rt_path_outputs o = out;
+    if (o.max_vertices == 0) { o.hit_index = nullptr; o.strike = nullptr; o.colour_after = nullptr; o.ray_after = nullptr; }
+    return o;
+}
+
+extern "C" {
+
+int rt_camera_paths_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                           const void *d_pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, const rt_path_outputs *out, void *stream,
+                           const rt_render_options *options, rt_stats *stats) {
+    RT_TRY(check_camera_paths(scene, camera, max_w, max_h, n, d_pixels, sample_first, n_samples, out, options));
+    RT_TRY(run_device(device, stats, n == 0, [&](bool want_stats, Pending &pd) {
+        return launch_camera_paths(scene, camera, max_w, max_h, seed, device, n, d_pixels, sample_first, n_samples, flags, *out, stream, options, want_stats, pd);
+    }));
+    if (n) paths_counts(stats, n, (uint64_t) n * (uint64_t) n_samples);
+    return RT_OK;
+}
+
+// The host variant checks a list here, before anything touches a device.
+int rt_camera_paths(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                    const int32_t *pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, const rt_path_outputs *out, rt_stats *stats) {
+    RT_TRY(check_camera_paths(scene, camera, max_w, max_h, n, pixels, sample_first, n_samples, out, nullptr));
+    if (pixels) RT_TRY(check_pixel_entries(pixels, n, max_w, max_h));
+    const rt_path_outputs o = host_path_outputs(*out);
+    const size_t slots = n * (size_t) n_samples, recs = slots * (size_t) o.max_vertices;
+    RT_TRY(run_host(device, stats, n == 0, {{pixels, n * 4u, SEG_IN}, RT_PATH_SEGMENTS(o, slots, recs, n)}, [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_camera_paths(scene, camera, max_w, max_h, seed, device, n, d[0], sample_first, n_samples, flags, staged_path_outputs(o, d + 1), nullptr, nullptr,
+                                   want_stats, pd);
+    }));
+    if (n) paths_counts(stats, n, (uint64_t) slots);
+    return RT_OK;
+}
+
+int rt_trace_paths_device(const rt_scene *scene, int32_t device, size_t n, const void *d_rays, void *d_rng, uint64_t seed, uint64_t stream_base, uint32_t sample,
+                          int32_t bounce_depth, uint32_t flags, const rt_path_outputs *out, void *stream, const rt_render_options *options, rt_stats *stats) {
+    RT_TRY(check_trace_paths(scene, n, d_rays, bounce_depth, out, options));
+    RT_TRY(run_device(device, stats, n == 0, [&](bool want_stats, Pending &pd) {
+        return launch_trace_paths(scene, device, n, d_rays, d_rng, seed, stream_base, sample, bounce_depth, flags, *out, stream, options, want_stats, pd);
+    }));
+    if (n) paths_counts(stats, n, (uint64_t) n);
+    return RT_OK;
+}
+
+int rt_trace_paths(const rt_scene *scene, int32_t device, size_t n, const double *rays, uint32_t *rng, uint64_t seed, uint64_t stream_base, uint32_t sample,
+                   int32_t bounce_depth, uint32_t flags, const rt_path_outputs *out, rt_stats *stats) {
+    RT_TRY(check_trace_paths(scene, n, rays, bounce_depth, out, nullptr));
+    const rt_path_outputs o = host_path_outputs(*out);
+    const size_t recs = n * (size_t) o.max_vertices;
+    RT_TRY(run_host(device, stats, n == 0, {{rays, n * 48u, SEG_IN}, {rng, n * 16u, SEG_INOUT}, RT_PATH_SEGMENTS(o, n, recs, (size_t) 0)},
+                    [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_trace_paths(scene, device, n, d[0], d[1], seed, stream_base, sample, bounce_depth, flags, staged_path_outputs(o, d + 2), nullptr, nullptr,
+                                  want_stats, pd);
+    }));
+    if (n) paths_counts(stats, n, (uint64_t) n);
+    return RT_OK;
+}
+
+int rt_dev_last_paths_plan(int64_t out[8]) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    for (int i = 0; i < 8; ++i) out[i] = g_last_paths_plan[i];
     return RT_OK;
 }
 

@@ -143,6 +143,16 @@ PLAN_PASS = ("mode", "grid", "lds_bytes", "chunk", "park", "park_l", "park_l_lds
 PLAN_WORDS = 80
 
 
+PATHS_PLAN = ("block", "grid", "chunk", "lds_bytes", "lds_resident", "counting", "textured", "slots")
+
+
+def last_paths_plan():
+    """The plan (csrc/rt_paths_plan.h) of the calling thread's last path launch (cameraPaths / tracePaths), or None before the first."""
+    w = (C.c_int64 * 8)()
+    check(lib.rt_dev_last_paths_plan(w))
+    return dict(zip(PATHS_PLAN, w)) if w[0] else None
+
+
 def last_launch_plan():
     """The launch plan (csrc/rt_launch_plan.h) of the calling thread's last launch as the library executed it: {"in": the planner's
     inputs, "out": its decisions}, keyed as launch_plan_table.cpp's lines are (F_ for a fused or ray-list launch, A_ and B_ for a

@@ -401,6 +401,33 @@ class CameraHits(NamedTuple):
     stats: Optional[dict]
 
 
+class CameraPaths(NamedTuple):
+    """Path records of camera paths, [n, n_samples, ...] in list order (a field not asked for is None)."""
+    n_vertices: np.ndarray             # [n, n_samples] int32: vertices the path has (not capped by max_vertices)
+    end: np.ndarray                    # [n, n_samples] int32: RT_PATH_MISS 0, STOPPED 1, BOUNCE_LIMIT 2, NO_RAY 3
+    colour: np.ndarray                 # [n, n_samples, 3] uint8: Scene.traceRay's result
+    first_ray: Optional[np.ndarray]    # [n, n_samples, 6] float64: the camera ray, NaN at NO_RAY
+    hit_index: Optional[np.ndarray]    # [n, n_samples, K] int32, -1 past the path's end
+    strike: Optional[np.ndarray]       # [n, n_samples, K, 3] float64
+    colour_after: Optional[np.ndarray] # [n, n_samples, K, 3] uint8
+    ray_after: Optional[np.ndarray]    # [n, n_samples, K, 6] float64, NaN where Reflection gave ValueSome
+    summary: Optional[np.ndarray]      # [n, 16] int32 (include/rtfs_amd.h: RT_PATH_SUMMARY_WORDS)
+    stats: Optional[dict]
+
+
+class TracePaths(NamedTuple):
+    """Path records of a ray list, [n, ...]; rng is the advanced states (None without rng)."""
+    n_vertices: np.ndarray
+    end: np.ndarray
+    colour: np.ndarray
+    rng: Optional[np.ndarray]
+    hit_index: Optional[np.ndarray]
+    strike: Optional[np.ndarray]
+    colour_after: Optional[np.ndarray]
+    ray_after: Optional[np.ndarray]
+    stats: Optional[dict]
+
+
 class Scene:
     def __init__(self, handle: int, keep):
         self._h = C.c_void_p(handle)
@@ -859,6 +886,121 @@ class Scene:
                                  _f64(ry) if rays else None, C.byref(st)))
         self.last_stats = st.as_dict()
         return CameraHits(hit, sk, ry, self.last_stats)
+
+    @staticmethod
+    def _path_buffers(lead, k, records, make, first_ray=False, summary_entries=None):
+        """The output buffers of a path call, shaped lead + (...): make(shape, kind) allocates, kind one of "i32", "u8", "f64"."""
+        bufs = {"n_vertices": make(lead, "i32"), "end": make(lead, "i32"), "colour": make(lead + (3,), "u8")}
+        bufs["first_ray"] = make(lead + (6,), "f64") if first_ray else None
+        rec = records and k > 0
+        bufs["hit_index"] = make(lead + (k,), "i32") if rec else None
+        bufs["strike"] = make(lead + (k, 3), "f64") if rec else None
+        bufs["colour_after"] = make(lead + (k, 3), "u8") if rec else None
+        bufs["ray_after"] = make(lead + (k, 6), "f64") if rec else None
+        bufs["summary"] = make((summary_entries, A.RT_PATH_SUMMARY_WORDS), "i32") if summary_entries is not None else None
+        return bufs
+
+    def cameraPaths(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, pixels=None, *, sample_first: int = 0, n_samples: int = 1,
+                    max_vertices: int = 8, records: bool = True, first_ray: bool = True, summary: bool = False, seed: int = 0,
+                    n: Optional[int] = None, tensors: bool = False, device: Optional[int] = None, counters: bool = False, stats: bool = True,
+                    options: Optional[A.rt_render_options] = None) -> CameraPaths:
+        """The path behind every sample: Scene.traceRay (Scene.fs:93-114) of the ray Scene.traceOnce builds for samples sample_first ..
+        sample_first + n_samples - 1 of the FRAME's pixels in `pixels` (as cameraHits: [n] int32 global pixel indices; None: pixels
+        0 .. n-1), with the sample's own generator -- the very path that sample follows in render_rows and renderPixels -> CameraPaths.
+        max_vertices (K): records kept per path; n_vertices counts them all.  records=False / first_ray=False: not computed (None);
+        summary=True adds the per-entry reduction [n, 16].  numpy arrays / torch tensors as for cameraHits (a tensor list, or
+        pixels=None with tensors=True, goes through rt_camera_paths_device on torch.cuda.current_stream())."""
+        flags = A.RT_RENDER_COUNTERS if counters else 0
+        cam = camera.to_abi()
+        frame = (2 * maxWidthCoord + 1) * (2 * maxHeightCoord + 1)
+        if not isinstance(n_samples, int) or not isinstance(sample_first, int) or not isinstance(max_vertices, int):
+            raise TypeError("sample_first, n_samples and max_vertices must be ints")
+        if pixels is not None and n is not None:
+            raise ValueError("n applies to pixels=None")
+        per, k = max(n_samples, 0), max(max_vertices, 0)
+        if _is_torch(pixels) or (pixels is None and tensors):
+            torch = _torch()
+            if pixels is None:
+                tdev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+                dev, count, ptr = tdev.index, frame if n is None else int(n), None
+            else:
+                px = _list_tensor(pixels)
+                tdev, dev, count, ptr = px.device, _tensor_device(px, device), px.shape[0], px.data_ptr()
+            kinds = {"i32": torch.int32, "u8": torch.uint8, "f64": torch.float64}
+            bufs = Scene._path_buffers((count, per), k, records, lambda shape, kind: torch.empty(shape, dtype=kinds[kind], device=tdev), first_ray,
+                                       count if summary else None)
+            out = A.rt_path_outputs(max_vertices=max_vertices, **{f: (b.data_ptr() if b is not None else None) for f, b in bufs.items()})
+            st = A.rt_stats() if stats else None
+            check(lib.rt_camera_paths_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, count, ptr, sample_first, n_samples, flags,
+                                             C.byref(out), torch.cuda.current_stream(tdev).cuda_stream, _ref(options), _ref(st)))
+            self.last_stats = st.as_dict() if st is not None else None
+            return CameraPaths(stats=self.last_stats, **bufs)
+        _no_options(options, "set_launch_config")
+        if pixels is None:
+            px, count = None, frame if n is None else int(n)
+        else:
+            px = _list_array(pixels)
+            count = px.shape[0]
+        if count < 0:
+            raise ValueError("n must be >= 0")
+        big = count * per * max(k, 1) > 2**31 - 1  # (refused by the library: no buffers are made for it)
+        kinds = {"i32": np.int32, "u8": np.uint8, "f64": np.float64}
+        bufs = Scene._path_buffers((0, 0) if big else (count, per), k, records, lambda shape, kind: np.zeros(shape, kinds[kind]), first_ray,
+                                   (0 if big else count) if summary else None)
+        out = A.rt_path_outputs(max_vertices=max_vertices, **{f: (b.ctypes.data if b is not None else None) for f, b in bufs.items()})
+        st = A.rt_stats()
+        check(lib.rt_camera_paths(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, count,
+                                  _i32(px) if px is not None else None, sample_first, n_samples, flags, C.byref(out), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return CameraPaths(stats=self.last_stats, **bufs)
+
+    def tracePaths(self, rays, bounceDepth: int, *, rng=None, seed: int = 0, stream_base: int = 0, sample: int = 0, max_vertices: int = 8,
+                   records: bool = True, device: Optional[int] = None, counters: bool = False, stats: bool = True,
+                   options: Optional[A.rt_render_options] = None) -> TracePaths:
+        """traceRays with the path written down: rays, rng, seed, stream_base, sample and bounceDepth are traceRays' (colour and the
+        advanced states equal its) -> TracePaths.  numpy arrays / torch tensors as for traceRays."""
+        flags = A.RT_RENDER_COUNTERS if counters else 0
+        if not isinstance(max_vertices, int):
+            raise TypeError("max_vertices must be an int")
+        k = max(max_vertices, 0)
+        if _is_torch(rays):
+            torch = _torch()
+            r = _tensor_arg(rays, "rays", (torch.float64,), 6)
+            dev = _tensor_device(r, device)
+            n = r.shape[0]
+            g = None
+            if rng is not None:
+                if not _is_torch(rng):
+                    raise TypeError("rng must be a torch tensor when rays is one")
+                g = _tensor_arg(rng, "rng", (torch.uint32, torch.int32), 4).clone()
+                if g.shape[0] != n or g.device != r.device:
+                    raise ValueError("rng must be [n, 4] on the rays' device")
+            kinds = {"i32": torch.int32, "u8": torch.uint8, "f64": torch.float64}
+            bufs = Scene._path_buffers((n,), k, records, lambda shape, kind: torch.empty(shape, dtype=kinds[kind], device=r.device))
+            out = A.rt_path_outputs(max_vertices=max_vertices, **{f: (b.data_ptr() if b is not None else None) for f, b in bufs.items()})
+            st = A.rt_stats() if stats else None
+            check(lib.rt_trace_paths_device(self._h, dev, n, r.data_ptr(), g.data_ptr() if g is not None else None, seed, stream_base, sample,
+                                            bounceDepth, flags, C.byref(out), torch.cuda.current_stream(r.device).cuda_stream, _ref(options), _ref(st)))
+            self.last_stats = st.as_dict() if st is not None else None
+        else:
+            _no_options(options)
+            r = _array_arg(rays, "rays", np.float64, 6)
+            n = r.shape[0]
+            g = None
+            if rng is not None:
+                g = _array_arg(rng, "rng", np.uint32, 4).copy()
+                if g.shape[0] != n:
+                    raise ValueError("rng must be [n, 4] for n rays")
+            big = n * max(k, 1) > 2**31 - 1
+            kinds = {"i32": np.int32, "u8": np.uint8, "f64": np.float64}
+            bufs = Scene._path_buffers((0,) if big else (n,), k, records, lambda shape, kind: np.zeros(shape, kinds[kind]))
+            out = A.rt_path_outputs(max_vertices=max_vertices, **{f: (b.ctypes.data if b is not None else None) for f, b in bufs.items()})
+            st = A.rt_stats()
+            check(lib.rt_trace_paths(self._h, 0 if device is None else device, n, _f64(r), _u32(g) if g is not None else None, seed, stream_base,
+                                     sample, bounceDepth, flags, C.byref(out), C.byref(st)))
+            self.last_stats = st.as_dict()
+        return TracePaths(bufs["n_vertices"], bufs["end"], bufs["colour"], g, bufs["hit_index"], bufs["strike"], bufs["colour_after"], bufs["ray_after"],
+                          self.last_stats)
 
     @staticmethod
     def render(progressIncrement: Callable[[float], None], log: Callable[[str], None], maxWidthCoord: int, maxHeightCoord: int,
