@@ -738,6 +738,77 @@ int rt_render_png(const rt_scene *scene, const rt_camera *camera, int32_t max_wi
                   uint64_t seed, int32_t device, uint32_t flags, int32_t gamma_correct, const char *path,
                   const rt_render_options *options, rt_stats *stats);
 
+/* ---- Resuming from a pixel map, on the device (DESIGN.md "Resuming from a pixel map") ------------------
+ * Program.fs:39-50 spills the frame as a pixel map (ImageOutput.toPpm), reads it back (ImageOutput.readPixelMap, ImageOutput.fs:46-113),
+ * insists that it is complete (ImageOutput.assertComplete, ImageOutput.fs:199-200) and writes the PNG.  These calls are the read-back
+ * from bytes that are on the device, and the completion of a partial map by rendering only what it lacks.  The device output stage's
+ * contract holds: any byte alignment of d_data, d_rgb and d_present; everything enqueued on `stream` with stream-ordered scratch, so any
+ * number of calls may be in flight; the caller's current device left as it was; argument checks before any device call, then
+ * RT_ERR_NO_DEVICE.  Added symbols only, so RT_ABI_VERSION stays 7. */
+
+/* The shapes of the parse kernels (csrc/rt_pixel_map.h): bytes per thread, bytes per workgroup, tiles per trip of the scanning workgroup. */
+int32_t rt_pixel_map_chunk_bytes(void);
+int32_t rt_pixel_map_tile_bytes(void);
+int32_t rt_pixel_map_scan_tiles(void);
+
+/* ImageOutput.readPixelMap (ImageOutput.fs:46-113; Program.fs:47) from n_bytes of map on the device, as a scan (csrc/rt_pixel_map.h).
+ * Exactly the records rt_parse_pixel_map handles: a record counts iff its third colour byte exists, a truncated tail is ignored, a
+ * terminator is any non-digit, an empty digit run is 0, leading zeros of any length are allowed.
+ * d_rgb (rows*cols*3) is written for the pixels the data names and every other byte of it is left alone; d_present (rows*cols) is
+ * written in full, 0 or 1.  A pixel named more than once keeps its LAST record in file order, whatever the scheduling.  The count is the
+ * number of complete records, duplicates included; it goes to d_count (an int64 on the device) when given, and to `count` when given,
+ * which synchronises the stream.
+ * A malformed map -- a complete record whose row or column is outside the image, or whose digit run exceeds INT32_MAX -- is found ON THE
+ * DEVICE, in front of the storing kernels: NOTHING of d_rgb or d_present is written, and the call returns RT_ERR_INVALID_ARGUMENT when
+ * `count` is given; with count == NULL it returns RT_OK, and d_count == -RT_ERR_INVALID_ARGUMENT and the untouched buffers are the
+ * caller's evidence (the pattern of a malformed device pixel list).  rt_parse_pixel_map differs: by the time it fails it has stored the
+ * records in front of the bad one.
+ * RT_ERR_INVALID_ARGUMENT for a NULL d_data with n_bytes > 0, a NULL d_rgb or d_present, rows or cols <= 0, more than INT32_MAX pixels;
+ * then RT_ERR_UNSUPPORTED for n_bytes > INT32_MAX.  n_bytes == 0 clears d_present and counts 0. */
+int rt_parse_pixel_map_device(int32_t device, const void *d_data, size_t n_bytes, int32_t rows, int32_t cols, void *d_rgb, void *d_present,
+                              void *d_count /* int64 on the device, may be NULL */, void *stream,
+                              int64_t *count /* host; may be NULL */);
+
+/* What ImageOutput.assertComplete (ImageOutput.fs:199-200; Program.fs:49) would throw on: the global pixel indices r*cols + c of the zero
+ * bytes of d_present (rows*cols), ascending, as int32 -- the list rt_render_pixels_device takes.  A compaction by scan, no atomic append.
+ * The length always goes to d_n (int64 on the device) when given, and to `n` when given, which synchronises.  d_pixels == NULL: the
+ * length only.  The capacity (in entries) follows rt_format_ppm_device's rule: one that is too small is found on the device, no entry is
+ * written, RT_ERR_INVALID_ARGUMENT when `n` is given, RT_OK and d_n > capacity otherwise. */
+int rt_missing_pixels_device(int32_t device, const void *d_present, int32_t rows, int32_t cols, void *d_pixels /* int32, may be NULL */,
+                             size_t capacity, void *d_n /* int64 on the device, may be NULL */, void *stream, int64_t *n /* host; may be NULL */);
+
+/* frame[d_pixels[i]] = d_rgb_list[i], three bytes each, for i < n: a rendered pixel list (rt_render_pixels_device's d_rgb) put into a
+ * frame of rows*cols*3 bytes -- what makes the map of Program.fs:47 the complete one Program.fs:49 asks for.  An entry outside the frame
+ * is found on the device in front of the storing kernel and then NOTHING is written; the call does not synchronise and returns RT_OK, the
+ * untouched frame being the caller's evidence.  Of duplicate entries the LAST in list order wins.  n == 0 is a no-op. */
+int rt_scatter_pixels_device(int32_t device, size_t n, const void *d_pixels, const void *d_rgb_list, int32_t rows, int32_t cols,
+                             void *d_rgb_frame, void *stream);
+
+/* Program.fs:45-49 for an interrupted frame: the map's bytes (host) uploaded and parsed, the pixels it lacks listed, rendered with
+ * rt_render_pixels_device and scattered into the frame, which is copied to rgb_out (rows*cols*3, rows = 2*max_height_coord+1).
+ * Synchronises.  Rejects what rt_render rejects about scene, camera, geometry and options (the same check list), NULL data with
+ * n_bytes > 0, a NULL rgb_out, RT_ERR_UNSUPPORTED for n_bytes > INT32_MAX; a malformed map is RT_ERR_INVALID_ARGUMENT before anything is
+ * rendered, and rgb_out is then untouched.
+ * For a map whose records come from rt_render's frame with the same scene, camera, geometry and seed -- in any order, any subset,
+ * duplicated or truncated -- rgb_out is that frame's rgb byte for byte.  For any other map every named pixel keeps the map's bytes and
+ * every other pixel is the frame's.  stats (may be NULL) as rt_render_pixels fills them: pixels = the number rendered, total_ms = the
+ * whole call; a complete map renders nothing and leaves every other field zero. */
+int rt_resume_pixel_map(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                        uint64_t seed, int32_t device, uint32_t flags, const uint8_t *data, size_t n_bytes, uint8_t *rgb_out,
+                        const rt_render_options *options, rt_stats *stats);
+
+/* Program.fs:45-50 with the missing pixels rendered where ImageOutput.assertComplete would throw: the spill at map_path read,
+ * resumed on the device as rt_resume_pixel_map does, formatted there (rt_format_png_device / rt_format_ppm_device: the frame never visits
+ * the host as rgb) and written to out_path.  The file is byte for byte rt_format_png / rt_format_ppm of rt_resume_pixel_map's rgb_out.
+ * The order of checks is rt_render_png's: the arguments, then both files (map_path read whole, out_path opened: RT_ERR_IO before any
+ * device work; the two may name one file), then the device. */
+int rt_resume_png(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                  uint64_t seed, int32_t device, uint32_t flags, const char *map_path, int32_t gamma_correct, const char *out_path,
+                  const rt_render_options *options, rt_stats *stats);
+int rt_resume_ppm(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                  uint64_t seed, int32_t device, uint32_t flags, const char *map_path, int32_t gamma_correct, const char *out_path,
+                  const rt_render_options *options, rt_stats *stats);
+
 /* ---- Runtime ------------------------------------------------------------------------------------- */
 int rt_device_count(void);         /* 0 when no HIP device is visible (never an error) */
 const char *rt_last_error(void);   /* thread-local message of the last failing call */

@@ -163,6 +163,19 @@ SIGNATURES = {
     "rt_write_png_device": (C.c_int, [C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rt_render_png": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32, C.c_char_p,
                                 _P(A.rt_render_options), _P(A.rt_stats)]),
+    "rt_pixel_map_chunk_bytes": (C.c_int32, []),
+    "rt_pixel_map_tile_bytes": (C.c_int32, []),
+    "rt_pixel_map_scan_tiles": (C.c_int32, []),
+    "rt_parse_pixel_map_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            _P(C.c_int64)]),
+    "rt_missing_pixels_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, _P(C.c_int64)]),
+    "rt_scatter_pixels_device": (C.c_int, [C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rt_resume_pixel_map": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_uint32, C.c_char_p, C.c_size_t, _u8p,
+                                      _P(A.rt_render_options), _P(A.rt_stats)]),
+    "rt_resume_png": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_uint32, C.c_char_p, C.c_int32, C.c_char_p,
+                                _P(A.rt_render_options), _P(A.rt_stats)]),
+    "rt_resume_ppm": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_uint32, C.c_char_p, C.c_int32, C.c_char_p,
+                                _P(A.rt_render_options), _P(A.rt_stats)]),
     "rt_dev_float_producer": (C.c_int, [C.c_int32, _u32p, C.c_int32, _dp]),
     "rt_dev_stream_state": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32, _u64p, _u32p, _u32p]),
     "rt_dev_bbox_hits": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _i32p]),

@@ -7,6 +7,7 @@
 #include "rt_output.h"
 #include "rt_paths_kernels.h"
 #include "rt_paths_plan.h"
+#include "rt_pixel_map_kernels.h"
 #include "rt_png_kernels.h"
 #include "rt_render_kernel.h"
 #include "rt_scene.h"
@@ -2407,6 +2408,287 @@ int rt_render_png(const rt_scene *scene, const rt_camera *camera, int32_t max_w,
 } // extern "C"
 
 static int64_t file_max_bytes(int fmt, int32_t rows, int32_t cols) { return fmt == rto::FMT_PNG ? rt_png_max_bytes(rows, cols) : rt_ppm_max_bytes(rows, cols); }
+
+// ------------------------------------------------------------------------------------------------------------
+// resuming from a pixel map (rt_pixel_map.h, rt_pixel_map_kernels.h; DESIGN.md "Resuming from a pixel map"): ImageOutput.readPixelMap
+// (ImageOutput.fs:46-113) from bytes on the device, the list of the pixels a presence map lacks, the scatter of a rendered list into a
+// frame, and Program.fs:45-50 with the missing pixels rendered where ImageOutput.assertComplete would throw
+// ------------------------------------------------------------------------------------------------------------
+static const char *const kMalformedMap = "pixel map names a pixel outside the image; nothing was written";
+
+static int check_map_bytes(const void *data, size_t n_bytes) {
+    if (n_bytes > 0 && !data) return fail(RT_ERR_INVALID_ARGUMENT, "the pixel map's bytes are NULL");
+    return RT_OK;
+}
+static int check_map_size(size_t n_bytes) { // after every RT_ERR_INVALID_ARGUMENT
+    if (n_bytes > (size_t) INT32_MAX) return fail(RT_ERR_UNSUPPORTED, "a pixel map of more than INT32_MAX bytes");
+    return RT_OK;
+}
+static int check_parse(const void *d_data, size_t n_bytes, int32_t rows, int32_t cols, const void *d_rgb, const void *d_present) {
+    RT_TRY(check_map_bytes(d_data, n_bytes));
+    RT_TRY(check_image_size(rows, cols));
+    if (!d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "d_rgb is NULL");
+    if (!d_present) return fail(RT_ERR_INVALID_ARGUMENT, "d_present is NULL");
+    return check_map_size(n_bytes);
+}
+static int check_missing(const void *d_present, int32_t rows, int32_t cols, const void *d_pixels, size_t capacity) {
+    if (!d_present) return fail(RT_ERR_INVALID_ARGUMENT, "d_present is NULL");
+    RT_TRY(check_image_size(rows, cols));
+    if (d_pixels && capacity == 0) return fail(RT_ERR_INVALID_ARGUMENT, "d_pixels is given but capacity is 0");
+    return RT_OK;
+}
+static int check_scatter(size_t n, const void *d_pixels, const void *d_rgb_list, int32_t rows, int32_t cols, const void *d_rgb_frame) {
+    if (n > 0 && !d_pixels) return fail(RT_ERR_INVALID_ARGUMENT, "d_pixels is NULL");
+    if (n > 0 && !d_rgb_list) return fail(RT_ERR_INVALID_ARGUMENT, "d_rgb_list is NULL");
+    RT_TRY(check_count(n, "list entries"));
+    RT_TRY(check_image_size(rows, cols));
+    if (!d_rgb_frame) return fail(RT_ERR_INVALID_ARGUMENT, "d_rgb_frame is NULL");
+    return RT_OK;
+}
+static unsigned grid_for(size_t items) { // grid-stride kernels of RPM_BLOCK threads
+    const size_t want = (items + RPM_BLOCK - 1u) / RPM_BLOCK;
+    return (unsigned) (want < 1u ? 1u : want < 4096u ? want : 4096u);
+}
+
+// Enqueues one parse on `st` (arguments checked, the device current).  Scratch: the head and one winner word per pixel (zeroed), then one
+// rpm::Entry and one rpm::Map per tile.  An empty map: present cleared, the count 0, no scratch.  Never waits for the device.
+static int enqueue_parse(const void *d_data, size_t n_bytes, int32_t rows, int32_t cols, void *d_rgb, void *d_present, void *d_count, hipStream_t st,
+                         FormatPending &fp) {
+    const uint32_t npx = (uint32_t) ((uint64_t) rows * (uint64_t) cols), n = (uint32_t) n_bytes;
+    if (n == 0u) {
+        HIP_TRY(hipMemsetAsync(d_present, 0, npx, st));
+        if (d_count) HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(long long), st));
+        return RT_OK;
+    }
+    const uint32_t n_tiles = (n + (uint32_t) RPM_TILE_BYTES - 1u) / (uint32_t) RPM_TILE_BYTES;
+    const size_t zeroed = RPM_HEAD_BYTES + (size_t) npx * sizeof(unsigned int), entries_at = (zeroed + 7u) & ~(size_t) 7u,
+                 maps_at = entries_at + (size_t) n_tiles * sizeof(rpm::Entry);
+    HIP_TRY(hipMallocAsync((void **) &fp.scr, maps_at + (size_t) n_tiles * sizeof(rpm::Map), st));
+    fp.st = st;
+    HIP_TRY(hipMemsetAsync(fp.scr, 0, zeroed, st));
+    rpm::ParseHead *head = (rpm::ParseHead *) fp.scr;
+    unsigned int *winner = (unsigned int *) (fp.scr + RPM_HEAD_BYTES);
+    rpm::Entry *entries = (rpm::Entry *) (fp.scr + entries_at);
+    rpm::Map *maps = (rpm::Map *) (fp.scr + maps_at);
+    const uint8_t *data = (const uint8_t *) d_data;
+    hipLaunchKernelGGL(rpm::parse_maps_kernel, dim3(n_tiles), dim3(RPM_BLOCK), 0, st, data, n, maps);
+    hipLaunchKernelGGL(rpm::parse_scan_kernel, dim3(1), dim3(RPM_SCAN_THREADS), 0, st, (const rpm::Map *) maps, n_tiles, entries, head);
+    hipLaunchKernelGGL(rpm::parse_records_kernel<false>, dim3(n_tiles), dim3(RPM_BLOCK), 0, st, data, n, (uint32_t) rows, (uint32_t) cols, (const rpm::Entry *) entries, head,
+                       winner, (uint8_t *) d_rgb);
+    hipLaunchKernelGGL(rpm::parse_records_kernel<true>, dim3(n_tiles), dim3(RPM_BLOCK), 0, st, data, n, (uint32_t) rows, (uint32_t) cols, (const rpm::Entry *) entries, head,
+                       winner, (uint8_t *) d_rgb);
+    hipLaunchKernelGGL(rpm::parse_finish_kernel, dim3(grid_for(npx)), dim3(RPM_BLOCK), 0, st, (const rpm::ParseHead *) head, (const unsigned int *) winner, npx,
+                       (uint8_t *) d_present, (long long *) d_count, (long long) -RT_ERR_INVALID_ARGUMENT);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+// Waits for the stream and reads what the device found: the count, or a malformed map (of which it wrote nothing).
+static int finish_parse(FormatPending &fp, hipStream_t st, int64_t *count) {
+    rpm::ParseHead head{};
+    if (fp.scr) HIP_TRY(hipMemcpyAsync(&head, fp.scr, sizeof(head), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (head.bad) return fail(RT_ERR_INVALID_ARGUMENT, kMalformedMap);
+    *count = (int64_t) head.count;
+    return RT_OK;
+}
+
+// Enqueues one list of absent pixels on `st`: rt_output.h's three steps over presence bytes (scratch: rto::FormatScratch and one uint64 per tile).
+static int enqueue_missing(const void *d_present, int32_t rows, int32_t cols, void *d_pixels, size_t capacity, void *d_n, hipStream_t st, FormatPending &fp) {
+    const uint32_t npx = (uint32_t) ((uint64_t) rows * (uint64_t) cols), n_tiles = (npx + (uint32_t) RPM_TILE_BYTES - 1u) / (uint32_t) RPM_TILE_BYTES;
+    HIP_TRY(hipMallocAsync((void **) &fp.scr, RTO_SCRATCH_HEAD + (size_t) n_tiles * sizeof(unsigned long long), st));
+    fp.st = st;
+    rto::FormatScratch *head = (rto::FormatScratch *) fp.scr;
+    unsigned long long *tiles = (unsigned long long *) (fp.scr + RTO_SCRATCH_HEAD);
+    hipLaunchKernelGGL(rpm::missing_sums_kernel, dim3(n_tiles), dim3(RPM_BLOCK), 0, st, (const uint8_t *) d_present, npx, tiles);
+    hipLaunchKernelGGL(rto::format_scan_kernel, dim3(1), dim3(RTO_SCAN_THREADS), 0, st, tiles, n_tiles, 0ull, head, (long long *) d_n, (unsigned long long) capacity,
+                       d_pixels ? 1 : 0);
+    if (d_pixels)
+        hipLaunchKernelGGL(rpm::missing_scatter_kernel, dim3(n_tiles), dim3(RPM_BLOCK), 0, st, (const uint8_t *) d_present, npx, (const unsigned long long *) tiles,
+                           (const rto::FormatScratch *) head, (int32_t *) d_pixels);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+static int finish_missing(FormatPending &fp, const void *d_pixels, size_t capacity, int64_t *n) {
+    long long total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, fp.scr + offsetof(rto::FormatScratch, total), sizeof(total), hipMemcpyDeviceToHost, fp.st));
+    HIP_TRY(hipStreamSynchronize(fp.st));
+    *n = (int64_t) total;
+    if (d_pixels && (unsigned long long) total > (unsigned long long) capacity)
+        return fail(RT_ERR_INVALID_ARGUMENT, "capacity " + std::to_string(capacity) + " below the " + std::to_string(total) + " entries needed");
+    return RT_OK;
+}
+
+// Enqueues one scatter on `st` (n > 0).  Scratch: the head and one winner word per pixel of the frame, zeroed.
+static int enqueue_scatter(size_t n, const void *d_pixels, const void *d_rgb_list, int32_t rows, int32_t cols, void *d_rgb_frame, hipStream_t st, FormatPending &fp) {
+    const uint32_t npx = (uint32_t) ((uint64_t) rows * (uint64_t) cols);
+    const size_t bytes = RPM_HEAD_BYTES + (size_t) npx * sizeof(unsigned int);
+    HIP_TRY(hipMallocAsync((void **) &fp.scr, bytes, st));
+    fp.st = st;
+    HIP_TRY(hipMemsetAsync(fp.scr, 0, bytes, st));
+    rpm::ParseHead *head = (rpm::ParseHead *) fp.scr;
+    unsigned int *winner = (unsigned int *) (fp.scr + RPM_HEAD_BYTES);
+    hipLaunchKernelGGL(rpm::scatter_claim_kernel, dim3(grid_for(n)), dim3(RPM_BLOCK), 0, st, (uint32_t) n, (const int32_t *) d_pixels, npx, head, winner);
+    hipLaunchKernelGGL(rpm::scatter_store_kernel, dim3(grid_for(n)), dim3(RPM_BLOCK), 0, st, (uint32_t) n, (const int32_t *) d_pixels, (const uint8_t *) d_rgb_list,
+                       (const rpm::ParseHead *) head, (const unsigned int *) winner, (uint8_t *) d_rgb_frame);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// rt_resume_*'s checks: rt_render's list about scene, camera, geometry and options, then the map's bytes and the frame a pixel list can index
+static int check_resume(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, const void *data, size_t n_bytes,
+                        const rt_render_options *options, int32_t &rows, int32_t &cols) {
+    rows = (max_h > 0 && max_h <= (1 << 20)) ? 2 * max_h + 1 : 0;
+    cols = (max_w > 0 && max_w <= (1 << 20)) ? 2 * max_w + 1 : 0;
+    RT_TRY(check_frame(scene, camera, max_w, max_h, 0, 1, rows, scene, "", options)); // (the buffers are this call's own)
+    RT_TRY(check_map_bytes(data, n_bytes));
+    RT_TRY(check_list_frame(max_w, max_h));
+    return RT_OK;
+}
+
+// The resumed frame on the device (the device current, arguments checked; everything on the null stream; waits for it): the map's bytes
+// uploaded and parsed into `frame` (rows*cols*3, from the null stream's pool), the absent pixels listed, rendered as a pixel list and
+// scattered into it.  `local` as a pixel-list render fills it; all zero when the map is complete.
+static int resume_on_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, uint32_t flags,
+                            const uint8_t *data, size_t n_bytes, int32_t rows, int32_t cols, const rt_render_options *options, StreamBuf &frame, rt_stats &local) {
+    const size_t npx = (size_t) rows * (size_t) cols, present_at = (npx * 3u + 15u) & ~(size_t) 15u, pixels_at = present_at + ((npx + 15u) & ~(size_t) 15u),
+                 map_at = pixels_at + npx * 4u;
+    HIP_TRY(hipMallocAsync((void **) &frame.p, map_at + n_bytes, frame.st));
+    if (n_bytes) HIP_TRY(hipMemcpyAsync(frame.p + map_at, data, n_bytes, hipMemcpyHostToDevice, frame.st));
+    int64_t count = 0, missing = 0;
+    {
+        FormatPending fp;
+        RT_TRY(enqueue_parse(frame.p + map_at, n_bytes, rows, cols, frame.p, frame.p + present_at, nullptr, frame.st, fp));
+        RT_TRY(finish_parse(fp, frame.st, &count)); // a malformed map: before anything is rendered
+    }
+    {
+        FormatPending fp;
+        RT_TRY(enqueue_missing(frame.p + present_at, rows, cols, frame.p + pixels_at, npx, nullptr, frame.st, fp));
+        RT_TRY(finish_missing(fp, frame.p + pixels_at, npx, &missing));
+    }
+    memset(&local, 0, sizeof(local));
+    if (missing == 0) return RT_OK;
+    const size_t n = (size_t) missing, list_at = n * 16u;
+    StreamBuf out; // accum [n][4] int32, then rgb [n][3]
+    HIP_TRY(hipMallocAsync((void **) &out.p, list_at + n * 3u, out.st));
+    {
+        Pending pd;
+        RT_TRY(launch_pixels(scene, camera, max_w, max_h, seed, device, n, frame.p + pixels_at, flags, out.p, out.p + list_at, nullptr, options, true, pd));
+        RT_TRY(collect_stats(pd, &local));
+    }
+    FormatPending fp;
+    RT_TRY(enqueue_scatter(n, frame.p + pixels_at, out.p + list_at, rows, cols, frame.p, frame.st, fp));
+    HIP_TRY(hipStreamSynchronize(frame.st));
+    return RT_OK;
+}
+
+// rt_resume_ppm / rt_resume_png
+static int resume_file(const char *name, int fmt, const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device,
+                       uint32_t flags, const char *map_path, int32_t gamma_correct, const char *out_path, const rt_render_options *options, rt_stats *stats) {
+    int32_t rows = 0, cols = 0;
+    RT_TRY(check_resume(scene, camera, max_w, max_h, nullptr, 0, options, rows, cols));
+    if (!map_path) return fail(RT_ERR_INVALID_ARGUMENT, "map_path is NULL");
+    if (!out_path) return fail(RT_ERR_INVALID_ARGUMENT, "out_path is NULL");
+    if (fmt == rto::FMT_PNG) RT_TRY(check_png_size(rows, cols));
+    return guarded(name, [&]() {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<uint8_t> map; // the spill is read whole before the output is opened: the two paths may name one file
+        {
+            FileCloser in;
+            if (!(in.f = fopen(map_path, "rb"))) return fail(RT_ERR_IO, std::string("cannot open ") + map_path);
+            unsigned char block[1 << 16];
+            for (size_t got; (got = fread(block, 1, sizeof(block), in.f)) > 0;) {
+                map.insert(map.end(), block, block + got);
+                if (map.size() > (size_t) INT32_MAX) return check_map_size(map.size());
+            }
+            if (ferror(in.f)) return fail(RT_ERR_IO, std::string("cannot read ") + map_path);
+        }
+        FileCloser file;
+        if (!(file.f = fopen(out_path, "wb"))) return fail(RT_ERR_IO, std::string("cannot open ") + out_path);
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        StreamBuf frame;
+        rt_stats local;
+        RT_TRY(resume_on_device(scene, camera, max_w, max_h, seed, device, flags, map.data(), map.size(), rows, cols, options, frame, local));
+        const size_t capacity = (size_t) file_max_bytes(fmt, rows, cols);
+        StreamBuf d_text;
+        HIP_TRY(hipMallocAsync((void **) &d_text.p, capacity, d_text.st));
+        std::unique_ptr<char[]> text;
+        int64_t len = 0;
+        RT_TRY(file_to_host(fmt, frame.p, rows, cols, gamma_correct != 0, d_text.st, d_text.p, capacity, text, len));
+        RT_TRY(write_all(file, out_path, text.get(), len));
+        if (stats) {
+            *stats = local;
+            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return (int) RT_OK;
+    });
+}
+
+extern "C" {
+
+int32_t rt_pixel_map_chunk_bytes(void) { return RPM_CHUNK_BYTES; }
+int32_t rt_pixel_map_tile_bytes(void) { return RPM_TILE_BYTES; }
+int32_t rt_pixel_map_scan_tiles(void) { return RPM_SCAN_THREADS; }
+
+int rt_parse_pixel_map_device(int32_t device, const void *d_data, size_t n_bytes, int32_t rows, int32_t cols, void *d_rgb, void *d_present, void *d_count,
+                              void *stream, int64_t *count) {
+    RT_TRY(check_parse(d_data, n_bytes, rows, cols, d_rgb, d_present));
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    FormatPending fp;
+    RT_TRY(enqueue_parse(d_data, n_bytes, rows, cols, d_rgb, d_present, d_count, (hipStream_t) stream, fp));
+    return count ? finish_parse(fp, (hipStream_t) stream, count) : RT_OK;
+}
+
+int rt_missing_pixels_device(int32_t device, const void *d_present, int32_t rows, int32_t cols, void *d_pixels, size_t capacity, void *d_n, void *stream,
+                             int64_t *n) {
+    RT_TRY(check_missing(d_present, rows, cols, d_pixels, capacity));
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    FormatPending fp;
+    RT_TRY(enqueue_missing(d_present, rows, cols, d_pixels, capacity, d_n, (hipStream_t) stream, fp));
+    return n ? finish_missing(fp, d_pixels, capacity, n) : RT_OK;
+}
+
+int rt_scatter_pixels_device(int32_t device, size_t n, const void *d_pixels, const void *d_rgb_list, int32_t rows, int32_t cols, void *d_rgb_frame, void *stream) {
+    RT_TRY(check_scatter(n, d_pixels, d_rgb_list, rows, cols, d_rgb_frame));
+    if (n == 0) return RT_OK;
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    FormatPending fp;
+    return enqueue_scatter(n, d_pixels, d_rgb_list, rows, cols, d_rgb_frame, (hipStream_t) stream, fp);
+}
+
+int rt_resume_pixel_map(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, uint32_t flags,
+                        const uint8_t *data, size_t n_bytes, uint8_t *rgb_out, const rt_render_options *options, rt_stats *stats) {
+    int32_t rows = 0, cols = 0;
+    RT_TRY(check_resume(scene, camera, max_w, max_h, data, n_bytes, options, rows, cols));
+    if (!rgb_out) return fail(RT_ERR_INVALID_ARGUMENT, "rgb_out is NULL");
+    RT_TRY(check_map_size(n_bytes));
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    StreamBuf frame;
+    rt_stats local;
+    RT_TRY(resume_on_device(scene, camera, max_w, max_h, seed, device, flags, data, n_bytes, rows, cols, options, frame, local));
+    HIP_TRY(hipMemcpy(rgb_out, frame.p, (size_t) rows * (size_t) cols * 3u, hipMemcpyDeviceToHost));
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+int rt_resume_ppm(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, uint32_t flags,
+                  const char *map_path, int32_t gamma_correct, const char *out_path, const rt_render_options *options, rt_stats *stats) {
+    return resume_file("rt_resume_ppm", rto::FMT_PPM, scene, camera, max_w, max_h, seed, device, flags, map_path, gamma_correct, out_path, options, stats);
+}
+int rt_resume_png(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, uint32_t flags,
+                  const char *map_path, int32_t gamma_correct, const char *out_path, const rt_render_options *options, rt_stats *stats) {
+    return resume_file("rt_resume_png", rto::FMT_PNG, scene, camera, max_w, max_h, seed, device, flags, map_path, gamma_correct, out_path, options, stats);
+}
+
+} // extern "C"
 
 // ============================================================================================================
 // Device unit hooks: tiny kernels that call the SAME inlined device functions the render kernel uses.

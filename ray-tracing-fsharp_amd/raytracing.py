@@ -542,6 +542,39 @@ class Scene:
         self.last_stats = st.as_dict()
         return self.last_stats
 
+    def resume(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, data: bytes, *, seed: int = 0, device: int = 0, counters: bool = False,
+               options: Optional[A.rt_render_options] = None) -> np.ndarray:
+        """rt_resume_pixel_map: Program.fs:45-49 for an interrupted frame -- the pixel map `data` (bytes) parsed on the device, the pixels
+        it lacks rendered alone and scattered in -> rgb [rows, cols, 3] uint8.  For a map of render_rows' own records (any order, any
+        subset, duplicated or truncated) that is render_rows' rgb byte for byte.  last_stats: pixels = the number rendered."""
+        data = bytes(data)
+        rgb = np.zeros((2 * maxHeightCoord + 1, 2 * maxWidthCoord + 1, 3), np.uint8)
+        st = A.rt_stats()
+        cam = camera.to_abi()
+        check(lib.rt_resume_pixel_map(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, device, A.RT_RENDER_COUNTERS if counters else 0,
+                                      data, len(data), _u8(rgb), _ref(options), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return rgb
+
+    def resumePng(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, mapPath: str, path: str, *, gammaCorrect: bool = True, seed: int = 0,
+                  device: int = 0, counters: bool = False, options: Optional[A.rt_render_options] = None) -> dict:
+        """rt_resume_png: Program.fs:45-50 with the missing pixels rendered where ImageOutput.assertComplete would throw -- the spill at
+        mapPath resumed on the device, encoded there and written to `path`; byte for byte Png.format of resume()'s rgb."""
+        return self._resume_file(lib.rt_resume_png, maxWidthCoord, maxHeightCoord, camera, mapPath, path, gammaCorrect, seed, device, counters, options)
+
+    def resumePpm(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, mapPath: str, path: str, *, gammaCorrect: bool = True, seed: int = 0,
+                  device: int = 0, counters: bool = False, options: Optional[A.rt_render_options] = None) -> dict:
+        """rt_resume_ppm: resumePng with ImageOutput.writePpm's P3 text."""
+        return self._resume_file(lib.rt_resume_ppm, maxWidthCoord, maxHeightCoord, camera, mapPath, path, gammaCorrect, seed, device, counters, options)
+
+    def _resume_file(self, fn, maxWidthCoord, maxHeightCoord, camera, mapPath, path, gammaCorrect, seed, device, counters, options) -> dict:
+        st = A.rt_stats()
+        cam = camera.to_abi()
+        check(fn(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, device, A.RT_RENDER_COUNTERS if counters else 0, str(mapPath).encode(),
+                 int(bool(gammaCorrect)), str(path).encode(), _ref(options), C.byref(st)))
+        self.last_stats = st.as_dict()
+        return self.last_stats
+
     def extend_rows(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, accum, samplesDone: int, *, seed: int = 0,
                     device: Optional[int] = None, row_first: int = 0, row_stride: int = 1, counters: bool = False, stats: bool = True,
                     options: Optional[A.rt_render_options] = None) -> RenderResult:
@@ -1127,6 +1160,37 @@ class ImageOutput:
         if n < 0:
             check(int(-n))
         return rgb, present.astype(bool)
+
+    @staticmethod
+    def parsePixelMap(data, numRows: int, numCols: int):
+        """rt_parse_pixel_map_device: ImageOutput.readPixelMap (ImageOutput.fs:46-113) of map bytes that are on a GPU -- `data` a uint8 torch
+        tensor [n] there -> (pixels [rows, cols, 3] uint8, present [rows, cols] bool), tensors on that GPU, on torch.cuda.current_stream().
+        Pixels the map does not name are 0.  Waits for the device; a map naming a pixel outside the image raises RtError."""
+        torch = _torch()
+        t = _bytes_tensor(data).reshape(-1)
+        rgb = torch.zeros((numRows, numCols, 3), dtype=torch.uint8, device=t.device)
+        present = torch.empty((numRows, numCols), dtype=torch.uint8, device=t.device)
+        n = C.c_int64(0)
+        check(lib.rt_parse_pixel_map_device(t.device.index, t.data_ptr() if t.numel() else None, t.numel(), numRows, numCols, rgb.data_ptr(), present.data_ptr(),
+                                            None, torch.cuda.current_stream(t.device).cuda_stream, C.byref(n)))
+        return rgb, present.bool()
+
+    @staticmethod
+    def missingPixels(present):
+        """rt_missing_pixels_device: the global pixel indices row * cols + col of the pixels a presence map [rows, cols] (bool or uint8 tensor
+        on a GPU) lacks, ascending, as an int32 tensor there -- what Scene.renderPixels takes.  Waits for the device."""
+        torch = _torch()
+        if present.dim() != 2:
+            raise ValueError(f"present must have shape [rows, cols], not {list(present.shape)}")
+        t = _bytes_tensor(present.to(torch.uint8) if present.dtype == torch.bool else present)
+        rows, cols = int(t.shape[0]), int(t.shape[1])
+        stream = torch.cuda.current_stream(t.device).cuda_stream
+        n = C.c_int64(0)
+        check(lib.rt_missing_pixels_device(t.device.index, t.data_ptr(), rows, cols, None, 0, None, stream, C.byref(n)))
+        pixels = torch.empty(n.value, dtype=torch.int32, device=t.device)
+        if n.value:
+            check(lib.rt_missing_pixels_device(t.device.index, t.data_ptr(), rows, cols, pixels.data_ptr(), n.value, None, stream, C.byref(n)))
+        return pixels
 
     @staticmethod
     def assertComplete(pixel_map) -> np.ndarray:
