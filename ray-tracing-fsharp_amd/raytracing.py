@@ -504,6 +504,19 @@ class Scene:
         check(lib.rt_scene_tune_rays(self._h, _f64(r), r.shape[0], C.byref(info)))
         return {n: getattr(info, n) for n, _ in info._fields_ if n != "struct_size"}
 
+    def _call(self, fn, *args, stats: bool = True) -> Optional[dict]:
+        """fn(scene, *args, stats), checked.  The statistics go to last_stats and are returned (None where none were asked for)."""
+        st = A.rt_stats() if stats else None
+        check(fn(self._h, *args, _ref(st)))
+        self.last_stats = st.as_dict() if st is not None else None
+        return self.last_stats
+
+    def _launch(self, route, base: str, *args, stats: bool, options) -> Optional[dict]:
+        """The entry point `base` of the route (base itself for arrays, base_device for tensors) with the arguments between the scene
+        and the tail, which is the route's: stats for arrays, which always collect them; stream, options, stats for tensors."""
+        assert base in _ROUTED, base
+        return self._call(getattr(lib, base + route.suffix), *args, *route.tail(options), stats=stats or not route.suffix)
+
     def render_rows(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, *, seed: int = 0, device: int = 0,
                     row_first: int = 0, row_stride: int = 1, n_rows: Optional[int] = None, counters: bool = False) -> RenderResult:
         """rt_render for the image rows row_first + i*row_stride (the whole frame by default)."""
@@ -513,34 +526,23 @@ class Scene:
             n_rows = max(0, (rows - row_first + row_stride - 1) // row_stride)
         accum = np.zeros((n_rows, cols, 4), np.int32)
         rgb = np.zeros((n_rows, cols, 3), np.uint8)
-        st = A.rt_stats()
-        cam = camera.to_abi()
-        check(lib.rt_render(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, device, row_first, row_stride, n_rows,
-                            A.RT_RENDER_COUNTERS if counters else 0, _i32(accum), _u8(rgb), C.byref(st)))
-        self.last_stats = st.as_dict()
-        return RenderResult(accum, rgb, self.last_stats)
+        st = self._call(lib.rt_render, C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, device, row_first, row_stride, n_rows,
+                        _flags(counters), _i32(accum), _u8(rgb))
+        return RenderResult(accum, rgb, st)
 
     def renderPpm(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, path: str, *, gammaCorrect: bool = True, seed: int = 0,
                   device: int = 0, counters: bool = False) -> dict:
         """rt_render_ppm: Scene.render |> ImageOutput.writePpm in one call -- the frame rendered, formatted as P3 text on the device and
         written to `path`; byte for byte ImageOutput.writePpm of render_rows' rgb.  Returns the statistics (total_ms covers the file)."""
-        st = A.rt_stats()
-        cam = camera.to_abi()
-        check(lib.rt_render_ppm(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, device, A.RT_RENDER_COUNTERS if counters else 0,
-                                int(bool(gammaCorrect)), str(path).encode(), None, C.byref(st)))
-        self.last_stats = st.as_dict()
-        return self.last_stats
+        return self._call(lib.rt_render_ppm, C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, device, _flags(counters),
+                          int(bool(gammaCorrect)), str(path).encode(), None)
 
     def renderPng(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, path: str, *, gammaCorrect: bool = True, seed: int = 0,
                   device: int = 0, counters: bool = False) -> dict:
         """rt_render_png: Scene.render |> Png.write (Program.fs:47-50) in one call -- the frame rendered, encoded as a PNG on the device and
         written to `path`; byte for byte Png.format of render_rows' rgb.  Returns the statistics (total_ms covers the file)."""
-        st = A.rt_stats()
-        cam = camera.to_abi()
-        check(lib.rt_render_png(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, device, A.RT_RENDER_COUNTERS if counters else 0,
-                                int(bool(gammaCorrect)), str(path).encode(), None, C.byref(st)))
-        self.last_stats = st.as_dict()
-        return self.last_stats
+        return self._call(lib.rt_render_png, C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, device, _flags(counters),
+                          int(bool(gammaCorrect)), str(path).encode(), None)
 
     def resume(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, data: bytes, *, seed: int = 0, device: int = 0, counters: bool = False,
                options: Optional[A.rt_render_options] = None) -> np.ndarray:
@@ -549,11 +551,8 @@ class Scene:
         subset, duplicated or truncated) that is render_rows' rgb byte for byte.  last_stats: pixels = the number rendered."""
         data = bytes(data)
         rgb = np.zeros((2 * maxHeightCoord + 1, 2 * maxWidthCoord + 1, 3), np.uint8)
-        st = A.rt_stats()
-        cam = camera.to_abi()
-        check(lib.rt_resume_pixel_map(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, device, A.RT_RENDER_COUNTERS if counters else 0,
-                                      data, len(data), _u8(rgb), _ref(options), C.byref(st)))
-        self.last_stats = st.as_dict()
+        self._call(lib.rt_resume_pixel_map, C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, device, _flags(counters), data, len(data),
+                   _u8(rgb), _ref(options))
         return rgb
 
     def resumePng(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, mapPath: str, path: str, *, gammaCorrect: bool = True, seed: int = 0,
@@ -568,12 +567,8 @@ class Scene:
         return self._resume_file(lib.rt_resume_ppm, maxWidthCoord, maxHeightCoord, camera, mapPath, path, gammaCorrect, seed, device, counters, options)
 
     def _resume_file(self, fn, maxWidthCoord, maxHeightCoord, camera, mapPath, path, gammaCorrect, seed, device, counters, options) -> dict:
-        st = A.rt_stats()
-        cam = camera.to_abi()
-        check(fn(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, device, A.RT_RENDER_COUNTERS if counters else 0, str(mapPath).encode(),
-                 int(bool(gammaCorrect)), str(path).encode(), _ref(options), C.byref(st)))
-        self.last_stats = st.as_dict()
-        return self.last_stats
+        return self._call(fn, C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, device, _flags(counters), str(mapPath).encode(),
+                          int(bool(gammaCorrect)), str(path).encode(), _ref(options))
 
     def extend_rows(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, accum, samplesDone: int, *, seed: int = 0,
                     device: Optional[int] = None, row_first: int = 0, row_stride: int = 1, counters: bool = False, stats: bool = True,
@@ -584,32 +579,12 @@ class Scene:
         is and a new one returned; a torch tensor on a GPU is extended IN PLACE through rt_render_extend_device on
         torch.cuda.current_stream() (stats=False: no wait for the device; a malformed buffer then goes unreported and unchanged)."""
         cols = 2 * maxWidthCoord + 1
-        flags = A.RT_RENDER_COUNTERS if counters else 0
-        cam = camera.to_abi()
-        if _is_torch(accum):
-            torch = _torch()
-            if accum.dtype != torch.int32 or accum.dim() != 3 or tuple(accum.shape[1:]) != (cols, 4) or not accum.is_cuda or not accum.is_contiguous():
-                raise ValueError(f"accum must be a contiguous int32 tensor [n_rows, {cols}, 4] on a GPU")
-            dev = _tensor_device(accum, device)
-            n_rows = accum.shape[0]
-            rgb = torch.empty((n_rows, cols, 3), dtype=torch.uint8, device=accum.device)
-            st = A.rt_stats() if stats else None
-            check(lib.rt_render_extend_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, row_first, row_stride, n_rows, flags,
-                                              samplesDone, accum.data_ptr(), rgb.data_ptr(), torch.cuda.current_stream(accum.device).cuda_stream,
-                                              _ref(options), _ref(st)))
-            self.last_stats = st.as_dict() if st is not None else None
-            return RenderResult(accum, rgb, self.last_stats)
-        _no_options(options)
-        if not isinstance(accum, np.ndarray) or accum.dtype != np.int32 or accum.ndim != 3 or accum.shape[1:] != (cols, 4):
-            raise ValueError(f"accum must be an int32 array [n_rows, {cols}, 4] or such a tensor on a GPU")
-        out = np.array(accum, dtype=np.int32, order="C")
+        route, out, _ = _frame(accum, cols, device, options)
         n_rows = out.shape[0]
-        rgb = np.zeros((n_rows, cols, 3), np.uint8)
-        st = A.rt_stats()
-        check(lib.rt_render_extend(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, row_first, row_stride,
-                                   n_rows, flags, samplesDone, _i32(out), _u8(rgb), C.byref(st)))
-        self.last_stats = st.as_dict()
-        return RenderResult(out, rgb, self.last_stats)
+        rgb = route.make((n_rows, cols, 3), "u8")
+        st = self._launch(route, "rt_render_extend", C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, route.device, row_first, row_stride,
+                          n_rows, _flags(counters), samplesDone, route.ptr(out), route.ptr(rgb), stats=stats, options=options)
+        return RenderResult(out, rgb, st)
 
     def extend_rows_map(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, accum, targets, *, seed: int = 0,
                         device: Optional[int] = None, row_first: int = 0, row_stride: int = 1, counters: bool = False, stats: bool = True,
@@ -621,38 +596,12 @@ class Scene:
         extend_rows: an array is copied, a GPU tensor (with `targets` a tensor on the same device) is extended in place on the
         current stream."""
         cols = 2 * maxWidthCoord + 1
-        flags = A.RT_RENDER_COUNTERS if counters else 0
-        cam = camera.to_abi()
-        if _is_torch(accum):
-            torch = _torch()
-            if accum.dtype != torch.int32 or accum.dim() != 3 or tuple(accum.shape[1:]) != (cols, 4) or not accum.is_cuda or not accum.is_contiguous():
-                raise ValueError(f"accum must be a contiguous int32 tensor [n_rows, {cols}, 4] on a GPU")
-            n_rows = accum.shape[0]
-            if (not _is_torch(targets) or targets.dtype != torch.int32 or tuple(targets.shape) != (n_rows, cols) or targets.device != accum.device
-                    or not targets.is_contiguous()):
-                raise ValueError(f"targets must be a contiguous int32 tensor [n_rows, {cols}] on accum's device")
-            dev = _tensor_device(accum, device)
-            rgb = torch.empty((n_rows, cols, 3), dtype=torch.uint8, device=accum.device)
-            st = A.rt_stats() if stats else None
-            check(lib.rt_render_extend_map_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, row_first, row_stride, n_rows, flags,
-                                                  targets.data_ptr(), accum.data_ptr(), rgb.data_ptr(),
-                                                  torch.cuda.current_stream(accum.device).cuda_stream, _ref(options), _ref(st)))
-            self.last_stats = st.as_dict() if st is not None else None
-            return RenderResult(accum, rgb, self.last_stats)
-        _no_options(options)
-        if not isinstance(accum, np.ndarray) or accum.dtype != np.int32 or accum.ndim != 3 or accum.shape[1:] != (cols, 4):
-            raise ValueError(f"accum must be an int32 array [n_rows, {cols}, 4] or such a tensor on a GPU")
-        out = np.array(accum, dtype=np.int32, order="C")
+        route, out, tg = _frame(accum, cols, device, options, mapped=True, targets=targets)
         n_rows = out.shape[0]
-        if not isinstance(targets, np.ndarray) or targets.dtype != np.int32 or targets.shape != (n_rows, cols):
-            raise ValueError(f"targets must be an int32 array [n_rows, {cols}]")
-        tg = np.ascontiguousarray(targets)
-        rgb = np.zeros((n_rows, cols, 3), np.uint8)
-        st = A.rt_stats()
-        check(lib.rt_render_extend_map(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, row_first,
-                                       row_stride, n_rows, flags, _i32(tg), _i32(out), _u8(rgb), C.byref(st)))
-        self.last_stats = st.as_dict()
-        return RenderResult(out, rgb, self.last_stats)
+        rgb = route.make((n_rows, cols, 3), "u8")
+        st = self._launch(route, "rt_render_extend_map", C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, route.device, row_first,
+                          row_stride, n_rows, _flags(counters), route.ptr(tg), route.ptr(out), route.ptr(rgb), stats=stats, options=options)
+        return RenderResult(out, rgb, st)
 
     def render_frame(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, *, seed: int = 0, devices: Sequence[int] = (0,),
                      gather: int = A.RT_GATHER_AUTO, counters: bool = False, options: Optional[A.rt_render_options] = None) -> RenderResult:
@@ -676,27 +625,10 @@ class Scene:
         NaN where hit_index < 0).  A numpy array goes through rt_hit_objects; a torch tensor on a GPU through rt_hit_objects_device
         on torch.cuda.current_stream(), and the results are tensors on that device (stats=False: no wait for the device, and
         last_stats is None).  The statistics go to last_stats, which is per thread.  device: the GPU (default 0, or the tensor's)."""
-        flags = A.RT_RENDER_COUNTERS if counters else 0
-        if _is_torch(rays):
-            torch = _torch()
-            r = _tensor_arg(rays, "rays", (torch.float64,), 6)
-            dev = _tensor_device(r, device)
-            n = r.shape[0]
-            hit = torch.empty(n, dtype=torch.int32, device=r.device)
-            strike = torch.empty((n, 3), dtype=torch.float64, device=r.device)
-            st = A.rt_stats() if stats else None
-            check(lib.rt_hit_objects_device(self._h, dev, n, r.data_ptr(), flags, hit.data_ptr(), strike.data_ptr(),
-                                            torch.cuda.current_stream(r.device).cuda_stream, _ref(options), _ref(st)))
-            self.last_stats = st.as_dict() if st is not None else None
-            return hit, strike
-        _no_options(options)
-        r = _array_arg(rays, "rays", np.float64, 6)
+        route, r = _route(rays, "rays", "f64", 6, device, options)
         n = r.shape[0]
-        hit = np.zeros(n, np.int32)
-        strike = np.zeros((n, 3), np.float64)
-        st = A.rt_stats()
-        check(lib.rt_hit_objects(self._h, 0 if device is None else device, n, _f64(r), flags, _i32(hit), _f64(strike), C.byref(st)))
-        self.last_stats = st.as_dict()
+        hit, strike = route.make((n,), "i32"), route.make((n, 3), "f64")
+        self._launch(route, "rt_hit_objects", route.device, n, route.ptr(r), _flags(counters), route.ptr(hit), route.ptr(strike), stats=stats, options=options)
         return hit, strike
 
     def traceRays(self, rays, bounceDepth: int, *, rng=None, seed: int = 0, stream_base: int = 0, sample: int = 0,
@@ -706,39 +638,12 @@ class Scene:
         are not modified: rng_out holds them advanced.  rng=None: ray i draws from the stream keyed (seed, stream_base + i, sample),
         as a render's (pixel, sample), and rng_out is None.  numpy arrays / torch tensors as for hitObject (a tensor rng may be
         uint32 or int32: the bits are the state)."""
-        flags = A.RT_RENDER_COUNTERS if counters else 0
-        if _is_torch(rays):
-            torch = _torch()
-            r = _tensor_arg(rays, "rays", (torch.float64,), 6)
-            dev = _tensor_device(r, device)
-            n = r.shape[0]
-            g = None
-            if rng is not None:
-                if not _is_torch(rng):
-                    raise TypeError("rng must be a torch tensor when rays is one")
-                g = _tensor_arg(rng, "rng", (torch.uint32, torch.int32), 4).clone()
-                if g.shape[0] != n or g.device != r.device:
-                    raise ValueError("rng must be [n, 4] on the rays' device")
-            colour = torch.empty((n, 3), dtype=torch.uint8, device=r.device)
-            st = A.rt_stats() if stats else None
-            check(lib.rt_trace_rays_device(self._h, dev, n, r.data_ptr(), g.data_ptr() if g is not None else None, seed, stream_base, sample,
-                                           bounceDepth, flags, colour.data_ptr(), torch.cuda.current_stream(r.device).cuda_stream,
-                                           _ref(options), _ref(st)))
-            self.last_stats = st.as_dict() if st is not None else None
-            return colour, g
-        _no_options(options)
-        r = _array_arg(rays, "rays", np.float64, 6)
+        route, r = _route(rays, "rays", "f64", 6, device, options)
         n = r.shape[0]
-        g = None
-        if rng is not None:
-            g = _array_arg(rng, "rng", np.uint32, 4).copy()
-            if g.shape[0] != n:
-                raise ValueError("rng must be [n, 4] for n rays")
-        colour = np.zeros((n, 3), np.uint8)
-        st = A.rt_stats()
-        check(lib.rt_trace_rays(self._h, 0 if device is None else device, n, _f64(r), _u32(g) if g is not None else None, seed, stream_base,
-                                sample, bounceDepth, flags, _u8(colour), C.byref(st)))
-        self.last_stats = st.as_dict()
+        g = _rng(route, rng, n)
+        colour = route.make((n, 3), "u8")
+        self._launch(route, "rt_trace_rays", route.device, n, route.ptr(r), route.ptr(g), seed, stream_base, sample, bounceDepth, _flags(counters),
+                     route.ptr(colour), stats=stats, options=options)
         return colour, g
 
     def renderFootprints(self, footprints, samplesPerPixel: int, bounceDepth: int, *, seed: int = 0, stream_base: int = 0,
@@ -757,60 +662,13 @@ class Scene:
         most samplesPerPixel; the classes and the array / tensor rules of extend_rows_map."""
         if extend is not None and extend_map is not None:
             raise ValueError("extend and extend_map exclude each other")
-        flags = A.RT_RENDER_COUNTERS if counters else 0
-        if _is_torch(footprints):
-            torch = _torch()
-            f = _tensor_arg(footprints, "footprints", (torch.float64,), 12)
-            dev = _tensor_device(f, device)
-            n = f.shape[0]
-            rgb = torch.empty((n, 3), dtype=torch.uint8, device=f.device)
-            st = A.rt_stats() if stats else None
-            stream = torch.cuda.current_stream(f.device).cuda_stream
-            if extend is not None:
-                accum, done = extend
-                _accum_tensor(accum, n, f.device, "extend=(accum, samplesDone)", "the footprints' device")
-                check(lib.rt_render_footprints_extend_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
-                                                             done, accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
-            elif extend_map is not None:
-                accum, tg = extend_map
-                _accum_tensor(accum, n, f.device, "extend_map=(accum, targets)", "the footprints' device")
-                if not _is_torch(tg) or tg.dtype != torch.int32 or tuple(tg.shape) != (n,) or tg.device != f.device or not tg.is_contiguous():
-                    raise ValueError("extend_map=(accum, targets): targets must be a contiguous int32 tensor [n] on the footprints' device")
-                check(lib.rt_render_footprints_extend_map_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
-                                                                 tg.data_ptr(), accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
-            else:
-                accum = torch.empty((n, 4), dtype=torch.int32, device=f.device)
-                check(lib.rt_render_footprints_device(self._h, dev, n, f.data_ptr(), samplesPerPixel, bounceDepth, seed, stream_base, flags,
-                                                      accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
-            self.last_stats = st.as_dict() if st is not None else None
-            return RenderResult(accum, rgb, self.last_stats)
-        _no_options(options)
-        f = _array_arg(footprints, "footprints", np.float64, 12)
+        route, f = _route(footprints, "footprints", "f64", 12, device, options)
         n = f.shape[0]
-        rgb = np.zeros((n, 3), np.uint8)
-        st = A.rt_stats()
-        if extend is not None:
-            accum = np.array(_array_arg(extend[0], "extend's accum", np.int32, 4), order="C")
-            if accum.shape[0] != n:
-                raise ValueError("extend=(accum, samplesDone): accum must be [n, 4] for n footprints")
-            check(lib.rt_render_footprints_extend(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed,
-                                                  stream_base, flags, extend[1], _i32(accum), _u8(rgb), C.byref(st)))
-        elif extend_map is not None:
-            accum = np.array(_array_arg(extend_map[0], "extend_map's accum", np.int32, 4), order="C")
-            tg = extend_map[1]
-            if accum.shape[0] != n:
-                raise ValueError("extend_map=(accum, targets): accum must be [n, 4] for n footprints")
-            if not isinstance(tg, np.ndarray) or tg.dtype != np.int32 or tg.shape != (n,):
-                raise ValueError("extend_map=(accum, targets): targets must be an int32 array [n]")
-            tg = np.ascontiguousarray(tg)
-            check(lib.rt_render_footprints_extend_map(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed,
-                                                      stream_base, flags, _i32(tg), _i32(accum), _u8(rgb), C.byref(st)))
-        else:
-            accum = np.zeros((n, 4), np.int32)
-            check(lib.rt_render_footprints(self._h, 0 if device is None else device, n, _f64(f), samplesPerPixel, bounceDepth, seed, stream_base,
-                                           flags, _i32(accum), _u8(rgb), C.byref(st)))
-        self.last_stats = st.as_dict()
-        return RenderResult(accum, rgb, self.last_stats)
+        kind, before, accum = _list_extension(route, n, extend, extend_map, "footprints", "the footprints' device")
+        rgb = route.make((n, 3), "u8")
+        st = self._launch(route, "rt_render_footprints" + kind, route.device, n, route.ptr(f), samplesPerPixel, bounceDepth, seed, stream_base,
+                          _flags(counters), *before, route.ptr(accum), route.ptr(rgb), stats=stats, options=options)
+        return RenderResult(accum, rgb, st)
 
     def renderPixels(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, pixels, *, seed: int = 0, device: Optional[int] = None,
                      counters: bool = False, stats: bool = True, options: Optional[A.rt_render_options] = None, extend=None) -> RenderResult:
@@ -823,44 +681,13 @@ class Scene:
         extend=(accum, samplesDone): rt_render_pixels_extend -- `accum` [n, 4] int32, this list's PixelStats at samplesDone (>= 12)
         samples, is continued to camera.SamplesPerPixel; bit for bit a list render at that count.  An array is copied, a tensor (on the
         list's device) extended in place."""
-        flags = A.RT_RENDER_COUNTERS if counters else 0
-        cam = camera.to_abi()
-        if _is_torch(pixels):
-            torch = _torch()
-            px = _list_tensor(pixels)
-            dev = _tensor_device(px, device)
-            n = px.shape[0]
-            rgb = torch.empty((n, 3), dtype=torch.uint8, device=px.device)
-            st = A.rt_stats() if stats else None
-            stream = torch.cuda.current_stream(px.device).cuda_stream
-            if extend is not None:
-                accum, done = extend
-                _accum_tensor(accum, n, px.device, "extend=(accum, samplesDone)", "the list's device")
-                check(lib.rt_render_pixels_extend_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, n, px.data_ptr(), flags, done,
-                                                         accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
-            else:
-                accum = torch.empty((n, 4), dtype=torch.int32, device=px.device)
-                check(lib.rt_render_pixels_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, n, px.data_ptr(), flags,
-                                                  accum.data_ptr(), rgb.data_ptr(), stream, _ref(options), _ref(st)))
-            self.last_stats = st.as_dict() if st is not None else None
-            return RenderResult(accum, rgb, self.last_stats)
-        _no_options(options)
-        px = _list_array(pixels)
+        route, px = _route(pixels, "pixels", "i32", None, device, options)
         n = px.shape[0]
-        rgb = np.zeros((n, 3), np.uint8)
-        st = A.rt_stats()
-        if extend is not None:
-            accum = np.array(_array_arg(extend[0], "extend's accum", np.int32, 4), order="C")
-            if accum.shape[0] != n:
-                raise ValueError("extend=(accum, samplesDone): accum must be [n, 4] for n list entries")
-            check(lib.rt_render_pixels_extend(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, n, _i32(px),
-                                              flags, extend[1], _i32(accum), _u8(rgb), C.byref(st)))
-        else:
-            accum = np.zeros((n, 4), np.int32)
-            check(lib.rt_render_pixels(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, n, _i32(px), flags,
-                                       _i32(accum), _u8(rgb), C.byref(st)))
-        self.last_stats = st.as_dict()
-        return RenderResult(accum, rgb, self.last_stats)
+        kind, before, accum = _list_extension(route, n, extend, None, "list entries", "the list's device")
+        rgb = route.make((n, 3), "u8")
+        st = self._launch(route, "rt_render_pixels" + kind, C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, route.device, n, route.ptr(px),
+                          _flags(counters), *before, route.ptr(accum), route.ptr(rgb), stats=stats, options=options)
+        return RenderResult(accum, rgb, st)
 
     def cameraHits(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, pixels=None, *, sample_first: int = 0, n_samples: int = 1,
                    seed: int = 0, n: Optional[int] = None, strike: bool = True, rays: bool = True, tensors: bool = False, device: Optional[int] = None,
@@ -874,64 +701,31 @@ class Scene:
         tensor goes through rt_camera_hits_device on torch.cuda.current_stream() and the results are tensors (stats=False: no wait for
         the device; a list with an entry outside the frame then goes unreported and nothing is written); with pixels=None,
         tensors=True does the same on `device` (default: torch's current one)."""
-        flags = A.RT_RENDER_COUNTERS if counters else 0
-        cam = camera.to_abi()
-        frame = (2 * maxWidthCoord + 1) * (2 * maxHeightCoord + 1)
         if not isinstance(n_samples, int) or not isinstance(sample_first, int):
             raise TypeError("sample_first and n_samples must be ints")
-        if pixels is not None and n is not None:
-            raise ValueError("n applies to pixels=None")
-        if _is_torch(pixels) or (pixels is None and tensors):
-            torch = _torch()
-            if pixels is None:
-                tdev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-                dev, count, ptr = tdev.index, frame if n is None else int(n), None
-            else:
-                px = _list_tensor(pixels)
-                tdev, dev, count, ptr = px.device, _tensor_device(px, device), px.shape[0], px.data_ptr()
-            per = max(n_samples, 0)
-            hit = torch.empty((count, per), dtype=torch.int32, device=tdev)
-            sk = torch.empty((count, per, 3), dtype=torch.float64, device=tdev) if strike else None
-            ry = torch.empty((count, per, 6), dtype=torch.float64, device=tdev) if rays else None
-            st = A.rt_stats() if stats else None
-            check(lib.rt_camera_hits_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, count, ptr, sample_first, n_samples, flags,
-                                            hit.data_ptr(), sk.data_ptr() if strike else None, ry.data_ptr() if rays else None,
-                                            torch.cuda.current_stream(tdev).cuda_stream, _ref(options), _ref(st)))
-            self.last_stats = st.as_dict() if st is not None else None
-            return CameraHits(hit, sk, ry, self.last_stats)
-        _no_options(options, "set_launch_config")
-        if pixels is None:
-            px, count = None, frame if n is None else int(n)
-        else:
-            px = _list_array(pixels)
-            count = px.shape[0]
-        if count < 0:
-            raise ValueError("n must be >= 0")
+        route, px, count = _pixel_list(pixels, n, tensors, maxWidthCoord, maxHeightCoord, device, options)
         per = max(n_samples, 0)
-        big = count * per > 2**31 - 1  # (refused by the library: no buffers are made for it)
-        shape = (0, 0) if big else (count, per)
-        hit = np.zeros(shape, np.int32)
-        sk = np.zeros(shape + (3,), np.float64) if strike else None
-        ry = np.zeros(shape + (6,), np.float64) if rays else None
-        st = A.rt_stats()
-        check(lib.rt_camera_hits(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, count,
-                                 _i32(px) if px is not None else None, sample_first, n_samples, flags, _i32(hit), _f64(sk) if strike else None,
-                                 _f64(ry) if rays else None, C.byref(st)))
-        self.last_stats = st.as_dict()
-        return CameraHits(hit, sk, ry, self.last_stats)
+        shape = _lead(route, (count, per), count * per)
+        hit = route.make(shape, "i32")
+        sk = route.make(shape + (3,), "f64") if strike else None
+        ry = route.make(shape + (6,), "f64") if rays else None
+        st = self._launch(route, "rt_camera_hits", C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, route.device, count, route.ptr(px),
+                          sample_first, n_samples, _flags(counters), route.ptr(hit), route.ptr(sk), route.ptr(ry), stats=stats, options=options)
+        return CameraHits(hit, sk, ry, st)
 
     @staticmethod
-    def _path_buffers(lead, k, records, make, first_ray=False, summary_entries=None):
-        """The output buffers of a path call, shaped lead + (...): make(shape, kind) allocates, kind one of "i32", "u8", "f64"."""
-        bufs = {"n_vertices": make(lead, "i32"), "end": make(lead, "i32"), "colour": make(lead + (3,), "u8")}
-        bufs["first_ray"] = make(lead + (6,), "f64") if first_ray else None
+    def _path_buffers(route, lead, max_vertices, records, first_ray=False, summary_entries=None):
+        """The output buffers of a path call, shaped lead + (...), and the rt_path_outputs that names them."""
+        k = max(max_vertices, 0)
+        bufs = {"n_vertices": route.make(lead, "i32"), "end": route.make(lead, "i32"), "colour": route.make(lead + (3,), "u8")}
+        bufs["first_ray"] = route.make(lead + (6,), "f64") if first_ray else None
         rec = records and k > 0
-        bufs["hit_index"] = make(lead + (k,), "i32") if rec else None
-        bufs["strike"] = make(lead + (k, 3), "f64") if rec else None
-        bufs["colour_after"] = make(lead + (k, 3), "u8") if rec else None
-        bufs["ray_after"] = make(lead + (k, 6), "f64") if rec else None
-        bufs["summary"] = make((summary_entries, A.RT_PATH_SUMMARY_WORDS), "i32") if summary_entries is not None else None
-        return bufs
+        bufs["hit_index"] = route.make(lead + (k,), "i32") if rec else None
+        bufs["strike"] = route.make(lead + (k, 3), "f64") if rec else None
+        bufs["colour_after"] = route.make(lead + (k, 3), "u8") if rec else None
+        bufs["ray_after"] = route.make(lead + (k, 6), "f64") if rec else None
+        bufs["summary"] = route.make((summary_entries, A.RT_PATH_SUMMARY_WORDS), "i32") if summary_entries is not None else None
+        return bufs, A.rt_path_outputs(max_vertices=max_vertices, **{f: C.cast(route.ptr(b), C.c_void_p).value for f, b in bufs.items()})
 
     def cameraPaths(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, pixels=None, *, sample_first: int = 0, n_samples: int = 1,
                     max_vertices: int = 8, records: bool = True, first_ray: bool = True, summary: bool = False, seed: int = 0,
@@ -943,97 +737,30 @@ class Scene:
         max_vertices (K): records kept per path; n_vertices counts them all.  records=False / first_ray=False: not computed (None);
         summary=True adds the per-entry reduction [n, 16].  numpy arrays / torch tensors as for cameraHits (a tensor list, or
         pixels=None with tensors=True, goes through rt_camera_paths_device on torch.cuda.current_stream())."""
-        flags = A.RT_RENDER_COUNTERS if counters else 0
-        cam = camera.to_abi()
-        frame = (2 * maxWidthCoord + 1) * (2 * maxHeightCoord + 1)
         if not isinstance(n_samples, int) or not isinstance(sample_first, int) or not isinstance(max_vertices, int):
             raise TypeError("sample_first, n_samples and max_vertices must be ints")
-        if pixels is not None and n is not None:
-            raise ValueError("n applies to pixels=None")
-        per, k = max(n_samples, 0), max(max_vertices, 0)
-        if _is_torch(pixels) or (pixels is None and tensors):
-            torch = _torch()
-            if pixels is None:
-                tdev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-                dev, count, ptr = tdev.index, frame if n is None else int(n), None
-            else:
-                px = _list_tensor(pixels)
-                tdev, dev, count, ptr = px.device, _tensor_device(px, device), px.shape[0], px.data_ptr()
-            kinds = {"i32": torch.int32, "u8": torch.uint8, "f64": torch.float64}
-            bufs = Scene._path_buffers((count, per), k, records, lambda shape, kind: torch.empty(shape, dtype=kinds[kind], device=tdev), first_ray,
-                                       count if summary else None)
-            out = A.rt_path_outputs(max_vertices=max_vertices, **{f: (b.data_ptr() if b is not None else None) for f, b in bufs.items()})
-            st = A.rt_stats() if stats else None
-            check(lib.rt_camera_paths_device(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, dev, count, ptr, sample_first, n_samples, flags,
-                                             C.byref(out), torch.cuda.current_stream(tdev).cuda_stream, _ref(options), _ref(st)))
-            self.last_stats = st.as_dict() if st is not None else None
-            return CameraPaths(stats=self.last_stats, **bufs)
-        _no_options(options, "set_launch_config")
-        if pixels is None:
-            px, count = None, frame if n is None else int(n)
-        else:
-            px = _list_array(pixels)
-            count = px.shape[0]
-        if count < 0:
-            raise ValueError("n must be >= 0")
-        big = count * per * max(k, 1) > 2**31 - 1  # (refused by the library: no buffers are made for it)
-        kinds = {"i32": np.int32, "u8": np.uint8, "f64": np.float64}
-        bufs = Scene._path_buffers((0, 0) if big else (count, per), k, records, lambda shape, kind: np.zeros(shape, kinds[kind]), first_ray,
-                                   (0 if big else count) if summary else None)
-        out = A.rt_path_outputs(max_vertices=max_vertices, **{f: (b.ctypes.data if b is not None else None) for f, b in bufs.items()})
-        st = A.rt_stats()
-        check(lib.rt_camera_paths(self._h, C.byref(cam), maxWidthCoord, maxHeightCoord, seed, 0 if device is None else device, count,
-                                  _i32(px) if px is not None else None, sample_first, n_samples, flags, C.byref(out), C.byref(st)))
-        self.last_stats = st.as_dict()
-        return CameraPaths(stats=self.last_stats, **bufs)
+        route, px, count = _pixel_list(pixels, n, tensors, maxWidthCoord, maxHeightCoord, device, options)
+        per = max(n_samples, 0)
+        lead = _lead(route, (count, per), count * per * max(max_vertices, 1))
+        bufs, out = Scene._path_buffers(route, lead, max_vertices, records, first_ray, lead[0] if summary else None)
+        st = self._launch(route, "rt_camera_paths", C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, route.device, count, route.ptr(px),
+                          sample_first, n_samples, _flags(counters), C.byref(out), stats=stats, options=options)
+        return CameraPaths(stats=st, **bufs)
 
     def tracePaths(self, rays, bounceDepth: int, *, rng=None, seed: int = 0, stream_base: int = 0, sample: int = 0, max_vertices: int = 8,
                    records: bool = True, device: Optional[int] = None, counters: bool = False, stats: bool = True,
                    options: Optional[A.rt_render_options] = None) -> TracePaths:
         """traceRays with the path written down: rays, rng, seed, stream_base, sample and bounceDepth are traceRays' (colour and the
         advanced states equal its) -> TracePaths.  numpy arrays / torch tensors as for traceRays."""
-        flags = A.RT_RENDER_COUNTERS if counters else 0
         if not isinstance(max_vertices, int):
             raise TypeError("max_vertices must be an int")
-        k = max(max_vertices, 0)
-        if _is_torch(rays):
-            torch = _torch()
-            r = _tensor_arg(rays, "rays", (torch.float64,), 6)
-            dev = _tensor_device(r, device)
-            n = r.shape[0]
-            g = None
-            if rng is not None:
-                if not _is_torch(rng):
-                    raise TypeError("rng must be a torch tensor when rays is one")
-                g = _tensor_arg(rng, "rng", (torch.uint32, torch.int32), 4).clone()
-                if g.shape[0] != n or g.device != r.device:
-                    raise ValueError("rng must be [n, 4] on the rays' device")
-            kinds = {"i32": torch.int32, "u8": torch.uint8, "f64": torch.float64}
-            bufs = Scene._path_buffers((n,), k, records, lambda shape, kind: torch.empty(shape, dtype=kinds[kind], device=r.device))
-            out = A.rt_path_outputs(max_vertices=max_vertices, **{f: (b.data_ptr() if b is not None else None) for f, b in bufs.items()})
-            st = A.rt_stats() if stats else None
-            check(lib.rt_trace_paths_device(self._h, dev, n, r.data_ptr(), g.data_ptr() if g is not None else None, seed, stream_base, sample,
-                                            bounceDepth, flags, C.byref(out), torch.cuda.current_stream(r.device).cuda_stream, _ref(options), _ref(st)))
-            self.last_stats = st.as_dict() if st is not None else None
-        else:
-            _no_options(options)
-            r = _array_arg(rays, "rays", np.float64, 6)
-            n = r.shape[0]
-            g = None
-            if rng is not None:
-                g = _array_arg(rng, "rng", np.uint32, 4).copy()
-                if g.shape[0] != n:
-                    raise ValueError("rng must be [n, 4] for n rays")
-            big = n * max(k, 1) > 2**31 - 1
-            kinds = {"i32": np.int32, "u8": np.uint8, "f64": np.float64}
-            bufs = Scene._path_buffers((0,) if big else (n,), k, records, lambda shape, kind: np.zeros(shape, kinds[kind]))
-            out = A.rt_path_outputs(max_vertices=max_vertices, **{f: (b.ctypes.data if b is not None else None) for f, b in bufs.items()})
-            st = A.rt_stats()
-            check(lib.rt_trace_paths(self._h, 0 if device is None else device, n, _f64(r), _u32(g) if g is not None else None, seed, stream_base,
-                                     sample, bounceDepth, flags, C.byref(out), C.byref(st)))
-            self.last_stats = st.as_dict()
-        return TracePaths(bufs["n_vertices"], bufs["end"], bufs["colour"], g, bufs["hit_index"], bufs["strike"], bufs["colour_after"], bufs["ray_after"],
-                          self.last_stats)
+        route, r = _route(rays, "rays", "f64", 6, device, options)
+        n = r.shape[0]
+        g = _rng(route, rng, n)
+        bufs, out = Scene._path_buffers(route, _lead(route, (n,), n * max(max_vertices, 1)), max_vertices, records)
+        st = self._launch(route, "rt_trace_paths", route.device, n, route.ptr(r), route.ptr(g), seed, stream_base, sample, bounceDepth, _flags(counters),
+                          C.byref(out), stats=stats, options=options)
+        return TracePaths(bufs["n_vertices"], bufs["end"], bufs["colour"], g, bufs["hit_index"], bufs["strike"], bufs["colour_after"], bufs["ray_after"], st)
 
     @staticmethod
     def render(progressIncrement: Callable[[float], None], log: Callable[[str], None], maxWidthCoord: int, maxHeightCoord: int,
@@ -1086,30 +813,13 @@ class ImageOutput:
         if _is_torch(pixels):
             text, length = ImageOutput.formatPpmDevice(gammaCorrect, pixels)
             return text[: int(length)].cpu().numpy().tobytes()
-        px = np.ascontiguousarray(pixels, dtype=np.uint8)
-        rows, cols = px.shape[0], px.shape[1]
-        n = lib.rt_format_ppm(_u8(px), rows, cols, int(bool(gammaCorrect)), None, 0)
-        if n < 0:
-            check(int(-n))
-        buf = C.create_string_buffer(int(n) + 1)
-        lib.rt_format_ppm(_u8(px), rows, cols, int(bool(gammaCorrect)), buf, int(n) + 1)
-        return buf.raw[: int(n)]
+        return _format_host(lib.rt_format_ppm, pixels, int(bool(gammaCorrect)), spare=1)
 
     @staticmethod
     def formatPpmDevice(gammaCorrect: bool, pixels):
         """rt_format_ppm_device on torch.cuda.current_stream(), without waiting for the device: (text, length) -- a uint8 tensor of
         rt_ppm_max_bytes(rows, cols) bytes whose first `length` (an int64 tensor) are ImageOutput.writePpm's; the rest is not written."""
-        t = _image_tensor(pixels)
-        torch = _torch()
-        rows, cols = int(t.shape[0]), int(t.shape[1])
-        cap = lib.rt_ppm_max_bytes(rows, cols)
-        if cap < 0:
-            check(int(-cap))
-        text = torch.empty(int(cap), dtype=torch.uint8, device=t.device)
-        length = torch.empty((), dtype=torch.int64, device=t.device)
-        check(lib.rt_format_ppm_device(t.device.index, t.data_ptr(), rows, cols, int(bool(gammaCorrect)), text.data_ptr(), int(cap), length.data_ptr(),
-                                       torch.cuda.current_stream(t.device).cuda_stream, None))
-        return text, length
+        return _format_device(lib.rt_ppm_max_bytes, lib.rt_format_ppm_device, gammaCorrect, pixels)
 
     @staticmethod
     def formatPixelMap(pixels) -> bytes:
@@ -1119,33 +829,20 @@ class ImageOutput:
             t = _image_tensor(pixels)
             torch = _torch()
             rows, cols = int(t.shape[0]), int(t.shape[1])
-            cap = lib.rt_pixel_map_bytes(rows, cols)
-            if cap < 0:
-                check(int(-cap))
-            out = torch.empty(int(cap), dtype=torch.uint8, device=t.device)
+            cap = _size(lib.rt_pixel_map_bytes(rows, cols))
+            out = torch.empty(cap, dtype=torch.uint8, device=t.device)
             n = C.c_int64(0)
-            check(lib.rt_format_pixel_map_device(t.device.index, t.data_ptr(), rows, cols, out.data_ptr(), int(cap), None,
+            check(lib.rt_format_pixel_map_device(t.device.index, t.data_ptr(), rows, cols, out.data_ptr(), cap, None,
                                                  torch.cuda.current_stream(t.device).cuda_stream, C.byref(n)))
             return out[: n.value].cpu().numpy().tobytes()
-        px = np.ascontiguousarray(pixels, dtype=np.uint8)
-        n = lib.rt_format_pixel_map(_u8(px), px.shape[0], px.shape[1], None, 0)
-        if n < 0:
-            check(int(-n))
-        buf = C.create_string_buffer(int(n))
-        lib.rt_format_pixel_map(_u8(px), px.shape[0], px.shape[1], buf, int(n))
-        return buf.raw[: int(n)]
+        return _format_host(lib.rt_format_pixel_map, pixels)
 
     @staticmethod
     def toPpm(progressIncrement: Callable[[float], None], image: "Image", path: str) -> str:
         """ImageOutput.toPpm = resume (ImageOutput.fs:131-161, 205): force the image and spill it as `<row>,<col>\\nRGB` records."""
-        px = np.ascontiguousarray(Image.render(image), dtype=np.uint8)
-        n = lib.rt_format_pixel_map(_u8(px), px.shape[0], px.shape[1], None, 0)
-        if n < 0:
-            check(int(-n))
-        buf = C.create_string_buffer(int(n))
-        lib.rt_format_pixel_map(_u8(px), px.shape[0], px.shape[1], buf, int(n))
+        px = Image.render(image)
         with open(path, "wb") as f:
-            f.write(buf.raw[: int(n)])
+            f.write(_format_host(lib.rt_format_pixel_map, px))
         for _ in range(px.shape[0]):
             progressIncrement(1.0)
         return path
@@ -1156,9 +853,7 @@ class ImageOutput:
         data = open(path, "rb").read()
         rgb = np.zeros((numRows, numCols, 3), np.uint8)
         present = np.zeros((numRows, numCols), np.uint8)
-        n = lib.rt_parse_pixel_map(data, len(data), numRows, numCols, _u8(rgb), _u8(present))
-        if n < 0:
-            check(int(-n))
+        _size(lib.rt_parse_pixel_map(data, len(data), numRows, numCols, _u8(rgb), _u8(present)))
         return rgb, present.astype(bool)
 
     @staticmethod
@@ -1204,16 +899,7 @@ class ImageOutput:
     def writePpm(gammaCorrect: bool, incrementProgress: Callable[[float], None], pixels, output: str) -> None:
         """ImageOutput.writePpm (ImageOutput.fs:163-197).  A torch tensor on a GPU is formatted there (rt_write_ppm_device, on
         torch.cuda.current_stream()); a numpy array takes rt_write_ppm."""
-        if _is_torch(pixels):
-            t = _image_tensor(pixels)
-            check(lib.rt_write_ppm_device(str(output).encode(), t.device.index, t.data_ptr(), int(t.shape[0]), int(t.shape[1]), int(bool(gammaCorrect)),
-                                          _torch().cuda.current_stream(t.device).cuda_stream))
-            for _ in range(int(t.shape[0]) * int(t.shape[1])):
-                incrementProgress(1.0)
-            return
-        px = np.ascontiguousarray(pixels, dtype=np.uint8)
-        check(lib.rt_write_ppm(str(output).encode(), _u8(px), px.shape[0], px.shape[1], int(bool(gammaCorrect))))
-        for _ in range(px.shape[0] * px.shape[1]):
+        for _ in range(_write_image("ppm", gammaCorrect, pixels, output)):
             incrementProgress(1.0)
 
 
@@ -1231,47 +917,70 @@ class Png:
             return data[: int(length)].cpu().numpy().tobytes()
         px = np.ascontiguousarray(pixels, dtype=np.uint8)
         rows, cols = px.shape[0], px.shape[1]
-        cap = lib.rt_png_max_bytes(rows, cols)
-        if cap < 0:
-            check(int(-cap))
-        buf = np.empty(int(cap), np.uint8)
-        n = lib.rt_format_png(_u8(px), rows, cols, int(bool(gammaCorrect)), buf.ctypes.data, int(cap))
-        if n < 0:
-            check(int(-n))
-        return buf[: int(n)].tobytes()
+        cap = _size(lib.rt_png_max_bytes(rows, cols))
+        buf = np.empty(cap, np.uint8)
+        n = _size(lib.rt_format_png(_u8(px), rows, cols, int(bool(gammaCorrect)), buf.ctypes.data, cap))
+        return buf[:n].tobytes()
 
     @staticmethod
     def formatDevice(gammaCorrect: bool, pixels):
         """rt_format_png_device on torch.cuda.current_stream(), without waiting for the device: (data, length) -- a uint8 tensor of
         rt_png_max_bytes(rows, cols) bytes whose first `length` (an int64 tensor) are the file; the rest is not written."""
-        t = _image_tensor(pixels)
-        torch = _torch()
-        rows, cols = int(t.shape[0]), int(t.shape[1])
-        cap = lib.rt_png_max_bytes(rows, cols)
-        if cap < 0:
-            check(int(-cap))
-        data = torch.empty(int(cap), dtype=torch.uint8, device=t.device)
-        length = torch.empty((), dtype=torch.int64, device=t.device)
-        check(lib.rt_format_png_device(t.device.index, t.data_ptr(), rows, cols, int(bool(gammaCorrect)), data.data_ptr(), int(cap), length.data_ptr(),
-                                       torch.cuda.current_stream(t.device).cuda_stream, None))
-        return data, length
+        return _format_device(lib.rt_png_max_bytes, lib.rt_format_png_device, gammaCorrect, pixels)
 
     @staticmethod
     def write(gammaCorrect: bool, incrementProgress: Callable[[float], None], pixels, output: str) -> None:
         """Png.write (ImageOutput.fs:216-251).  A torch tensor on a GPU is encoded there (rt_write_png_device, on
         torch.cuda.current_stream()); a numpy array takes rt_write_png.  Progress as the reference counts it: once per pixel but a row's
         last (ImageOutput.fs:230-233), once per row but the last (:239-241) -- rows * cols - 1 in all."""
-        if _is_torch(pixels):
-            t = _image_tensor(pixels)
-            rows, cols = int(t.shape[0]), int(t.shape[1])
-            check(lib.rt_write_png_device(str(output).encode(), t.device.index, t.data_ptr(), rows, cols, int(bool(gammaCorrect)),
-                                          _torch().cuda.current_stream(t.device).cuda_stream))
-        else:
-            px = np.ascontiguousarray(pixels, dtype=np.uint8)
-            rows, cols = px.shape[0], px.shape[1]
-            check(lib.rt_write_png(str(output).encode(), _u8(px), rows, cols, int(bool(gammaCorrect))))
-        for _ in range(rows * cols - 1):
+        for _ in range(_write_image("png", gammaCorrect, pixels, output) - 1):
             incrementProgress(1.0)
+
+
+# ---- the output classes' shared pieces ----------------------------------------------------------------------------------
+def _size(n: int) -> int:
+    """A byte count of the library's, which is minus the error code where it refuses."""
+    if n < 0:
+        check(int(-n))
+    return int(n)
+
+
+def _format_host(fn, pixels, *args, spare: int = 0) -> bytes:
+    """A host formatter's two calls: ask for the size, make a buffer of it (and `spare` bytes for a terminator), call again."""
+    px = np.ascontiguousarray(pixels, dtype=np.uint8)
+    head = (_u8(px), px.shape[0], px.shape[1]) + args
+    n = _size(fn(*head, None, 0))
+    buf = C.create_string_buffer(n + spare)
+    fn(*head, buf, n + spare)
+    return buf.raw[:n]
+
+
+def _format_device(size_fn, format_fn, gammaCorrect: bool, pixels):
+    """An image on a GPU to (bytes, length): a uint8 tensor of size_fn(rows, cols) bytes and an int64 tensor, both filled by format_fn on
+    torch.cuda.current_stream() without waiting for the device."""
+    t = _image_tensor(pixels)
+    torch = _torch()
+    rows, cols = int(t.shape[0]), int(t.shape[1])
+    cap = _size(size_fn(rows, cols))
+    data = torch.empty(cap, dtype=torch.uint8, device=t.device)
+    length = torch.empty((), dtype=torch.int64, device=t.device)
+    check(format_fn(t.device.index, t.data_ptr(), rows, cols, int(bool(gammaCorrect)), data.data_ptr(), cap, length.data_ptr(),
+                    torch.cuda.current_stream(t.device).cuda_stream, None))
+    return data, length
+
+
+def _write_image(kind: str, gammaCorrect: bool, pixels, output: str) -> int:
+    """rt_write_<kind> of a numpy array, rt_write_<kind>_device of a torch tensor on a GPU (on torch.cuda.current_stream()) -> rows * cols."""
+    if _is_torch(pixels):
+        t = _image_tensor(pixels)
+        rows, cols = int(t.shape[0]), int(t.shape[1])
+        check(getattr(lib, f"rt_write_{kind}_device")(str(output).encode(), t.device.index, t.data_ptr(), rows, cols, int(bool(gammaCorrect)),
+                                                      _torch().cuda.current_stream(t.device).cuda_stream))
+    else:
+        px = np.ascontiguousarray(pixels, dtype=np.uint8)
+        rows, cols = px.shape[0], px.shape[1]
+        check(getattr(lib, f"rt_write_{kind}")(str(output).encode(), _u8(px), rows, cols, int(bool(gammaCorrect))))
+    return rows * cols
 
 
 def _f64(a: np.ndarray):
@@ -1294,7 +1003,53 @@ def _u64(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
 
 
-# ---- argument checks of the ray-list calls (Scene.hitObject / Scene.traceRays) ----------------------------------------
+# ---- the two routes of a launching Scene call -------------------------------------------------------------------------
+# Every entry point Scene._launch serves: NAME takes numpy arrays, NAME_device tensors on a GPU, and NAME_device's arguments are NAME's
+# with `stream, options` in front of the trailing `stats` (tests/test_abi.py holds _lib.SIGNATURES to that).
+_ROUTED = ("rt_hit_objects", "rt_trace_rays", "rt_render_footprints", "rt_render_footprints_extend", "rt_render_footprints_extend_map",
+           "rt_render_pixels", "rt_render_pixels_extend", "rt_camera_hits", "rt_camera_paths", "rt_trace_paths", "rt_render_extend",
+           "rt_render_extend_map")
+# a buffer's kind -> its dtype's name (numpy's and torch's) and how an array of it is handed to the library
+_KINDS = {"i32": ("int32", _i32), "u8": ("uint8", _u8), "f64": ("float64", _f64), "u32": ("uint32", _u32)}
+_TYPED = {name: typed for name, typed in _KINDS.values()}
+
+
+class _Arrays:
+    """The array route: numpy buffers through the host entry point, on device 0 unless told otherwise; statistics always."""
+    suffix = ""
+
+    def __init__(self, device: Optional[int]):
+        self.device = 0 if device is None else device
+
+    def make(self, shape, kind: str) -> np.ndarray:
+        return np.zeros(shape, _KINDS[kind][0])
+
+    def ptr(self, a: Optional[np.ndarray]):
+        return None if a is None else _TYPED[a.dtype.name](a)
+
+    def tail(self, options) -> tuple:
+        return ()
+
+
+class _Tensors:
+    """The tensor route: torch buffers on the GPU `where` through the _device entry point, on torch's current stream there."""
+    suffix = "_device"
+
+    def __init__(self, where, device: Optional[int] = None):
+        _tensor_device(where, device)
+        self.where, self.device = where, where.index
+
+    def make(self, shape, kind: str):
+        torch = _torch()
+        return torch.empty(shape, dtype=getattr(torch, _KINDS[kind][0]), device=self.where)
+
+    def ptr(self, t):
+        return None if t is None else t.data_ptr()
+
+    def tail(self, options) -> tuple:
+        return _torch().cuda.current_stream(self.where).cuda_stream, _ref(options)
+
+
 def _is_torch(x) -> bool:
     return type(x).__module__.split(".")[0] == "torch"
 
@@ -1304,24 +1059,161 @@ def _torch():
     return torch
 
 
-def _array_arg(a, name: str, dtype, width: int) -> np.ndarray:
+def _ref(x):
+    return C.byref(x) if x is not None else None
+
+
+def _tensor_device(where, device: Optional[int]) -> None:
+    if device is not None and device != where.index:
+        raise ValueError(f"device={device} but the tensors are on {where}")
+
+
+def _flags(counters: bool) -> int:
+    return A.RT_RENDER_COUNTERS if counters else 0
+
+
+def _no_options(options, instead: str = "set_launch_config / set_park") -> None:
+    if options is not None:
+        raise ValueError(f"options apply to the device entry point (torch tensors); use {instead} for arrays")
+
+
+def _shape_text(width: Optional[int]) -> str:
+    return "[n]" if width is None else f"[n, {width}]"
+
+
+def _is_list_shape(shape, width: Optional[int]) -> bool:
+    return len(shape) == 1 if width is None else len(shape) == 2 and shape[1] == width
+
+
+def _array_arg(a, name: str, kind: str, width: Optional[int]) -> np.ndarray:
+    """A list argument of the array route, [n, width] or (width None) [n], made contiguous."""
+    dtype = np.dtype(_KINDS[kind][0])
     if not isinstance(a, np.ndarray):
         raise TypeError(f"{name} must be a numpy array or a torch tensor on a GPU, not {type(a).__name__}")
     if a.dtype != dtype:
-        raise TypeError(f"{name} must have dtype {np.dtype(dtype).name}, not {a.dtype}")
-    if a.ndim != 2 or a.shape[1] != width:
-        raise ValueError(f"{name} must have shape [n, {width}], not {list(a.shape)}")
+        raise TypeError(f"{name} must have dtype {dtype.name}, not {a.dtype}")
+    if not _is_list_shape(a.shape, width):
+        raise ValueError(f"{name} must have shape {_shape_text(width)}, not {list(a.shape)}")
     return np.ascontiguousarray(a)
 
 
-def _tensor_arg(t, name: str, dtypes, width: int):
+def _tensor_arg(t, name: str, kinds: Sequence[str], width: Optional[int]):
+    """A list argument of the tensor route (of one of `kinds`), made contiguous."""
+    dtypes = [getattr(_torch(), _KINDS[k][0]) for k in kinds]
     if t.dtype not in dtypes:
         raise TypeError(f"{name} must have dtype {' or '.join(str(d) for d in dtypes)}, not {t.dtype}")
-    if t.dim() != 2 or t.shape[1] != width:
-        raise ValueError(f"{name} must have shape [n, {width}], not {list(t.shape)}")
+    if not _is_list_shape(t.shape, width):
+        raise ValueError(f"{name} must have shape {_shape_text(width)}, not {list(t.shape)}")
     if not t.is_cuda:
         raise ValueError(f"{name} must be on a GPU (a numpy array takes the host entry point)")
     return t.contiguous()
+
+
+def _route(x, name: str, kind: str, width: Optional[int], device: Optional[int], options, instead: str = "set_launch_config / set_park"):
+    """The route of a call, chosen from its leading argument x, and x checked: (route, x made contiguous).  Arrays refuse options
+    (`instead` names what to use), tensors a device= that is not theirs."""
+    if _is_torch(x):
+        t = _tensor_arg(x, name, (kind,), width)
+        return _Tensors(t.device, device), t
+    _no_options(options, instead)
+    return _Arrays(device), _array_arg(x, name, kind, width)
+
+
+def _pixel_list(pixels, n: Optional[int], tensors: bool, maxWidthCoord: int, maxHeightCoord: int, device: Optional[int], options):
+    """The pixel list of cameraHits / cameraPaths: (route, the list or None, its count).  pixels=None stands for the frame's first n
+    pixels (all of them by default), on the tensor route if `tensors`, there on `device` or torch's current one."""
+    if pixels is not None and n is not None:
+        raise ValueError("n applies to pixels=None")
+    if pixels is not None:
+        route, px = _route(pixels, "pixels", "i32", None, device, options, "set_launch_config")
+        return route, px, px.shape[0]
+    count = (2 * maxWidthCoord + 1) * (2 * maxHeightCoord + 1) if n is None else int(n)
+    if tensors:
+        torch = _torch()
+        return _Tensors(torch.device("cuda", torch.cuda.current_device() if device is None else device)), None, count
+    _no_options(options, "set_launch_config")
+    if count < 0:
+        raise ValueError("n must be >= 0")
+    return _Arrays(device), None, count
+
+
+def _lead(route, shape: tuple, slots: int) -> tuple:
+    """The leading shape of a call's outputs.  More than INT32_MAX slots are refused by the library, so the array route, which would
+    have to zero them first, makes empty buffers for that call."""
+    return (0,) * len(shape) if not route.suffix and slots > 2**31 - 1 else shape
+
+
+def _rng(route, rng, n: int):
+    """The caller's generator states [n, 4] for n rays, copied for the call to advance (None: none given).  A tensor's may be uint32 or int32."""
+    if rng is None:
+        return None
+    if route.suffix:
+        if not _is_torch(rng):
+            raise TypeError("rng must be a torch tensor when rays is one")
+        g = _tensor_arg(rng, "rng", ("u32", "i32"), 4).clone()
+        if g.shape[0] != n or g.device != route.where:
+            raise ValueError("rng must be [n, 4] on the rays' device")
+    else:
+        g = _array_arg(rng, "rng", "u32", 4).copy()
+        if g.shape[0] != n:
+            raise ValueError("rng must be [n, 4] for n rays")
+    return g
+
+
+def _targets(route, targets, shape: tuple, text: str, owner: str, prefix: str = ""):
+    """The int32 targets of a map extension, `text` their shape in words; a tensor must be contiguous and on the device of `owner`."""
+    if route.suffix:
+        if (not _is_torch(targets) or targets.dtype != _torch().int32 or tuple(targets.shape) != shape or targets.device != route.where
+                or not targets.is_contiguous()):
+            raise ValueError(f"{prefix}targets must be a contiguous int32 tensor {text} on {owner}")
+        return targets
+    if not isinstance(targets, np.ndarray) or targets.dtype != np.int32 or targets.shape != shape:
+        raise ValueError(f"{prefix}targets must be an int32 array {text}")
+    return np.ascontiguousarray(targets)
+
+
+def _frame(accum, cols: int, device: Optional[int], options, mapped: bool = False, targets=None):
+    """The buffer a frame extension continues, [n_rows, cols, 4] int32, and (mapped) its targets [n_rows, cols]: (route, buffer, targets).
+    An array is copied and the copy extended; a tensor is extended in place, so it must be contiguous already."""
+    if _is_torch(accum):
+        if accum.dtype != _torch().int32 or accum.dim() != 3 or tuple(accum.shape[1:]) != (cols, 4) or not accum.is_cuda or not accum.is_contiguous():
+            raise ValueError(f"accum must be a contiguous int32 tensor [n_rows, {cols}, 4] on a GPU")
+        route, out = _Tensors(accum.device), accum
+    else:
+        _no_options(options)
+        if not isinstance(accum, np.ndarray) or accum.dtype != np.int32 or accum.ndim != 3 or accum.shape[1:] != (cols, 4):
+            raise ValueError(f"accum must be an int32 array [n_rows, {cols}, 4] or such a tensor on a GPU")
+        route, out = _Arrays(device), np.array(accum, dtype=np.int32, order="C")
+    tg = _targets(route, targets, (out.shape[0], cols), f"[n_rows, {cols}]", "accum's device") if mapped else None
+    if route.suffix:
+        _tensor_device(route.where, device)  # (after the targets, as it always was)
+    return route, out, tg
+
+
+def _list_accum(route, accum, n: int, what: str, entries: str, owner: str):
+    """The buffer an extension of n list entries continues, [n, 4] int32: an array is copied, a tensor extended in place.  `what` names
+    the argument, `entries` what the list holds, `owner` the device a tensor must be on."""
+    if route.suffix:
+        if not _is_torch(accum) or accum.dtype != _torch().int32 or tuple(accum.shape) != (n, 4) or accum.device != route.where or not accum.is_contiguous():
+            raise ValueError(f"{what}: accum must be a contiguous int32 tensor [n, 4] on {owner}")
+        return accum
+    out = np.array(_array_arg(accum, what.split("=")[0] + "'s accum", "i32", 4), order="C")
+    if out.shape[0] != n:
+        raise ValueError(f"{what}: accum must be [n, 4] for n {entries}")
+    return out
+
+
+def _list_extension(route, n: int, extend, extend_map, entries: str, owner: str):
+    """What extend= / extend_map= make of a list call: (the entry point's suffix, the arguments in front of accum, accum)."""
+    if extend is not None:
+        accum, done = extend
+        return "_extend", (done,), _list_accum(route, accum, n, "extend=(accum, samplesDone)", entries, owner)
+    if extend_map is not None:
+        accum, targets = extend_map
+        accum = _list_accum(route, accum, n, "extend_map=(accum, targets)", entries, owner)
+        targets = _targets(route, targets, (n,), "[n]", owner, "extend_map=(accum, targets): ")
+        return "_extend_map", (route.ptr(targets),), accum
+    return "", (), route.make((n, 4), "i32")
 
 
 def _bytes_tensor(t):
@@ -1338,46 +1230,3 @@ def _image_tensor(t):
     if t.dim() != 3 or t.shape[2] != 3:
         raise ValueError(f"pixels must have shape [rows, cols, 3], not {list(t.shape)}")
     return _bytes_tensor(t)
-
-
-def _list_array(a) -> np.ndarray:
-    """A pixel list [n] int32 for the host entry points."""
-    if not isinstance(a, np.ndarray):
-        raise TypeError(f"pixels must be a numpy array or a torch tensor on a GPU, not {type(a).__name__}")
-    if a.dtype != np.int32:
-        raise TypeError(f"pixels must have dtype int32, not {a.dtype}")
-    if a.ndim != 1:
-        raise ValueError(f"pixels must have shape [n], not {list(a.shape)}")
-    return np.ascontiguousarray(a)
-
-
-def _list_tensor(t):
-    """A pixel list [n] int32 for the device entry points."""
-    if t.dtype != _torch().int32:
-        raise TypeError(f"pixels must have dtype torch.int32, not {t.dtype}")
-    if t.dim() != 1:
-        raise ValueError(f"pixels must have shape [n], not {list(t.shape)}")
-    if not t.is_cuda:
-        raise ValueError("pixels must be on a GPU (a numpy array takes the host entry point)")
-    return t.contiguous()
-
-
-def _accum_tensor(accum, n: int, device, what: str, where: str) -> None:
-    """The buffer an extension of n list entries continues in place: `what` names the argument, `where` the device it must be on."""
-    if not _is_torch(accum) or accum.dtype != _torch().int32 or tuple(accum.shape) != (n, 4) or accum.device != device or not accum.is_contiguous():
-        raise ValueError(f"{what}: accum must be a contiguous int32 tensor [n, 4] on {where}")
-
-
-def _no_options(options, instead: str = "set_launch_config / set_park") -> None:
-    if options is not None:
-        raise ValueError(f"options apply to the device entry point (torch tensors); use {instead} for arrays")
-
-
-def _tensor_device(t, device: Optional[int]) -> int:
-    if device is not None and device != t.device.index:
-        raise ValueError(f"device={device} but the tensors are on {t.device}")
-    return t.device.index
-
-
-def _ref(x):
-    return C.byref(x) if x is not None else None

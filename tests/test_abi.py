@@ -27,6 +27,25 @@ def test_every_declared_symbol_is_exported_and_bound(rt):
     assert set(_lib.SIGNATURES) <= set(names)
 
 
+def test_a_device_entry_point_takes_its_host_twins_arguments_with_stream_and_options_before_stats(rt):
+    """What Scene._launch rests on, for exactly the pairs it serves: NAME_device's arguments are NAME's with `stream, options` put in
+    front of the trailing `stats`, and nothing else differs but the types of pointers."""
+    from ray_tracing_fsharp_amd import _lib, raytracing
+
+    A = rt._abi
+    assert len(set(raytracing._ROUTED)) == len(raytracing._ROUTED) == 12
+    for name in raytracing._ROUTED:
+        host, device = _lib.SIGNATURES[name][1], _lib.SIGNATURES[name + "_device"][1]
+        assert len(device) == len(host) + 2, name
+        assert host[-1] is device[-1] is C.POINTER(A.rt_stats), name
+        assert device[-2] is C.POINTER(A.rt_render_options) and device[-3] is C.c_void_p, name
+        for h, d in zip(host[:-1], device[:-3]):  # the same scalars at the same places; a host pointer is a device address there
+            assert h is d or (d is C.c_void_p and issubclass(h, C._Pointer)), (name, h, d)
+    # and no other pair follows the scheme unserved (the oldest, rt_render / rt_render_device, does not follow it)
+    paired = {n for n in _lib.SIGNATURES if n + "_device" in _lib.SIGNATURES and _lib.SIGNATURES[n][1][-1:] == [C.POINTER(A.rt_stats)]}
+    assert paired - set(raytracing._ROUTED) == {"rt_render"}
+
+
 def test_the_library_is_the_in_tree_hip_build(rt):
     assert os.path.samefile(os.path.dirname(rt.LIB_PATH), os.path.join(ROOT, "ray-tracing-fsharp_amd"))
     blob = open(rt.LIB_PATH, "rb").read()
