@@ -935,6 +935,48 @@ int rt_dev_texture_colour_at(int32_t device, const rt_scene *scene, int32_t text
  * a,b: n doubles (b may be NULL for unary ops). */
 int rt_dev_arith(int32_t device, int32_t op, int32_t n, const double *a, const double *b, double *out);
 
+/* ---- BoundingBoxTree.make's tree on the device (BoundingBoxTree.fs:9-43; csrc/rt_tree_plan.h, csrc/rt_tree_kernels.h; DESIGN.md "The
+ * reference tree on the device").  Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7.
+ *
+ * The tree's shape is a function of the number of boxes alone: a node over c boxes has children over c/2 + 1 and c - c/2 - 1 boxes
+ * (BoundingBoxTree.fs:28-29), two boxes make two Leaves without sorting, so the tree has 2n - 1 nodes, and in pre-order skip[me] =
+ * me + 2c - 1.  rt_tree_nodes: 2n - 1, 0 for n == 0.  rt_tree_depth: the nodes on the longest path from the root (BoundingBoxTree.fs:9-43).
+ * rt_tree_lds_boxes: the largest segment the device build finishes in one workgroup's LDS (a whole build of at most that many boxes
+ * is one launch behind the NaN check). */
+int64_t rt_tree_nodes(size_t n);
+int32_t rt_tree_depth(size_t n);
+int32_t rt_tree_lds_boxes(void);
+/* BoundingBoxTree.make (BoundingBoxTree.fs:9-43) over the caller's boxes, Array.sortBy defined stable (DESIGN.md "Tree shape").
+ * boxes: n*6 doubles (minx,maxx,miny,maxy,minz,maxz), the form of rt_scene_get_tree.  Outputs, any may be NULL:
+ * skip, prim (input index of a Leaf's box, -1 for a Branch): rt_tree_nodes(n) int32 each; node_boxes: rt_tree_nodes(n)*6 doubles;
+ * order: n int32, the depth-first leaf order (the rank table of rt_scene_create).
+ *
+ * rt_tree_make_host is the host builder of rt_scene_create on these boxes and touches no device: the yardstick for inputs a sphere
+ * cannot express (signed zeros, infinities, arbitrary inverted boxes).  rt_tree_make stages the boxes, runs rt_tree_make_device on the
+ * null stream and copies back.  rt_tree_make_device builds on `stream` (NULL = the null stream) from and into device memory, with
+ * stream-ordered scratch (any number of builds may be in flight), and returns after the stream has finished the build.  All three give
+ * the same four arrays, the boxes bit for bit (the sign of a zero in a Branch box included: BoundingBox.mergeTwo keeps the later
+ * operand of a tied minimum and the earlier one of a tied maximum, BoundingBox.fs:96-108).
+ *
+ * Argument checks come before any device call, nothing is written when one fails: RT_ERR_INVALID_ARGUMENT for NULL boxes with n > 0,
+ * a device pointer that is not 8-byte (boxes, node_boxes) or 4-byte (skip, prim, order) aligned; then RT_ERR_UNSUPPORTED for
+ * n > 4,500,000 (the scene's own limit).  n == 0 is a no-op RT_OK.  A NaN coordinate has no order: RT_ERR_INVALID_ARGUMENT, found on
+ * the host by rt_tree_make_host and on the device by the other two -- in front of the build, on the same stream, with no output written.
+ * RT_ERR_NO_DEVICE without a GPU (not rt_tree_make_host).  The caller's current device is left as it was. */
+int rt_tree_make_host(size_t n, const double *boxes, int32_t *skip, int32_t *prim, double *node_boxes, int32_t *order);
+int rt_tree_make(int32_t device, size_t n, const double *boxes, int32_t *skip, int32_t *prim, double *node_boxes, int32_t *order);
+int rt_tree_make_device(int32_t device, size_t n, const void *d_boxes, void *d_skip, void *d_prim, void *d_node_boxes,
+                        void *d_order, void *stream);
+/* rt_scene_create_ex with BoundingBoxTree.make's tree (BoundingBoxTree.fs:9-43), and with it the ranks, taken from the device build on
+ * `device`; everything after the tree -- object table, walk tree, device image -- is the same host code, and the scene is the same scene:
+ * rt_scene_get_info, _get_tree, _get_walk_tree, _get_filter_tree and every render are identical.  With fewer than 3 bounded spheres, or a
+ * NaN box coordinate, the host builder is used (the device is still entered: RT_ERR_NO_DEVICE without a GPU, before anything else).
+ * Measured on one MI355X against the host builder on 16 CPUs (same section): the crossover is at about 1e4 spheres -- the tree
+ * takes 1.2 ms instead of 0.25 ms at 485 spheres, 4.5 ms on both routes at 1e4, 7 instead of 43 ms at 1e5 and 25 ms instead of 1.1-1.3 s at
+ * 1e6, where creating the scene goes from 2.96 s to 1.98 s (the surface-area build, still on the host, is 1.56 s of that). */
+int rt_scene_create_gpu_tree(const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                             const rt_scene_options *options, int32_t device, rt_scene **out);
+
 #ifdef __cplusplus
 }
 #endif

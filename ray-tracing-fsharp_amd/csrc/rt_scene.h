@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <future>
 #include <string>
 #include <system_error>
@@ -420,8 +421,13 @@ static inline uint32_t pack_rgb(const uint8_t rgb[3]) { return (uint32_t) rgb[0]
 static inline size_t align16(size_t v) { return (v + 15u) & ~(size_t) 15u; }
 
 static void encode_image(HostScene &s);
-// Returns an empty string on success, otherwise the message for rt_last_error().
-static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture *tex, size_t ntex, int walk_kind, HostScene &s, int &status) {
+// BoundingBoxTree.make's tree from somewhere else than TreeBuilder (rt_scene_create_gpu_tree: the device build of rt_tree_kernels.h): fills
+// skip, prim (position of the Leaf's box in `boxes`), box and depth as TreeBuilder would, or returns an error code and sets `msg`.
+typedef std::function<int(const std::vector<Box> &boxes, FlatTree &tree, std::string &msg)> TreeMaker;
+// Returns an empty string on success, otherwise the message for rt_last_error().  `maker` (may be null: TreeBuilder) is asked for the tree of
+// a scene with at least 3 bounded spheres and no NaN box coordinate; everything after the tree is the same code for both.
+static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture *tex, size_t ntex, int walk_kind, HostScene &s, int &status,
+                               const TreeMaker *maker = nullptr) {
     status = RT_ERR_INVALID_ARGUMENT;
     if (n > 0 && !h) return "hittables is NULL";
     if (ntex > 0 && !tex) return "textures is NULL";
@@ -486,17 +492,22 @@ static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture 
     if (nb > 4500000u || nobj > 16000000u) { status = RT_ERR_UNSUPPORTED; return "scene too large for 32-bit walk offsets (4,500,000 bounded spheres)"; } // (2n-1) * 112 B < 2^30 (bit 30 = RTD_LEAF)
     // ---- Sphere.make's box (Sphere.fs:333-336): centre + (-r,-r,-r) .. centre + (r,r,r); inverted when r < 0 ----
     std::vector<Box> boxes(nb); // by position in `bounded` (input order), which is what BoundingBoxTree.make receives
-    bool finite = true;
+    bool finite = true, ordered = true; // ordered: no NaN coordinate
     for (size_t j = 0; j < nb; ++j) {
         const rt_hittable &o = h[(size_t) bounded[j]];
         for (int a = 0; a < 3; ++a) {
             boxes[j].mn[a] = o.point[a] + (-o.radius);
             boxes[j].mx[a] = o.point[a] + o.radius;
             finite = finite && std::isfinite(boxes[j].mn[a]) && std::isfinite(boxes[j].mx[a]);
+            ordered = ordered && !std::isnan(boxes[j].mn[a]) && !std::isnan(boxes[j].mx[a]);
         }
     }
     s.tree = FlatTree{};
-    if (nb > 0) {
+    if (maker && nb >= 3 && ordered) {
+        std::string msg;
+        const int rc = (*maker)(boxes, s.tree, msg);
+        if (rc != RT_OK) { status = rc; return msg; }
+    } else if (nb > 0) {
         std::vector<int32_t> ids(nb);
         for (size_t j = 0; j < nb; ++j) ids[j] = (int32_t) j;
         TreeBuilder(boxes, s.tree).go(ids, 1);

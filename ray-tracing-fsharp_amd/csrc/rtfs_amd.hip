@@ -11,11 +11,14 @@
 #include "rt_png_kernels.h"
 #include "rt_render_kernel.h"
 #include "rt_scene.h"
+#include "rt_tree_kernels.h"
+#include "rt_tree_plan.h"
 
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstddef>
@@ -3181,6 +3184,195 @@ int rt_dev_texture_colour_at(int32_t device, const rt_scene *scene, int32_t text
         auto duv = dev_out(uv_out, uv_out ? (size_t) n * 2 : 0);
         auto dc = dev_out(colour_out, (size_t) n * 3);
         return hook_run([&] { launch_n(k_texture, n, p, texture, n, dp.p, duv.p, dc.p); }, dp, duv, dc);
+    });
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// BoundingBoxTree.make's tree on the device (rt_tree_plan.h, rt_tree_kernels.h; DESIGN.md "The reference tree on the device")
+// ------------------------------------------------------------------------------------------------------------
+static const char *const kNanBox = "a box coordinate is NaN: it has no order; nothing was written";
+
+static int check_tree_host(size_t n, const double *boxes) {
+    if (n > 0 && !boxes) return fail(RT_ERR_INVALID_ARGUMENT, "boxes is NULL");
+    if (n > (size_t) RTT_MAX_BOXES) return fail(RT_ERR_UNSUPPORTED, "more than 4,500,000 boxes (the scene's own limit)");
+    return RT_OK;
+}
+static int check_tree_device(size_t n, const void *d_boxes, const void *d_skip, const void *d_prim, const void *d_node_boxes, const void *d_order) {
+    if (n > 0 && !d_boxes) return fail(RT_ERR_INVALID_ARGUMENT, "d_boxes is NULL");
+    if ((uintptr_t) d_boxes % 8u) return fail(RT_ERR_INVALID_ARGUMENT, "d_boxes is not 8-byte aligned");
+    if ((uintptr_t) d_node_boxes % 8u) return fail(RT_ERR_INVALID_ARGUMENT, "d_node_boxes is not 8-byte aligned");
+    if ((uintptr_t) d_skip % 4u) return fail(RT_ERR_INVALID_ARGUMENT, "d_skip is not 4-byte aligned");
+    if ((uintptr_t) d_prim % 4u) return fail(RT_ERR_INVALID_ARGUMENT, "d_prim is not 4-byte aligned");
+    if ((uintptr_t) d_order % 4u) return fail(RT_ERR_INVALID_ARGUMENT, "d_order is not 4-byte aligned");
+    if (n > (size_t) RTT_MAX_BOXES) return fail(RT_ERR_UNSUPPORTED, "more than 4,500,000 boxes (the scene's own limit)");
+    return RT_OK;
+}
+static bool any_nan(const double *v, size_t count) {
+    for (size_t i = 0; i < count; ++i) if (v[i] != v[i]) return true;
+    return false;
+}
+// TreeBuilder on the caller's boxes (n > 0, checked)
+static void tree_on_host(size_t n, const double *boxes, rth::FlatTree &t) {
+    std::vector<rth::Box> ob(n);
+    for (size_t j = 0; j < n; ++j)
+        for (int a = 0; a < 3; ++a) { ob[j].mn[a] = boxes[j * 6 + (size_t) a * 2]; ob[j].mx[a] = boxes[j * 6 + (size_t) a * 2 + 1]; }
+    std::vector<int32_t> ids(n);
+    for (size_t j = 0; j < n; ++j) ids[j] = (int32_t) j;
+    rth::TreeBuilder(ob, t).go(ids, 1);
+}
+
+// Enqueues one build on `st` (n > 0, arguments checked, the device current).  Scratch, stream-ordered: the NaN flag; above RTT_S boxes also
+// the order (twice), the slots, the winning axes, three arrays of sort records and the partial boxes.  Never waits for the device.
+static int enqueue_tree(size_t n_boxes, const void *d_boxes, void *d_skip, void *d_prim, void *d_node_boxes, void *d_order, hipStream_t st, FormatPending &fp) {
+    const uint32_t n = (uint32_t) n_boxes;
+    const double *boxes = (const double *) d_boxes;
+    const rtk::Outputs out{(int32_t *) d_skip, (int32_t *) d_prim, (double *) d_node_boxes, (int32_t *) d_order};
+    const int32_t Lg = rtt::levels_above(n, RTT_S);
+    uint32_t P = RTK_TILE;
+    while (P < n) P <<= 1;
+    size_t partials = (n + RTT_PART - 1u) / RTT_PART;
+    for (int32_t l = 0; l < Lg; ++l) {
+        const size_t parts = (rtt::left_count(rtt::max_count(n, l)) + RTT_PART - 1u) / RTT_PART;
+        partials = std::max(partials, ((size_t) 1 << l) * parts * 6u);
+    }
+    auto up = [](size_t v) { return (v + 15u) & ~(size_t) 15u; };
+    const size_t ids_at = 16, slot_at = ids_at + up((size_t) n * 8u), best_at = slot_at + up((size_t) n * 4u), rec_at = best_at + up(((size_t) 1 << Lg) * 4u),
+                 part_at = rec_at + (size_t) P * 3u * sizeof(rtk::Rec), total = part_at + partials * sizeof(rtt::Box);
+    HIP_TRY(hipMallocAsync((void **) &fp.scr, Lg == 0 ? 16 : total, st));
+    fp.st = st;
+    HIP_TRY(hipMemsetAsync(fp.scr, 0, 16, st));
+    int *bad = (int *) fp.scr;
+    {
+        const uint64_t count = (uint64_t) n * 6u;
+        const uint64_t want = (count + RTK_BLOCK - 1u) / RTK_BLOCK;
+        hipLaunchKernelGGL(rtk::tree_check_kernel, dim3((unsigned) (want < 4096u ? want : 4096u)), dim3(RTK_BLOCK), 0, st, boxes, count, bad);
+    }
+    if (Lg == 0) {
+        hipLaunchKernelGGL(rtk::tree_lds_kernel, dim3(1), dim3(RTK_LDS_THREADS), 0, st, n, 0, (const uint32_t *) nullptr, boxes, out, (const int *) bad);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    }
+    uint32_t *ids[2] = {(uint32_t *) (fp.scr + ids_at), (uint32_t *) (fp.scr + ids_at) + n};
+    uint32_t *slot = (uint32_t *) (fp.scr + slot_at), *best = (uint32_t *) (fp.scr + best_at);
+    rtk::Rec *rec = (rtk::Rec *) (fp.scr + rec_at);
+    rtt::Box *partial = (rtt::Box *) (fp.scr + part_at);
+    const unsigned per_n = (n + RTK_BLOCK - 1u) / RTK_BLOCK, per_P = P / RTK_BLOCK;
+    hipLaunchKernelGGL(rtk::tree_init_kernel, dim3(per_n), dim3(RTK_BLOCK), 0, st, n, ids[0], slot, (const int *) bad);
+    {
+        const uint32_t parts = (n + RTT_PART - 1u) / RTT_PART;
+        hipLaunchKernelGGL(rtk::tree_root_parts_kernel, dim3(parts), dim3(RTK_BLOCK), 0, st, n, boxes, partial, (const int *) bad);
+        hipLaunchKernelGGL(rtk::tree_root_finish_kernel, dim3(1), dim3(64), 0, st, n, parts, (const rtt::Box *) partial, out, (const int *) bad);
+    }
+    for (int32_t l = 0; l < Lg; ++l) {
+        const uint32_t *cur = ids[l & 1];
+        uint32_t *nxt = ids[(l + 1) & 1];
+        hipLaunchKernelGGL(rtk::tree_fill_kernel, dim3(per_P), dim3(RTK_BLOCK), 0, st, n, P, cur, (const uint32_t *) slot, boxes, rec, (const int *) bad);
+        hipLaunchKernelGGL(rtk::tree_sort_tile_kernel, dim3(P / RTK_TILE, 3), dim3(RTK_TILE_THREADS), 0, st, rec, P, 2u, (uint32_t) RTK_TILE, (const int *) bad);
+        for (uint32_t k = 2u * RTK_TILE; k <= P && k != 0u; k <<= 1) {
+            for (uint32_t j = k >> 1; j >= (uint32_t) RTK_TILE; j >>= 1)
+                hipLaunchKernelGGL(rtk::tree_sort_step_kernel, dim3(P / 2u / RTK_BLOCK, 3), dim3(RTK_BLOCK), 0, st, rec, P, k, j, (const int *) bad);
+            hipLaunchKernelGGL(rtk::tree_sort_tile_kernel, dim3(P / RTK_TILE, 3), dim3(RTK_TILE_THREADS), 0, st, rec, P, k, k, (const int *) bad);
+        }
+        const uint32_t slots = 1u << l, parts = (rtt::left_count(rtt::max_count(n, l)) + RTT_PART - 1u) / RTT_PART;
+        hipLaunchKernelGGL(rtk::tree_parts_kernel, dim3(slots * parts, 6), dim3(RTK_BLOCK), 0, st, n, P, l, parts, cur, (const rtk::Rec *) rec, boxes, partial,
+                           (const int *) bad);
+        hipLaunchKernelGGL(rtk::tree_choose_kernel, dim3((slots + RTK_BLOCK - 1u) / RTK_BLOCK), dim3(RTK_BLOCK), 0, st, n, P, l, parts, cur, (const rtk::Rec *) rec,
+                           boxes, (const rtt::Box *) partial, best, out, (const int *) bad);
+        hipLaunchKernelGGL(rtk::tree_reorder_kernel, dim3(per_n), dim3(RTK_BLOCK), 0, st, n, P, l, cur, nxt, slot, (const rtk::Rec *) rec, (const uint32_t *) best,
+                           (const int *) bad);
+    }
+    hipLaunchKernelGGL(rtk::tree_lds_kernel, dim3(1u << Lg), dim3(RTK_LDS_THREADS), 0, st, n, Lg, (const uint32_t *) ids[Lg & 1], boxes, out, (const int *) bad);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+// Waits for the stream and reads what the check found: a NaN coordinate, of which nothing was written.
+static int finish_tree(FormatPending &fp) {
+    int bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, fp.scr, sizeof(bad), hipMemcpyDeviceToHost, fp.st));
+    HIP_TRY(hipStreamSynchronize(fp.st));
+    if (bad) return fail(RT_ERR_INVALID_ARGUMENT, kNanBox);
+    return RT_OK;
+}
+
+extern "C" {
+
+int64_t rt_tree_nodes(size_t n) { return rtt::node_count((uint64_t) n); }
+int32_t rt_tree_depth(size_t n) { return rtt::depth((uint64_t) n); }
+int32_t rt_tree_lds_boxes(void) { return RTT_S; }
+
+int rt_tree_make_host(size_t n, const double *boxes, int32_t *skip, int32_t *prim, double *node_boxes, int32_t *order) {
+    RT_TRY(check_tree_host(n, boxes));
+    if (n == 0) return RT_OK;
+    return guarded("rt_tree_make_host", [&]() {
+        if (any_nan(boxes, n * 6u)) return fail(RT_ERR_INVALID_ARGUMENT, kNanBox);
+        rth::FlatTree t;
+        tree_on_host(n, boxes, t);
+        size_t leaf = 0;
+        for (size_t i = 0; i < t.skip.size(); ++i) {
+            if (skip) skip[i] = t.skip[i];
+            if (prim) prim[i] = t.prim[i];
+            if (node_boxes) for (int a = 0; a < 3; ++a) { node_boxes[i * 6 + (size_t) a * 2] = t.box[i].mn[a]; node_boxes[i * 6 + (size_t) a * 2 + 1] = t.box[i].mx[a]; }
+            if (t.prim[i] >= 0) { if (order) order[leaf] = t.prim[i]; ++leaf; }
+        }
+        return (int) RT_OK;
+    });
+}
+
+int rt_tree_make_device(int32_t device, size_t n, const void *d_boxes, void *d_skip, void *d_prim, void *d_node_boxes, void *d_order, void *stream) {
+    RT_TRY(check_tree_device(n, d_boxes, d_skip, d_prim, d_node_boxes, d_order));
+    if (n == 0) return RT_OK;
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    FormatPending fp;
+    RT_TRY(enqueue_tree(n, d_boxes, d_skip, d_prim, d_node_boxes, d_order, (hipStream_t) stream, fp));
+    return finish_tree(fp);
+}
+
+int rt_tree_make(int32_t device, size_t n, const double *boxes, int32_t *skip, int32_t *prim, double *node_boxes, int32_t *order) {
+    RT_TRY(check_tree_host(n, boxes));
+    if (n == 0) return RT_OK;
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    const size_t nn = (size_t) rtt::node_count(n);
+    Staging sg;
+    RT_TRY(sg.in({{boxes, n * 48u, SEG_IN}, {skip, nn * 4u, SEG_OUT}, {prim, nn * 4u, SEG_OUT}, {node_boxes, nn * 48u, SEG_OUT}, {order, n * 4u, SEG_OUT}}));
+    FormatPending fp;
+    RT_TRY(enqueue_tree(n, sg.dev[0], sg.dev[1], sg.dev[2], sg.dev[3], sg.dev[4], nullptr, fp));
+    RT_TRY(finish_tree(fp));
+    return sg.out();
+}
+
+int rt_scene_create_gpu_tree(const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                             const rt_scene_options *options, int32_t device, rt_scene **out) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    int walk = -1;
+    if (options && options->struct_size >= offsetof(rt_scene_options, walk_tree) + sizeof(int32_t)) walk = options->walk_tree;
+    if (walk == -1) walk = g_walk_tree.load();
+    if (walk != RT_WALK_TREE_SAH && walk != RT_WALK_TREE_REFERENCE) return fail(RT_ERR_INVALID_ARGUMENT, "walk_tree must be RT_WALK_TREE_SAH, RT_WALK_TREE_REFERENCE or -1");
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    return guarded("rt_scene_create_gpu_tree", [&]() {
+        const rth::TreeMaker maker = [&](const std::vector<rth::Box> &ob, rth::FlatTree &t, std::string &msg) -> int {
+            const size_t n = ob.size(), nn = (size_t) rtt::node_count(n);
+            std::vector<double> flat(n * 6u), nb(nn * 6u);
+            for (size_t j = 0; j < n; ++j)
+                for (int a = 0; a < 3; ++a) { flat[j * 6 + (size_t) a * 2] = ob[j].mn[a]; flat[j * 6 + (size_t) a * 2 + 1] = ob[j].mx[a]; }
+            t.skip.resize(nn); t.prim.resize(nn); t.box.resize(nn);
+            const int rc = rt_tree_make(device, n, flat.data(), t.skip.data(), t.prim.data(), nb.data(), nullptr);
+            if (rc != RT_OK) { msg = g_err; return rc; }
+            for (size_t i = 0; i < nn; ++i)
+                for (int a = 0; a < 3; ++a) { t.box[i].mn[a] = nb[i * 6 + (size_t) a * 2]; t.box[i].mx[a] = nb[i * 6 + (size_t) a * 2 + 1]; }
+            t.depth = rtt::depth(n);
+            return RT_OK;
+        };
+        std::unique_ptr<rt_scene> s(new rt_scene());
+        int status = RT_OK;
+        std::string msg = rth::build_scene(hittables, n_hittables, textures, n_textures, walk, s->host, status, &maker);
+        if (status != RT_OK) return fail(status, msg);
+        *out = s.release();
+        return (int) RT_OK;
     });
 }
 

@@ -450,14 +450,18 @@ class Scene:
             lib.rt_scene_destroy(h)
 
     @staticmethod
-    def make(objects: Sequence[Hittable], walk_tree: Optional[str] = None) -> "Scene":  # Scene.fs:15-28
-        """walk_tree: None = the process default (set_walk_tree), "sah" or "reference" = this scene's own choice (rt_scene_create_ex)."""
+    def make(objects: Sequence[Hittable], walk_tree: Optional[str] = None, tree_device: Optional[int] = None) -> "Scene":  # Scene.fs:15-28
+        """walk_tree: None = the process default (set_walk_tree), "sah" or "reference" = this scene's own choice (rt_scene_create_ex).
+        tree_device: None = BoundingBoxTree.make's tree is built on the host; a device index = on that GPU (rt_scene_create_gpu_tree): the
+        same scene, node for node."""
         hs, n, tex, ntex, keep = flatten_hittables(objects)
         out = C.c_void_p()
-        if walk_tree is None:
+        opt = None if walk_tree is None else A.rt_scene_options({"sah": A.RT_WALK_TREE_SAH, "reference": A.RT_WALK_TREE_REFERENCE}[walk_tree])
+        if tree_device is not None:
+            check(lib.rt_scene_create_gpu_tree(hs, n, tex, ntex, _ref(opt), int(tree_device), C.byref(out)))
+        elif opt is None:
             check(lib.rt_scene_create(hs, n, tex, ntex, C.byref(out)))
         else:
-            opt = A.rt_scene_options({"sah": A.RT_WALK_TREE_SAH, "reference": A.RT_WALK_TREE_REFERENCE}[walk_tree])
             check(lib.rt_scene_create_ex(hs, n, tex, ntex, C.byref(opt), C.byref(out)))
         return Scene(out.value, keep)
 
@@ -1001,6 +1005,50 @@ def _u32(a: np.ndarray):
 
 def _u64(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+# ---- BoundingBoxTree.make over caller-supplied boxes (BoundingBoxTree.fs:9-43) ----------------------------------------------------
+def _tree_boxes(boxes) -> np.ndarray:
+    b = np.asarray(boxes)
+    if b.dtype != np.float64 or b.ndim != 2 or b.shape[1] != 6:
+        raise ValueError(f"boxes must be float64 [n, 6] (minx, maxx, miny, maxy, minz, maxz), got {b.dtype} {tuple(b.shape)}")
+    return np.ascontiguousarray(b)
+
+
+def tree_make_host(boxes):
+    """rt_tree_make_host: the host builder over boxes [n, 6] (minx, maxx, miny, maxy, minz, maxz); no device.  Returns (skip, prim, boxes,
+    order): skip and prim [2n-1] int32 (prim: the input index of a Leaf's box, -1 for a Branch), the node boxes [2n-1, 6], and the
+    depth-first leaf order [n]."""
+    b = _tree_boxes(boxes)
+    n, nn = b.shape[0], int(lib.rt_tree_nodes(b.shape[0]))
+    skip, prim, nb, order = np.zeros(nn, np.int32), np.zeros(nn, np.int32), np.zeros((nn, 6), np.float64), np.zeros(n, np.int32)
+    check(lib.rt_tree_make_host(n, _f64(b), _i32(skip), _i32(prim), _f64(nb), _i32(order)))
+    return skip, prim, nb, order
+
+
+def tree_make(boxes, device: Optional[int] = None):
+    """The same four arrays from the device build: a numpy array goes through rt_tree_make (on `device`, 0 by default) and comes back as
+    arrays; a float64 torch tensor on a GPU through rt_tree_make_device on torch's current stream there, and comes back as tensors."""
+    if not _is_torch(boxes):
+        b = _tree_boxes(boxes)
+        n, nn = b.shape[0], int(lib.rt_tree_nodes(b.shape[0]))
+        skip, prim, nb, order = np.zeros(nn, np.int32), np.zeros(nn, np.int32), np.zeros((nn, 6), np.float64), np.zeros(n, np.int32)
+        check(lib.rt_tree_make(0 if device is None else int(device), n, _f64(b), _i32(skip), _i32(prim), _f64(nb), _i32(order)))
+        return skip, prim, nb, order
+    torch = _torch()
+    if not boxes.is_cuda:
+        raise ValueError(f"boxes must be on a GPU, got {boxes.device} (use a numpy array for the host route)")
+    if boxes.dtype != torch.float64 or boxes.dim() != 2 or boxes.shape[1] != 6:
+        raise ValueError(f"boxes must be float64 [n, 6] (minx, maxx, miny, maxy, minz, maxz), got {boxes.dtype} {tuple(boxes.shape)}")
+    where = boxes.device
+    _tensor_device(where, device)
+    b = boxes.contiguous()
+    n, nn = b.shape[0], int(lib.rt_tree_nodes(b.shape[0]))
+    skip, prim = torch.empty(nn, dtype=torch.int32, device=where), torch.empty(nn, dtype=torch.int32, device=where)
+    nb, order = torch.empty((nn, 6), dtype=torch.float64, device=where), torch.empty(n, dtype=torch.int32, device=where)
+    check(lib.rt_tree_make_device(where.index, n, b.data_ptr(), skip.data_ptr(), prim.data_ptr(), nb.data_ptr(), order.data_ptr(),
+                                  torch.cuda.current_stream(where).cuda_stream))
+    return skip, prim, nb, order
 
 
 # ---- the two routes of a launching Scene call -------------------------------------------------------------------------
