@@ -977,6 +977,42 @@ int rt_tree_make_device(int32_t device, size_t n, const void *d_boxes, void *d_s
 int rt_scene_create_gpu_tree(const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
                              const rt_scene_options *options, int32_t device, rt_scene **out);
 
+/* ---- The tree the device walks, built on the device (csrc/rt_walk_plan.h, csrc/rt_walk_kernels.h; DESIGN.md "The walk tree on the
+ * device").  Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7.
+ *
+ * The surface-area build of rt_scene_create (RT_WALK_TREE_SAH, the arms without probe rays) over the caller's boxes: a node over n boxes
+ * holds their union; in pre-order node `me` has its left child at me + 1 over k boxes, its right child at me + 2k over n - k, and
+ * skip[me] = me + 2n - 1.  k is chosen by cost (csrc/rt_walk_plan.h: a full sweep up to 4096 boxes, 32 centroid bins above, halving from
+ * depth 48 on), so the shape depends on the boxes; there are always rt_tree_nodes(n) nodes.
+ * boxes: n*6 doubles (minx,maxx,miny,maxy,minz,maxz).  Outputs, any may be NULL: skip, prim (input index of a Leaf's box, -1 for a
+ * Branch): rt_tree_nodes(n) int32 each; node_boxes: rt_tree_nodes(n)*6 doubles.
+ *
+ * rt_walk_tree_make_host is the host builder of rt_scene_create on these boxes and touches no device: the yardstick.
+ * rt_walk_tree_make stages the boxes, builds on the null stream and copies back.  rt_walk_tree_make_device builds on `stream` (NULL = the
+ * null stream) from and into device memory with stream-ordered scratch (any number of builds may be in flight) and returns after the
+ * stream has finished the build; it waits for the stream once per level of nodes above 4096 boxes.  All three give the same skip and
+ * prim, and boxes that are equal as numbers: a Branch box of the device build has +0.0 for either zero, where the host builder's sign
+ * depends on the order its std::nth_element leaves (no cost, comparison, split or render depends on it).  The two device routes agree
+ * byte for byte, and so do two builds of one input.
+ *
+ * Argument checks come before any device call, nothing is written when one fails: RT_ERR_INVALID_ARGUMENT for NULL boxes with n > 0 or a
+ * device pointer that is not 8-byte (boxes, node_boxes) or 4-byte (skip, prim) aligned; then RT_ERR_UNSUPPORTED for n > 4,500,000.
+ * n == 0 is a no-op RT_OK.  A coordinate that is not finite: RT_ERR_INVALID_ARGUMENT (a scene never builds this tree over such boxes),
+ * found on the host by rt_walk_tree_make_host and on the device by the other two -- in front of the build, on the same stream, with no
+ * output written.  RT_ERR_NO_DEVICE without a GPU (not rt_walk_tree_make_host).  The caller's current device is left as it was. */
+int rt_walk_tree_make_host(size_t n, const double *boxes, int32_t *skip, int32_t *prim, double *node_boxes);
+int rt_walk_tree_make(int32_t device, size_t n, const double *boxes, int32_t *skip, int32_t *prim, double *node_boxes);
+int rt_walk_tree_make_device(int32_t device, size_t n, const void *d_boxes, void *d_skip, void *d_prim, void *d_node_boxes, void *stream);
+/* rt_scene_create_gpu_tree with the walk tree taken from the device build as well: both trees come from `device`, everything else is the
+ * same host code, and the scene is the same scene -- rt_scene_get_info, _get_tree, _get_walk_tree (boxes equal as numbers),
+ * _get_filter_tree and every render are identical, before and after rt_scene_tune*.  The host builders are used exactly where they are
+ * otherwise: RT_WALK_TREE_REFERENCE (no surface-area tree at all), fewer than 3 bounded spheres, a box coordinate that is not finite.
+ * Measured on one MI355X (DESIGN.md "The walk tree on the device"): the walk tree takes 17.7 ms instead of 1.83 s at 1e6 boxes, 9.2 instead of
+ * 160 ms at 1e5, 6.8 instead of 13.4 ms at 1e4 and 1.32 instead of 0.43 ms at 485; creating a scene of 1e6 spheres goes from 1.98 s
+ * (rt_scene_create_gpu_tree) to 0.51 s.  The crossover is at about 8000 spheres: below it rt_scene_create(_ex) is the faster route. */
+int rt_scene_create_gpu_trees(const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                              const rt_scene_options *options, int32_t device, rt_scene **out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
 #pragma once
 #include "../../include/rtfs_amd.h"
 #include "rt_device.h"
+#include "rt_walk_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -150,11 +151,9 @@ class TreeBuilder {
 // tree built for fewer box tests -- surface-area heuristic below -- and return the same hit, bit for bit.  The reference's own
 // tree (above) is still built: it defines the ranks, rt_scene_get_tree reports it, and RT_WALK_TREE_REFERENCE walks it
 // (then the box-test counter equals the oracle's as well).
-static inline double half_area(const Box &b) {
-    double d[3];
-    for (int a = 0; a < 3; ++a) { d[a] = b.mx[a] - b.mn[a]; if (!(d[a] > 0.0)) d[a] = 0.0; } // inverted (negative-radius) boxes count as empty
-    return d[0] * d[1] + d[1] * d[2] + d[0] * d[2];
-}
+// The rules of the arms without probe rays -- the constants, half_area, the costs, the bin index, the binned choice -- are rt_walk_plan.h's,
+// shared with the device build of the same tree (rt_walk_kernels.h).
+static inline double half_area(const Box &b) { return rtw::half_area(b); }
 // Probe rays (rt_scene_tune): rays of a small render with the scene's camera, as the device logged them.  With them the split
 // cost of a candidate box is the NUMBER OF PROBE RAYS THAT HIT IT instead of its area -- rays of this renderer start on surfaces
 // inside the scene, for which area is a poor predictor -- and the finished tree is then thinned (collapse_tree below).
@@ -191,11 +190,11 @@ class SahBuilder {
     std::vector<double> suffix;
     std::vector<Box> pre, suf;          // boxes of ids[0, k) and ids[k, n) of the axis being swept (probe mode)
     std::vector<uint32_t> cntP, cntS;
-    static const size_t kSweepMax = 4096; // above this a node is split on 32 centroid bins per axis instead of a full sweep
+    static const size_t kSweepMax = RTW_SWEEP; // above this a node is split on 32 centroid bins per axis instead of a full sweep
     static const size_t kProbeMin = 32;   // fewer probe rays than this in a box: its subtree is split by area
     static const size_t kSweepRays = 128; // rays a sweep looks at, at most (about): the split costs need a few percent only (final scene, box tests
                                           // per held-out ray after thinning: 18.08 with 512, 18.15 with 256, 18.17 with 128, 18.27 with 64; time ~linear)
-    double centroid2(int32_t id, int axis) const { return ob[(size_t) id].mn[axis] + ob[(size_t) id].mx[axis]; }
+    double centroid2(int32_t id, int axis) const { return rtw::centroid2(ob[(size_t) id], axis); }
     void sort_axis(int32_t *ids, size_t n, int axis) const {
         std::sort(ids, ids + n, [&](int32_t a, int32_t b) {
             const double ca = centroid2(a, axis), cb = centroid2(b, axis);
@@ -230,7 +229,7 @@ class SahBuilder {
         if (n > 1) {
             size_t k = n / 2;
             int bestAxis = -1;
-            if (depth < 48) { // a degenerate input cannot make the recursion deeper than this: below, halve by centroid order
+            if (depth < RTW_DEPTH) { // a degenerate input cannot make the recursion deeper than this: below, halve by centroid order
                 double bestCost = 0.0;
                 for (int axis = 0; axis < 3; ++axis) {
                     if (probe) {
@@ -269,39 +268,29 @@ class SahBuilder {
                         acc = ob[(size_t) ids[0]];
                         for (size_t i = 1; i < n; ++i) { // left = ids[0, i), right = ids[i, n); a subtree of m leaves has 2m-1 boxes
                             if (i > 1) acc = merge_two(acc, ob[(size_t) ids[i - 1]]);
-                            const double cost = half_area(acc) * (double) (2 * i - 1) + suffix[i] * (double) (2 * (n - i) - 1);
+                            const double cost = rtw::sweep_cost(half_area(acc), i, suffix[i], n);
                             if (bestAxis < 0 || cost < bestCost) { bestCost = cost; bestAxis = axis; k = i; }
                         }
                     } else {
-                        const int B = 32;
+                        const int B = RTW_BINS;
                         double lo = centroid2(ids[0], axis), hi = lo;
                         for (size_t i = 1; i < n; ++i) { const double c = centroid2(ids[i], axis); if (c < lo) lo = c; if (c > hi) hi = c; }
                         if (!(hi > lo)) continue;
-                        Box bb[B]; size_t cnt[B]; bool used[B];
-                        for (int b = 0; b < B; ++b) { cnt[b] = 0; used[b] = false; }
-                        const double scale = (double) B / (hi - lo);
+                        Box bb[B]; uint64_t cnt[B];
+                        for (int b = 0; b < B; ++b) cnt[b] = 0;
+                        const double scale = rtw::bin_scale(lo, hi);
                         for (size_t i = 0; i < n; ++i) {
-                            int b = (int) ((centroid2(ids[i], axis) - lo) * scale); if (b >= B) b = B - 1; if (b < 0) b = 0;
-                            bb[b] = used[b] ? merge_two(bb[b], ob[(size_t) ids[i]]) : ob[(size_t) ids[i]]; used[b] = true; cnt[b]++;
+                            const int b = rtw::bin_index(centroid2(ids[i], axis), lo, scale);
+                            bb[b] = cnt[b] ? merge_two(bb[b], ob[(size_t) ids[i]]) : ob[(size_t) ids[i]]; cnt[b]++;
                         }
-                        double sufA[B + 1]; size_t sufN[B + 1]; Box acc{}; bool any = false; sufN[B] = 0; sufA[B] = 0.0;
-                        for (int b = B - 1; b >= 0; --b) {
-                            if (used[b]) { acc = any ? merge_two(acc, bb[b]) : bb[b]; any = true; }
-                            sufN[b] = sufN[b + 1] + cnt[b]; sufA[b] = any ? half_area(acc) : 0.0;
-                        }
-                        any = false; size_t nl = 0;
-                        for (int b = 1; b < B; ++b) { // left = bins [0, b)
-                            if (used[b - 1]) { acc = any ? merge_two(acc, bb[b - 1]) : bb[b - 1]; any = true; }
-                            nl += cnt[b - 1];
-                            if (nl == 0 || sufN[b] == 0) continue;
-                            const double cost = half_area(acc) * (double) (2 * nl - 1) + sufA[b] * (double) (2 * sufN[b] - 1);
-                            if (bestAxis < 0 || cost < bestCost) { bestCost = cost; bestAxis = axis; k = nl; }
-                        }
+                        uint64_t kb = k; int bestB = 0;
+                        rtw::bin_choose(axis, bb, cnt, bestAxis, bestCost, kb, bestB); // left = bins [0, bestB)
+                        k = (size_t) kb;
                     }
                 }
             }
             if (bestAxis < 0) { bestAxis = 0; k = n / 2; }
-            if (n <= kSweepMax) { if (bestAxis != 2 || depth >= 48) sort_axis(ids, n, bestAxis); } // ids are in axis-2 order after the sweeps
+            if (n <= kSweepMax) { if (bestAxis != 2 || depth >= RTW_DEPTH) sort_axis(ids, n, bestAxis); } // ids are in axis-2 order after the sweeps
             else std::nth_element(ids, ids + k, ids + n, [&](int32_t a, int32_t b) {
                      const double ca = centroid2(a, bestAxis), cb = centroid2(b, bestAxis);
                      return ca < cb || (ca == cb && a < b);
@@ -426,8 +415,10 @@ static void encode_image(HostScene &s);
 typedef std::function<int(const std::vector<Box> &boxes, FlatTree &tree, std::string &msg)> TreeMaker;
 // Returns an empty string on success, otherwise the message for rt_last_error().  `maker` (may be null: TreeBuilder) is asked for the tree of
 // a scene with at least 3 bounded spheres and no NaN box coordinate; everything after the tree is the same code for both.
+// `walk_maker` (may be null: SahBuilder) is asked for the surface-area tree over the leaf boxes in rank order exactly where SahBuilder would
+// be: RT_WALK_TREE_SAH, at least 3 bounded spheres, every box finite (rt_scene_create_gpu_trees: the device build of rt_walk_kernels.h).
 static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture *tex, size_t ntex, int walk_kind, HostScene &s, int &status,
-                               const TreeMaker *maker = nullptr) {
+                               const TreeMaker *maker = nullptr, const TreeMaker *walk_maker = nullptr) {
     status = RT_ERR_INVALID_ARGUMENT;
     if (n > 0 && !h) return "hittables is NULL";
     if (ntex > 0 && !tex) return "textures is NULL";
@@ -531,7 +522,11 @@ static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture 
     s.nBounded = nb; s.nUnbounded = nu;
     if (s.walkKind == RT_WALK_TREE_SAH) {
         s.walkTree = FlatTree{};
-        SahBuilder(s.leafBoxes, s.walkTree).build();
+        if (walk_maker) {
+            std::string msg;
+            const int rc = (*walk_maker)(s.leafBoxes, s.walkTree, msg);
+            if (rc != RT_OK) { status = rc; return msg; }
+        } else SahBuilder(s.leafBoxes, s.walkTree).build();
     } else s.walkTree = s.tree;
     encode_image(s);
     status = RT_OK;

@@ -13,6 +13,8 @@
 #include "rt_scene.h"
 #include "rt_tree_kernels.h"
 #include "rt_tree_plan.h"
+#include "rt_walk_kernels.h"
+#include "rt_walk_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -3192,6 +3194,8 @@ int rt_dev_texture_colour_at(int32_t device, const rt_scene *scene, int32_t text
 // ------------------------------------------------------------------------------------------------------------
 // BoundingBoxTree.make's tree on the device (rt_tree_plan.h, rt_tree_kernels.h; DESIGN.md "The reference tree on the device")
 // ------------------------------------------------------------------------------------------------------------
+static int create_scene_on_device(const char *entry, const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                                  const rt_scene_options *options, int32_t device, bool walk_tree_too, rt_scene **out);
 static const char *const kNanBox = "a box coordinate is NaN: it has no order; nothing was written";
 
 static int check_tree_host(size_t n, const double *boxes) {
@@ -3346,6 +3350,157 @@ int rt_tree_make(int32_t device, size_t n, const double *boxes, int32_t *skip, i
 
 int rt_scene_create_gpu_tree(const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
                              const rt_scene_options *options, int32_t device, rt_scene **out) {
+    return create_scene_on_device("rt_scene_create_gpu_tree", hittables, n_hittables, textures, n_textures, options, device, false, out);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// The tree the device walks, built on the device (rt_walk_plan.h, rt_walk_kernels.h; DESIGN.md "The walk tree on the device")
+// ------------------------------------------------------------------------------------------------------------
+static const char *const kNonFiniteBox = "a box coordinate is not finite: a scene never builds the walk tree over such boxes; nothing was written";
+
+static bool any_non_finite(const double *v, size_t count) {
+    for (size_t i = 0; i < count; ++i) if (!(v[i] - v[i] == 0.0)) return true;
+    return false;
+}
+static void boxes_of(size_t n, const double *boxes, std::vector<rth::Box> &ob) {
+    ob.resize(n);
+    for (size_t j = 0; j < n; ++j)
+        for (int a = 0; a < 3; ++a) { ob[j].mn[a] = boxes[j * 6 + (size_t) a * 2]; ob[j].mx[a] = boxes[j * 6 + (size_t) a * 2 + 1]; }
+}
+// the longest root-to-leaf path of a pre-order tree with skip links
+static int depth_of(const std::vector<int32_t> &skip) {
+    std::vector<int32_t> up; // the ends of the subtrees the walk is inside
+    int depth = 0;
+    for (size_t i = 0; i < skip.size(); ++i) {
+        while (!up.empty() && (int32_t) i >= up.back()) up.pop_back();
+        up.push_back(skip[i]);
+        if ((int) up.size() > depth) depth = (int) up.size();
+    }
+    return depth;
+}
+
+// One build on `st` (n > 0, arguments checked, the device current); returns when the stream has finished it.  Scratch, stream-ordered: the
+// counters, the order (twice), the segment lists, and per segment of a level its bounds, bins, choice and children's boxes.  The host reads
+// two counters per level of segments above RTW_SWEEP (how many, the largest) and sizes the next level's launches from them; the number of
+// levels is bounded by rtw::levels_below.
+static int build_walk_tree(size_t n_boxes, const void *d_boxes, void *d_skip, void *d_prim, void *d_node_boxes, hipStream_t st) {
+    using namespace rtwk;
+    const uint32_t n = (uint32_t) n_boxes;
+    const double *boxes = (const double *) d_boxes;
+    const Outputs out{(int32_t *) d_skip, (int32_t *) d_prim, (double *) d_node_boxes, nullptr};
+    const uint32_t capBig = n / (uint32_t) (RTW_SWEEP + 1) + 1u, capSmall = n / 2u + 1u;
+    auto up = [](size_t v) { return (v + 63u) & ~(size_t) 63u; };
+    const size_t ids_at = up(sizeof(Ctrl)), big_at = ids_at + up((size_t) n * 8u), small_at = big_at + up((size_t) capBig * 2u * sizeof(Seg)),
+                 dec_at = small_at + up((size_t) capSmall * sizeof(Seg)), ones_at = dec_at + up((size_t) capBig * sizeof(Dec)),
+                 zeros_at = ones_at + up((size_t) capBig * sizeof(Ones)), total = zeros_at + up((size_t) capBig * sizeof(Zeros));
+    FormatPending fp;
+    HIP_TRY(hipMallocAsync((void **) &fp.scr, total, st));
+    fp.st = st;
+    HIP_TRY(hipMemsetAsync(fp.scr, 0, sizeof(Ctrl), st));
+    Ctrl *ctrl = (Ctrl *) fp.scr;
+    uint32_t *ids[2] = {(uint32_t *) (fp.scr + ids_at), (uint32_t *) (fp.scr + ids_at) + n};
+    Seg *big[2] = {(Seg *) (fp.scr + big_at), (Seg *) (fp.scr + big_at) + capBig};
+    Seg *small = (Seg *) (fp.scr + small_at);
+    Dec *dec = (Dec *) (fp.scr + dec_at);
+    Ones *ones = (Ones *) (fp.scr + ones_at);
+    Zeros *zeros = (Zeros *) (fp.scr + zeros_at);
+    {
+        const uint64_t count = (uint64_t) n * 6u, want = (count + RTWK_BLOCK - 1u) / RTWK_BLOCK;
+        hipLaunchKernelGGL(walk_check_kernel, dim3((unsigned) (want < 4096u ? want : 4096u)), dim3(RTWK_BLOCK), 0, st, boxes, count, &ctrl->bad);
+    }
+    HIP_TRY(hipMemsetAsync(ones, 0xFF, sizeof(Ones), st));
+    HIP_TRY(hipMemsetAsync(zeros, 0, sizeof(Zeros), st));
+    hipLaunchKernelGGL(walk_root_box_kernel, dim3((n + RTWK_PART - 1u) / RTWK_PART), dim3(RTWK_BLOCK), 0, st, n, boxes, ids[0], ones, zeros, (const int *) &ctrl->bad);
+    hipLaunchKernelGGL(walk_root_emit_kernel, dim3(1), dim3(64), 0, st, n, boxes, (const uint32_t *) ids[0], (const Ones *) ones, (const Zeros *) zeros, ctrl, big[0], capBig,
+                       small, capSmall, out);
+    Ctrl h{};
+    HIP_TRY(hipMemcpyAsync(&h, ctrl, sizeof(h), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int32_t bound = rtw::levels_below(n, 1);
+    uint32_t sel = 0u;
+    for (int32_t l = 0; l < bound && !h.bad && h.nbig[sel] > 0u; ++l, sel ^= 1u) {
+        const uint32_t nbig = h.nbig[sel], parts = (h.maxcount[sel] + RTWK_PART - 1u) / RTWK_PART, nxt = sel ^ 1u;
+        if (nbig > capBig) return fail(RT_ERR_HIP, "walk tree build: more segments than boxes allow");
+        const Seg *cur = big[sel];
+        HIP_TRY(hipMemsetAsync(ones, 0xFF, (size_t) nbig * sizeof(Ones), st));
+        HIP_TRY(hipMemsetAsync(zeros, 0, (size_t) nbig * sizeof(Zeros), st));
+        hipLaunchKernelGGL(walk_bounds_kernel, dim3(nbig, parts), dim3(RTWK_BLOCK), 0, st, cur, (const uint32_t *) ids[0], (const uint32_t *) ids[1], boxes, ones, zeros, ctrl, nxt);
+        hipLaunchKernelGGL(walk_bins_kernel, dim3(nbig, parts), dim3(RTWK_BLOCK), 0, st, cur, (const uint32_t *) ids[0], (const uint32_t *) ids[1], boxes, ones, zeros,
+                           (const Ctrl *) ctrl);
+        hipLaunchKernelGGL(walk_choose_kernel, dim3((nbig + 63u) / 64u), dim3(64), 0, st, nbig, cur, (const Ones *) ones, (const Zeros *) zeros, dec, (const Ctrl *) ctrl);
+        hipLaunchKernelGGL(walk_select_kernel, dim3(nbig), dim3(RTWK_SELECT_THREADS), 0, st, cur, (const uint32_t *) ids[0], (const uint32_t *) ids[1], boxes, dec,
+                           (const Ctrl *) ctrl);
+        hipLaunchKernelGGL(walk_partition_kernel, dim3(nbig, parts), dim3(RTWK_BLOCK), 0, st, cur, (const uint32_t *) ids[0], (const uint32_t *) ids[1], ids[0], ids[1], boxes,
+                           (const Dec *) dec, ones, zeros, (const Ctrl *) ctrl);
+        hipLaunchKernelGGL(walk_emit_kernel, dim3((nbig + 63u) / 64u), dim3(64), 0, st, nbig, cur, (const uint32_t *) ids[0], (const uint32_t *) ids[1], boxes, (const Dec *) dec,
+                           (const Ones *) ones, (const Zeros *) zeros, ctrl, nxt, big[nxt], capBig, small, capSmall, out);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&h, ctrl, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (h.bad) return fail(RT_ERR_INVALID_ARGUMENT, kNonFiniteBox);
+    if (h.nbig[sel] > 0u || h.nsmall > capSmall) return fail(RT_ERR_HIP, "walk tree build: the level bound was reached");
+    if (h.nsmall > 0u) {
+        hipLaunchKernelGGL(walk_subtree_kernel, dim3(h.nsmall), dim3(RTWK_SUB_THREADS), 0, st, (const Seg *) small, (const uint32_t *) ids[0], (const uint32_t *) ids[1], boxes,
+                           out, (const Ctrl *) ctrl);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+extern "C" {
+
+int rt_walk_tree_make_host(size_t n, const double *boxes, int32_t *skip, int32_t *prim, double *node_boxes) {
+    RT_TRY(check_tree_host(n, boxes));
+    if (n == 0) return RT_OK;
+    return guarded("rt_walk_tree_make_host", [&]() {
+        if (any_non_finite(boxes, n * 6u)) return fail(RT_ERR_INVALID_ARGUMENT, kNonFiniteBox);
+        std::vector<rth::Box> ob;
+        boxes_of(n, boxes, ob);
+        rth::FlatTree t;
+        rth::SahBuilder(ob, t).build();
+        for (size_t i = 0; i < t.skip.size(); ++i) {
+            if (skip) skip[i] = t.skip[i];
+            if (prim) prim[i] = t.prim[i];
+            if (node_boxes) for (int a = 0; a < 3; ++a) { node_boxes[i * 6 + (size_t) a * 2] = t.box[i].mn[a]; node_boxes[i * 6 + (size_t) a * 2 + 1] = t.box[i].mx[a]; }
+        }
+        return (int) RT_OK;
+    });
+}
+
+int rt_walk_tree_make_device(int32_t device, size_t n, const void *d_boxes, void *d_skip, void *d_prim, void *d_node_boxes, void *stream) {
+    RT_TRY(check_tree_device(n, d_boxes, d_skip, d_prim, d_node_boxes, nullptr));
+    if (n == 0) return RT_OK;
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    return build_walk_tree(n, d_boxes, d_skip, d_prim, d_node_boxes, (hipStream_t) stream);
+}
+
+int rt_walk_tree_make(int32_t device, size_t n, const double *boxes, int32_t *skip, int32_t *prim, double *node_boxes) {
+    RT_TRY(check_tree_host(n, boxes));
+    if (n == 0) return RT_OK;
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    const size_t nn = (size_t) rtt::node_count(n);
+    Staging sg;
+    RT_TRY(sg.in({{boxes, n * 48u, SEG_IN}, {skip, nn * 4u, SEG_OUT}, {prim, nn * 4u, SEG_OUT}, {node_boxes, nn * 48u, SEG_OUT}}));
+    RT_TRY(build_walk_tree(n, sg.dev[0], sg.dev[1], sg.dev[2], sg.dev[3], nullptr));
+    return sg.out();
+}
+
+int rt_scene_create_gpu_trees(const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                              const rt_scene_options *options, int32_t device, rt_scene **out) {
+    return create_scene_on_device("rt_scene_create_gpu_trees", hittables, n_hittables, textures, n_textures, options, device, true, out);
+}
+
+} // extern "C"
+
+// rt_scene_create_ex with BoundingBoxTree.make's tree from the device build on `device`, and (walk_tree_too) the surface-area walk tree as well
+static int create_scene_on_device(const char *entry, const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                                  const rt_scene_options *options, int32_t device, bool walk_tree_too, rt_scene **out) {
     if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
     int walk = -1;
     if (options && options->struct_size >= offsetof(rt_scene_options, walk_tree) + sizeof(int32_t)) walk = options->walk_tree;
@@ -3353,27 +3508,29 @@ int rt_scene_create_gpu_tree(const rt_hittable *hittables, size_t n_hittables, c
     if (walk != RT_WALK_TREE_SAH && walk != RT_WALK_TREE_REFERENCE) return fail(RT_ERR_INVALID_ARGUMENT, "walk_tree must be RT_WALK_TREE_SAH, RT_WALK_TREE_REFERENCE or -1");
     DeviceGuard guard;
     RT_TRY(guard.enter(device));
-    return guarded("rt_scene_create_gpu_tree", [&]() {
-        const rth::TreeMaker maker = [&](const std::vector<rth::Box> &ob, rth::FlatTree &t, std::string &msg) -> int {
+    return guarded(entry, [&]() {
+        // either tree through its staged call: the boxes flattened, the arrays back into a FlatTree
+        auto via = [&](bool sah, const std::vector<rth::Box> &ob, rth::FlatTree &t, std::string &msg) -> int {
             const size_t n = ob.size(), nn = (size_t) rtt::node_count(n);
             std::vector<double> flat(n * 6u), nb(nn * 6u);
             for (size_t j = 0; j < n; ++j)
                 for (int a = 0; a < 3; ++a) { flat[j * 6 + (size_t) a * 2] = ob[j].mn[a]; flat[j * 6 + (size_t) a * 2 + 1] = ob[j].mx[a]; }
             t.skip.resize(nn); t.prim.resize(nn); t.box.resize(nn);
-            const int rc = rt_tree_make(device, n, flat.data(), t.skip.data(), t.prim.data(), nb.data(), nullptr);
+            const int rc = sah ? rt_walk_tree_make(device, n, flat.data(), t.skip.data(), t.prim.data(), nb.data())
+                               : rt_tree_make(device, n, flat.data(), t.skip.data(), t.prim.data(), nb.data(), nullptr);
             if (rc != RT_OK) { msg = g_err; return rc; }
             for (size_t i = 0; i < nn; ++i)
                 for (int a = 0; a < 3; ++a) { t.box[i].mn[a] = nb[i * 6 + (size_t) a * 2]; t.box[i].mx[a] = nb[i * 6 + (size_t) a * 2 + 1]; }
-            t.depth = rtt::depth(n);
+            t.depth = sah ? depth_of(t.skip) : rtt::depth(n);
             return RT_OK;
         };
+        const rth::TreeMaker maker = [&](const std::vector<rth::Box> &ob, rth::FlatTree &t, std::string &msg) { return via(false, ob, t, msg); };
+        const rth::TreeMaker walkMaker = [&](const std::vector<rth::Box> &ob, rth::FlatTree &t, std::string &msg) { return via(true, ob, t, msg); };
         std::unique_ptr<rt_scene> s(new rt_scene());
         int status = RT_OK;
-        std::string msg = rth::build_scene(hittables, n_hittables, textures, n_textures, walk, s->host, status, &maker);
+        std::string msg = rth::build_scene(hittables, n_hittables, textures, n_textures, walk, s->host, status, &maker, walk_tree_too ? &walkMaker : nullptr);
         if (status != RT_OK) return fail(status, msg);
         *out = s.release();
         return (int) RT_OK;
     });
 }
-
-} // extern "C"

@@ -450,14 +450,20 @@ class Scene:
             lib.rt_scene_destroy(h)
 
     @staticmethod
-    def make(objects: Sequence[Hittable], walk_tree: Optional[str] = None, tree_device: Optional[int] = None) -> "Scene":  # Scene.fs:15-28
+    def make(objects: Sequence[Hittable], walk_tree: Optional[str] = None, tree_device: Optional[int] = None,
+             walk_tree_device: Optional[int] = None) -> "Scene":  # Scene.fs:15-28
         """walk_tree: None = the process default (set_walk_tree), "sah" or "reference" = this scene's own choice (rt_scene_create_ex).
         tree_device: None = BoundingBoxTree.make's tree is built on the host; a device index = on that GPU (rt_scene_create_gpu_tree): the
-        same scene, node for node."""
+        same scene, node for node.  walk_tree_device: a device index = the surface-area walk tree is built on that GPU too
+        (rt_scene_create_gpu_trees; tree_device defaults to the same device and must be it): the same scene again."""
         hs, n, tex, ntex, keep = flatten_hittables(objects)
         out = C.c_void_p()
         opt = None if walk_tree is None else A.rt_scene_options({"sah": A.RT_WALK_TREE_SAH, "reference": A.RT_WALK_TREE_REFERENCE}[walk_tree])
-        if tree_device is not None:
+        if walk_tree_device is not None:
+            if tree_device is not None and int(tree_device) != int(walk_tree_device):
+                raise ValueError(f"tree_device {tree_device} and walk_tree_device {walk_tree_device} must be the same device")
+            check(lib.rt_scene_create_gpu_trees(hs, n, tex, ntex, _ref(opt), int(walk_tree_device), C.byref(out)))
+        elif tree_device is not None:
             check(lib.rt_scene_create_gpu_tree(hs, n, tex, ntex, _ref(opt), int(tree_device), C.byref(out)))
         elif opt is None:
             check(lib.rt_scene_create(hs, n, tex, ntex, C.byref(out)))
@@ -1049,6 +1055,43 @@ def tree_make(boxes, device: Optional[int] = None):
     check(lib.rt_tree_make_device(where.index, n, b.data_ptr(), skip.data_ptr(), prim.data_ptr(), nb.data_ptr(), order.data_ptr(),
                                   torch.cuda.current_stream(where).cuda_stream))
     return skip, prim, nb, order
+
+
+# ---- the surface-area walk tree over caller-supplied boxes (csrc/rt_walk_plan.h) ----------------------------------------------------
+def walk_tree_make_host(boxes):
+    """rt_walk_tree_make_host: the host builder of the tree the device walks over boxes [n, 6] (minx, maxx, miny, maxy, minz, maxz); no
+    device.  Returns (skip, prim, boxes): skip and prim [2n-1] int32 (prim: the input index of a Leaf's box, -1 for a Branch) and the node
+    boxes [2n-1, 6]."""
+    b = _tree_boxes(boxes)
+    n, nn = b.shape[0], int(lib.rt_tree_nodes(b.shape[0]))
+    skip, prim, nb = np.zeros(nn, np.int32), np.zeros(nn, np.int32), np.zeros((nn, 6), np.float64)
+    check(lib.rt_walk_tree_make_host(n, _f64(b), _i32(skip), _i32(prim), _f64(nb)))
+    return skip, prim, nb
+
+
+def walk_tree_make(boxes, device: Optional[int] = None):
+    """The same three arrays from the device build: a numpy array goes through rt_walk_tree_make (on `device`, 0 by default) and comes back
+    as arrays; a float64 torch tensor on a GPU through rt_walk_tree_make_device on torch's current stream there, and comes back as tensors."""
+    if not _is_torch(boxes):
+        b = _tree_boxes(boxes)
+        n, nn = b.shape[0], int(lib.rt_tree_nodes(b.shape[0]))
+        skip, prim, nb = np.zeros(nn, np.int32), np.zeros(nn, np.int32), np.zeros((nn, 6), np.float64)
+        check(lib.rt_walk_tree_make(0 if device is None else int(device), n, _f64(b), _i32(skip), _i32(prim), _f64(nb)))
+        return skip, prim, nb
+    torch = _torch()
+    if not boxes.is_cuda:
+        raise ValueError(f"boxes must be on a GPU, got {boxes.device} (use a numpy array for the host route)")
+    if boxes.dtype != torch.float64 or boxes.dim() != 2 or boxes.shape[1] != 6:
+        raise ValueError(f"boxes must be float64 [n, 6] (minx, maxx, miny, maxy, minz, maxz), got {boxes.dtype} {tuple(boxes.shape)}")
+    where = boxes.device
+    _tensor_device(where, device)
+    b = boxes.contiguous()
+    n, nn = b.shape[0], int(lib.rt_tree_nodes(b.shape[0]))
+    skip, prim = torch.empty(nn, dtype=torch.int32, device=where), torch.empty(nn, dtype=torch.int32, device=where)
+    nb = torch.empty((nn, 6), dtype=torch.float64, device=where)
+    check(lib.rt_walk_tree_make_device(where.index, n, b.data_ptr(), skip.data_ptr(), prim.data_ptr(), nb.data_ptr(),
+                                       torch.cuda.current_stream(where).cuda_stream))
+    return skip, prim, nb
 
 
 # ---- the two routes of a launching Scene call -------------------------------------------------------------------------
