@@ -1013,6 +1013,56 @@ int rt_walk_tree_make_device(int32_t device, size_t n, const void *d_boxes, void
 int rt_scene_create_gpu_trees(const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
                               const rt_scene_options *options, int32_t device, rt_scene **out);
 
+/* ---- Scene.make from hittables in device memory (Scene.fs:15-28; csrc/rt_scene_plan.h, csrc/rt_scene_kernels.h; DESIGN.md "Scene.make on
+ * the device").  Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7.
+ *
+ * d_hittables: n_hittables rt_hittable records in `device`'s memory, 8-byte aligned; they are read, not kept (the scene holds a copy of its
+ * own).  textures: a HOST array, as for rt_scene_create (at most 254 records, copied the same way).  The build runs on `stream` (NULL = the
+ * null stream) with stream-ordered scratch, so any number of builds may be in flight, and the call returns after the stream has finished
+ * it.  The scene is the scene rt_scene_create_gpu_trees returns for the same records: every rt_scene_get_*, every render, the rt_hit_objects
+ * family (indices into d_hittables), rt_scene_tune* and rt_scene_destroy behave identically.
+ *
+ * On the device, on `stream`: the check of every hittable; Array.partition with order kept on both sides (a scan of the bounded flags);
+ * Sphere.make's boxes; both trees, by the builds of rt_tree_make_device and rt_walk_tree_make_device from and into device memory with no
+ * staging; the ranks (the reference tree's depth-first leaf order, which that build gives as `order`) and the object table; the leaf boxes
+ * in rank order as the walk build's input; the whole image node | geo | meta | node32 | mat, its node32 section in the stable order by
+ * depth (a difference array over the pre-order ranges of the Branches, a scan, and a radix sort on the depth alone); bmax and the inputs
+ * of leaf_box_implied.  Read back: the counts, the error word, the NaN / not-finite flags, bmax, the largest radius and the radius flag,
+ * the largest depth -- O(1) bytes -- and the walk build's per-level counters.  The device's copy of the scene (image, object table,
+ * texture records, texels) is installed directly: nothing proportional to the scene goes to the host in this call or in renders on `device`.
+ *
+ * Fetched lazily, once, under the scene's lock: the host's copy of the hittables, both trees, the leaf boxes, the object table and the
+ * image.  What needs it fetches it: rt_scene_get_tree, _get_walk_tree, _get_filter_tree, rt_scene_tune* (where they rebuild the tree), the
+ * first use of the scene on ANOTHER device, and the rt_dev_* hooks that translate hittable indices.  rt_scene_get_info does not.
+ *
+ * Where the host code still runs: the texture records (O(textures)); the empty scene; and a NaN box coordinate, which has no order --
+ * found on the device, after which the records are downloaded and the scene is rt_scene_create_gpu_trees' own (slow for many records, but
+ * the same scene; it has its host copy from the start).  With fewer than 3 bounded spheres the tree is trivial and is written directly on
+ * the device (so a scene of planes and unbounded spheres alone never passes through the host either).  Boxes that are not finite but
+ * ordered walk the reference tree, as on every route, and are still encoded on the device.
+ *
+ * Refusals.  Argument checks come before any device call: RT_ERR_INVALID_ARGUMENT for NULL d_hittables with n_hittables > 0, NULL textures
+ * with n_textures > 0, d_hittables not 8-byte aligned, NULL out, an options->walk_tree that is not a creation option.  RT_ERR_NO_DEVICE
+ * without a GPU.  Then the textures' own refusals, and for the records the status and rt_last_error() text of rt_scene_create_ex: with
+ * several bad hittables the smallest index is reported, with the first failing check of that hittable (one minimum over index * 8 +
+ * reason); then RT_ERR_UNSUPPORTED for more than 4,500,000 bounded spheres or 16,000,000 objects.  *out is written on success only. */
+int rt_scene_create_device(int32_t device, const void *d_hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                           const rt_scene_options *options, void *stream, rt_scene **out);
+
+/* ---- Test hooks of the device-made scene ---- */
+/* The image bytes as `device` holds them (for a scene made on the host: the host's image once that device has its copy) and the
+ * thirteen words of the kernel's SceneOffsets (node, geo, meta, node32, mat, total, lds_total, lds32_total, n_nodes, n_bounded,
+ * n_unbounded, the bits of bmax, box_implied; the rest 0).  *bytes: the image's size; out may be NULL to ask for it, offsets may be NULL. */
+int rt_dev_scene_image(const rt_scene *scene, int32_t device, void *out, size_t cap, size_t *bytes, uint32_t offsets[16]);
+/* The device encoder alone (the depth, the order by depth and the records) on the scene's own walk tree, object table and hittables, staged
+ * up: the bytes encode_image gives, also for the n-ary tree of a tuned scene.  out may be NULL to ask for *bytes. */
+int rt_dev_encode_image(int32_t device, const rt_scene *host_made, void *out, size_t cap, size_t *bytes);
+/* The same with the order by depth sorted in passes of digit_bits bits (1 .. 8; the product's are 8 wide, so only a tree of 256 levels or
+ * more takes a second pass there): with narrow digits a tree of a few dozen levels runs the later passes -- the same bytes. */
+int rt_dev_encode_image_radix(int32_t device, const rt_scene *host_made, int32_t digit_bits, void *out, size_t cap, size_t *bytes);
+/* 1 when the host holds its copy of the scene's arrays (always, for a scene made on the host), 0 while they are still on the device. */
+int rt_dev_scene_has_host_mirror(const rt_scene *scene);
+
 #ifdef __cplusplus
 }
 #endif

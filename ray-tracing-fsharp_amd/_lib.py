@@ -189,6 +189,12 @@ SIGNATURES = {
     "rt_walk_tree_make_device": (C.c_int, [C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_scene_create_gpu_trees": (C.c_int, [_P(A.rt_hittable), C.c_size_t, _P(A.rt_texture), C.c_size_t, _P(A.rt_scene_options), C.c_int32,
                                             _P(C.c_void_p)]),
+    "rt_scene_create_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_size_t, _P(A.rt_texture), C.c_size_t, _P(A.rt_scene_options), C.c_void_p,
+                                         _P(C.c_void_p)]),
+    "rt_dev_scene_image": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, _P(C.c_size_t), _u32p]),  # offsets[16]
+    "rt_dev_encode_image": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "rt_dev_encode_image_radix": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "rt_dev_scene_has_host_mirror": (C.c_int, [C.c_void_p]),
     "rt_dev_float_producer": (C.c_int, [C.c_int32, _u32p, C.c_int32, _dp]),
     "rt_dev_stream_state": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32, _u64p, _u32p, _u32p]),
     "rt_dev_bbox_hits": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _i32p]),

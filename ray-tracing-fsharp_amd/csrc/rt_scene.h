@@ -6,6 +6,7 @@
 #pragma once
 #include "../../include/rtfs_amd.h"
 #include "rt_device.h"
+#include "rt_scene_plan.h"
 #include "rt_walk_plan.h"
 
 #include <algorithm>
@@ -410,23 +411,13 @@ static inline uint32_t pack_rgb(const uint8_t rgb[3]) { return (uint32_t) rgb[0]
 static inline size_t align16(size_t v) { return (v + 15u) & ~(size_t) 15u; }
 
 static void encode_image(HostScene &s);
-// BoundingBoxTree.make's tree from somewhere else than TreeBuilder (rt_scene_create_gpu_tree: the device build of rt_tree_kernels.h): fills
-// skip, prim (position of the Leaf's box in `boxes`), box and depth as TreeBuilder would, or returns an error code and sets `msg`.
-typedef std::function<int(const std::vector<Box> &boxes, FlatTree &tree, std::string &msg)> TreeMaker;
-// Returns an empty string on success, otherwise the message for rt_last_error().  `maker` (may be null: TreeBuilder) is asked for the tree of
-// a scene with at least 3 bounded spheres and no NaN box coordinate; everything after the tree is the same code for both.
-// `walk_maker` (may be null: SahBuilder) is asked for the surface-area tree over the leaf boxes in rank order exactly where SahBuilder would
-// be: RT_WALK_TREE_SAH, at least 3 bounded spheres, every box finite (rt_scene_create_gpu_trees: the device build of rt_walk_kernels.h).
-static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture *tex, size_t ntex, int walk_kind, HostScene &s, int &status,
-                               const TreeMaker *maker = nullptr, const TreeMaker *walk_maker = nullptr) {
+
+// The texture half of build_scene (s.textures, texRecs, texelBlob): O(textures) host work on every route.  status is RT_OK on success.
+static std::string build_textures(const rt_texture *tex, size_t ntex, HostScene &s, int &status) {
     status = RT_ERR_INVALID_ARGUMENT;
-    if (n > 0 && !h) return "hittables is NULL";
     if (ntex > 0 && !tex) return "textures is NULL";
     if (ntex > (size_t) RTD_MAX_TEXTURES) { status = RT_ERR_UNSUPPORTED; return "at most 254 textures"; }
-    s.hittables.assign(h, h + n);
     s.textures.assign(tex, tex + ntex);
-
-    // ---- textures ----
     s.texRecs.resize(ntex);
     for (size_t i = 0; i < ntex; ++i) {
         const rt_texture &t = tex[i];
@@ -463,32 +454,46 @@ static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture 
         s.texRecs[i] = r;
         s.textures[i].texels = nullptr; // not owned
     }
+    status = RT_OK;
+    return std::string();
+}
+
+// BoundingBoxTree.make's tree from somewhere else than TreeBuilder (rt_scene_create_gpu_tree: the device build of rt_tree_kernels.h): fills
+// skip, prim (position of the Leaf's box in `boxes`), box and depth as TreeBuilder would, or returns an error code and sets `msg`.
+typedef std::function<int(const std::vector<Box> &boxes, FlatTree &tree, std::string &msg)> TreeMaker;
+// Returns an empty string on success, otherwise the message for rt_last_error().  `maker` (may be null: TreeBuilder) is asked for the tree of
+// a scene with at least 3 bounded spheres and no NaN box coordinate; everything after the tree is the same code for both.
+// `walk_maker` (may be null: SahBuilder) is asked for the surface-area tree over the leaf boxes in rank order exactly where SahBuilder would
+// be: RT_WALK_TREE_SAH, at least 3 bounded spheres, every box finite (rt_scene_create_gpu_trees: the device build of rt_walk_kernels.h).
+static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture *tex, size_t ntex, int walk_kind, HostScene &s, int &status,
+                               const TreeMaker *maker = nullptr, const TreeMaker *walk_maker = nullptr) {
+    status = RT_ERR_INVALID_ARGUMENT;
+    if (n > 0 && !h) return "hittables is NULL";
+    {
+        std::string msg = build_textures(tex, ntex, s, status);
+        if (status != RT_OK) return msg;
+        status = RT_ERR_INVALID_ARGUMENT;
+    }
+    s.hittables.assign(h, h + n);
 
     // ---- Scene.make: Array.partition (snd >> ValueOption.isSome), order kept on both sides (Scene.fs:16-22) ----
     std::vector<int32_t> bounded, unbounded;
     for (size_t i = 0; i < n; ++i) {
         const rt_hittable &o = h[i];
-        if (o.kind > RT_HITTABLE_INFINITE_PLANE) return "hittable " + std::to_string(i) + ": bad kind";
-        const bool plane = o.kind == RT_HITTABLE_INFINITE_PLANE;
-        if (plane ? o.style > RT_PLANE_FUZZED_REFLECTION : o.style > RT_SPHERE_GLASS) return "hittable " + std::to_string(i) + ": bad style";
-        if (o.texture >= (int32_t) ntex) return "hittable " + std::to_string(i) + ": texture index out of range";
-        if (o.texture >= 0) {
-            const bool carries = plane ? o.style == RT_PLANE_LIGHT_SOURCE : o.style != RT_SPHERE_LIGHT_SOURCE_CAP;
-            if (!carries) return "hittable " + std::to_string(i) + ": this style carries a Pixel, not a Texture";
-        }
-        (o.kind == RT_HITTABLE_SPHERE ? bounded : unbounded).push_back((int32_t) i);
+        if (const int why = rts::check_hittable(o, (int64_t) ntex)) return "hittable " + std::to_string(i) + ": " + rts::reason_text(why);
+        (rts::is_bounded(o) ? bounded : unbounded).push_back((int32_t) i);
     }
     const size_t nb = bounded.size(), nu = unbounded.size(), nobj = nb + nu;
     // walk offsets are int32 byte offsets with bit 30 reserved for the pending-leaf flag (RTD_LEAF)
-    if (nb > 4500000u || nobj > 16000000u) { status = RT_ERR_UNSUPPORTED; return "scene too large for 32-bit walk offsets (4,500,000 bounded spheres)"; } // (2n-1) * 112 B < 2^30 (bit 30 = RTD_LEAF)
+    if (rts::too_large(nb, nobj)) { status = RT_ERR_UNSUPPORTED; return rts::too_large_text(); } // (2n-1) * 112 B < 2^30 (bit 30 = RTD_LEAF)
     // ---- Sphere.make's box (Sphere.fs:333-336): centre + (-r,-r,-r) .. centre + (r,r,r); inverted when r < 0 ----
     std::vector<Box> boxes(nb); // by position in `bounded` (input order), which is what BoundingBoxTree.make receives
     bool finite = true, ordered = true; // ordered: no NaN coordinate
     for (size_t j = 0; j < nb; ++j) {
-        const rt_hittable &o = h[(size_t) bounded[j]];
+        const rtt::Box sb = rts::sphere_box(h[(size_t) bounded[j]]);
         for (int a = 0; a < 3; ++a) {
-            boxes[j].mn[a] = o.point[a] + (-o.radius);
-            boxes[j].mx[a] = o.point[a] + o.radius;
+            boxes[j].mn[a] = sb.mn[a];
+            boxes[j].mx[a] = sb.mx[a];
             finite = finite && std::isfinite(boxes[j].mn[a]) && std::isfinite(boxes[j].mx[a]);
             ordered = ordered && !std::isnan(boxes[j].mn[a]) && !std::isnan(boxes[j].mx[a]);
         }
@@ -535,16 +540,8 @@ static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture 
 
 // Outward rounding of a box coordinate to single precision (the node32 records of the timed kernel's filter loop, rt_device.h):
 // the largest float <= v / the smallest float >= v.  +-inf and NaN pass through.
-static inline float f32_down(double v) {
-    float f = (float) v; // round to nearest
-    if ((double) f > v) f = std::nextafterf(f, -HUGE_VALF);
-    return f;
-}
-static inline float f32_up(double v) {
-    float f = (float) v;
-    if ((double) f < v) f = std::nextafterf(f, HUGE_VALF);
-    return f;
-}
+using rts::f32_down;
+using rts::f32_up;
 
 // The device image of s.walkTree and the object table (layout: rt_device.h).  Called again when the walk tree changes.
 static void encode_image(HostScene &s) {
@@ -553,22 +550,13 @@ static void encode_image(HostScene &s) {
     const FlatTree &wt = s.walkTree;
     const size_t nn = wt.skip.size();
 
-    // ---- device image: node | geo | meta | node32 | mat ----
+    // ---- device image: node | geo | meta | node32 | mat (rt_scene_plan.h) ----
     rtd::SceneOffsets &off = s.off;
-    size_t cur = 0;
-    off.node = (uint32_t) cur; cur = align16(cur + nn * RTD_NODE_BYTES);
-    off.geo = (uint32_t) cur;  cur = align16(cur + nobj * 48u);
-    off.meta = (uint32_t) cur; cur = align16(cur + nobj * 8u);
-    off.lds_total = (uint32_t) cur; // [0, lds_total): what the counting variant stages
-    off.node32 = (uint32_t) cur; cur = align16(cur + nn * RTD_NODE32_BYTES);
-    off.lds32_total = (uint32_t) cur - off.geo; // [geo, node32 end): what the timed variant stages
-    off.mat = (uint32_t) cur;  cur = align16(cur + nobj * 32u);
-    off.total = (uint32_t) cur;
-    off.n_nodes = (int32_t) nn; off.n_bounded = (int32_t) nb; off.n_unbounded = (int32_t) nu;
-    s.image.assign(cur == 0 ? 16 : cur, 0);
-    if (cur == 0) off.total = 16;
-    if (off.lds_total == 0) off.lds_total = 16;
-    if (off.lds32_total == 0) off.lds32_total = 16;
+    const rts::Offsets ro = rts::offsets(nn, nb, nu);
+    off.node = ro.node; off.geo = ro.geo; off.meta = ro.meta; off.node32 = ro.node32; off.mat = ro.mat; off.total = ro.total;
+    off.lds_total = ro.lds_total; off.lds32_total = ro.lds32_total;
+    off.n_nodes = ro.n_nodes; off.n_bounded = ro.n_bounded; off.n_unbounded = ro.n_unbounded;
+    s.image.assign((size_t) ro.image_bytes, 0);
     unsigned char *pnode = s.image.data() + off.node;
     unsigned char *pnode32 = s.image.data() + off.node32;
     double *pgeo = (double *) (s.image.data() + off.geo);
@@ -593,86 +581,39 @@ static void encode_image(HostScene &s) {
         place[nn] = (uint32_t) nn;
     }
     for (size_t i = 0; i < nn; ++i) {
-        double *bx = (double *) (pnode + i * RTD_NODE_BYTES);
-        int32_t *lk = (int32_t *) (pnode + i * RTD_NODE_BYTES + 96);
-        for (int a = 0; a < 3; ++a) { bx[a * 4] = wt.box[i].mn[a]; bx[a * 4 + 1] = wt.box[i].mx[a]; bx[a * 4 + 2] = wt.box[i].mx[a]; bx[a * 4 + 3] = wt.box[i].mn[a]; }
-        const int32_t onMiss = wt.skip[i] * RTD_NODE_BYTES; // byte offset of the record to visit on a miss
-        lk[0] = wt.prim[i] >= 0 ? (int32_t) (RTD_LEAF | (i * RTD_NODE_BYTES)) : (int32_t) ((i + 1) * RTD_NODE_BYTES); // on_hit
-        lk[1] = onMiss;
-        lk[2] = wt.prim[i]; // object index of a Leaf, -1 for a Branch
-        lk[3] = 0;
-        // the filter loop's record: the box rounded outward, {lo, hi, hi, lo} per axis; links in the queue form of node_loop_lds32:
-        // a Leaf's on_hit is its on_miss (the walk goes on), the third word its queue entry, the fourth the shift that pushes it
-        float *fx = (float *) (pnode32 + (size_t) place[i] * RTD_NODE32_BYTES);
-        int32_t *lk32 = (int32_t *) (pnode32 + (size_t) place[i] * RTD_NODE32_BYTES + 48);
-        for (int a = 0; a < 3; ++a) {
-            const float lo = f32_down(wt.box[i].mn[a]), hi = f32_up(wt.box[i].mx[a]);
-            fx[a * 4] = lo; fx[a * 4 + 1] = hi; fx[a * 4 + 2] = hi; fx[a * 4 + 3] = lo;
-            if (std::fabs(lo) > bmax) bmax = std::fabs(lo); // (a NaN coordinate compares false and leaves bmax alone; it makes its own products NaN)
-            if (std::fabs(hi) > bmax) bmax = std::fabs(hi);
-        }
-        const bool leaf = wt.prim[i] >= 0;
-        const int32_t onMiss32 = (int32_t) (place[(size_t) wt.skip[i]] * RTD_NODE32_BYTES);
-        lk32[0] = leaf ? onMiss32 : (int32_t) (place[i + 1] * RTD_NODE32_BYTES);
-        lk32[1] = onMiss32;
-        // the queue entry: 16 bits for scenes the LDS loop may walk (< 16384 objects), full width beyond (global loop only)
-        lk32[2] = !leaf ? 0 : (nobj < 16384u ? (int32_t) (RTD_PEND_MARK | (uint32_t) wt.prim[i]) : (int32_t) (RTD_PEND_WIDE | (uint32_t) wt.prim[i]));
-        lk32[3] = leaf ? 16 : 0;
+        const rtt::Box b{{wt.box[i].mn[0], wt.box[i].mn[1], wt.box[i].mn[2]}, {wt.box[i].mx[0], wt.box[i].mx[1], wt.box[i].mx[2]}};
+        const rts::NodeRec nr = rts::node_record(b, (uint32_t) i, wt.skip[i], wt.prim[i]);
+        const rts::Node32Rec fr = rts::node32_record(b, wt.prim[i], place[i + 1], place[(size_t) wt.skip[i]], nobj);
+        memcpy(pnode + i * RTD_NODE_BYTES, &nr, sizeof(nr));
+        memcpy(pnode32 + (size_t) place[i] * RTD_NODE32_BYTES, &fr, sizeof(fr));
+        bmax = rts::bmax_with(bmax, fr);
     }
     off.bmax = bmax;
     {   // the hypotheses of leaf_test_object_exact's claim (rt_device.h): the exact leaf-box test is then implied by a sphere hit
         double rmax = 0.0;
-        bool ok = std::isfinite(bmax) && bmax <= 1000.0f;
+        bool ok = true;
         for (size_t j = 0; j < nb; ++j) {
             const double r = h[(size_t) s.objToOrig[j]].radius;
-            if (!(r > 0.0 && r <= 100.0)) ok = false;
+            if (!rts::radius_ok(r)) ok = false;
             if (r > rmax) rmax = r;
         }
-        off.box_implied = (ok && rmax * (double) bmax <= 500.0) ? 1 : 0;
+        off.box_implied = rts::box_implied(bmax, ok, rmax);
     }
     for (size_t j = 0; j < nobj; ++j) {
-        const rt_hittable &o = h[(size_t) s.objToOrig[j]];
-        double *g = pgeo + j * 6;
-        uint32_t m0;
-        if (o.kind == RT_HITTABLE_INFINITE_PLANE) {
-            g[0] = o.point[0]; g[1] = o.point[1]; g[2] = o.point[2];
-            g[3] = o.normal[0]; g[4] = o.normal[1]; g[5] = o.normal[2];
-            m0 = RTD_KIND_PLANE | (o.style << 2);
-            pmat[j * 4 + 0] = o.albedo; pmat[j * 4 + 1] = o.fuzz; pmat[j * 4 + 2] = 0.0; pmat[j * 4 + 3] = 0.0;
-        } else {
-            g[0] = o.point[0]; g[1] = o.point[1]; g[2] = o.point[2];
-            g[3] = o.radius * o.radius; // RadiusSquared (Sphere.fs:326)
-            g[4] = o.albedo; g[5] = o.radius; // the radius itself: LightSourceCap (Sphere.fs:191) and the leaf pass' exact box (leaf_test_object_exact)
-            // flipped = Float.compare this.Radius 0.0 = Less (Sphere.fs:321)
-            const bool flipped = !(std::fabs(o.radius - 0.0) < 0.00000001) && (o.radius < 0.0);
-            m0 = RTD_KIND_SPHERE | (o.style << 2) | (flipped ? 32u : 0u);
-            const bool usesIor = o.style == RT_SPHERE_DIELECTRIC || o.style == RT_SPHERE_GLASS;
-            pmat[j * 4 + 0] = 0.0; pmat[j * 4 + 1] = usesIor ? o.ior : o.fuzz; pmat[j * 4 + 2] = o.prob; pmat[j * 4 + 3] = 0.0;
-            if (usesIor) {
-                // Per-material values the reference recomputes at every hit from the same inputs with the same IEEE operations
-                // (this translation unit is built with -ffp-contract=off): `1.0 / ior` (Sphere.fs:117, 283-284) and Schlick's
-                // `param * param`, param = (1.0 - sr) / (1.0 + sr), for sr = ior (outside) and sr = 1.0 / ior (inside) (Sphere.fs:288-289).
-                const double ior = o.ior;
-                const double inv = 1.0 / ior;
-                if (o.style == RT_SPHERE_DIELECTRIC) pmat[j * 4 + 3] = inv;
-                else {
-                    const double po = (1.0 - ior) / (1.0 + ior), pi = (1.0 - inv) / (1.0 + inv);
-                    pmat[j * 4 + 0] = pi * pi;  // Schlick's term inside the glass
-                    pmat[j * 4 + 2] = inv;      // Glass carries no refraction probability
-                    pmat[j * 4 + 3] = po * po;
-                }
-            }
-        }
-        pmeta[j * 2] = (int32_t) m0;
-        pmeta[j * 2 + 1] = (int32_t) (pack_rgb(o.rgb) | ((uint32_t) (o.texture + 1) << 24));
+        const rts::ObjectRec r = rts::object_record(h[(size_t) s.objToOrig[j]]);
+        memcpy(pgeo + j * 6, r.geo, sizeof(r.geo));
+        memcpy(pmeta + j * 2, r.meta, sizeof(r.meta));
+        memcpy(pmat + j * 4, r.mat, sizeof(r.mat));
     }
 }
 
 // rt_scene_tune's host half: the walk tree rebuilt from probe rays (split costs from ray counts, then thinned) and the image
 // encoded again.  Returns false (and changes nothing) for a scene that walks the reference's own tree.
 struct TuneResult { double visitsBefore = 0.0, visitsAfter = 0.0; int32_t nodesBefore = 0, nodesAfter = 0; };
+// whether tune_walk_tree goes on to rebuild (it then reads the scene's leaf boxes, hittables and walk tree)
+static inline bool tune_applies(const HostScene &s, size_t n_rays) { return !(s.walkKind == RT_WALK_TREE_REFERENCE || s.nBounded < 3 || n_rays == 0); }
 static bool tune_walk_tree(HostScene &s, const std::vector<ProbeRay> &rays, TuneResult &r) {
-    if (s.walkKind == RT_WALK_TREE_REFERENCE || s.nBounded < 3 || rays.empty()) return false;
+    if (!tune_applies(s, rays.size())) return false;
     const double total = (double) rays.size();
     {   // what the tree walked so far costs these rays
         const FlatTree &cur = s.walkTree;

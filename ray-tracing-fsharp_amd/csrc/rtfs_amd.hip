@@ -11,6 +11,8 @@
 #include "rt_png_kernels.h"
 #include "rt_render_kernel.h"
 #include "rt_scene.h"
+#include "rt_scene_kernels.h"
+#include "rt_scene_plan.h"
 #include "rt_tree_kernels.h"
 #include "rt_tree_plan.h"
 #include "rt_walk_kernels.h"
@@ -113,11 +115,29 @@ struct DeviceScene {
     int cu_count = 0;
 };
 
+// What rt_scene_create_device leaves on its device instead of filling HostScene's arrays: one allocation with the records, both trees
+// (prim = rank) and the leaf boxes by rank.  ensure_host_mirror fetches them once, with the image and the object table of that device's
+// DeviceScene, and frees the allocation.
+struct MirrorSource {
+    int device = -1;
+    unsigned char *keep = nullptr;
+    size_t n = 0, nb = 0, nn = 0;
+    size_t records_at = 0, tree_at[3] = {0, 0, 0}, walk_at[3] = {0, 0, 0}, leaf_at = 0; // skip, prim, boxes
+};
 struct rt_scene {
     rth::HostScene host;
     std::map<int, DeviceScene> dev;
     std::mutex mu;
+    std::atomic<bool> mirrored{true}; // false: host.hittables, tree, walkTree, leafBoxes, objToOrig, origToObj and image are still on src.device
+    MirrorSource src;
 };
+static int ensure_host_mirror_locked(rt_scene *s); // (s->mu held)
+static int ensure_host_mirror(const rt_scene *scene) {
+    rt_scene *s = const_cast<rt_scene *>(scene);
+    if (s->mirrored.load(std::memory_order_acquire)) return RT_OK;
+    std::lock_guard<std::mutex> lock(s->mu);
+    return ensure_host_mirror_locked(s);
+}
 
 // Process-wide DEFAULTS of the launch settings (rt_set_*): read once per call, and only for the rt_render_options fields a
 // caller leaves at 0.
@@ -133,6 +153,7 @@ static int device_scene(rt_scene *s, int device, DeviceScene **out) {
     std::lock_guard<std::mutex> lock(s->mu);
     auto it = s->dev.find(device);
     if (it != s->dev.end()) { *out = &it->second; return RT_OK; }
+    RT_TRY(ensure_host_mirror_locked(s)); // (a scene made on another device: its image comes through the host)
     DeviceScene d;
     const rth::HostScene &h = s->host;
     HIP_TRY(hipMalloc((void **) &d.image, h.image.size()));
@@ -401,7 +422,8 @@ void rt_scene_destroy(rt_scene *s) {
         (void) hipFree(kv.second.texels);
         (void) hipFree(kv.second.obj_to_orig);
     }
-    if (prev >= 0 && !s->dev.empty()) (void) hipSetDevice(prev);
+    if (s->src.keep && hipSetDevice(s->src.device) == hipSuccess) (void) hipFree(s->src.keep);
+    if (prev >= 0 && (!s->dev.empty() || s->src.keep)) (void) hipSetDevice(prev);
     delete s;
 }
 
@@ -410,7 +432,7 @@ int rt_scene_get_info(const rt_scene *s, rt_scene_info *out) {
     const rth::HostScene &h = s->host;
     out->n_bounded = h.off.n_bounded;
     out->n_unbounded = h.off.n_unbounded;
-    out->n_nodes = (int32_t) h.tree.skip.size();
+    out->n_nodes = (int32_t) rtt::node_count(h.nBounded); // (= tree.skip.size(), which a scene made on the device fills only with its host mirror)
     out->walk_tree_nodes = h.off.n_nodes;
     out->leaf_box_implied = h.off.box_implied;
     out->tree_depth = h.tree.depth;
@@ -434,16 +456,19 @@ static int copy_tree(const rth::HostScene &h, const rth::FlatTree &t, int32_t *s
 }
 int rt_scene_get_tree(const rt_scene *s, int32_t *skip, int32_t *prim, double *boxes) {
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "NULL scene");
+    RT_TRY(ensure_host_mirror(s));
     return copy_tree(s->host, s->host.tree, skip, prim, boxes);
 }
 int rt_scene_get_walk_tree(const rt_scene *s, int32_t *skip, int32_t *prim, double *boxes) {
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "NULL scene");
+    RT_TRY(ensure_host_mirror(s));
     return copy_tree(s->host, s->host.walkTree, skip, prim, boxes);
 }
 
 int rt_scene_get_filter_tree(const rt_scene *s, float *boxes, int32_t *links) {
     if (!s) return fail(RT_ERR_INVALID_ARGUMENT, "NULL scene");
     if (!boxes || !links) return fail(RT_ERR_INVALID_ARGUMENT, "NULL output");
+    RT_TRY(ensure_host_mirror(s));
     const rth::HostScene &h = s->host;
     const unsigned char *sec = h.image.data() + h.off.node32;
     for (int32_t p = 0; p < h.off.n_nodes; ++p) {
@@ -938,6 +963,7 @@ static int apply_tune(rt_scene *scene, const std::vector<RawRay> &raw, rt_tune_i
     rth::TuneResult tr;
     std::lock_guard<std::mutex> lock(scene->mu);
     rth::HostScene &h = scene->host;
+    if (rth::tune_applies(h, rays.size())) RT_TRY(ensure_host_mirror_locked(scene)); // (tune_walk_tree reads the scene's arrays exactly then)
     // Failure-atomic: the host tree and every device copy change together or not at all.  The new image is uploaded to fresh
     // allocations first; only when every device has its copy are the old ones released and the pointers swapped.  On any failure
     // the host scene is put back as it was and the new allocations are freed, so no launch can pair an old image with new offsets.
@@ -3069,6 +3095,7 @@ int rt_dev_reflection(int32_t device, const rt_scene *scene, int32_t n, const in
         return fail(RT_ERR_INVALID_ARGUMENT, "bad argument");
     return scene_hook("rt_dev_reflection", device, scene, [&](const RenderParams &p) -> int {
         std::vector<int32_t> obj((size_t) n);
+        RT_TRY(ensure_host_mirror(scene));
         for (int i = 0; i < n; ++i) {
             if (index[i] < 0 || (size_t) index[i] >= scene->host.origToObj.size()) return fail(RT_ERR_INVALID_ARGUMENT, "hittable index out of range");
             obj[(size_t) i] = scene->host.origToObj[(size_t) index[i]];
@@ -3085,8 +3112,10 @@ int rt_dev_reflection(int32_t device, const rt_scene *scene, int32_t n, const in
 }
 
 // hittable indices of the scene's object table -> rt_scene_create's
-static void to_orig(const rt_scene *scene, int32_t n, int32_t *hit_index) {
+static int to_orig(const rt_scene *scene, int32_t n, int32_t *hit_index) {
+    RT_TRY(ensure_host_mirror(scene));
     for (int i = 0; i < n; ++i) if (hit_index[i] >= 0) hit_index[i] = scene->host.objToOrig[(size_t) hit_index[i]];
+    return RT_OK;
 }
 
 int rt_dev_hit_object(int32_t device, const rt_scene *scene, int32_t n, const double *rays, int32_t *hit_index, double *strike, uint32_t *counters) {
@@ -3097,8 +3126,7 @@ int rt_dev_hit_object(int32_t device, const rt_scene *scene, int32_t n, const do
         auto dsk = dev_out(strike, strike ? (size_t) n * 3 : 0);
         auto dc = dev_out(counters, counters ? (size_t) n * 2 : 0);
         const int rc = hook_run([&] { launch_n(k_hit_object, n, p, n, dr.p, dh.p, dsk.p, dc.p); }, dr, dh, dsk, dc);
-        if (rc == RT_OK) to_orig(scene, n, hit_index);
-        return rc;
+        return rc == RT_OK ? to_orig(scene, n, hit_index) : rc;
     });
 }
 
@@ -3114,8 +3142,7 @@ int rt_dev_hit_object_lds(int32_t device, const rt_scene *scene, int32_t n, cons
         auto dh = dev_out(hit_index, (size_t) n);
         auto dsk = dev_out(strike, (size_t) n * 3);
         rc = hook_run([&] { if (n) hipLaunchKernelGGL(k_hit_object_lds, dim3((unsigned) ((n + 1023) / 1024)), dim3(1024), ldsBytes, 0, p, n, dr.p, dh.p, dsk.p); }, dr, dh, dsk);
-        if (rc == RT_OK) to_orig(scene, n, hit_index);
-        return rc;
+        return rc == RT_OK ? to_orig(scene, n, hit_index) : rc;
     });
 }
 
@@ -3141,6 +3168,7 @@ static int pixel_candidates(const RenderParams &p, const rt_scene *scene, const 
     // decode: up to four hittable indices per pixel (-1 = none); leaves_out[i*4] = -2 when the pixel's camera rays walk the tree.
     // Below 16384 objects the words hold two 16-bit entries each (RTD_PEND_MARK | object); beyond, one full-width entry each
     // (RTD_PEND_WIDE | object, at most two candidates).
+    RT_TRY(ensure_host_mirror(scene));
     const size_t nObj = scene->host.objToOrig.size();
     for (int i = 0; i < n; ++i) {
         int32_t *o = leaves_out + (size_t) i * 4;
@@ -3196,6 +3224,8 @@ int rt_dev_texture_colour_at(int32_t device, const rt_scene *scene, int32_t text
 // ------------------------------------------------------------------------------------------------------------
 static int create_scene_on_device(const char *entry, const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
                                   const rt_scene_options *options, int32_t device, bool walk_tree_too, rt_scene **out);
+static int scene_from_host_records(const char *entry, const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures, int walk,
+                                   int32_t device, bool walk_tree_too, rt_scene **out);
 static const char *const kNanBox = "a box coordinate is NaN: it has no order; nothing was written";
 
 static int check_tree_host(size_t n, const double *boxes) {
@@ -3508,6 +3538,11 @@ static int create_scene_on_device(const char *entry, const rt_hittable *hittable
     if (walk != RT_WALK_TREE_SAH && walk != RT_WALK_TREE_REFERENCE) return fail(RT_ERR_INVALID_ARGUMENT, "walk_tree must be RT_WALK_TREE_SAH, RT_WALK_TREE_REFERENCE or -1");
     DeviceGuard guard;
     RT_TRY(guard.enter(device));
+    return scene_from_host_records(entry, hittables, n_hittables, textures, n_textures, walk, device, walk_tree_too, out);
+}
+// (the device entered, the arguments checked)
+static int scene_from_host_records(const char *entry, const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures, int walk,
+                                   int32_t device, bool walk_tree_too, rt_scene **out) {
     return guarded(entry, [&]() {
         // either tree through its staged call: the boxes flattened, the arrays back into a FlatTree
         auto via = [&](bool sah, const std::vector<rth::Box> &ob, rth::FlatTree &t, std::string &msg) -> int {
@@ -3534,3 +3569,362 @@ static int create_scene_on_device(const char *entry, const rt_hittable *hittable
         return (int) RT_OK;
     });
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// Scene.make from hittables in device memory (rt_scene_plan.h, rt_scene_kernels.h; DESIGN.md "Scene.make on the device")
+// ------------------------------------------------------------------------------------------------------------
+static_assert(RTS_LEAF == RTD_LEAF && RTS_PEND_MARK == RTD_PEND_MARK && RTS_PEND_WIDE == RTD_PEND_WIDE && RTS_KIND_SPHERE == RTD_KIND_SPHERE &&
+              RTS_KIND_PLANE == RTD_KIND_PLANE && RTS_MAX_BOUNDED == RTT_MAX_BOXES, "rt_scene_plan.h restates rt_device.h");
+static_assert(sizeof(rts::Offsets) >= 11 * 4 && offsetof(rtd::SceneOffsets, bmax) == 11 * 4, "rts::Offsets' first eleven words are SceneOffsets'");
+
+namespace {
+
+// Stream-ordered scratch of one build: every block is freed on the stream by whichever path leaves.
+struct StreamScratch {
+    hipStream_t st = nullptr;
+    std::vector<void *> blocks;
+    ~StreamScratch() { for (void *q : blocks) (void) hipFreeAsync(q, st); }
+    template <class T> int get(T **out, size_t count) {
+        void *q = nullptr;
+        blocks.reserve(blocks.size() + 1);
+        HIP_TRY(hipMallocAsync(&q, count ? count * sizeof(T) : 16, st));
+        blocks.push_back(q);
+        *out = (T *) q;
+        return RT_OK;
+    }
+};
+struct DeviceBlock { // hipMalloc'd memory that belongs to the scene once the build has succeeded
+    unsigned char *p = nullptr;
+    ~DeviceBlock() { if (p) (void) hipFree(p); }
+    unsigned char *release() { unsigned char *q = p; p = nullptr; return q; }
+};
+
+} // namespace
+
+static rtsk::Ctrl fresh_ctrl() {
+    rtsk::Ctrl c{};
+    c.err = ~0ull;
+    const float tiny = 1e-30f;
+    memcpy(&c.bmax_bits, &tiny, sizeof(tiny));
+    return c;
+}
+static unsigned blocks_for(uint64_t count, unsigned per) { return (unsigned) ((count + per - 1u) / per); }
+// a[0 .. m) scanned into out (which may be a); sums: m / RTSK_TILE + 2 words.  sums[tiles] ends as the sum of all.
+static void enqueue_scan(const uint32_t *a, uint32_t m, uint32_t *out, bool inclusive, uint32_t *sums, hipStream_t st) {
+    const unsigned tiles = blocks_for(m, RTSK_TILE);
+    hipLaunchKernelGGL(rtsk::scan_sums_kernel, dim3(tiles), dim3(RTSK_BLOCK), 0, st, a, m, sums);
+    hipLaunchKernelGGL(rtsk::scan_top_kernel, dim3(1), dim3(RTSK_BLOCK), 0, st, sums, tiles);
+    hipLaunchKernelGGL(rtsk::scan_apply_kernel, dim3(tiles), dim3(RTSK_BLOCK), 0, st, a, m, (const uint32_t *) sums, out, inclusive ? 1 : 0);
+}
+
+// Stages 3 and 4 on `st` (the device current): the image of a pre-order skip tree of nn nodes (boxes: nn * 6 doubles in the ABI's form) and of
+// the object table, into `image` (ro.image_bytes).  ctrl is a fresh Ctrl on the device; it ends with bmax, the radii and the largest depth,
+// which the caller reads.  Waits for the stream once, for the largest depth (which says how many passes the order by depth needs).
+static int encode_on_device(uint32_t nn, uint32_t nb, uint32_t nobj, uint64_t n_hittables, const rt_hittable *d_h, const int32_t *d_skip, const int32_t *d_prim,
+                            const double *d_box, const int32_t *d_o2o, const rts::Offsets &ro, unsigned char *image, rtsk::Ctrl *ctrl, hipStream_t st,
+                            StreamScratch &sc, uint32_t digit_bits = 8u) {
+    HIP_TRY(hipMemsetAsync(image, 0, (size_t) ro.image_bytes, st));
+    if (nn > 0u) {
+        const unsigned tiles = blocks_for(nn, RTSK_TILE), per = blocks_for(nn, RTSK_BLOCK);
+        const uint32_t hist_words = (uint32_t) RTSK_RADIX * tiles;
+        uint32_t *key[2], *idx[2], *hist, *sums, *place;
+        RT_TRY(sc.get(&key[0], (size_t) nn + 1u));
+        RT_TRY(sc.get(&key[1], nn));
+        RT_TRY(sc.get(&idx[0], nn));
+        RT_TRY(sc.get(&idx[1], nn));
+        RT_TRY(sc.get(&hist, hist_words));
+        RT_TRY(sc.get(&sums, (size_t) std::max(hist_words, nn) / RTSK_TILE + 2u));
+        RT_TRY(sc.get(&place, (size_t) nn + 1u));
+        HIP_TRY(hipMemsetAsync(key[0], 0, ((size_t) nn + 1u) * 4u, st));
+        hipLaunchKernelGGL(rtsk::scene_diff_kernel, dim3(per), dim3(RTSK_BLOCK), 0, st, nn, d_skip, d_prim, key[0]);
+        enqueue_scan(key[0], nn, key[0], true, sums, st); // the depth of every node
+        uint32_t maxDepth = 0;
+        int cur = 0;
+        const uint32_t mask = (1u << digit_bits) - 1u;
+        for (uint32_t shift = 0; shift < 32u; shift += digit_bits) {
+            if (shift > 0u && (maxDepth >> shift) == 0u) break;
+            hipLaunchKernelGGL(rtsk::sort_hist_kernel, dim3(tiles), dim3(RTSK_BLOCK), 0, st, (const uint32_t *) key[cur], nn, shift, mask, hist, tiles,
+                               shift == 0u ? &ctrl->max_depth : (uint32_t *) nullptr);
+            enqueue_scan(hist, hist_words, hist, false, sums, st);
+            hipLaunchKernelGGL(rtsk::sort_scatter_kernel, dim3(tiles), dim3(RTSK_BLOCK), 0, st, (const uint32_t *) key[cur],
+                               shift == 0u ? (const uint32_t *) nullptr : (const uint32_t *) idx[cur], nn, shift, mask, (const uint32_t *) hist, tiles, key[cur ^ 1], idx[cur ^ 1]);
+            cur ^= 1;
+            if (shift == 0u) {
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(&maxDepth, &ctrl->max_depth, sizeof(maxDepth), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+            }
+        }
+        hipLaunchKernelGGL(rtsk::scene_place_kernel, dim3(blocks_for((uint64_t) nn + 1u, RTSK_BLOCK)), dim3(RTSK_BLOCK), 0, st, nn, (const uint32_t *) idx[cur], place);
+        hipLaunchKernelGGL(rtsk::scene_nodes_kernel, dim3(per), dim3(RTSK_BLOCK), 0, st, nn, (uint64_t) nobj, d_skip, d_prim, d_box, (const uint32_t *) place,
+                           image + ro.node, image + ro.node32, ctrl);
+    }
+    if (nobj > 0u)
+        hipLaunchKernelGGL(rtsk::scene_objects_kernel, dim3(blocks_for(nobj, RTSK_BLOCK)), dim3(RTSK_BLOCK), 0, st, nobj, nb, n_hittables, d_h, d_o2o, image + ro.geo,
+                           image + ro.meta, image + ro.mat, ctrl);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+// SceneOffsets from the plan's offsets and what the encoder's Ctrl ended with
+static rtd::SceneOffsets scene_offsets(const rts::Offsets &ro, const rtsk::Ctrl &c) {
+    rtd::SceneOffsets off{};
+    off.node = ro.node; off.geo = ro.geo; off.meta = ro.meta; off.node32 = ro.node32; off.mat = ro.mat; off.total = ro.total;
+    off.lds_total = ro.lds_total; off.lds32_total = ro.lds32_total;
+    off.n_nodes = ro.n_nodes; off.n_bounded = ro.n_bounded; off.n_unbounded = ro.n_unbounded;
+    memcpy(&off.bmax, &c.bmax_bits, sizeof(float));
+    double rmax = 0.0;
+    memcpy(&rmax, &c.rmax_key, sizeof(double));
+    off.box_implied = rts::box_implied(off.bmax, c.bad_radius == 0u, rmax);
+    return off;
+}
+static int upload(unsigned char **out, const void *src, size_t bytes) {
+    HIP_TRY(hipMalloc((void **) out, bytes));
+    HIP_TRY(hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+static int ensure_host_mirror_locked(rt_scene *s) {
+    if (s->mirrored.load(std::memory_order_acquire)) return RT_OK;
+    return guarded("host mirror of a scene made on the device", [&]() -> int {
+        const MirrorSource &m = s->src;
+        rth::HostScene &h = s->host;
+        DeviceGuard guard;
+        RT_TRY(guard.enter(m.device));
+        const DeviceScene &ds = s->dev.at(m.device);
+        auto down = [&](void *dst, const void *src, size_t bytes) -> int {
+            if (bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+            return RT_OK;
+        };
+        auto tree = [&](const size_t at[3], rth::FlatTree &t) -> int {
+            const int depth = t.depth;
+            std::vector<double> flat(m.nn * 6u);
+            t.skip.resize(m.nn); t.prim.resize(m.nn); t.box.resize(m.nn);
+            RT_TRY(down(t.skip.data(), m.keep + at[0], m.nn * 4u));
+            RT_TRY(down(t.prim.data(), m.keep + at[1], m.nn * 4u));
+            RT_TRY(down(flat.data(), m.keep + at[2], m.nn * 48u));
+            for (size_t i = 0; i < m.nn; ++i)
+                for (int a = 0; a < 3; ++a) { t.box[i].mn[a] = flat[i * 6 + (size_t) a * 2]; t.box[i].mx[a] = flat[i * 6 + (size_t) a * 2 + 1]; }
+            t.depth = depth;
+            return RT_OK;
+        };
+        h.hittables.resize(m.n);
+        RT_TRY(down(h.hittables.data(), m.keep + m.records_at, m.n * sizeof(rt_hittable)));
+        RT_TRY(tree(m.tree_at, h.tree));
+        if (m.walk_at[0] == m.tree_at[0]) { const int depth = h.walkTree.depth; h.walkTree = h.tree; h.walkTree.depth = depth; }
+        else RT_TRY(tree(m.walk_at, h.walkTree));
+        {
+            std::vector<double> flat(m.nb * 6u);
+            RT_TRY(down(flat.data(), m.keep + m.leaf_at, m.nb * 48u));
+            h.leafBoxes.resize(m.nb);
+            for (size_t j = 0; j < m.nb; ++j)
+                for (int a = 0; a < 3; ++a) { h.leafBoxes[j].mn[a] = flat[j * 6 + (size_t) a * 2]; h.leafBoxes[j].mx[a] = flat[j * 6 + (size_t) a * 2 + 1]; }
+        }
+        h.objToOrig.resize(m.n);
+        RT_TRY(down(h.objToOrig.data(), ds.obj_to_orig, m.n * 4u));
+        h.origToObj.assign(m.n, -1);
+        for (size_t j = 0; j < m.n; ++j) h.origToObj[(size_t) h.objToOrig[j]] = (int32_t) j;
+        h.image.resize(h.off.total);
+        RT_TRY(down(h.image.data(), ds.image, h.off.total));
+        (void) hipFree(s->src.keep);
+        s->src.keep = nullptr;
+        s->mirrored.store(true, std::memory_order_release);
+        return RT_OK;
+    });
+}
+
+// rt_scene_create_device behind its argument checks, the device entered
+static int scene_on_device(int32_t device, const rt_hittable *d_h, size_t n, const rt_texture *textures, size_t n_textures, int walk, hipStream_t st, rt_scene **out) {
+    return guarded("rt_scene_create_device", [&]() -> int {
+        std::unique_ptr<rt_scene> s(new rt_scene());
+        rth::HostScene &h = s->host;
+        {
+            int status = RT_OK;
+            const std::string msg = rth::build_textures(textures, n_textures, h, status);
+            if (status != RT_OK) return fail(status, msg);
+        }
+        StreamScratch sc;
+        sc.st = st;
+        rtsk::Ctrl *ctrl = nullptr, c = fresh_ctrl();
+        RT_TRY(sc.get(&ctrl, 1));
+        HIP_TRY(hipMemcpyAsync(ctrl, &c, sizeof(c), hipMemcpyHostToDevice, st));
+        // ---- stage 1: check, classify, partition, boxes ----
+        const bool countable = n <= (size_t) RTS_MAX_OBJECTS;
+        uint32_t *flag = nullptr, *pos = nullptr, *sums = nullptr;
+        uint32_t nb32 = 0;
+        if (n > 0) {
+            if (countable) {
+                RT_TRY(sc.get(&flag, n));
+                RT_TRY(sc.get(&pos, n));
+                RT_TRY(sc.get(&sums, n / RTSK_TILE + 2u));
+            }
+            hipLaunchKernelGGL(rtsk::scene_check_kernel, dim3(blocks_for(std::min(n, (size_t) RTS_MAX_OBJECTS), RTSK_BLOCK)), dim3(RTSK_BLOCK), 0, st, d_h, (uint64_t) n, (int64_t) n_textures, ctrl, flag);
+            if (countable) {
+                enqueue_scan(flag, (uint32_t) n, pos, false, sums, st);
+                HIP_TRY(hipMemcpyAsync(&nb32, sums + blocks_for(n, RTSK_TILE), sizeof(nb32), hipMemcpyDeviceToHost, st));
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(&c, ctrl, sizeof(c), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (c.err != ~0ull) return fail(RT_ERR_INVALID_ARGUMENT, "hittable " + std::to_string(c.err / 8u) + ": " + rts::reason_text((int) (c.err % 8u)));
+        const size_t nb = nb32, nu = n - nb, nobj = n;
+        if (!countable || rts::too_large(nb, nobj)) return fail(RT_ERR_UNSUPPORTED, rts::too_large_text());
+        DeviceBlock o2o, image, keep, tex, texels;
+        int32_t *bounded = nullptr;
+        double *boxes = nullptr;
+        if (n > 0) {
+            HIP_TRY(hipMalloc((void **) &o2o.p, n * sizeof(int32_t)));
+            RT_TRY(sc.get(&bounded, nb));
+            RT_TRY(sc.get(&boxes, nb * 6u));
+            hipLaunchKernelGGL(rtsk::scene_partition_kernel, dim3(blocks_for(n, RTSK_BLOCK)), dim3(RTSK_BLOCK), 0, st, d_h, (uint32_t) n, (const uint32_t *) flag,
+                               (const uint32_t *) pos, (const uint32_t *) (sums + blocks_for(n, RTSK_TILE)), ctrl, bounded, boxes, (int32_t *) o2o.p);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&c, ctrl, sizeof(c), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        if (n == 0 || c.nan_box) {
+            // The host's ground: nothing at all, or a NaN coordinate, which has no order.  The records come down and the scene is
+            // rt_scene_create_gpu_trees' (slow for many records, but the same scene).
+            std::vector<rt_hittable> rec(n);
+            if (n) HIP_TRY(hipMemcpy(rec.data(), d_h, n * sizeof(rt_hittable), hipMemcpyDeviceToHost));
+            return scene_from_host_records("rt_scene_create_device", rec.data(), n, textures, n_textures, walk, device, true, out);
+        }
+        // ---- both trees, from and into device memory; the ranks between them ----
+        const size_t nn = (size_t) rtt::node_count(nb);
+        const int walkKind = (walk == RT_WALK_TREE_REFERENCE || c.non_finite || nb < 3u) ? RT_WALK_TREE_REFERENCE : RT_WALK_TREE_SAH; // (build_scene's rule)
+        MirrorSource src;
+        src.device = device; src.n = n; src.nb = nb; src.nn = nn;
+        {
+            auto up = [](size_t v) { return (v + 15u) & ~(size_t) 15u; };
+            size_t at = 0;
+            src.records_at = at; at += up(n * sizeof(rt_hittable));
+            for (int k = 0; k < 3; ++k) { src.tree_at[k] = at; at += up(nn * (k == 2 ? 48u : 4u)); }
+            for (int k = 0; k < 3; ++k) {
+                if (walkKind == RT_WALK_TREE_SAH) { src.walk_at[k] = at; at += up(nn * (k == 2 ? 48u : 4u)); }
+                else src.walk_at[k] = src.tree_at[k];
+            }
+            src.leaf_at = at; at += up(nb * 48u);
+            HIP_TRY(hipMalloc((void **) &keep.p, at));
+        }
+        HIP_TRY(hipMemcpyAsync(keep.p + src.records_at, d_h, n * sizeof(rt_hittable), hipMemcpyDeviceToDevice, st));
+        int32_t *tskip = (int32_t *) (keep.p + src.tree_at[0]), *tprim = (int32_t *) (keep.p + src.tree_at[1]);
+        int32_t *wskip = (int32_t *) (keep.p + src.walk_at[0]), *wprim = (int32_t *) (keep.p + src.walk_at[1]);
+        double *tbox = (double *) (keep.p + src.tree_at[2]), *wbox = (double *) (keep.p + src.walk_at[2]), *leaf = (double *) (keep.p + src.leaf_at);
+        int32_t *order = nullptr, *rankOf = nullptr;
+        RT_TRY(sc.get(&order, nb));
+        RT_TRY(sc.get(&rankOf, nb));
+        if (nb >= 3u) {
+            FormatPending fp;
+            RT_TRY(enqueue_tree(nb, boxes, tskip, tprim, tbox, order, st, fp));
+        } else if (nb > 0u) // fewer than 3 spheres: the tree is trivial and is written directly
+            hipLaunchKernelGGL(rtsk::scene_small_tree_kernel, dim3(1), dim3(64), 0, st, (uint32_t) nb, (const double *) boxes, tskip, tprim, tbox, order);
+        if (nb > 0u) hipLaunchKernelGGL(rtsk::scene_rank_kernel, dim3(blocks_for(nb, RTSK_BLOCK)), dim3(RTSK_BLOCK), 0, st, (uint32_t) nb, (const int32_t *) order, (const int32_t *) bounded,
+                           (const double *) boxes, (int32_t *) o2o.p, rankOf, leaf);
+        if (nb > 0u) hipLaunchKernelGGL(rtsk::scene_prim_kernel, dim3(blocks_for(nn, RTSK_BLOCK)), dim3(RTSK_BLOCK), 0, st, (uint32_t) nn, tprim, (const int32_t *) rankOf);
+        HIP_TRY(hipGetLastError());
+        if (walkKind == RT_WALK_TREE_SAH) RT_TRY(build_walk_tree(nb, leaf, wskip, wprim, wbox, st));
+        // ---- the image ----
+        const rts::Offsets ro = rts::offsets(nn, nb, nu);
+        HIP_TRY(hipMalloc((void **) &image.p, (size_t) ro.image_bytes));
+        RT_TRY(encode_on_device((uint32_t) nn, (uint32_t) nb, (uint32_t) nobj, n, d_h, wskip, wprim, wbox, (const int32_t *) o2o.p, ro, image.p, ctrl, st, sc));
+        HIP_TRY(hipMemcpyAsync(&c, ctrl, sizeof(c), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        // ---- what the host keeps: O(1) and the textures ----
+        h.off = scene_offsets(ro, c);
+        h.nBounded = nb; h.nUnbounded = nu;
+        h.walkKind = walkKind;
+        h.tree.depth = rtt::depth(nb);
+        h.walkTree.depth = walkKind == RT_WALK_TREE_SAH ? (int) c.max_depth + 1 : h.tree.depth;
+        DeviceScene d;
+        if (!h.texRecs.empty()) RT_TRY(upload(&tex.p, h.texRecs.data(), h.texRecs.size() * sizeof(TexRec)));
+        if (!h.texelBlob.empty()) RT_TRY(upload(&texels.p, h.texelBlob.data(), h.texelBlob.size()));
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, device));
+        d.cu_count = prop.multiProcessorCount;
+        d.image = image.p; d.tex = (TexRec *) tex.p; d.texels = texels.p; d.obj_to_orig = (int32_t *) o2o.p;
+        s->dev.emplace(device, d);
+        (void) image.release(); (void) tex.release(); (void) texels.release(); (void) o2o.release();
+        src.keep = keep.release();
+        s->src = src;
+        s->mirrored.store(false, std::memory_order_release);
+        *out = s.release();
+        return (int) RT_OK;
+    });
+}
+
+extern "C" {
+
+int rt_scene_create_device(int32_t device, const void *d_hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                           const rt_scene_options *options, void *stream, rt_scene **out) {
+    if (n_hittables > 0 && !d_hittables) return fail(RT_ERR_INVALID_ARGUMENT, "d_hittables is NULL");
+    if (n_textures > 0 && !textures) return fail(RT_ERR_INVALID_ARGUMENT, "textures is NULL");
+    if ((uintptr_t) d_hittables % 8u) return fail(RT_ERR_INVALID_ARGUMENT, "d_hittables is not 8-byte aligned");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    int walk = -1;
+    if (options && options->struct_size >= offsetof(rt_scene_options, walk_tree) + sizeof(int32_t)) walk = options->walk_tree;
+    if (walk == -1) walk = g_walk_tree.load();
+    if (walk != RT_WALK_TREE_SAH && walk != RT_WALK_TREE_REFERENCE) return fail(RT_ERR_INVALID_ARGUMENT, "walk_tree must be RT_WALK_TREE_SAH, RT_WALK_TREE_REFERENCE or -1");
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    return scene_on_device(device, (const rt_hittable *) d_hittables, n_hittables, textures, n_textures, walk, (hipStream_t) stream, out);
+}
+
+int rt_dev_scene_has_host_mirror(const rt_scene *scene) { return scene && scene->mirrored.load(std::memory_order_acquire) ? 1 : 0; }
+
+int rt_dev_scene_image(const rt_scene *scene, int32_t device, void *out, size_t cap, size_t *bytes, uint32_t offsets[16]) {
+    if (!scene || !bytes) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded("rt_dev_scene_image", [&]() -> int {
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        DeviceScene *ds = nullptr;
+        RT_TRY(device_scene(const_cast<rt_scene *>(scene), device, &ds));
+        const rtd::SceneOffsets off = scene->host.off;
+        *bytes = off.total;
+        if (offsets) { memset(offsets, 0, 16 * sizeof(uint32_t)); memcpy(offsets, &off, sizeof(off)); }
+        if (!out) return RT_OK;
+        if (cap < off.total) return fail(RT_ERR_INVALID_ARGUMENT, "out is smaller than the image");
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(out, ds->image, off.total, hipMemcpyDeviceToHost));
+        return RT_OK;
+    });
+}
+static_assert(sizeof(rtd::SceneOffsets) <= 16 * sizeof(uint32_t), "rt_dev_scene_image's offsets");
+
+int rt_dev_encode_image(int32_t device, const rt_scene *host_made, void *out, size_t cap, size_t *bytes) {
+    return rt_dev_encode_image_radix(device, host_made, 8, out, cap, bytes);
+}
+int rt_dev_encode_image_radix(int32_t device, const rt_scene *host_made, int32_t digit_bits, void *out, size_t cap, size_t *bytes) {
+    if (!host_made || !bytes) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (digit_bits < 1 || digit_bits > 8) return fail(RT_ERR_INVALID_ARGUMENT, "digit_bits must be 1 .. 8");
+    return guarded("rt_dev_encode_image", [&]() -> int {
+        RT_TRY(ensure_host_mirror(host_made));
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        std::lock_guard<std::mutex> lock(const_cast<rt_scene *>(host_made)->mu); // (rt_scene_tune* changes the walk tree under it)
+        const rth::HostScene &h = host_made->host;
+        const rth::FlatTree &wt = h.walkTree;
+        const size_t nn = wt.skip.size(), nb = h.nBounded, nu = h.nUnbounded, nobj = nb + nu, n = h.hittables.size();
+        const rts::Offsets ro = rts::offsets(nn, nb, nu);
+        *bytes = ro.total;
+        if (!out) return RT_OK;
+        if (cap < ro.total) return fail(RT_ERR_INVALID_ARGUMENT, "out is smaller than the image");
+        std::vector<double> flat(nn * 6u);
+        for (size_t i = 0; i < nn; ++i)
+            for (int a = 0; a < 3; ++a) { flat[i * 6 + (size_t) a * 2] = wt.box[i].mn[a]; flat[i * 6 + (size_t) a * 2 + 1] = wt.box[i].mx[a]; }
+        const rtsk::Ctrl c = fresh_ctrl();
+        std::vector<unsigned char> img((size_t) ro.image_bytes);
+        Staging sg;
+        RT_TRY(sg.in({{h.hittables.data(), n * sizeof(rt_hittable), SEG_IN}, {wt.skip.data(), nn * 4u, SEG_IN}, {wt.prim.data(), nn * 4u, SEG_IN},
+                      {flat.data(), nn * 48u, SEG_IN}, {h.objToOrig.data(), nobj * 4u, SEG_IN}, {&c, sizeof(c), SEG_IN}, {img.data(), img.size(), SEG_OUT}}));
+        StreamScratch sc;
+        RT_TRY(encode_on_device((uint32_t) nn, (uint32_t) nb, (uint32_t) nobj, n, (const rt_hittable *) sg.dev[0], (const int32_t *) sg.dev[1], (const int32_t *) sg.dev[2],
+                                (const double *) sg.dev[3], (const int32_t *) sg.dev[4], ro, (unsigned char *) sg.dev[6], (rtsk::Ctrl *) sg.dev[5], nullptr, sc,
+                                (uint32_t) digit_bits));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        RT_TRY(sg.out());
+        memcpy(out, img.data(), ro.total);
+        return RT_OK;
+    });
+}
+
+} // extern "C"

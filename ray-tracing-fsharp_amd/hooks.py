@@ -174,3 +174,26 @@ def last_launch_plan():
                                  # (camera hits, kind 5: sample_first)
     inp["map"] = w[at + 1]       # word 78: 1 = an extension by map (first_sample is then 12, spp the cap, B_mode 9 or 10)
     return {"in": inp, "out": out}
+
+
+def scene_image(scene: Scene, device=0):
+    """rt_dev_scene_image: (the image bytes as `device` holds them, the 16 offset words: SceneOffsets' thirteen, then zeros)."""
+    size, offsets = C.c_size_t(0), np.zeros(16, np.uint32)
+    check(lib.rt_dev_scene_image(scene.handle, device, None, 0, C.byref(size), _u32(offsets)))
+    out = np.zeros(size.value, np.uint8)
+    check(lib.rt_dev_scene_image(scene.handle, device, out.ctypes.data, out.size, C.byref(size), _u32(offsets)))
+    return out, offsets
+
+
+def encode_image(scene: Scene, device=0, digit_bits=8):
+    """rt_dev_encode_image(_radix): the device encoder alone on the scene's own walk tree, object table and hittables -> the image bytes.
+    digit_bits: the width of a pass of the order by depth (8 in the product)."""
+    size = C.c_size_t(0)
+    check(lib.rt_dev_encode_image_radix(device, scene.handle, digit_bits, None, 0, C.byref(size)))
+    out = np.zeros(size.value, np.uint8)
+    check(lib.rt_dev_encode_image_radix(device, scene.handle, digit_bits, out.ctypes.data, out.size, C.byref(size)))
+    return out
+
+
+def scene_has_host_mirror(scene: Scene) -> bool:
+    return bool(lib.rt_dev_scene_has_host_mirror(scene.handle))

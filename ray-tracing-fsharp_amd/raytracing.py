@@ -360,6 +360,34 @@ def flatten_hittables(objects: Sequence[Hittable]):
     return hs, len(objects), tex_arr, len(texs), keep
 
 
+# rt_hittable as a numpy structured dtype: what Scene.make_device takes (a numpy array of it, or its bytes as a uint8 tensor [n, itemsize]
+# on a GPU).  Held to the library as compiled, like the ctypes mirrors in _lib.py.
+HITTABLE_DTYPE = np.dtype([("kind", "<u4"), ("style", "<u4"), ("point", "<f8", (3,)), ("normal", "<f8", (3,)), ("radius", "<f8"), ("albedo", "<f8"),
+                           ("fuzz", "<f8"), ("ior", "<f8"), ("prob", "<f8"), ("rgb", "u1", (3,)), ("reserved", "u1"), ("texture", "<i4")], align=True)
+if lib.rt_abi_sizeof(0) != HITTABLE_DTYPE.itemsize:
+    raise ImportError(f"ABI mismatch for HITTABLE_DTYPE: library {lib.rt_abi_sizeof(0)} vs numpy {HITTABLE_DTYPE.itemsize}")
+for _k, _name in enumerate(HITTABLE_DTYPE.names):
+    if lib.rt_abi_offsetof(0, _k) != HITTABLE_DTYPE.fields[_name][1]:
+        raise ImportError(f"ABI mismatch for HITTABLE_DTYPE.{_name}: library offset {lib.rt_abi_offsetof(0, _k)} vs numpy {HITTABLE_DTYPE.fields[_name][1]}")
+if lib.rt_abi_offsetof(0, len(HITTABLE_DTYPE.names)) != C.c_size_t(-1).value:
+    raise ImportError("ABI mismatch for HITTABLE_DTYPE: the library has more fields than the numpy dtype")
+
+
+class TextureTable(NamedTuple):
+    """The rt_texture records of a list of hittables (hittable_records(..., textures=True)), for Scene.make_device(textures=...)."""
+    records: object  # a ctypes array of rt_texture
+    count: int
+    keep: list       # the texel arrays the records point into
+
+
+def hittable_records(objects: Sequence[Hittable], textures: bool = False):
+    """The rt_hittable array Scene.make builds from `objects`, as a numpy array of HITTABLE_DTYPE (a copy).  textures=True: (records, the
+    TextureTable their texture indices refer to)."""
+    hs, n, tex, ntex, keep = flatten_hittables(objects)
+    rec = np.frombuffer(hs, dtype=HITTABLE_DTYPE, count=n).copy()
+    return (rec, TextureTable(tex, ntex, keep)) if textures else rec
+
+
 # ---- Domain.fs ----------------------------------------------------------------------------------------------------
 class Image:  # Domain.fs:9-31: rows are produced lazily, on first use
     def __init__(self, rowCount: int, colCount: int, force: Callable[[], np.ndarray]):
@@ -469,6 +497,43 @@ class Scene:
             check(lib.rt_scene_create(hs, n, tex, ntex, C.byref(out)))
         else:
             check(lib.rt_scene_create_ex(hs, n, tex, ntex, C.byref(opt), C.byref(out)))
+        return Scene(out.value, keep)
+
+    @staticmethod
+    def make_device(records, textures=(), walk_tree: Optional[str] = None, device: Optional[int] = None, stream: Optional[int] = None) -> "Scene":
+        """Scene.make from rt_hittable records that live in device memory (rt_scene_create_device): partition, boxes, both trees, ranks and
+        the device image are computed on the GPU; the host never passes over the objects.  records: a torch uint8 tensor
+        [n, HITTABLE_DTYPE.itemsize] on a GPU, used in place on its device and torch's current stream there (or `stream`, a HIP stream
+        handle); or a numpy array of HITTABLE_DTYPE, which is staged onto `device` (0 by default) first.  textures: a TextureTable
+        (hittable_records(objects, textures=True)) or nothing.  A Scene holds no Python list of its objects on any route (only the texel
+        arrays its texture records point into), so nothing else changes for a scene made this way."""
+        opt = None if walk_tree is None else A.rt_scene_options({"sah": A.RT_WALK_TREE_SAH, "reference": A.RT_WALK_TREE_REFERENCE}[walk_tree])
+        if isinstance(textures, TextureTable):
+            tex, ntex, keep = textures.records, textures.count, list(textures.keep)
+        elif len(textures) == 0:
+            tex, ntex, keep = None, 0, []
+        else:
+            raise TypeError(f"textures must be a TextureTable (hittable_records(objects, textures=True)), not {type(textures).__name__}")
+        size = HITTABLE_DTYPE.itemsize
+        if _is_torch(records):
+            t = _tensor_arg(records, "records", ("u8",), size)
+            route = _Tensors(t.device, device)
+        else:
+            if not isinstance(records, np.ndarray):
+                raise TypeError(f"records must be a numpy array or a torch tensor on a GPU, not {type(records).__name__}")
+            if records.dtype != HITTABLE_DTYPE:
+                raise TypeError(f"records must have dtype HITTABLE_DTYPE, not {records.dtype}")
+            if records.ndim != 1:
+                raise ValueError(f"records must have shape [n], not {list(records.shape)}")
+            torch = _torch()
+            where = torch.device("cuda", _Arrays(device).device)
+            # (the staged tensor lives until this function returns: rt_scene_create_device copies the records into the scene's own
+            # memory and returns only after the stream has finished the build, so nothing reads it afterwards)
+            t = torch.from_numpy(np.ascontiguousarray(records).view(np.uint8).reshape(-1, size)).to(where)
+            route = _Tensors(where)
+        st = _torch().cuda.current_stream(route.where).cuda_stream if stream is None else int(stream)
+        out = C.c_void_p()
+        check(lib.rt_scene_create_device(route.device, route.ptr(t) if t.shape[0] else None, t.shape[0], tex, ntex, _ref(opt), st, C.byref(out)))
         return Scene(out.value, keep)
 
     @property
