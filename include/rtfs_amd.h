@@ -1063,6 +1063,58 @@ int rt_dev_encode_image_radix(int32_t device, const rt_scene *host_made, int32_t
 /* 1 when the host holds its copy of the scene's arrays (always, for a scene made on the host), 0 while they are still on the device. */
 int rt_dev_scene_has_host_mirror(const rt_scene *scene);
 
+/* ---- LoadImage.fromResource (RayTracing.App/LoadImage.fs:9-18): a baseline JPEG to the bitmap ParameterisedTexture.ofImage takes ----
+ * The reference hands the file to SKBitmap.Decode, which is libjpeg-turbo; its decode of a baseline file is integer arithmetic
+ * throughout (Huffman, jpeg_idct_islow, "fancy" upsampling, the fixed-point YCbCr tables), and csrc/rt_jpeg.h restates it bit for bit.
+ * The bitmap: `height` rows, top first, of `width` pixels as R, G, B bytes -- rt_texture.texels' layout.  EXIF orientation is ignored.
+ *
+ * Accepted: SOF0, 8-bit samples, 1 component or 3 (YCbCr) in ONE interleaved scan, 8-bit quantisation tables, sampling 4:4:4, 4:2:2
+ * (2x1) and 4:2:0 (2x2), with or without restart markers.  RT_ERR_UNSUPPORTED: progressive and every other SOFn, arithmetic coding,
+ * 12-bit samples, 4 components, multiple scans, other sampling factors, 16-bit quantisers, a 3-component file whose Adobe marker names
+ * a transform other than 1, more than 2^28 entropy-coded bytes (2^31 - 1 with the restart markers).  RT_ERR_INVALID_ARGUMENT, with rt_last_error() naming what and where:
+ * NULL arguments, no SOI, a segment that runs past the end, a table or component referenced before it is defined, a zero dimension,
+ * more than INT32_MAX pixels, a capacity below width * height * 3; and for the entropy-coded data: a code that is not in its table, a
+ * coefficient index past 63, or a number of blocks -- in front of any restart marker, or in all -- other than the frame and the restart
+ * interval call for (a stream that ends early is one), or restart markers that do not number one between every two intervals.  No byte at or behind data + n is read, and on any error nothing is written.
+ *
+ * Added symbols and two added structs only -- no existing struct, field or symbol changed, so RT_ABI_VERSION stays 7. */
+#define RT_JPEG_GREY 0
+#define RT_JPEG_444 1
+#define RT_JPEG_422 2
+#define RT_JPEG_420 3
+typedef struct rt_jpeg_info {
+    uint32_t struct_size;     /* sizeof(rt_jpeg_info), set by the caller */
+    int32_t width, height;
+    int32_t components;       /* 1 or 3 */
+    int32_t sampling;         /* RT_JPEG_GREY .. RT_JPEG_420 */
+    int32_t restart_interval; /* MCUs; 0: none */
+    int64_t entropy_bytes;    /* the scan's entropy-coded bytes as they are in the file (stuffing and restart markers included) */
+} rt_jpeg_info;
+typedef struct rt_jpeg_stats {
+    uint32_t struct_size;       /* sizeof(rt_jpeg_stats), set by the caller */
+    int32_t subsequence_bytes;  /* clean-stream bytes per thread of the synchronising rounds */
+    int64_t subsequences, rounds, decodes, blocks, boundaries;
+    double total_ms;            /* wall time of the call */
+} rt_jpeg_stats;
+/* The header alone (the scan's entropy-coded bytes are measured, not decoded).  Works without a GPU. */
+int rt_jpeg_get_info(const uint8_t *data, size_t n, rt_jpeg_info *out);
+/* The decode on the host, sequentially.  Works without a GPU and with no device visible. */
+int rt_decode_jpeg(const uint8_t *data, size_t n, uint8_t *rgb, size_t capacity);
+/* The decode on `device` into d_rgb (device memory of `capacity` bytes, any alignment); `data` is HOST memory, where files come from.
+ * The header is parsed on the host -- its refusals come before any device call -- and the tables and the entropy-coded bytes go up;
+ * the rest is kernels on `stream` (csrc/rt_jpeg_kernels.h): the byte stream is cleaned, decoded in subsequences from guessed states
+ * that are synchronised in rounds (the host reads one word per round between batches of launches; no workgroup waits for another),
+ * placed, and turned into samples and colours.  Scratch is stream-ordered; any number of decodes may be in flight.  Errors of the
+ * entropy-coded data are found on the device, in front of the one kernel that writes d_rgb: nothing of d_rgb is written.  With
+ * stats == NULL the call returns RT_OK after its last launch with nothing promised about such a file; with stats it synchronises and
+ * returns what rt_decode_jpeg returns for the same bytes, text included.  RT_ERR_NO_DEVICE without a GPU (not rt_decode_jpeg). */
+int rt_decode_jpeg_device(int32_t device, const uint8_t *data, size_t n, void *d_rgb, size_t capacity, void *stream, rt_jpeg_stats *stats);
+/* Test hooks.  rt_decode_jpeg_device on the null stream with subsequences of subsequence_bytes (at least 4: a symbol is at most 31 bits,
+ * so every 32-bit run holds a symbol start; 0: the default); it synchronises and returns the status.  The plan of this thread's last
+ * device decode: subsequence bytes, subsequences, rounds, subsequence decodes run, blocks, boundaries, 0, 0. */
+int rt_dev_decode_jpeg(int32_t device, const uint8_t *data, size_t n, int32_t subsequence_bytes, void *d_rgb, size_t capacity);
+int rt_dev_last_jpeg_plan(int64_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,23 @@ class rt_path_outputs(C.Structure):
         super().__init__(struct_size=C.sizeof(rt_path_outputs), **kw)
 
 
+class rt_jpeg_info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
+                ("restart_interval", C.c_int32), ("entropy_bytes", C.c_int64)]
+
+    def __init__(self):
+        super().__init__(struct_size=C.sizeof(rt_jpeg_info))
+
+
+class rt_jpeg_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("subsequence_bytes", C.c_int32), ("subsequences", C.c_int64), ("rounds", C.c_int64),
+                ("decodes", C.c_int64), ("blocks", C.c_int64), ("boundaries", C.c_int64), ("total_ms", C.c_double)]
+
+    def __init__(self):
+        super().__init__(struct_size=C.sizeof(rt_jpeg_stats))
+
+
+RT_JPEG_GREY, RT_JPEG_444, RT_JPEG_422, RT_JPEG_420 = 0, 1, 2, 3
 RT_PATH_MISS, RT_PATH_STOPPED, RT_PATH_BOUNCE_LIMIT, RT_PATH_NO_RAY = 0, 1, 2, 3  # enum rt_path_end
 RT_PATH_SUMMARY_WORDS = 16
 

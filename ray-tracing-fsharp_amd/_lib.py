@@ -195,6 +195,11 @@ SIGNATURES = {
     "rt_dev_encode_image": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "rt_dev_encode_image_radix": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "rt_dev_scene_has_host_mirror": (C.c_int, [C.c_void_p]),
+    "rt_jpeg_get_info": (C.c_int, [C.c_char_p, C.c_size_t, _P(A.rt_jpeg_info)]),
+    "rt_decode_jpeg": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "rt_decode_jpeg_device": (C.c_int, [C.c_int32, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, _P(A.rt_jpeg_stats)]),
+    "rt_dev_decode_jpeg": (C.c_int, [C.c_int32, C.c_char_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_size_t]),
+    "rt_dev_last_jpeg_plan": (C.c_int, [_P(C.c_int64)]),  # out[8]
     "rt_dev_float_producer": (C.c_int, [C.c_int32, _u32p, C.c_int32, _dp]),
     "rt_dev_stream_state": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32, _u64p, _u32p, _u32p]),
     "rt_dev_bbox_hits": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _i32p]),

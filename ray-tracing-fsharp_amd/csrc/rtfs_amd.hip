@@ -3,6 +3,7 @@
 // There is NO CPU fallback: every compute entry point returns RT_ERR_NO_DEVICE when no HIP device is visible.
 #include "../../include/rtfs_amd.h"
 #include "rt_device.h"
+#include "rt_jpeg_kernels.h"
 #include "rt_launch_plan.h"
 #include "rt_output.h"
 #include "rt_paths_kernels.h"
@@ -301,6 +302,8 @@ size_t rt_abi_sizeof(int which) {
     case 6: return sizeof(rt_scene_options);
     case 7: return sizeof(rt_tune_info);
     case 9: return sizeof(rt_path_outputs); // (8 stays unused: bindings probe it as "no such struct")
+    case 10: return sizeof(rt_jpeg_info);
+    case 11: return sizeof(rt_jpeg_stats);
     default: return 0;
     }
 }
@@ -3925,6 +3928,180 @@ int rt_dev_encode_image_radix(int32_t device, const rt_scene *host_made, int32_t
         memcpy(out, img.data(), ro.total);
         return RT_OK;
     });
+}
+
+} // extern "C"
+
+// ============================================================================================================
+// LoadImage.fromResource: baseline JPEG (rt_jpeg.h; the kernels: rt_jpeg_kernels.h)
+// ============================================================================================================
+static_assert(rtj::INVALID == RT_ERR_INVALID_ARGUMENT && rtj::UNSUPPORTED == RT_ERR_UNSUPPORTED && rtj::OK == RT_OK, "rt_jpeg.h restates the status codes");
+static_assert(rtj::GREY == RT_JPEG_GREY && rtj::S444 == RT_JPEG_444 && rtj::S422 == RT_JPEG_422 && rtj::S420 == RT_JPEG_420, "rt_jpeg.h restates the sampling classes");
+static thread_local int64_t g_last_jpeg_plan[8] = {0};
+
+static int check_jpeg(const uint8_t *data, size_t n, const void *out) {
+    if (!data) return fail(RT_ERR_INVALID_ARGUMENT, "data is NULL");
+    if (n == 0) return fail(RT_ERR_INVALID_ARGUMENT, "jpeg: no SOI marker at byte 0");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "the output is NULL");
+    return RT_OK;
+}
+static int parse_jpeg(const uint8_t *data, size_t n, rtj::Parsed &ps) {
+    std::string err;
+    const int rc = rtj::parse(data, n, ps, err);
+    return rc == RT_OK ? RT_OK : fail(rc, err);
+}
+
+// The decode of `ps` on `st` (the device current) into d_rgb, in subsequences of S bytes.  plan: rt_dev_last_jpeg_plan's words.  With
+// `wait` it synchronises and reports what the device found in the entropy-coded data.
+static int jpeg_on_device(const uint8_t *data, const rtj::Parsed &ps, uint32_t S, uint8_t *d_rgb, hipStream_t st, bool wait, int64_t plan[8]) {
+    const rtj::Frame &f = ps.f;
+    const uint32_t n_raw = (uint32_t) ps.ecs_raw, n_clean = ps.n_clean, nb = ps.n_rst, nbits = n_clean * 8u, ns = (n_clean + S - 1u) / S;
+    plan[0] = S; plan[1] = ns; plan[2] = plan[3] = plan[4] = 0; plan[5] = nb; plan[6] = plan[7] = 0;
+    if (ns == 0u) return wait ? fail(RT_ERR_INVALID_ARGUMENT, rtj::stream_error(rtj::BAD_COUNT)) : RT_OK; // no entropy-coded byte: nothing to launch
+    StreamScratch sc;
+    sc.st = st;
+    uint8_t *raw, *clean, *planes;
+    uint32_t *keep, *rst, *sums, *bounds, *count, *first, *dcarr, *head_words;
+    rtj::Tables *tables;
+    rtj::State *start, *end[2];
+    int16_t *coefs;
+    const uint32_t scan_most = std::max(std::max(n_raw, ns), f.total);
+    RT_TRY(sc.get(&raw, n_raw));
+    RT_TRY(sc.get(&clean, (size_t) n_clean + 8u));
+    RT_TRY(sc.get(&keep, n_raw));
+    RT_TRY(sc.get(&rst, n_raw));
+    RT_TRY(sc.get(&sums, (size_t) scan_most / RTSK_TILE + 2u));
+    RT_TRY(sc.get(&bounds, (size_t) nb + 1u));
+    RT_TRY(sc.get(&tables, 1));
+    RT_TRY(sc.get(&start, ns));
+    RT_TRY(sc.get(&end[0], ns));
+    RT_TRY(sc.get(&end[1], ns));
+    RT_TRY(sc.get(&count, ns));
+    RT_TRY(sc.get(&first, ns));
+    RT_TRY(sc.get(&head_words, sizeof(rtjk::Head) / 4u + (size_t) ns));
+    RT_TRY(sc.get(&coefs, (size_t) f.total * 64u));
+    RT_TRY(sc.get(&dcarr, f.total));
+    RT_TRY(sc.get(&planes, (size_t) f.plane_bytes));
+    rtjk::Head *head = (rtjk::Head *) head_words;
+    uint32_t *ran = head_words + sizeof(rtjk::Head) / 4u;
+    HIP_TRY(hipMemcpyAsync(raw, data + ps.ecs_at, n_raw, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(tables, &ps.t, sizeof(rtj::Tables), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(head_words, 0, sizeof(rtjk::Head) + (size_t) ns * 4u, st));
+    HIP_TRY(hipMemsetAsync(coefs, 0, (size_t) f.total * 128u, st));
+    // (a) clean
+    hipLaunchKernelGGL(rtjk::clean_flags_kernel, dim3(blocks_for(n_raw, RTJK_BLOCK)), dim3(RTJK_BLOCK), 0, st, (const uint8_t *) raw, n_raw, keep, rst);
+    enqueue_scan(keep, n_raw, keep, false, sums, st);
+    enqueue_scan(rst, n_raw, rst, false, sums, st);
+    hipLaunchKernelGGL(rtjk::clean_scatter_kernel, dim3(blocks_for(n_raw, RTJK_BLOCK)), dim3(RTJK_BLOCK), 0, st, (const uint8_t *) raw, n_raw, (const uint32_t *) keep,
+                       (const uint32_t *) rst, clean, n_clean, bounds, nb);
+    HIP_TRY(hipGetLastError());
+    // (b) synchronise: after round r the first r + 1 subsequences are true, so round ns - 1 is the last one there can be
+    const unsigned sync_grid = blocks_for(ns, RTJK_SYNC_BLOCK);
+    uint32_t rounds = 0;
+    uint64_t decodes = 0;
+    for (uint32_t r0 = 0; r0 < ns;) {
+        const uint32_t batch = std::min<uint32_t>(RTJK_ROUND_BATCH, ns - r0);
+        for (uint32_t r = r0; r < r0 + batch; ++r)
+            hipLaunchKernelGGL(rtjk::sync_kernel, dim3(sync_grid), dim3(RTJK_SYNC_BLOCK), 0, st, f, (const rtj::Tables *) tables, (const uint8_t *) clean, nbits,
+                               (const uint32_t *) bounds, nb, S, ns, r, start, (const rtj::State *) end[(r + 1u) & 1u], end[r & 1u], count, ran);
+        HIP_TRY(hipGetLastError());
+        uint32_t got[RTJK_ROUND_BATCH] = {0};
+        HIP_TRY(hipMemcpyAsync(got, ran + r0, batch * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        bool done = false;
+        for (uint32_t k = 0; k < batch && !done; ++k) {
+            if (got[k] == 0u) done = true;
+            else { ++rounds; decodes += got[k]; }
+        }
+        if (done) break;
+        r0 += batch;
+    }
+    plan[2] = rounds; plan[3] = (int64_t) decodes;
+    // (c) place, (d) DC, (e) samples, (f) colours
+    enqueue_scan(count, ns, first, false, sums, st);
+    hipLaunchKernelGGL(rtjk::place_kernel, dim3(sync_grid), dim3(RTJK_SYNC_BLOCK), 0, st, f, (const rtj::Tables *) tables, (const uint8_t *) clean, nbits,
+                       (const uint32_t *) bounds, nb, S, ns, (const rtj::State *) start, (const uint32_t *) first, (const uint32_t *) (sums + blocks_for(ns, RTSK_TILE)),
+                       coefs, head);
+    hipLaunchKernelGGL(rtjk::dc_gather_kernel, dim3(blocks_for(f.total, RTJK_BLOCK)), dim3(RTJK_BLOCK), 0, st, f, (const int16_t *) coefs, dcarr, (const rtjk::Head *) head);
+    uint32_t *sums2;
+    RT_TRY(sc.get(&sums2, (size_t) f.total / RTSK_TILE + 2u)); // (place_kernel still reads the sum of all in `sums`)
+    enqueue_scan(dcarr, f.total, dcarr, true, sums2, st);
+    hipLaunchKernelGGL(rtjk::idct_kernel, dim3(blocks_for(f.total, RTJK_BLOCK)), dim3(RTJK_BLOCK), 0, st, f, (const int16_t *) coefs, (const uint32_t *) dcarr, planes,
+                       (const rtjk::Head *) head);
+    hipLaunchKernelGGL(rtjk::colour_kernel, dim3(blocks_for((uint64_t) f.W * f.H, RTJK_BLOCK)), dim3(RTJK_BLOCK), 0, st, f, (const uint8_t *) planes, d_rgb,
+                       (const rtjk::Head *) head);
+    HIP_TRY(hipGetLastError());
+    plan[4] = f.total;
+    if (!wait) return RT_OK;
+    rtjk::Head found{};
+    uint32_t blocks = 0;
+    HIP_TRY(hipMemcpyAsync(&found, head, sizeof(found), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&blocks, sums + blocks_for(ns, RTSK_TILE), sizeof(blocks), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    plan[4] = blocks;
+    return found.flags ? fail(RT_ERR_INVALID_ARGUMENT, rtj::stream_error(found.flags)) : RT_OK;
+}
+
+static int decode_jpeg_device(int32_t device, const uint8_t *data, size_t n, int32_t subsequence_bytes, void *d_rgb, size_t capacity, hipStream_t st, bool wait,
+                              rt_jpeg_stats *stats) {
+    RT_TRY(check_jpeg(data, n, d_rgb));
+    if (subsequence_bytes != 0 && subsequence_bytes < RTJ_MIN_SUBSEQUENCE) return fail(RT_ERR_INVALID_ARGUMENT, "subsequence_bytes must be at least 4");
+    return guarded("rt_decode_jpeg_device", [&]() -> int {
+        const auto t0 = std::chrono::steady_clock::now();
+        rtj::Parsed ps;
+        RT_TRY(parse_jpeg(data, n, ps));
+        const size_t need = (size_t) ps.f.W * ps.f.H * 3u;
+        if (capacity < need) return fail(RT_ERR_INVALID_ARGUMENT, "jpeg: capacity " + std::to_string(capacity) + " below the " + std::to_string(need) + " bytes of the bitmap");
+        if (rtj::marker_flags(ps)) return fail(RT_ERR_INVALID_ARGUMENT, rtj::stream_error(rtj::marker_flags(ps))); // known on the host: before any device call
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        int64_t *plan = g_last_jpeg_plan;
+        const int rc = jpeg_on_device(data, ps, subsequence_bytes ? (uint32_t) subsequence_bytes : (uint32_t) RTJ_DEFAULT_SUBSEQUENCE, (uint8_t *) d_rgb, st, wait, plan);
+        if (stats && stats->struct_size >= sizeof(rt_jpeg_stats)) {
+            stats->subsequence_bytes = (int32_t) plan[0]; stats->subsequences = plan[1]; stats->rounds = plan[2]; stats->decodes = plan[3];
+            stats->blocks = plan[4]; stats->boundaries = plan[5];
+            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return rc;
+    });
+}
+
+extern "C" {
+
+int rt_jpeg_get_info(const uint8_t *data, size_t n, rt_jpeg_info *out) {
+    RT_TRY(check_jpeg(data, n, out));
+    if (out->struct_size < sizeof(rt_jpeg_info)) return fail(RT_ERR_INVALID_ARGUMENT, "out->struct_size is smaller than rt_jpeg_info");
+    return guarded("rt_jpeg_get_info", [&]() -> int {
+        rtj::Parsed ps;
+        RT_TRY(parse_jpeg(data, n, ps));
+        out->width = (int32_t) ps.f.W; out->height = (int32_t) ps.f.H; out->components = (int32_t) ps.f.ncomp; out->sampling = (int32_t) ps.f.cls;
+        out->restart_interval = (int32_t) ps.f.Ri; out->entropy_bytes = (int64_t) ps.ecs_raw;
+        return RT_OK;
+    });
+}
+
+int rt_decode_jpeg(const uint8_t *data, size_t n, uint8_t *rgb, size_t capacity) {
+    RT_TRY(check_jpeg(data, n, rgb));
+    return guarded("rt_decode_jpeg", [&]() -> int {
+        std::string err;
+        const int rc = rtj::decode_host(data, n, rgb, capacity, 0u, nullptr, err);
+        return rc == RT_OK ? RT_OK : fail(rc, err);
+    });
+}
+
+int rt_decode_jpeg_device(int32_t device, const uint8_t *data, size_t n, void *d_rgb, size_t capacity, void *stream, rt_jpeg_stats *stats) {
+    if (stats && stats->struct_size < sizeof(rt_jpeg_stats)) return fail(RT_ERR_INVALID_ARGUMENT, "stats->struct_size is smaller than rt_jpeg_stats");
+    return decode_jpeg_device(device, data, n, 0, d_rgb, capacity, (hipStream_t) stream, stats != nullptr, stats);
+}
+
+int rt_dev_decode_jpeg(int32_t device, const uint8_t *data, size_t n, int32_t subsequence_bytes, void *d_rgb, size_t capacity) {
+    return decode_jpeg_device(device, data, n, subsequence_bytes, d_rgb, capacity, nullptr, true, nullptr);
+}
+
+int rt_dev_last_jpeg_plan(int64_t out[8]) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    for (int i = 0; i < 8; ++i) out[i] = g_last_jpeg_plan[i];
+    return RT_OK;
 }
 
 } // extern "C"

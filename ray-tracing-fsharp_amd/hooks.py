@@ -197,3 +197,26 @@ def encode_image(scene: Scene, device=0, digit_bits=8):
 
 def scene_has_host_mirror(scene: Scene) -> bool:
     return bool(lib.rt_dev_scene_has_host_mirror(scene.handle))
+
+
+JPEG_PLAN = ("subsequence_bytes", "subsequences", "rounds", "decodes", "blocks", "boundaries")
+
+
+def decode_jpeg(data: bytes, subsequence_bytes=0, device=0, out=None):
+    """rt_dev_decode_jpeg: the device decode with subsequences of subsequence_bytes (0: the default) into `out`, a uint8 torch tensor on
+    the device (made from the header when None) -> (status, out).  The status is returned, not raised: refusals are what the hook tests."""
+    import torch
+
+    from .raytracing import LoadImage
+    data = bytes(data)
+    if out is None:
+        i = LoadImage.info(data)
+        out = torch.empty((i["height"], i["width"], 3), dtype=torch.uint8, device=torch.device("cuda", device))
+    return int(lib.rt_dev_decode_jpeg(device, data, len(data), subsequence_bytes, out.data_ptr(), out.numel())), out
+
+
+def last_jpeg_plan():
+    """The plan of the calling thread's last device decode of a JPEG, or None before the first."""
+    w = (C.c_int64 * 8)()
+    check(lib.rt_dev_last_jpeg_plan(w))
+    return dict(zip(JPEG_PLAN, w)) if w[0] else None

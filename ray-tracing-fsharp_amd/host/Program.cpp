@@ -3,6 +3,7 @@
 // (the reference writes the same pixels as PNG through SkiaSharp), and the randomness comes from --seed.
 // Options: --seed N  --spp N  --depth N  --scale K (divide maxWidthCoord/maxHeightCoord by K)  --device D  --no-gamma  --list
 //          --host-output (format the file on the host: Scene::render, then ImageOutput::writePpm; the default formats it on the device)
+//          --earthmap PATH (the `earth` sample's texture, a baseline JPEG: the reference embeds earthmap.jpg as a resource, LoadImage.fs:9-18)
 #include "SampleImages.hpp"
 
 #include <cstdio>
@@ -17,16 +18,19 @@ int main(int argc, char **argv) {
         uint64_t seed = 2024;
         int spp = 0, depth = -1, scale = 1, device = 0;
         bool gamma = true, info = false, hostOutput = false;
+        std::string earthmap;
         for (int i = 1; i < argc; ++i) {
             const std::string a = argv[i];
             auto val = [&]() -> std::string { if (i + 1 >= argc) throw std::runtime_error("missing value for " + a); return argv[++i]; };
-            if (a == "--list") { for (auto &kv : SampleImages::catalogue()) std::cout << kv.first << "\n"; std::cout << "gradient\n"; return 0; }
+            if (a == "--list") { for (auto &kv : SampleImages::catalogue()) std::cout << kv.first << "\n"; std::cout << "gradient\n";
+                                 std::cerr << "earth (with --earthmap PATH: the texture's baseline JPEG)\n"; return 0; }
             else if (a == "--seed") seed = std::stoull(val());
             else if (a == "--spp") spp = std::stoi(val());
             else if (a == "--depth") depth = std::stoi(val());
             else if (a == "--scale") scale = std::stoi(val());
             else if (a == "--device") device = std::stoi(val());
             else if (a == "--no-gamma") gamma = false;
+            else if (a == "--earthmap") earthmap = val();
             else if (a == "--host-output") hostOutput = true; // the same bytes by the old route, for A/B measurement
             else if (a == "--info") info = true; // print the flattened scene's shape and a hash of its tree, do not render
             else pos.push_back(a);
@@ -40,7 +44,9 @@ int main(int argc, char **argv) {
             std::cout << output << "\n";
             return 0;
         }
-        SampleImages::SceneDef def = name == "random-spheres" ? SampleImages::randomSpheres(seed) : SampleImages::get(name);
+        if (name == "earth" && earthmap.empty()) throw std::runtime_error("earth needs --earthmap PATH (the reference's earthmap.jpg)");
+        SampleImages::SceneDef def = name == "earth" ? SampleImages::earth(earthmap)
+                                     : name == "random-spheres" ? SampleImages::randomSpheres(seed) : SampleImages::get(name);
         if (spp > 0) def.camera.SamplesPerPixel = spp;
         if (depth >= 0) def.camera.BounceDepth = depth;
         if (scale > 1) { def.maxWidthCoord = std::max(1, def.maxWidthCoord / scale); def.maxHeightCoord = std::max(1, def.maxHeightCoord / scale); }

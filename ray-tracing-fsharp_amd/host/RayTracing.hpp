@@ -13,6 +13,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -357,5 +358,32 @@ inline void writePpm(bool gammaCorrect, const std::function<void(double)> &incre
     for (long i = 0; i < (long) rows * cols; ++i) incrementProgress(1.0);
 }
 } // namespace ImageOutput
+
+// ---- RayTracing.App/LoadImage.fs ----------------------------------------------------------------------------------------
+// LoadImage.fromResource (LoadImage.fs:9-18): a baseline JPEG to the bitmap ParameterisedTexture::ofImage takes (rows top first, RGB8).
+// The reference embeds its file as a resource; here the bytes or a path are given.  Decoded on the host (rt_decode_jpeg), bit for bit
+// libjpeg's; rt_decode_jpeg_device is the same decode into device memory, for callers that hold some.
+namespace LoadImage {
+struct Bitmap { std::vector<uint8_t> pixels; int width = 0, height = 0; };
+inline Bitmap fromBytes(const std::vector<uint8_t> &data) {
+    rt_jpeg_info info{};
+    info.struct_size = sizeof(info);
+    check(rt_jpeg_get_info(data.data(), data.size(), &info));
+    Bitmap b;
+    b.width = info.width; b.height = info.height;
+    b.pixels.resize((size_t) info.width * (size_t) info.height * 3u);
+    check(rt_decode_jpeg(data.data(), data.size(), b.pixels.data(), b.pixels.size()));
+    return b;
+}
+inline Bitmap fromFile(const std::string &path) {
+    std::unique_ptr<FILE, int (*)(FILE *)> f(std::fopen(path.c_str(), "rb"), std::fclose);
+    if (!f) throw std::runtime_error("cannot open " + path);
+    std::vector<uint8_t> data;
+    unsigned char block[1 << 16];
+    for (size_t got; (got = std::fread(block, 1, sizeof(block), f.get())) > 0;) data.insert(data.end(), block, block + got);
+    if (std::ferror(f.get())) throw std::runtime_error("cannot read " + path);
+    return fromBytes(data);
+}
+} // namespace LoadImage
 
 } // namespace RayTracing

@@ -174,6 +174,11 @@ inline SceneDef earth(const std::vector<uint8_t> &bitmapTopFirst, int width, int
     Texture t = toTexture(1.0, Point::make(0.0, 0.0, 0.0), ParameterisedTexture::ofImage(bitmapTopFirst, width, height));
     return mk({S(SphereStyle::LambertReflection(1.0, t), 0.0, 0.0, 0.0, 1.0), US(SphereStyle::LightSource(tc(130, 130, 200)), 0.0, 0.0, 0.0, 200.0)}, cam, aspect, 400);
 }
+// The same from the file the reference embeds as a resource (LoadImage.fs:9-18): a path instead.
+inline SceneDef earth(const std::string &earthmapPath) {
+    const LoadImage::Bitmap b = LoadImage::fromFile(earthmapPath);
+    return earth(b.pixels, b.width, b.height);
+}
 // SampleImages.gradient (SampleImages.fs:37-57): a 256x256 ramp, the renderer is not involved.
 inline std::vector<uint8_t> gradient() {
     std::vector<uint8_t> px(256 * 256 * 3);

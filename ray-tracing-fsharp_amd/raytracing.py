@@ -138,7 +138,10 @@ class ParameterisedTexture:  # Texture.fs:19-24
 
     @staticmethod
     def ofImage(bitmap_rows_top_first: np.ndarray) -> _ParamTex:
-        """ParameterisedTexture.ofImage (Texture.fs:30-48): rows are reversed (y = Height - y - 1)."""
+        """ParameterisedTexture.ofImage (Texture.fs:30-48): rows are reversed (y = Height - y - 1).  A bitmap that LoadImage left on a GPU
+        comes back to the host here: rt_texture.texels is a host pointer."""
+        if _is_torch(bitmap_rows_top_first):
+            bitmap_rows_top_first = bitmap_rows_top_first.cpu().numpy()
         return ParameterisedTexture.Image(np.ascontiguousarray(bitmap_rows_top_first[::-1]))
 
     @staticmethod
@@ -1010,6 +1013,51 @@ class Png:
         last (ImageOutput.fs:230-233), once per row but the last (:239-241) -- rows * cols - 1 in all."""
         for _ in range(_write_image("png", gammaCorrect, pixels, output) - 1):
             incrementProgress(1.0)
+
+
+class LoadImage:
+    """LoadImage.fromResource (RayTracing.App/LoadImage.fs:9-18): a baseline JPEG to the bitmap ParameterisedTexture.ofImage takes --
+    [height, width, 3] uint8, rows top first.  The reference embeds its file as a resource and hands it to Skia; here the bytes or a path are
+    given, and the decode is csrc/rt_jpeg.h's, bit for bit libjpeg's.  device=None: the first GPU when one is visible, the host decoder
+    otherwise; device="host": the host decoder; an index: that GPU (RT_ERR_NO_DEVICE without one, never the host decoder instead).
+    tensor=True: a torch uint8 tensor that stays on the GPU it was decoded on (decoded on torch.cuda.current_stream(), and waited for: the
+    status of the entropy-coded data is the device's to find)."""
+
+    @staticmethod
+    def info(data: bytes) -> dict:
+        """rt_jpeg_get_info: width, height, components, sampling ("grey", "4:4:4", "4:2:2", "4:2:0"), restart_interval, entropy_bytes."""
+        i = A.rt_jpeg_info()
+        data = bytes(data)
+        check(lib.rt_jpeg_get_info(data, len(data), C.byref(i)))
+        return {"width": i.width, "height": i.height, "components": i.components, "sampling": ("grey", "4:4:4", "4:2:2", "4:2:0")[i.sampling],
+                "restart_interval": i.restart_interval, "entropy_bytes": i.entropy_bytes}
+
+    @staticmethod
+    def fromBytes(data: bytes, device=None, tensor: bool = False):
+        data = bytes(data)
+        i = LoadImage.info(data)
+        shape = (i["height"], i["width"], 3)
+        if device is None:
+            device = 0 if tensor or lib.rt_device_count() > 0 else "host"
+        if device == "host":
+            if tensor:
+                raise ValueError('tensor=True needs a GPU: device="host" gives a numpy array')
+            out = np.empty(shape, np.uint8)
+            check(lib.rt_decode_jpeg(data, len(data), out.ctypes.data, out.size))
+            return out
+        if lib.rt_device_count() < 1:
+            raise RtError(A.RT_ERR_NO_DEVICE, "no HIP device visible: LoadImage on a device has no CPU fallback (device=\"host\" is the host decoder)")
+        torch = _torch()
+        where = torch.device("cuda", int(device))
+        out = torch.empty(shape, dtype=torch.uint8, device=where)
+        stats = A.rt_jpeg_stats()
+        check(lib.rt_decode_jpeg_device(int(device), data, len(data), out.data_ptr(), out.numel(), torch.cuda.current_stream(where).cuda_stream, C.byref(stats)))
+        return out if tensor else out.cpu().numpy()
+
+    @staticmethod
+    def fromFile(path: str, device=None, tensor: bool = False):
+        with open(path, "rb") as f:
+            return LoadImage.fromBytes(f.read(), device, tensor)
 
 
 # ---- the output classes' shared pieces ----------------------------------------------------------------------------------

@@ -9,12 +9,13 @@ The reference builds its random scene from unseeded `System.Random`s; here ONE F
 from __future__ import annotations
 
 import dataclasses
+import os
 from typing import List, Tuple
 
 import numpy as np
 
 from . import _abi as A
-from .raytracing import (Camera, Colour, FloatProducer, Hittable, InfinitePlane, InfinitePlaneStyle, ParameterisedTexture, Pixel,
+from .raytracing import (Camera, Colour, FloatProducer, Hittable, InfinitePlane, InfinitePlaneStyle, LoadImage, ParameterisedTexture, Pixel,
                          Point, Sphere, SphereStyle, Texture, Vector, TOLERANCE)
 
 
@@ -220,8 +221,14 @@ def randomSpheres(seed: int = 2024, spp: int = 500, pixels: int = 800, grid: int
     return (objs, camera) + _extent(aspect, pixels)
 
 
-def earth(earthmap_rows_top_first: np.ndarray):
-    """SampleImages.earth (SampleImages.fs:962-1010); the decoded bitmap is passed in (no JPEG decode here)."""
+def _bitmap(earthmap, device=None):
+    """The decoded bitmap itself, or the path of a baseline JPEG (LoadImage.fromFile: on a GPU when one is visible, else on the host)."""
+    return LoadImage.fromFile(os.fspath(earthmap), device) if isinstance(earthmap, (str, os.PathLike)) else earthmap
+
+
+def earth(earthmap_rows_top_first):
+    """SampleImages.earth (SampleImages.fs:962-1010); the decoded bitmap, or the path of earthmap.jpg (LoadImage.fs:9-18)."""
+    earthmap_rows_top_first = _bitmap(earthmap_rows_top_first)
     aspect = 16.0 / 9.0
     origin = Point.make(13.0, 2.0, -3.0)
     view = Vector.unitise(Point.differenceToThenFrom(Point.make(0.0, 0.0, 0.0), origin))
@@ -263,8 +270,10 @@ def config3_final(seed: int = 2024, spp: int = 500, depth: int = 50, pixels: int
     return objs, dataclasses.replace(camera, BounceDepth=depth), w, h
 
 
-def config5_mixed(earthmap_rows_top_first: np.ndarray, seed: int = 2024, spp: int = 2000, depth: int = 50, pixels: int = 800):
-    """C5: final scene + image-textured Lambert sphere + one InfinitePlane mirror + a Dielectric sphere."""
+def config5_mixed(earthmap_rows_top_first, seed: int = 2024, spp: int = 2000, depth: int = 50, pixels: int = 800):
+    """C5: final scene + image-textured Lambert sphere + one InfinitePlane mirror + a Dielectric sphere.  The decoded
+    bitmap, or the path of a baseline JPEG."""
+    earthmap_rows_top_first = _bitmap(earthmap_rows_top_first)
     objs, camera, w, h = config3_final(seed, spp, depth, pixels)
     S, H = SphereStyle, Hittable
     tex = ParameterisedTexture.toTexture((1.0, Point.make(0.0, 1.0, 3.0)), ParameterisedTexture.ofImage(earthmap_rows_top_first))
