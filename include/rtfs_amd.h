@@ -1060,7 +1060,8 @@ int rt_dev_encode_image(int32_t device, const rt_scene *host_made, void *out, si
 /* The same with the order by depth sorted in passes of digit_bits bits (1 .. 8; the product's are 8 wide, so only a tree of 256 levels or
  * more takes a second pass there): with narrow digits a tree of a few dozen levels runs the later passes -- the same bytes. */
 int rt_dev_encode_image_radix(int32_t device, const rt_scene *host_made, int32_t digit_bits, void *out, size_t cap, size_t *bytes);
-/* 1 when the host holds its copy of the scene's arrays (always, for a scene made on the host), 0 while they are still on the device. */
+/* 1 when the host holds its copy of the scene's arrays (always, for a scene made on the host), 0 while they are still on the device.
+ * (Scenes whose texels were placed on a device -- "Image textures from device memory" below -- report 0 until those are fetched too.) */
 int rt_dev_scene_has_host_mirror(const rt_scene *scene);
 
 /* ---- LoadImage.fromResource (RayTracing.App/LoadImage.fs:9-18): a baseline JPEG to the bitmap ParameterisedTexture.ofImage takes ----
@@ -1114,6 +1115,67 @@ int rt_decode_jpeg_device(int32_t device, const uint8_t *data, size_t n, void *d
  * device decode: subsequence bytes, subsequences, rounds, subsequence decodes run, blocks, boundaries, 0, 0. */
 int rt_dev_decode_jpeg(int32_t device, const uint8_t *data, size_t n, int32_t subsequence_bytes, void *d_rgb, size_t capacity);
 int rt_dev_last_jpeg_plan(int64_t out[8]);
+
+/* ---- Image textures from device memory (Texture.fs:34; csrc/rt_texture_plan.h, csrc/rt_texture_kernels.h; DESIGN.md "Textures from device
+ * memory").  Added symbols and one added struct only -- no existing struct, field or symbol changed, so RT_ABI_VERSION stays 7.
+ *
+ * rt_texture.texels is a host pointer.  A bitmap that is already in device memory -- rt_decode_jpeg_device's output, a frame a torch program
+ * made -- would have to come down, have its rows reversed (ParameterisedTexture.ofImage: img.[y] is the bitmap's row height - 1 - y) and go
+ * up again inside scene creation.  These calls take, per texture record, where its texels come from; the reversal and the placement into
+ * the scene's texel blob (images in record order, each zero-padded to 16 bytes) are one kernel launch for all device-sourced images of a
+ * table, on the caller's stream.
+ *
+ * The create calls.  sources: n_textures entries, or NULL = every record RT_TEXELS_RECORD, which IS the existing call
+ * (rt_scene_create_gpu_trees / rt_scene_create_device).  For a source that is not RT_TEXELS_RECORD the record's rt_texture.texels is
+ * ignored and may be NULL.  RECORD images are uploaded into their ranges, DEVICE images are placed by the kernel, JPEG images are decoded
+ * by rt_decode_jpeg_device's kernels on `stream` into stream-ordered scratch and placed by the same launch.  The device's copy of the scene
+ * is installed directly, and the calls return after the stream has finished the build.  The scene is the scene the existing call returns
+ * for the same records with the same texels on the host: every rt_scene_get_*, every render, rt_scene_tune* and rt_scene_destroy behave
+ * identically; rt_scene_get_info().texel_bytes is right without any fetch.
+ *
+ * The host's copy of the texels is empty until something needs it -- the first use of the scene on ANOTHER device -- and is then fetched
+ * once under the scene's lock, together with (and in the manner of) the lazy copy of a device-made scene's hittables: whatever fetches
+ * that copy (rt_scene_get_tree, rt_scene_tune* where it rebuilds, ...) fetches the texels too.  rt_scene_create_textures has its host
+ * arrays from the start; only its texels are lazy.  rt_dev_scene_has_host_mirror reports 0 while ANY part of the host's copy is still on
+ * a device, so 0 for a scene of either call that has an image (and for any scene after rt_scene_set_texels_device), 1 once fetched; a
+ * scene of these calls without an image reports what the existing call's scene reports.
+ *
+ * Refusals.  Before any device call, RT_ERR_INVALID_ARGUMENT: the existing call's own argument checks; a struct_size that is not
+ * sizeof(rt_texels_source); an unknown kind or flag bit; a source that is not RECORD on a record that is not RT_TEXTURE_IMAGE; DEVICE or
+ * JPEG with NULL data; DEVICE with bytes < width * height * 3.  RT_ERR_NO_DEVICE without a GPU.  Then the JPEG sources' headers, parsed on
+ * the host: rt_decode_jpeg's status and text prefixed "texture i: ", and RT_ERR_INVALID_ARGUMENT for a file whose width or height is not
+ * the record's.  Then the textures' own refusals and the hittables', unchanged in status and text; RT_ERR_UNSUPPORTED for a texel blob of
+ * more than UINT32_MAX - 15 bytes (texel offsets are 32 bits wide).  A damaged entropy-coded stream is found by the decoder on the device:
+ * the call waits for the stream, fails with rt_decode_jpeg's status and text, frees everything and leaves *out unwritten. */
+enum rt_texels_kind { RT_TEXELS_RECORD = 0,  /* rt_texture.texels, a host pointer, as today */
+                      RT_TEXELS_DEVICE = 1,  /* data: a bitmap in `device`'s memory, height*width*3 bytes, any alignment */
+                      RT_TEXELS_JPEG   = 2 };/* data: a baseline JPEG in HOST memory, `bytes` long; decoded on `device` */
+#define RT_TEXELS_TOP_FIRST 1u /* rows as a decoder leaves them: ofImage's reversal (Texture.fs:34) is applied on the device.
+                                  Without it the rows are already img.[y], rt_texture.texels' layout.  JPEG: always top first. */
+typedef struct rt_texels_source { uint32_t struct_size, kind, flags, reserved; const void *data; size_t bytes; } rt_texels_source;
+
+/* Scene.make with host hittables (as rt_scene_create_gpu_trees) / device hittables (as rt_scene_create_device). */
+int rt_scene_create_textures(const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                             const rt_texels_source *sources, const rt_scene_options *options, int32_t device, void *stream, rt_scene **out);
+int rt_scene_create_device_textures(int32_t device, const void *d_hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                                    const rt_texels_source *sources, const rt_scene_options *options, void *stream, rt_scene **out);
+/* ofImage alone: d_bitmap (top first) -> d_texels (rows reversed), capacity >= width*height*3, both of any alignment; exactly
+ * width*height*3 bytes are written.  Enqueued on `stream`; the call does not wait.  Overlapping buffers (in place) are refused. */
+int rt_of_image_device(int32_t device, const void *d_bitmap, int32_t width, int32_t height, void *d_texels, size_t capacity, void *stream);
+/* Replace the texels of IMAGE record `texture` (same width and height) from a bitmap in device memory (bytes >= width*height*3; flags:
+ * RT_TEXELS_TOP_FIRST or 0).  The copy is enqueued on `stream` into the scene's blob on `device` (that device's copy of the scene is made
+ * first if there is none) and the call does not wait: launches enqueued on `stream` afterwards see the new texels, ordering against other
+ * streams is the caller's, and a render in flight on another stream reads a mixture of old and new texels -- never a fault, the range is
+ * fixed.  d_rgb must stay valid until the stream has passed the copy.  The host's copy of the texels is dropped and fetched again when
+ * wanted.  RT_ERR_INVALID_ARGUMENT for a wrong index, a record that is not an image, short bytes, an unknown flag; RT_ERR_UNSUPPORTED for
+ * a scene that has a copy on another device.  On any refusal the scene is unchanged. */
+int rt_scene_set_texels_device(rt_scene *scene, int32_t texture, int32_t device, const void *d_rgb, size_t bytes, uint32_t flags, void *stream);
+/* Test hooks.  The texel blob as `device` holds it (out may be NULL to ask for *bytes) and every record's texel_off (n_textures words,
+ * UINT32_MAX: not an image; may be NULL).  The plan of this thread's last rt_scene_create_*textures call with sources: textures, images,
+ * device-sourced, jpeg-sourced, blob bytes; then, counted on from that call through rt_scene_set_texels_device and the lazy fetch on
+ * this thread: of_image_kernel launches, texel bytes copied host->device, texel bytes copied device->host. */
+int rt_dev_scene_texels(const rt_scene *scene, int32_t device, void *out, size_t cap, size_t *bytes, uint32_t *texel_off);
+int rt_dev_last_texture_plan(int64_t out[8]);
 
 #ifdef __cplusplus
 }

@@ -132,6 +132,18 @@ class rt_jpeg_stats(C.Structure):
         super().__init__(struct_size=C.sizeof(rt_jpeg_stats))
 
 
+class rt_texels_source(C.Structure):
+    """Where one texture record's texels come from (rt_scene_create_textures, rt_scene_create_device_textures)."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("data", C.c_void_p),
+                ("bytes", C.c_size_t)]
+
+    def __init__(self, kind=0, flags=0, data=None, bytes=0):
+        super().__init__(struct_size=C.sizeof(rt_texels_source), kind=kind, flags=flags, data=data, bytes=bytes)
+
+
+RT_TEXELS_RECORD, RT_TEXELS_DEVICE, RT_TEXELS_JPEG = 0, 1, 2  # enum rt_texels_kind
+RT_TEXELS_TOP_FIRST = 1
+ABI_STRUCT_TEXELS_SOURCE = 12  # rt_abi_sizeof only
 RT_JPEG_GREY, RT_JPEG_444, RT_JPEG_422, RT_JPEG_420 = 0, 1, 2, 3
 RT_PATH_MISS, RT_PATH_STOPPED, RT_PATH_BOUNCE_LIMIT, RT_PATH_NO_RAY = 0, 1, 2, 3  # enum rt_path_end
 RT_PATH_SUMMARY_WORDS = 16

@@ -200,6 +200,14 @@ SIGNATURES = {
     "rt_decode_jpeg_device": (C.c_int, [C.c_int32, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, _P(A.rt_jpeg_stats)]),
     "rt_dev_decode_jpeg": (C.c_int, [C.c_int32, C.c_char_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_size_t]),
     "rt_dev_last_jpeg_plan": (C.c_int, [_P(C.c_int64)]),  # out[8]
+    "rt_scene_create_textures": (C.c_int, [_P(A.rt_hittable), C.c_size_t, _P(A.rt_texture), C.c_size_t, _P(A.rt_texels_source), _P(A.rt_scene_options),
+                                           C.c_int32, C.c_void_p, _P(C.c_void_p)]),
+    "rt_scene_create_device_textures": (C.c_int, [C.c_int32, C.c_void_p, C.c_size_t, _P(A.rt_texture), C.c_size_t, _P(A.rt_texels_source),
+                                                  _P(A.rt_scene_options), C.c_void_p, _P(C.c_void_p)]),
+    "rt_of_image_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rt_scene_set_texels_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "rt_dev_scene_texels": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, _P(C.c_size_t), _u32p]),  # texel_off[n_textures]
+    "rt_dev_last_texture_plan": (C.c_int, [_P(C.c_int64)]),  # out[8]
     "rt_dev_float_producer": (C.c_int, [C.c_int32, _u32p, C.c_int32, _dp]),
     "rt_dev_stream_state": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32, _u64p, _u32p, _u32p]),
     "rt_dev_bbox_hits": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _i32p]),
@@ -236,5 +244,7 @@ for _i, _t in list(enumerate(A.ABI_STRUCTS)) + [(A.ABI_STRUCT_PATH_OUTPUTS, A.rt
             raise ImportError(f"ABI mismatch for {_t.__name__}.{_fname}: library offset {lib.rt_abi_offsetof(_i, _k)} vs ctypes {getattr(_t, _fname).offset}")
     if lib.rt_abi_offsetof(_i, len(_t._fields_)) != C.c_size_t(-1).value:
         raise ImportError(f"ABI mismatch for {_t.__name__}: the library has more fields than the ctypes mirror")
+if lib.rt_abi_sizeof(A.ABI_STRUCT_TEXELS_SOURCE) != C.sizeof(A.rt_texels_source):
+    raise ImportError(f"ABI mismatch for rt_texels_source: library {lib.rt_abi_sizeof(A.ABI_STRUCT_TEXELS_SOURCE)} vs ctypes {C.sizeof(A.rt_texels_source)}")
 if lib.rt_abi_version() != A.RT_ABI_VERSION:
     raise ImportError("ABI version mismatch between librtfs_amd.so and _abi.py")

@@ -7,6 +7,7 @@
 #include "../../include/rtfs_amd.h"
 #include "rt_device.h"
 #include "rt_scene_plan.h"
+#include "rt_texture_plan.h"
 #include "rt_walk_plan.h"
 
 #include <algorithm>
@@ -394,7 +395,8 @@ struct HostScene {
     std::vector<rt_hittable> hittables;
     std::vector<rt_texture> textures;
     std::vector<rtd::TexRec> texRecs;
-    std::vector<uint8_t> texelBlob;
+    std::vector<uint8_t> texelBlob; // (a scene whose texels were placed on a device: empty until the host mirror is fetched)
+    uint64_t texelBytes = 0;        // the blob's size on every route
     std::vector<int32_t> objToOrig; // object-table index -> index in `hittables`
     std::vector<int32_t> origToObj;
     FlatTree tree;     // BoundingBoxTree.make's tree; prim = object-table index (= the leaf's depth-first rank)
@@ -413,12 +415,15 @@ static inline size_t align16(size_t v) { return (v + 15u) & ~(size_t) 15u; }
 static void encode_image(HostScene &s);
 
 // The texture half of build_scene (s.textures, texRecs, texelBlob): O(textures) host work on every route.  status is RT_OK on success.
-static std::string build_textures(const rt_texture *tex, size_t ntex, HostScene &s, int &status) {
+// external (may be null; otherwise ntex flags): the routes that place texels on a device themselves.  A record whose flag is set needs no
+// rt_texture.texels, and with `external` given the blob is laid out (texel_off, s.texelBytes) but NOT filled: s.texelBlob stays empty.
+static std::string build_textures(const rt_texture *tex, size_t ntex, HostScene &s, int &status, const uint8_t *external = nullptr) {
     status = RT_ERR_INVALID_ARGUMENT;
     if (ntex > 0 && !tex) return "textures is NULL";
     if (ntex > (size_t) RTD_MAX_TEXTURES) { status = RT_ERR_UNSUPPORTED; return "at most 254 textures"; }
     s.textures.assign(tex, tex + ntex);
     s.texRecs.resize(ntex);
+    std::vector<int32_t> kind(ntex), width(ntex), height(ntex);
     for (size_t i = 0; i < ntex; ++i) {
         const rt_texture &t = tex[i];
         rtd::TexRec r{};
@@ -430,6 +435,7 @@ static std::string build_textures(const rt_texture *tex, size_t ntex, HostScene 
         r.grid = t.grid_size;
         r.cx = t.map_centre[0]; r.cy = t.map_centre[1]; r.cz = t.map_centre[2];
         r.map_radius = t.map_radius;
+        kind[i] = t.kind; width[i] = t.width; height[i] = t.height;
         switch (t.kind) {
         case RT_TEXTURE_COLOUR: break;
         case RT_TEXTURE_UV_RAMP:
@@ -441,18 +447,23 @@ static std::string build_textures(const rt_texture *tex, size_t ntex, HostScene 
             // sin(gridSize * u), u in [0, 1]: csrc/rt_trig.h reduces arguments below 2^20 exactly
             if (!(std::fabs(t.grid_size) <= 500000.0)) { status = RT_ERR_UNSUPPORTED; return "texture " + std::to_string(i) + ": Checkered grid size beyond 5e5 (or NaN)"; }
             break;
-        case RT_TEXTURE_IMAGE: {
-            if (!t.texels || t.width <= 0 || t.height <= 0) return "texture " + std::to_string(i) + ": image without texels";
-            const size_t bytes = (size_t) t.width * (size_t) t.height * 3u;
-            r.texel_off = (uint32_t) s.texelBlob.size();
-            s.texelBlob.insert(s.texelBlob.end(), t.texels, t.texels + bytes);
-            while (s.texelBlob.size() % 16u) s.texelBlob.push_back(0);
+        case RT_TEXTURE_IMAGE:
+            if ((!t.texels && !(external && external[i])) || t.width <= 0 || t.height <= 0) return "texture " + std::to_string(i) + ": image without texels";
             break;
-        }
         default: status = RT_ERR_UNSUPPORTED; return "texture " + std::to_string(i) + ": Texture.Arbitrary closures cannot cross the C ABI";
         }
         s.texRecs[i] = r;
         s.textures[i].texels = nullptr; // not owned
+    }
+    // the blob: images in index order, each zero-padded to a multiple of 16 (rt_texture_plan.h)
+    std::vector<uint64_t> off(ntex);
+    s.texelBytes = rtt::texel_layout(kind.data(), width.data(), height.data(), ntex, RT_TEXTURE_IMAGE, off.data());
+    if (external && s.texelBytes > rtt::MAX_BLOB) { status = RT_ERR_UNSUPPORTED; return "the image textures' texels exceed 4 GiB: texel offsets are 32 bits wide"; }
+    if (!external) s.texelBlob.assign((size_t) s.texelBytes, 0);
+    for (size_t i = 0; i < ntex; ++i) {
+        if (off[i] == rtt::NO_BYTE) continue;
+        s.texRecs[i].texel_off = (uint32_t) off[i]; // (32 bits: above 4 GiB the offset wraps on this route, as it always did -- DESIGN.md "Textures from device memory")
+        if (!external) memcpy(s.texelBlob.data() + (size_t) off[i], tex[i].texels, (size_t) rtt::image_bytes(width[i], height[i]));
     }
     status = RT_OK;
     return std::string();
@@ -466,11 +477,11 @@ typedef std::function<int(const std::vector<Box> &boxes, FlatTree &tree, std::st
 // `walk_maker` (may be null: SahBuilder) is asked for the surface-area tree over the leaf boxes in rank order exactly where SahBuilder would
 // be: RT_WALK_TREE_SAH, at least 3 bounded spheres, every box finite (rt_scene_create_gpu_trees: the device build of rt_walk_kernels.h).
 static std::string build_scene(const rt_hittable *h, size_t n, const rt_texture *tex, size_t ntex, int walk_kind, HostScene &s, int &status,
-                               const TreeMaker *maker = nullptr, const TreeMaker *walk_maker = nullptr) {
+                               const TreeMaker *maker = nullptr, const TreeMaker *walk_maker = nullptr, const uint8_t *external = nullptr) {
     status = RT_ERR_INVALID_ARGUMENT;
     if (n > 0 && !h) return "hittables is NULL";
     {
-        std::string msg = build_textures(tex, ntex, s, status);
+        std::string msg = build_textures(tex, ntex, s, status, external); // (external: build_textures)
         if (status != RT_OK) return msg;
         status = RT_ERR_INVALID_ARGUMENT;
     }

@@ -14,6 +14,8 @@
 #include "rt_scene.h"
 #include "rt_scene_kernels.h"
 #include "rt_scene_plan.h"
+#include "rt_texture_kernels.h"
+#include "rt_texture_plan.h"
 #include "rt_tree_kernels.h"
 #include "rt_tree_plan.h"
 #include "rt_walk_kernels.h"
@@ -130,7 +132,10 @@ struct rt_scene {
     std::map<int, DeviceScene> dev;
     std::mutex mu;
     std::atomic<bool> mirrored{true}; // false: host.hittables, tree, walkTree, leafBoxes, objToOrig, origToObj and image are still on src.device
+                                      // (src.keep set), or host.texelBlob is still on texDevice (texelsOnHost false), or both
     MirrorSource src;
+    bool texelsOnHost = true; // false: host.texelBlob is empty and the host.texelBytes bytes are dev[texDevice].texels (the rt_scene_create_*textures
+    int texDevice = -1;       // routes, and any scene after rt_scene_set_texels_device); ensure_host_mirror fetches them
 };
 static int ensure_host_mirror_locked(rt_scene *s); // (s->mu held)
 static int ensure_host_mirror(const rt_scene *scene) {
@@ -149,12 +154,16 @@ static std::atomic<int> g_walk_tree{RT_WALK_TREE_SAH};
 static thread_local unsigned long long g_last_stage_stats[16] = {0};
 static thread_local int64_t g_last_launch_plan[RT_LAUNCH_PLAN_WORDS] = {0};
 static thread_local int64_t g_last_paths_plan[8] = {0};
+// rt_dev_last_texture_plan: [0..4] of this thread's last rt_scene_create_*textures call; [5..7] (kernel launches, texel bytes host->device,
+// texel bytes device->host) count on from it through rt_scene_set_texels_device and the lazy fetch of the texels
+static thread_local int64_t g_last_texture_plan[8] = {0};
 
-static int device_scene(rt_scene *s, int device, DeviceScene **out) {
-    std::lock_guard<std::mutex> lock(s->mu);
+// (s->mu held, `device` current.)  placed: the scene's texel blob already on `device` (the scene's to free once this has succeeded), or NULL:
+// uploaded from the host's.
+static int device_scene_locked(rt_scene *s, int device, DeviceScene **out, uint8_t *placed = nullptr) {
     auto it = s->dev.find(device);
     if (it != s->dev.end()) { *out = &it->second; return RT_OK; }
-    RT_TRY(ensure_host_mirror_locked(s)); // (a scene made on another device: its image comes through the host)
+    if (!placed) RT_TRY(ensure_host_mirror_locked(s)); // (a scene made on another device: its image and its texels come through the host)
     DeviceScene d;
     const rth::HostScene &h = s->host;
     HIP_TRY(hipMalloc((void **) &d.image, h.image.size()));
@@ -163,7 +172,8 @@ static int device_scene(rt_scene *s, int device, DeviceScene **out) {
         HIP_TRY(hipMalloc((void **) &d.tex, h.texRecs.size() * sizeof(TexRec)));
         HIP_TRY(hipMemcpy(d.tex, h.texRecs.data(), h.texRecs.size() * sizeof(TexRec), hipMemcpyHostToDevice));
     }
-    if (!h.texelBlob.empty()) {
+    if (placed) d.texels = placed;
+    else if (!h.texelBlob.empty()) {
         HIP_TRY(hipMalloc((void **) &d.texels, h.texelBlob.size()));
         HIP_TRY(hipMemcpy(d.texels, h.texelBlob.data(), h.texelBlob.size(), hipMemcpyHostToDevice));
     }
@@ -177,10 +187,14 @@ static int device_scene(rt_scene *s, int device, DeviceScene **out) {
     try {
         *out = &s->dev.emplace(device, d).first->second;
     } catch (const std::bad_alloc &) {
-        (void) hipFree(d.image); (void) hipFree(d.tex); (void) hipFree(d.texels); (void) hipFree(d.obj_to_orig);
+        (void) hipFree(d.image); (void) hipFree(d.tex); if (!placed) (void) hipFree(d.texels); (void) hipFree(d.obj_to_orig);
         return fail(RT_ERR_HOST, "host memory exhausted");
     }
     return RT_OK;
+}
+static int device_scene(rt_scene *s, int device, DeviceScene **out) {
+    std::lock_guard<std::mutex> lock(s->mu);
+    return device_scene_locked(s, device, out);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -304,6 +318,7 @@ size_t rt_abi_sizeof(int which) {
     case 9: return sizeof(rt_path_outputs); // (8 stays unused: bindings probe it as "no such struct")
     case 10: return sizeof(rt_jpeg_info);
     case 11: return sizeof(rt_jpeg_stats);
+    case 12: return sizeof(rt_texels_source);
     default: return 0;
     }
 }
@@ -444,7 +459,7 @@ int rt_scene_get_info(const rt_scene *s, rt_scene_info *out) {
     out->n_textures = (int32_t) h.texRecs.size();
     out->lds_resident = default_lds_resident(h) ? 1 : 0; // the decision a render with default options takes
     out->scene_bytes = (int64_t) h.off.total;
-    out->texel_bytes = (int64_t) h.texelBlob.size();
+    out->texel_bytes = (int64_t) h.texelBytes; // (the blob itself may still be on a device)
     return RT_OK;
 }
 
@@ -3227,8 +3242,13 @@ int rt_dev_texture_colour_at(int32_t device, const rt_scene *scene, int32_t text
 // ------------------------------------------------------------------------------------------------------------
 static int create_scene_on_device(const char *entry, const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
                                   const rt_scene_options *options, int32_t device, bool walk_tree_too, rt_scene **out);
+struct TexelSources; // (rt_scene_create_*textures, below: where each IMAGE record's texels come from)
 static int scene_from_host_records(const char *entry, const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures, int walk,
-                                   int32_t device, bool walk_tree_too, rt_scene **out);
+                                   int32_t device, bool walk_tree_too, rt_scene **out, const TexelSources *sources = nullptr, hipStream_t st = nullptr);
+static const uint8_t *external_flags(const TexelSources *sources);
+// The texel blob of `h` (laid out by build_textures) on the current device, each image from its source, on `st`; waits for the stream.
+// *out: the blob (hipMalloc; the caller's to free), NULL when the scene has no image.
+static int place_texels(const rth::HostScene &h, const rt_texture *textures, size_t n_textures, const TexelSources &sources, hipStream_t st, unsigned char **out);
 static const char *const kNanBox = "a box coordinate is NaN: it has no order; nothing was written";
 
 static int check_tree_host(size_t n, const double *boxes) {
@@ -3545,7 +3565,7 @@ static int create_scene_on_device(const char *entry, const rt_hittable *hittable
 }
 // (the device entered, the arguments checked)
 static int scene_from_host_records(const char *entry, const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures, int walk,
-                                   int32_t device, bool walk_tree_too, rt_scene **out) {
+                                   int32_t device, bool walk_tree_too, rt_scene **out, const TexelSources *sources, hipStream_t st) {
     return guarded(entry, [&]() {
         // either tree through its staged call: the boxes flattened, the arrays back into a FlatTree
         auto via = [&](bool sah, const std::vector<rth::Box> &ob, rth::FlatTree &t, std::string &msg) -> int {
@@ -3566,8 +3586,22 @@ static int scene_from_host_records(const char *entry, const rt_hittable *hittabl
         const rth::TreeMaker walkMaker = [&](const std::vector<rth::Box> &ob, rth::FlatTree &t, std::string &msg) { return via(true, ob, t, msg); };
         std::unique_ptr<rt_scene> s(new rt_scene());
         int status = RT_OK;
-        std::string msg = rth::build_scene(hittables, n_hittables, textures, n_textures, walk, s->host, status, &maker, walk_tree_too ? &walkMaker : nullptr);
+        std::string msg = rth::build_scene(hittables, n_hittables, textures, n_textures, walk, s->host, status, &maker, walk_tree_too ? &walkMaker : nullptr,
+                                           external_flags(sources));
         if (status != RT_OK) return fail(status, msg);
+        if (sources) { // the texels go to `device` and stay there: its copy of the scene is installed now, the host's blob is fetched when wanted
+            unsigned char *placed = nullptr;
+            RT_TRY(place_texels(s->host, textures, n_textures, *sources, st, &placed));
+            if (placed) {
+                std::lock_guard<std::mutex> lock(s->mu);
+                DeviceScene *ds = nullptr;
+                const int rc = device_scene_locked(s.get(), device, &ds, placed);
+                if (rc != RT_OK) { (void) hipFree(placed); return rc; }
+                s->texelsOnHost = false;
+                s->texDevice = device;
+                s->mirrored.store(false, std::memory_order_release);
+            }
+        }
         *out = s.release();
         return (int) RT_OK;
     });
@@ -3686,9 +3720,30 @@ static int upload(unsigned char **out, const void *src, size_t bytes) {
     return RT_OK;
 }
 
+static int fetch_hittables_locked(rt_scene *s);
 static int ensure_host_mirror_locked(rt_scene *s) {
     if (s->mirrored.load(std::memory_order_acquire)) return RT_OK;
     return guarded("host mirror of a scene made on the device", [&]() -> int {
+        RT_TRY(fetch_hittables_locked(s));
+        if (!s->texelsOnHost) { // the texels: placed on texDevice by a rt_scene_create_*textures call or by rt_scene_set_texels_device
+            rth::HostScene &h = s->host;
+            DeviceGuard guard;
+            RT_TRY(guard.enter(s->texDevice));
+            const DeviceScene &ds = s->dev.at(s->texDevice);
+            h.texelBlob.resize((size_t) h.texelBytes);
+            HIP_TRY(hipDeviceSynchronize()); // (a replacement enqueued on a stream of the caller's)
+            if (h.texelBytes) HIP_TRY(hipMemcpy(h.texelBlob.data(), ds.texels, (size_t) h.texelBytes, hipMemcpyDeviceToHost));
+            g_last_texture_plan[7] += (int64_t) h.texelBytes;
+            s->texelsOnHost = true;
+        }
+        s->mirrored.store(true, std::memory_order_release);
+        return RT_OK;
+    });
+}
+// the hittables' half of the mirror (s->mu held; inside guarded())
+static int fetch_hittables_locked(rt_scene *s) {
+    if (!s->src.keep) return RT_OK;
+    {
         const MirrorSource &m = s->src;
         rth::HostScene &h = s->host;
         DeviceGuard guard;
@@ -3730,19 +3785,19 @@ static int ensure_host_mirror_locked(rt_scene *s) {
         RT_TRY(down(h.image.data(), ds.image, h.off.total));
         (void) hipFree(s->src.keep);
         s->src.keep = nullptr;
-        s->mirrored.store(true, std::memory_order_release);
         return RT_OK;
-    });
+    }
 }
 
 // rt_scene_create_device behind its argument checks, the device entered
-static int scene_on_device(int32_t device, const rt_hittable *d_h, size_t n, const rt_texture *textures, size_t n_textures, int walk, hipStream_t st, rt_scene **out) {
+static int scene_on_device(int32_t device, const rt_hittable *d_h, size_t n, const rt_texture *textures, size_t n_textures, int walk, hipStream_t st, rt_scene **out,
+                           const TexelSources *sources = nullptr) {
     return guarded("rt_scene_create_device", [&]() -> int {
         std::unique_ptr<rt_scene> s(new rt_scene());
         rth::HostScene &h = s->host;
         {
             int status = RT_OK;
-            const std::string msg = rth::build_textures(textures, n_textures, h, status);
+            const std::string msg = rth::build_textures(textures, n_textures, h, status, external_flags(sources));
             if (status != RT_OK) return fail(status, msg);
         }
         StreamScratch sc;
@@ -3790,7 +3845,7 @@ static int scene_on_device(int32_t device, const rt_hittable *d_h, size_t n, con
             // rt_scene_create_gpu_trees' (slow for many records, but the same scene).
             std::vector<rt_hittable> rec(n);
             if (n) HIP_TRY(hipMemcpy(rec.data(), d_h, n * sizeof(rt_hittable), hipMemcpyDeviceToHost));
-            return scene_from_host_records("rt_scene_create_device", rec.data(), n, textures, n_textures, walk, device, true, out);
+            return scene_from_host_records("rt_scene_create_device", rec.data(), n, textures, n_textures, walk, device, true, out, sources, st);
         }
         // ---- both trees, from and into device memory; the ranks between them ----
         const size_t nn = (size_t) rtt::node_count(nb);
@@ -3840,7 +3895,8 @@ static int scene_on_device(int32_t device, const rt_hittable *d_h, size_t n, con
         h.walkTree.depth = walkKind == RT_WALK_TREE_SAH ? (int) c.max_depth + 1 : h.tree.depth;
         DeviceScene d;
         if (!h.texRecs.empty()) RT_TRY(upload(&tex.p, h.texRecs.data(), h.texRecs.size() * sizeof(TexRec)));
-        if (!h.texelBlob.empty()) RT_TRY(upload(&texels.p, h.texelBlob.data(), h.texelBlob.size()));
+        if (sources) RT_TRY(place_texels(h, textures, n_textures, *sources, st, &texels.p));
+        else if (!h.texelBlob.empty()) RT_TRY(upload(&texels.p, h.texelBlob.data(), h.texelBlob.size()));
         hipDeviceProp_t prop;
         HIP_TRY(hipGetDeviceProperties(&prop, device));
         d.cu_count = prop.multiProcessorCount;
@@ -3849,6 +3905,7 @@ static int scene_on_device(int32_t device, const rt_hittable *d_h, size_t n, con
         (void) image.release(); (void) tex.release(); (void) texels.release(); (void) o2o.release();
         src.keep = keep.release();
         s->src = src;
+        if (sources && h.texelBytes) { s->texelsOnHost = false; s->texDevice = device; }
         s->mirrored.store(false, std::memory_order_release);
         *out = s.release();
         return (int) RT_OK;
@@ -4101,6 +4158,238 @@ int rt_dev_decode_jpeg(int32_t device, const uint8_t *data, size_t n, int32_t su
 int rt_dev_last_jpeg_plan(int64_t out[8]) {
     if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
     for (int i = 0; i < 8; ++i) out[i] = g_last_jpeg_plan[i];
+    return RT_OK;
+}
+
+} // extern "C"
+
+// ============================================================================================================
+// Image textures from device memory (rt_texture_plan.h, rt_texture_kernels.h; DESIGN.md "Textures from device memory")
+// ============================================================================================================
+static_assert(RTX_TOP_FIRST == RT_TEXELS_TOP_FIRST && RTX_MAX_IMAGES == RTD_MAX_TEXTURES, "rt_texture_plan.h restates the ABI");
+
+struct TexelSources {
+    const rt_texels_source *src = nullptr;     // n_textures entries
+    std::vector<uint8_t> external;             // per record: its texels are not rt_texture.texels
+    std::vector<std::unique_ptr<rtj::Parsed>> jpeg; // per record: the parsed header of a RT_TEXELS_JPEG source
+};
+static const uint8_t *external_flags(const TexelSources *sources) { return sources ? sources->external.data() : nullptr; }
+
+// The argument checks of `sources`, before any device call.
+static int check_sources(const rt_texture *textures, size_t n_textures, const rt_texels_source *sources, TexelSources &ts) {
+    ts.src = sources;
+    ts.external.assign(n_textures ? n_textures : 1, 0);
+    ts.jpeg.resize(n_textures);
+    for (size_t i = 0; i < n_textures; ++i) {
+        const rt_texels_source &q = sources[i];
+        const std::string who = "source " + std::to_string(i) + ": ";
+        if (q.struct_size != sizeof(rt_texels_source)) return fail(RT_ERR_INVALID_ARGUMENT, who + "struct_size is not sizeof(rt_texels_source)");
+        if (q.kind > RT_TEXELS_JPEG) return fail(RT_ERR_INVALID_ARGUMENT, who + "unknown kind");
+        if (q.flags & ~RT_TEXELS_TOP_FIRST) return fail(RT_ERR_INVALID_ARGUMENT, who + "unknown flag bit");
+        if (q.kind == RT_TEXELS_RECORD) continue;
+        const rt_texture &t = textures[i];
+        if (t.kind != RT_TEXTURE_IMAGE) return fail(RT_ERR_INVALID_ARGUMENT, who + "texels for a texture that is not an image");
+        if (!q.data) return fail(RT_ERR_INVALID_ARGUMENT, who + "data is NULL");
+        if (q.kind == RT_TEXELS_DEVICE && t.width > 0 && t.height > 0 && q.bytes < rtt::image_bytes(t.width, t.height))
+            return fail(RT_ERR_INVALID_ARGUMENT, who + "bytes is below width * height * 3");
+        ts.external[i] = 1;
+    }
+    return RT_OK;
+}
+// The JPEG sources' headers, on the host: rt_decode_jpeg's refusals, and the file's size against the record's.
+static int parse_sources(const rt_texture *textures, size_t n_textures, TexelSources &ts) {
+    for (size_t i = 0; i < n_textures; ++i) {
+        const rt_texels_source &q = ts.src[i];
+        if (q.kind != RT_TEXELS_JPEG) continue;
+        const std::string who = "texture " + std::to_string(i) + ": ";
+        if (q.bytes == 0) return fail(RT_ERR_INVALID_ARGUMENT, who + "jpeg: no SOI marker at byte 0");
+        ts.jpeg[i].reset(new rtj::Parsed());
+        std::string err;
+        const int rc = rtj::parse((const uint8_t *) q.data, q.bytes, *ts.jpeg[i], err);
+        if (rc != RT_OK) return fail(rc, who + err);
+        const rtj::Frame &f = ts.jpeg[i]->f;
+        if ((int64_t) f.W != (int64_t) textures[i].width || (int64_t) f.H != (int64_t) textures[i].height)
+            return fail(RT_ERR_INVALID_ARGUMENT, who + "the jpeg is " + std::to_string(f.W) + " x " + std::to_string(f.H) + ", the record " +
+                                                     std::to_string(textures[i].width) + " x " + std::to_string(textures[i].height));
+    }
+    return RT_OK;
+}
+
+// of_image_kernel over `units` 16-byte units from unit0 on.  table: device memory (n entries), or NULL with the one entry by value.
+static int launch_of_image(bool aligned, const rtt::ImageEntry *table, uint32_t n, const rtt::ImageEntry &one, uint8_t *blob, uint64_t unit0, uint64_t units, hipStream_t st) {
+    if (units == 0u) return RT_OK;
+    const uint64_t grid = (units + RTXK_BLOCK - 1u) / RTXK_BLOCK;
+    if (grid > 0x7FFFFFFFull) return fail(RT_ERR_UNSUPPORTED, "the image is too large for one launch");
+    if (aligned) hipLaunchKernelGGL(rtxk::of_image_kernel<true>, dim3((unsigned) grid), dim3(RTXK_BLOCK), 0, st, table, n, one, blob, unit0, units);
+    else hipLaunchKernelGGL(rtxk::of_image_kernel<false>, dim3((unsigned) grid), dim3(RTXK_BLOCK), 0, st, table, n, one, blob, unit0, units);
+    HIP_TRY(hipGetLastError());
+    g_last_texture_plan[5] += 1;
+    return RT_OK;
+}
+
+static int place_texels(const rth::HostScene &h, const rt_texture *textures, size_t n_textures, const TexelSources &ts, hipStream_t st, unsigned char **out) {
+    int64_t *plan = g_last_texture_plan;
+    for (int k = 0; k < 8; ++k) plan[k] = 0;
+    plan[0] = (int64_t) n_textures; plan[4] = (int64_t) h.texelBytes;
+    *out = nullptr;
+    DeviceBlock blob;
+    StreamScratch sc;
+    sc.st = st;
+    if (h.texelBytes) HIP_TRY(hipMalloc((void **) &blob.p, (size_t) h.texelBytes));
+    std::vector<rtt::ImageEntry> table;
+    bool any = false;
+    for (size_t i = 0; i < n_textures; ++i) {
+        if (textures[i].kind != RT_TEXTURE_IMAGE) continue;
+        const rt_texels_source &q = ts.src[i];
+        const int32_t w = textures[i].width, hgt = textures[i].height;
+        const uint64_t bytes = rtt::image_bytes(w, hgt), padded = rtt::padded_bytes(w, hgt);
+        rtt::ImageEntry e{};
+        e.off = h.texRecs[i].texel_off; e.width = w; e.height = hgt;
+        ++plan[1];
+        if (q.kind == RT_TEXELS_RECORD) { // as the existing routes: the record's host texels, already img.[y]
+            HIP_TRY(hipMemcpyAsync(blob.p + e.off, textures[i].texels, (size_t) bytes, hipMemcpyHostToDevice, st));
+            if (padded > bytes) HIP_TRY(hipMemsetAsync(blob.p + e.off + bytes, 0, (size_t) (padded - bytes), st));
+            plan[6] += (int64_t) bytes;
+        } else if (q.kind == RT_TEXELS_DEVICE) {
+            e.src = (const uint8_t *) q.data;
+            e.flags = RTX_FROM_DEVICE | (q.flags & RT_TEXELS_TOP_FIRST ? RTX_TOP_FIRST : 0u);
+            ++plan[2]; any = true;
+        } else { // a JPEG: decoded by the device decoder into scratch of this stream, top first
+            const rtj::Parsed &ps = *ts.jpeg[i];
+            if (rtj::marker_flags(ps)) return fail(RT_ERR_INVALID_ARGUMENT, rtj::stream_error(rtj::marker_flags(ps)));
+            uint8_t *bitmap = nullptr;
+            RT_TRY(sc.get(&bitmap, (size_t) bytes));
+            int64_t jplan[8];
+            const int rc = jpeg_on_device((const uint8_t *) q.data, ps, (uint32_t) RTJ_DEFAULT_SUBSEQUENCE, bitmap, st, true, jplan);
+            if (rc != RT_OK) { (void) hipStreamSynchronize(st); return rc; } // (a damaged stream: the call waits for what it enqueued, then fails)
+            e.src = bitmap;
+            e.flags = RTX_FROM_DEVICE | RTX_TOP_FIRST;
+            ++plan[3]; any = true;
+        }
+        table.push_back(e);
+    }
+    if (any) {
+        rtt::ImageEntry *d_table = nullptr;
+        RT_TRY(sc.get(&d_table, table.size()));
+        HIP_TRY(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(rtt::ImageEntry), hipMemcpyHostToDevice, st)); // (`table` outlives the wait below)
+        RT_TRY(launch_of_image(true, d_table, (uint32_t) table.size(), rtt::ImageEntry{}, blob.p, 0u, h.texelBytes / RTX_UNIT, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = blob.release();
+    return RT_OK;
+}
+
+// The walk_tree option of a create call (-1 / absent: the process default); false: not a creation option
+static bool creation_walk(const rt_scene_options *options, int &walk) {
+    walk = -1;
+    if (options && options->struct_size >= offsetof(rt_scene_options, walk_tree) + sizeof(int32_t)) walk = options->walk_tree;
+    if (walk == -1) walk = g_walk_tree.load();
+    return walk == RT_WALK_TREE_SAH || walk == RT_WALK_TREE_REFERENCE;
+}
+
+extern "C" {
+
+int rt_scene_create_textures(const rt_hittable *hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                             const rt_texels_source *sources, const rt_scene_options *options, int32_t device, void *stream, rt_scene **out) {
+    if (!sources) return rt_scene_create_gpu_trees(hittables, n_hittables, textures, n_textures, options, device, out);
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (n_textures > 0 && !textures) return fail(RT_ERR_INVALID_ARGUMENT, "textures is NULL");
+    int walk = -1;
+    if (!creation_walk(options, walk)) return fail(RT_ERR_INVALID_ARGUMENT, "walk_tree must be RT_WALK_TREE_SAH, RT_WALK_TREE_REFERENCE or -1");
+    return guarded("rt_scene_create_textures", [&]() -> int {
+        TexelSources ts;
+        RT_TRY(check_sources(textures, n_textures, sources, ts));
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        RT_TRY(parse_sources(textures, n_textures, ts));
+        return scene_from_host_records("rt_scene_create_textures", hittables, n_hittables, textures, n_textures, walk, device, true, out, &ts, (hipStream_t) stream);
+    });
+}
+
+int rt_scene_create_device_textures(int32_t device, const void *d_hittables, size_t n_hittables, const rt_texture *textures, size_t n_textures,
+                                    const rt_texels_source *sources, const rt_scene_options *options, void *stream, rt_scene **out) {
+    if (!sources) return rt_scene_create_device(device, d_hittables, n_hittables, textures, n_textures, options, stream, out);
+    if (n_hittables > 0 && !d_hittables) return fail(RT_ERR_INVALID_ARGUMENT, "d_hittables is NULL");
+    if (n_textures > 0 && !textures) return fail(RT_ERR_INVALID_ARGUMENT, "textures is NULL");
+    if ((uintptr_t) d_hittables % 8u) return fail(RT_ERR_INVALID_ARGUMENT, "d_hittables is not 8-byte aligned");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    int walk = -1;
+    if (!creation_walk(options, walk)) return fail(RT_ERR_INVALID_ARGUMENT, "walk_tree must be RT_WALK_TREE_SAH, RT_WALK_TREE_REFERENCE or -1");
+    return guarded("rt_scene_create_device_textures", [&]() -> int {
+        TexelSources ts;
+        RT_TRY(check_sources(textures, n_textures, sources, ts));
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        RT_TRY(parse_sources(textures, n_textures, ts));
+        return scene_on_device(device, (const rt_hittable *) d_hittables, n_hittables, textures, n_textures, walk, (hipStream_t) stream, out, &ts);
+    });
+}
+
+int rt_of_image_device(int32_t device, const void *d_bitmap, int32_t width, int32_t height, void *d_texels, size_t capacity, void *stream) {
+    if (!d_bitmap || !d_texels) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "width and height must be positive");
+    const uint64_t bytes = rtt::image_bytes(width, height);
+    if ((uint64_t) capacity < bytes) return fail(RT_ERR_INVALID_ARGUMENT, "capacity is below width * height * 3");
+    const uintptr_t a = (uintptr_t) d_bitmap, b = (uintptr_t) d_texels;
+    if (a < b + bytes && b < a + bytes) return fail(RT_ERR_INVALID_ARGUMENT, "d_texels overlaps d_bitmap: the reversal is not done in place");
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    rtt::ImageEntry e{};
+    e.src = (const uint8_t *) d_bitmap; e.width = width; e.height = height; e.flags = RTX_FROM_DEVICE | RTX_TOP_FIRST;
+    return launch_of_image(false, nullptr, 1u, e, (uint8_t *) d_texels, 0u, rtt::padded_bytes(width, height) / RTX_UNIT, (hipStream_t) stream);
+}
+
+int rt_scene_set_texels_device(rt_scene *scene, int32_t texture, int32_t device, const void *d_rgb, size_t bytes, uint32_t flags, void *stream) {
+    if (!scene || !d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (flags & ~RT_TEXELS_TOP_FIRST) return fail(RT_ERR_INVALID_ARGUMENT, "unknown flag bit");
+    return guarded("rt_scene_set_texels_device", [&]() -> int {
+        std::lock_guard<std::mutex> lock(scene->mu);
+        rth::HostScene &h = scene->host;
+        if (texture < 0 || (size_t) texture >= h.texRecs.size()) return fail(RT_ERR_INVALID_ARGUMENT, "texture index out of range");
+        const rtd::TexRec &r = h.texRecs[(size_t) texture];
+        if (r.kind != RT_TEXTURE_IMAGE) return fail(RT_ERR_INVALID_ARGUMENT, "texture " + std::to_string(texture) + " is not an image");
+        if ((uint64_t) bytes < rtt::image_bytes(r.width, r.height)) return fail(RT_ERR_INVALID_ARGUMENT, "bytes is below width * height * 3");
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        for (const auto &kv : scene->dev)
+            if (kv.first != device) return fail(RT_ERR_UNSUPPORTED, "the scene has a copy on another device: its texels cannot be replaced");
+        DeviceScene *ds = nullptr;
+        RT_TRY(device_scene_locked(scene, device, &ds));
+        rtt::ImageEntry e{};
+        e.off = r.texel_off; e.src = (const uint8_t *) d_rgb; e.width = r.width; e.height = r.height;
+        e.flags = RTX_FROM_DEVICE | (flags & RT_TEXELS_TOP_FIRST ? RTX_TOP_FIRST : 0u);
+        RT_TRY(launch_of_image(true, nullptr, 1u, e, ds->texels, e.off / RTX_UNIT, rtt::padded_bytes(r.width, r.height) / RTX_UNIT, (hipStream_t) stream));
+        // the host's blob is out of date from here: dropped, and fetched again when something wants it
+        std::vector<uint8_t>().swap(h.texelBlob);
+        scene->texelsOnHost = false;
+        scene->texDevice = device;
+        scene->mirrored.store(false, std::memory_order_release);
+        return RT_OK;
+    });
+}
+
+int rt_dev_scene_texels(const rt_scene *scene, int32_t device, void *out, size_t cap, size_t *bytes, uint32_t *texel_off) {
+    if (!scene || !bytes) return fail(RT_ERR_INVALID_ARGUMENT, "NULL argument");
+    return guarded("rt_dev_scene_texels", [&]() -> int {
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        DeviceScene *ds = nullptr;
+        RT_TRY(device_scene(const_cast<rt_scene *>(scene), device, &ds));
+        const rth::HostScene &h = scene->host;
+        *bytes = (size_t) h.texelBytes;
+        if (texel_off)
+            for (size_t i = 0; i < h.texRecs.size(); ++i) texel_off[i] = h.texRecs[i].kind == RT_TEXTURE_IMAGE ? h.texRecs[i].texel_off : UINT32_MAX;
+        if (!out) return RT_OK;
+        if (cap < h.texelBytes) return fail(RT_ERR_INVALID_ARGUMENT, "out is smaller than the texels");
+        HIP_TRY(hipDeviceSynchronize());
+        if (h.texelBytes) HIP_TRY(hipMemcpy(out, ds->texels, (size_t) h.texelBytes, hipMemcpyDeviceToHost));
+        return RT_OK;
+    });
+}
+
+int rt_dev_last_texture_plan(int64_t out[8]) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    for (int i = 0; i < 8; ++i) out[i] = g_last_texture_plan[i];
     return RT_OK;
 }
 

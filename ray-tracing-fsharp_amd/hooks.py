@@ -199,6 +199,27 @@ def scene_has_host_mirror(scene: Scene) -> bool:
     return bool(lib.rt_dev_scene_has_host_mirror(scene.handle))
 
 
+def scene_texels(scene: Scene, device=0):
+    """rt_dev_scene_texels: (the texel blob as `device` holds it, every record's texel_off as uint32 -- 0xFFFFFFFF: not an image)."""
+    size = C.c_size_t(0)
+    offs = np.zeros(max(1, scene.info()["n_textures"]), np.uint32)
+    check(lib.rt_dev_scene_texels(scene.handle, device, None, 0, C.byref(size), _u32(offs)))
+    out = np.zeros(size.value, np.uint8)
+    check(lib.rt_dev_scene_texels(scene.handle, device, out.ctypes.data if out.size else None, out.size, C.byref(size), _u32(offs)))
+    return out, offs[:scene.info()["n_textures"]]
+
+
+TEXTURE_PLAN = ("textures", "images", "device_sourced", "jpeg_sourced", "blob_bytes", "launches", "bytes_host_to_device", "bytes_device_to_host")
+
+
+def texture_plan() -> dict:
+    """rt_dev_last_texture_plan: the calling thread's last Scene.make with ofImageDevice / ofJpeg textures, and what was launched and
+    copied since (set_image, the lazy fetch of the host's texels)."""
+    w = (C.c_int64 * 8)()
+    check(lib.rt_dev_last_texture_plan(w))
+    return dict(zip(TEXTURE_PLAN, w))
+
+
 JPEG_PLAN = ("subsequence_bytes", "subsequences", "rounds", "decodes", "blocks", "boundaries")
 
 

@@ -118,6 +118,9 @@ class _ParamTex:
     grid: float = 0.0
     image: Optional[np.ndarray] = None  # [H, W, 3] uint8, img.[y].[x] order (Texture.fs:63-67)
     ramp: Tuple[int, int, int] = (0, 0, 0)
+    bitmap: object = None          # ofImageDevice: a torch uint8 [H, W, 3] tensor on a GPU, rows top first (the device reverses them)
+    jpeg: Optional[bytes] = None   # ofJpeg: a baseline JPEG file's bytes (decoded on the device, rows reversed there)
+    size: Tuple[int, int] = (0, 0)  # (height, width) of a bitmap / jpeg image
 
 
 class ParameterisedTexture:  # Texture.fs:19-24
@@ -143,6 +146,29 @@ class ParameterisedTexture:  # Texture.fs:19-24
         if _is_torch(bitmap_rows_top_first):
             bitmap_rows_top_first = bitmap_rows_top_first.cpu().numpy()
         return ParameterisedTexture.Image(np.ascontiguousarray(bitmap_rows_top_first[::-1]))
+
+    @staticmethod
+    def ofImageDevice(bitmap) -> _ParamTex:
+        """ofImage for a bitmap that is in device memory: a torch uint8 tensor [height, width, 3] on a GPU, rows top first as LoadImage
+        leaves them.  It is made contiguous on its device and kept; the rows are reversed on the GPU when the scene is made (Scene.make ->
+        rt_scene_create_textures), so the texels never visit the host."""
+        if not _is_torch(bitmap):
+            raise TypeError(f"bitmap must be a torch tensor on a GPU, not {type(bitmap).__name__} (ofImage takes numpy arrays)")
+        if bitmap.dtype != _torch().uint8:
+            raise TypeError(f"bitmap must have dtype torch.uint8, not {bitmap.dtype}")
+        if bitmap.ndim != 3 or bitmap.shape[2] != 3 or bitmap.shape[0] < 1 or bitmap.shape[1] < 1:
+            raise ValueError(f"bitmap must have shape [height, width, 3], not {list(bitmap.shape)}")
+        if not bitmap.is_cuda:
+            raise ValueError("bitmap must be on a GPU (ofImage takes a bitmap in host memory)")
+        return _ParamTex(A.RT_TEXTURE_IMAGE, bitmap=bitmap.contiguous(), size=(int(bitmap.shape[0]), int(bitmap.shape[1])))
+
+    @staticmethod
+    def ofJpeg(data: bytes) -> _ParamTex:
+        """ofImage (LoadImage.fromBytes data) without the bitmap ever being in host memory: the file is decoded on the GPU when the scene is
+        made.  The header is read here (rt_jpeg_get_info), so a file LoadImage refuses is refused here, with the same text."""
+        data = bytes(data)
+        info = LoadImage.info(data)
+        return _ParamTex(A.RT_TEXTURE_IMAGE, jpeg=data, size=(int(info["height"]), int(info["width"])))
 
     @staticmethod
     def UvRamp(red, green, blue) -> _ParamTex:
@@ -313,18 +339,36 @@ class Camera:  # Camera.fs:3-28; `dataclasses.replace(camera, BounceDepth=50)` i
 
 # ---- flatten hittables into the ABI arrays --------------------------------------------------------------------------
 def flatten_hittables(objects: Sequence[Hittable]):
-    """-> (rt_hittable array, rt_texture array, keepalive list)."""
+    """-> (rt_hittable array, count, rt_texture array, count, keepalive list).  Textures made by ofImageDevice / ofJpeg need the sources
+    that hittable_records(objects, textures=True) returns with them."""
+    return _flatten(objects)[:5]
+
+
+def _flatten(objects: Sequence[Hittable]):
+    """flatten_hittables' five, then the rt_texels_source array (None when every image's texels are host arrays) and {id(texture): index of
+    its first record, the texture)}."""
     texs: List[A.rt_texture] = []
-    keep: List[np.ndarray] = []
+    keep: list = []
+    srcs: List[A.rt_texels_source] = []
+    index: dict = {}
 
     def add_param(t: _ParamTex) -> int:
         r = A.rt_texture()
         r.kind = t.kind
         r.even = r.odd = -1
         r.map_radius = 1.0
+        src = A.rt_texels_source()
         if t.kind == A.RT_TEXTURE_CHECKERED:
             e, o = add_param(t.even), add_param(t.odd)  # children first: indices smaller than the parent's
             r.even, r.odd, r.grid_size = e, o, t.grid
+        elif t.kind == A.RT_TEXTURE_IMAGE and t.bitmap is not None:
+            keep.append(t.bitmap)
+            r.height, r.width = t.size
+            src = A.rt_texels_source(A.RT_TEXELS_DEVICE, A.RT_TEXELS_TOP_FIRST, t.bitmap.data_ptr(), t.bitmap.numel())
+        elif t.kind == A.RT_TEXTURE_IMAGE and t.jpeg is not None:
+            keep.append(t.jpeg)
+            r.height, r.width = t.size
+            src = A.rt_texels_source(A.RT_TEXELS_JPEG, A.RT_TEXELS_TOP_FIRST, C.cast(C.c_char_p(t.jpeg), C.c_void_p), len(t.jpeg))
         elif t.kind == A.RT_TEXTURE_IMAGE:
             keep.append(t.image)
             r.height, r.width = int(t.image.shape[0]), int(t.image.shape[1])
@@ -333,6 +377,8 @@ def flatten_hittables(objects: Sequence[Hittable]):
             r.ramp_src[:] = t.ramp
         r.rgb[:] = t.pixel
         texs.append(r)
+        srcs.append(src)
+        index.setdefault(id(t), (len(texs) - 1, t))  # (t is held so that its id stays its own)
         return len(texs) - 1
 
     hs = (A.rt_hittable * max(1, len(objects)))()
@@ -360,7 +406,8 @@ def flatten_hittables(objects: Sequence[Hittable]):
             o.point[:] = h.sphere.Centre
             o.radius = h.sphere.Radius
     tex_arr = (A.rt_texture * max(1, len(texs)))(*texs) if texs else (A.rt_texture * 1)()
-    return hs, len(objects), tex_arr, len(texs), keep
+    sources = (A.rt_texels_source * len(srcs))(*srcs) if any(q.kind != A.RT_TEXELS_RECORD for q in srcs) else None
+    return hs, len(objects), tex_arr, len(texs), keep, sources, index
 
 
 # rt_hittable as a numpy structured dtype: what Scene.make_device takes (a numpy array of it, or its bytes as a uint8 tensor [n, itemsize]
@@ -381,14 +428,24 @@ class TextureTable(NamedTuple):
     records: object  # a ctypes array of rt_texture
     count: int
     keep: list       # the texel arrays the records point into
+    sources: object = None  # a ctypes array of rt_texels_source, one per record, when a texture came from ofImageDevice / ofJpeg
+    index: object = None    # {id(ParameterisedTexture value): (index of its first record, the value)} (Scene.texture_index)
 
 
 def hittable_records(objects: Sequence[Hittable], textures: bool = False):
     """The rt_hittable array Scene.make builds from `objects`, as a numpy array of HITTABLE_DTYPE (a copy).  textures=True: (records, the
     TextureTable their texture indices refer to)."""
-    hs, n, tex, ntex, keep = flatten_hittables(objects)
+    hs, n, tex, ntex, keep, sources, index = _flatten(objects)
     rec = np.frombuffer(hs, dtype=HITTABLE_DTYPE, count=n).copy()
-    return (rec, TextureTable(tex, ntex, keep)) if textures else rec
+    return (rec, TextureTable(tex, ntex, keep, sources, index)) if textures else rec
+
+
+def _sources_device(keep) -> Optional[int]:
+    """The device the ofImageDevice bitmaps of a table are on (None: it has none); ValueError when they are on several."""
+    devices = sorted({t.device.index for t in keep if _is_torch(t)})
+    if len(devices) > 1:
+        raise ValueError(f"the textures' bitmaps are on different devices: {devices}")
+    return devices[0] if devices else None
 
 
 # ---- Domain.fs ----------------------------------------------------------------------------------------------------
@@ -460,9 +517,11 @@ class TracePaths(NamedTuple):
 
 
 class Scene:
-    def __init__(self, handle: int, keep):
+    def __init__(self, handle: int, keep, texture_index=None):
         self._h = C.c_void_p(handle)
         self._keep = keep
+        self._texture_index = texture_index or {}
+        self._images = {}  # texture index -> the tensor set_image last enqueued from
         self._local = threading.local()
 
     @property
@@ -486,11 +545,22 @@ class Scene:
         """walk_tree: None = the process default (set_walk_tree), "sah" or "reference" = this scene's own choice (rt_scene_create_ex).
         tree_device: None = BoundingBoxTree.make's tree is built on the host; a device index = on that GPU (rt_scene_create_gpu_tree): the
         same scene, node for node.  walk_tree_device: a device index = the surface-area walk tree is built on that GPU too
-        (rt_scene_create_gpu_trees; tree_device defaults to the same device and must be it): the same scene again."""
-        hs, n, tex, ntex, keep = flatten_hittables(objects)
+        (rt_scene_create_gpu_trees; tree_device defaults to the same device and must be it): the same scene again.
+        With textures from ofImageDevice / ofJpeg the scene is made by rt_scene_create_textures on the bitmaps' device (0 when there are
+        only JPEGs) and torch's current stream there: both trees on that GPU, the texels placed there without a host trip; a tree_device /
+        walk_tree_device that is given must be that device."""
+        hs, n, tex, ntex, keep, sources, index = _flatten(objects)
         out = C.c_void_p()
         opt = None if walk_tree is None else A.rt_scene_options({"sah": A.RT_WALK_TREE_SAH, "reference": A.RT_WALK_TREE_REFERENCE}[walk_tree])
-        if walk_tree_device is not None:
+        if sources is not None:
+            device = _sources_device(keep)
+            device = 0 if device is None else device
+            for name, given in (("tree_device", tree_device), ("walk_tree_device", walk_tree_device)):
+                if given is not None and int(given) != device:
+                    raise ValueError(f"{name} {given} is not the textures' device {device}")
+            st = _torch().cuda.current_stream(_torch().device("cuda", device)).cuda_stream
+            check(lib.rt_scene_create_textures(hs, n, tex, ntex, sources, _ref(opt), device, st, C.byref(out)))
+        elif walk_tree_device is not None:
             if tree_device is not None and int(tree_device) != int(walk_tree_device):
                 raise ValueError(f"tree_device {tree_device} and walk_tree_device {walk_tree_device} must be the same device")
             check(lib.rt_scene_create_gpu_trees(hs, n, tex, ntex, _ref(opt), int(walk_tree_device), C.byref(out)))
@@ -500,7 +570,7 @@ class Scene:
             check(lib.rt_scene_create(hs, n, tex, ntex, C.byref(out)))
         else:
             check(lib.rt_scene_create_ex(hs, n, tex, ntex, C.byref(opt), C.byref(out)))
-        return Scene(out.value, keep)
+        return Scene(out.value, keep, index)
 
     @staticmethod
     def make_device(records, textures=(), walk_tree: Optional[str] = None, device: Optional[int] = None, stream: Optional[int] = None) -> "Scene":
@@ -511,8 +581,9 @@ class Scene:
         (hittable_records(objects, textures=True)) or nothing.  A Scene holds no Python list of its objects on any route (only the texel
         arrays its texture records point into), so nothing else changes for a scene made this way."""
         opt = None if walk_tree is None else A.rt_scene_options({"sah": A.RT_WALK_TREE_SAH, "reference": A.RT_WALK_TREE_REFERENCE}[walk_tree])
+        sources, index = None, None
         if isinstance(textures, TextureTable):
-            tex, ntex, keep = textures.records, textures.count, list(textures.keep)
+            tex, ntex, keep, sources, index = textures.records, textures.count, list(textures.keep), textures.sources, textures.index
         elif len(textures) == 0:
             tex, ntex, keep = None, 0, []
         else:
@@ -536,8 +607,34 @@ class Scene:
             route = _Tensors(where)
         st = _torch().cuda.current_stream(route.where).cuda_stream if stream is None else int(stream)
         out = C.c_void_p()
-        check(lib.rt_scene_create_device(route.device, route.ptr(t) if t.shape[0] else None, t.shape[0], tex, ntex, _ref(opt), st, C.byref(out)))
-        return Scene(out.value, keep)
+        if sources is not None:  # (textures from ofImageDevice / ofJpeg: rt_scene_create_device_textures, the bitmaps on the records' device)
+            held = _sources_device(keep)
+            if held is not None and held != route.device:
+                raise ValueError(f"the textures' bitmaps are on device {held}, the records on device {route.device}")
+            check(lib.rt_scene_create_device_textures(route.device, route.ptr(t) if t.shape[0] else None, t.shape[0], tex, ntex, sources, _ref(opt), st,
+                                                      C.byref(out)))
+        else:
+            check(lib.rt_scene_create_device(route.device, route.ptr(t) if t.shape[0] else None, t.shape[0], tex, ntex, _ref(opt), st, C.byref(out)))
+        return Scene(out.value, keep, index)
+
+    def texture_index(self, texture) -> int:
+        """The index of the texture record Scene.make / hittable_records made for a ParameterisedTexture value (its first, when several
+        hittables share it): what set_image takes.  Records are numbered in the order of the hittables, a Checkered's children before it."""
+        try:
+            return self._texture_index[id(texture)][0]
+        except KeyError:
+            raise KeyError("this scene was not made from that texture value") from None
+
+    def set_image(self, texture_index: int, bitmap, top_first: bool = True, stream: Optional[int] = None) -> None:
+        """rt_scene_set_texels_device: replace the texels of image record `texture_index` by `bitmap`, a torch uint8 [height, width, 3]
+        tensor on a GPU of the record's own size (top_first: rows as a decoder leaves them; False: already img.[y]).  Enqueued on torch's
+        current stream on the bitmap's device (or `stream`); renders enqueued there afterwards see the new texels.  The scene keeps the
+        tensor until the next set_image of that record."""
+        t = ParameterisedTexture.ofImageDevice(bitmap).bitmap
+        st = _torch().cuda.current_stream(t.device).cuda_stream if stream is None else int(stream)
+        check(lib.rt_scene_set_texels_device(self._h, int(texture_index), t.device.index, t.data_ptr(), t.numel(),
+                                             A.RT_TEXELS_TOP_FIRST if top_first else 0, st))
+        self._images[int(texture_index)] = t
 
     @property
     def handle(self) -> C.c_void_p:

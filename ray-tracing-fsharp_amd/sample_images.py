@@ -242,6 +242,27 @@ def earth(earthmap_rows_top_first):
     return (objs, camera) + _extent(aspect, 400)
 
 
+def earth_device(earthmap, device: int = 0):
+    """earth's objects with the bitmap's texels never in host memory: `earthmap` is the path of a baseline JPEG or its bytes (ofJpeg: decoded
+    on the GPU when the scene is made) or a decoded bitmap as a torch uint8 [height, width, 3] tensor on a GPU (ofImageDevice).  `device`
+    is where a numpy bitmap is put; a tensor stays where it is, and Scene.make decodes a JPEG on device 0."""
+    if isinstance(earthmap, (str, os.PathLike)):
+        with open(os.fspath(earthmap), "rb") as f:
+            earthmap = f.read()
+    if isinstance(earthmap, (bytes, bytearray, memoryview)):
+        texture = ParameterisedTexture.ofJpeg(bytes(earthmap))
+    else:
+        if isinstance(earthmap, np.ndarray):
+            import torch
+            earthmap = torch.from_numpy(np.ascontiguousarray(earthmap, dtype=np.uint8)).to(torch.device("cuda", device))
+        texture = ParameterisedTexture.ofImageDevice(earthmap)
+    objs, camera, w, h = earth(np.zeros((1, 1, 3), np.uint8))
+    sphere = objs[0].sphere
+    tex = ParameterisedTexture.toTexture((1.0, Point.make(0.0, 0.0, 0.0)), texture)
+    objs[0] = Hittable.Sphere(Sphere.make(SphereStyle.LambertReflection(1.0, tex), sphere.Centre, sphere.Radius))
+    return objs, camera, w, h
+
+
 # ---- BASELINE.json configs (SURVEY.md 8d) ----------------------------------------------------------------------------
 def config1_empty():
     """C1 (ii): empty scene, maxW=100, maxH=50, 1 spp -> every pixel Black with exactly one sample (F2 in SURVEY.md)."""
