@@ -809,6 +809,79 @@ int rt_resume_ppm(const rt_scene *scene, const rt_camera *camera, int32_t max_wi
                   uint64_t seed, int32_t device, uint32_t flags, const char *map_path, int32_t gamma_correct, const char *out_path,
                   const rt_render_options *options, rt_stats *stats);
 
+/* ---- Render jobs: live progress, a stop request, a resumable partial frame (DESIGN.md "Render jobs") ----
+ * Scene.render ticks its progress bar once per finished row (Scene.fs:196-236, the tick at :232) and ImageOutput.resume spills finished
+ * pixels eagerly (ImageOutput.fs:131-161), so a reference run can be watched, interrupted and picked up again.  A render job is the
+ * producer half of that on the device: rt_render_device_ex's render of one shard, launched and left running, whose progress the host can
+ * read, which the host can ask to stop, and which then leaves a PARTIAL frame -- every pixel either the frame's own, bit for bit, or
+ * absent and zero -- together with the presence map that rt_render_job_finish, rt_missing_pixels_device and the pixel-map formatter below
+ * take.  The kernels are stoppable variants of the frame passes under symbols of their own (render_job_kernel); they POLL a word of
+ * pinned host memory once per work reservation and never wait on the host.  Added symbols and structs only: RT_ABI_VERSION stays 7. */
+typedef struct rt_render_job rt_render_job;
+typedef struct rt_job_progress {
+    uint32_t struct_size;  /* set to sizeof(rt_job_progress) by the caller */
+    int32_t state;         /* 0 running, 1 stop requested, 2 finished */
+    int64_t pixels_total;  /* n_rows * cols */
+    int64_t pixels_final;  /* pixels that have every sample the frame gives them; never decreases, never exceeds pixels_total */
+} rt_job_progress;
+typedef struct rt_job_result {
+    uint32_t struct_size;  /* set to sizeof(rt_job_result) by the caller */
+    int32_t complete;      /* 1: every pixel is present */
+    int32_t stop_requested;
+    int64_t pixels_total, n_present;
+} rt_job_result;
+
+/* Scene.render (Scene.fs:196-236) of one shard as a job whose spill ImageOutput.resume (ImageOutput.fs:131-161) would have left.
+ * Argument checks are rt_render_device_ex's, from the same check list, then a NULL d_present or `out`, a frame of more than INT32_MAX
+ * pixels (rt_render_job_finish lists pixels as int32) and RT_RENDER_COUNTERS (RT_ERR_UNSUPPORTED: there is no counting variant) -- all
+ * before any device call, and nothing is written when one fails.  The launch plan is rt_render_device_ex's for the same arguments
+ * (blocks of 512 or 768 threads run at 1024).  Everything -- pass A, the ordering, pass B, the finishing kernels -- is enqueued on
+ * `stream` up front and the call returns right after the launches.  The scene, the camera's values (copied), d_accum (n_rows*cols*16),
+ * d_rgb (n_rows*cols*3, may be NULL) and d_present (n_rows*cols bytes) must outlive the job. */
+int rt_render_job_start(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord, uint64_t seed,
+                        int32_t device, int32_t row_first, int32_t row_stride, int32_t n_rows, uint32_t flags, void *d_accum,
+                        void *d_rgb /* may be NULL */, void *d_present /* n_rows*cols bytes */, void *stream,
+                        const rt_render_options *options, rt_render_job **out);
+/* The tick of Scene.fs:232 (the progress bar of Scene.fs:196-236), read instead of called; the count is of the pixels an eager spill
+ * (ImageOutput.fs:131-161) would hold: no device call, never blocks.
+ * pixels_final never decreases across calls on one job; after rt_render_job_wait it equals n_present. */
+int rt_render_job_progress(const rt_render_job *job, rt_job_progress *progress);
+/* Asks the job's kernels to reserve no more work (the interrupt of a Scene.fs:196-236 run whose ImageOutput.fs:131-161 spill survives):
+ * one store to the polled word.  Idempotent; from any thread, also while another is in rt_render_job_wait.  Work already reserved is
+ * finished: at most one unit (fused, pass A) or two ranges (pass B) per wave. */
+int rt_render_job_stop(rt_render_job *job);
+/* Synchronises the job's stream and reports what is there (Scene.fs:196-236 up to the interrupt; ImageOutput.fs:131-161's spill):
+ * d_present written in full, 0 or 1; every present pixel's PixelStats and colour rt_render_device's, bit for bit; every absent
+ * pixel's zero.  stats (may be NULL): pixels = n_present, samples = every sample traced (those of discarded pixels included),
+ * kernel_ms, total_ms; the other fields zero.  May be called again: the same answer. */
+int rt_render_job_wait(rt_render_job *job, rt_job_result *result, rt_stats *stats);
+/* Picks the frame up again (Program.fs's resume of ImageOutput.fs:131-161's spill; the pixels Scene.fs:196-236 had not reached): after
+ * rt_render_job_wait (else RT_ERR_INVALID_ARGUMENT) lists the absent pixels, renders them as a pixel list on `stream`, scatters
+ * PixelStats and colour and sets every present byte.  Synchronises.  Afterwards d_accum and d_rgb are rt_render_device's byte for byte,
+ * whenever and wherever the stop landed.  A complete job renders nothing.  stats (may be NULL) as rt_render_pixels fills them. */
+int rt_render_job_finish(rt_render_job *job, void *stream, rt_stats *stats);
+/* Waits for the job's stream if nobody has, then frees the job (Scene.fs:196-236's run is over; ImageOutput.fs:131-161's buffers are the
+ * caller's).  NULL is a no-op. */
+void rt_render_job_destroy(rt_render_job *job);
+/* Test hooks (Scene.fs:196-236 stopped at a chosen unit; ImageOutput.fs:131-161's spill made deterministic).  A budget for the NEXT job
+ * this thread starts: exactly units [0, limit_a) of the fused kernel / pass A and exactly list entries [0, limit_b) of pass B are
+ * rendered; -1 = no limit.  Consumed by that job. */
+int rt_dev_set_job_limits(int64_t limit_a, int64_t limit_b);
+/* The last job this thread waited for: passes, chunk (pixels per unit of the fused kernel / pass A), units_a, n_list, done_a, done_b,
+ * block, textured (Scene.fs:196-236's schedule and ImageOutput.fs:131-161's prefix; csrc/rt_job_plan.h defines the present set from these). */
+int rt_dev_last_job_plan(int64_t out[8]);
+
+/* ImageOutput.resume's records (ImageOutput.fs:131-161, the record at :145-155; the spill a Scene.fs:196-236 run leaves when it is
+ * interrupted) for the PRESENT pixels only, in row-major order: rt_format_pixel_map restricted to present[r*cols + c] != 0.  With every
+ * byte of `present` set the output is rt_format_pixel_map's.  Returns the length; writes when out is given and out_capacity holds it. */
+int64_t rt_format_pixel_map_present(const uint8_t *rgb, const uint8_t *present, int32_t rows, int32_t cols, uint8_t *out, size_t out_capacity);
+/* ... on the device (ImageOutput.fs:131-161 over a Scene.fs:196-236 partial frame): lengths, scan and write with the output stage's scan
+ * kernels, byte for byte the host formatter's.  rt_format_ppm_device's capacity rule: a buffer that is too small is found on the
+ * device, no byte is written, RT_ERR_INVALID_ARGUMENT when `bytes` is given, RT_OK and d_bytes > out_capacity otherwise. */
+int rt_format_pixel_map_present_device(int32_t device, const void *d_rgb, const void *d_present, int32_t rows, int32_t cols, void *d_out,
+                                       size_t out_capacity, void *d_bytes /* int64 on the device, may be NULL */, void *stream,
+                                       int64_t *bytes /* host; may be NULL */);
+
 /* ---- Runtime ------------------------------------------------------------------------------------- */
 int rt_device_count(void);         /* 0 when no HIP device is visible (never an error) */
 const char *rt_last_error(void);   /* thread-local message of the last failing call */

@@ -132,6 +132,23 @@ class rt_jpeg_stats(C.Structure):
         super().__init__(struct_size=C.sizeof(rt_jpeg_stats))
 
 
+class rt_job_progress(C.Structure):
+    """rt_render_job_progress: state 0 running, 1 stop requested, 2 finished."""
+    _fields_ = [("struct_size", C.c_uint32), ("state", C.c_int32), ("pixels_total", C.c_int64), ("pixels_final", C.c_int64)]
+
+    def __init__(self):
+        super().__init__(struct_size=C.sizeof(rt_job_progress))
+
+
+class rt_job_result(C.Structure):
+    """rt_render_job_wait."""
+    _fields_ = [("struct_size", C.c_uint32), ("complete", C.c_int32), ("stop_requested", C.c_int32), ("pixels_total", C.c_int64),
+                ("n_present", C.c_int64)]
+
+    def __init__(self):
+        super().__init__(struct_size=C.sizeof(rt_job_result))
+
+
 class rt_texels_source(C.Structure):
     """Where one texture record's texels come from (rt_scene_create_textures, rt_scene_create_device_textures)."""
     _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32), ("data", C.c_void_p),

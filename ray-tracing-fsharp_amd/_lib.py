@@ -176,6 +176,18 @@ SIGNATURES = {
                                 _P(A.rt_render_options), _P(A.rt_stats)]),
     "rt_resume_ppm": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_uint32, C.c_char_p, C.c_int32, C.c_char_p,
                                 _P(A.rt_render_options), _P(A.rt_stats)]),
+    "rt_render_job_start": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(A.rt_render_options), _P(C.c_void_p)]),
+    "rt_render_job_progress": (C.c_int, [C.c_void_p, _P(A.rt_job_progress)]),
+    "rt_render_job_stop": (C.c_int, [C.c_void_p]),
+    "rt_render_job_wait": (C.c_int, [C.c_void_p, _P(A.rt_job_result), _P(A.rt_stats)]),
+    "rt_render_job_finish": (C.c_int, [C.c_void_p, C.c_void_p, _P(A.rt_stats)]),
+    "rt_render_job_destroy": (None, [C.c_void_p]),
+    "rt_dev_set_job_limits": (C.c_int, [C.c_int64, C.c_int64]),
+    "rt_dev_last_job_plan": (C.c_int, [_P(C.c_int64)]),  # out[8]
+    "rt_format_pixel_map_present": (C.c_int64, [_u8p, _u8p, C.c_int32, C.c_int32, C.c_char_p, C.c_size_t]),
+    "rt_format_pixel_map_present_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                     C.c_void_p, _P(C.c_int64)]),
     "rt_tree_nodes": (C.c_int64, [C.c_size_t]),
     "rt_tree_depth": (C.c_int32, [C.c_size_t]),
     "rt_tree_lds_boxes": (C.c_int32, []),

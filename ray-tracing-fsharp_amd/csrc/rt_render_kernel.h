@@ -20,6 +20,7 @@
 #pragma once
 #include "rt_device.h"
 #include "rt_extend_map.h"
+#include "rt_job_plan.h"
 #include "rt_modes.h"
 
 namespace rtd {
@@ -87,6 +88,25 @@ struct RenderParams {
     double *cam_rays_out;          // [ray_n * cam_n_samples][6]: the camera ray itself, origin then unit direction; or null
     int32_t cam_sample_first, cam_n_samples;
 };
+
+// A render job (render_job_kernel, rt_render_job_*; DESIGN.md "Render jobs"): what the stoppable variant of a frame pass reads and
+// publishes beside its RenderParams.  `stop` and `progress` are words of the job's control block -- pinned, mapped, coherent host
+// memory -- read and written with relaxed system-scope atomics; the kernel POLLS the stop word once per reservation and never waits on
+// it.  `done` is the device's own running total of final pixels (agent scope): the mirror may regress when stores race, this cannot.
+struct JobCtl {
+    const uint32_t *stop;         // host: nonzero = reserve nothing more
+    unsigned long long *progress; // host: mirror of *done after this wave's last addition
+    unsigned long long *done;     // device: pixels that became final, summed over the job's passes
+    long long limit;              // the budget of THIS pass (rt_dev_set_job_limits): units (fused, pass A) or list entries (pass B); < 0: none
+};
+// lane 0, in front of a reservation: has the host asked the job to stop?
+RTD_INLINE bool job_stop_requested(const JobCtl &j) { return __hip_atomic_load(j.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u; }
+// lane 0: n more pixels are final
+RTD_INLINE void job_publish(const JobCtl &j, uint32_t n) {
+    if (n == 0u) return;
+    const unsigned long long total = __hip_atomic_fetch_add(j.done, (unsigned long long) n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + (unsigned long long) n;
+    __hip_atomic_store(j.progress, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 // Per-wave LDS scratch (in 4-byte words), P = pixels per work unit:
 //   acc  [2][P][3]  sums of slot 0 / slot 1
@@ -897,9 +917,12 @@ RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc,
 // and the wave's scratch keeps per pixel its first item and (Count - first item); an item finds its pixel by rtm::map_find_pixel
 // (at most six LDS reads, no division) and is sample (Count - first item) + item; flush leaves Count = target.  n1 and n2 are unused.
 // PX (a pixel list, rt_render_pixels): list entry lp is the frame's pixel p.pixel_list[lp]; everything but that look-up is the frame's.
-template <bool LDS, bool COUNT, bool TEX, bool FP, bool MAP = false, bool PX = false>
+// JOB (a render job, render_job_kernel): in front of a reservation lane 0 polls the job's stop word -- set: nothing is reserved, exactly as when
+// the list is exhausted, and the ranges already reserved are finished and flushed as usual -- and clips the reservation to the job's
+// budget; a flushed range's pixels are final and are published (job_publish).
+template <bool LDS, bool COUNT, bool TEX, bool FP, bool MAP = false, bool PX = false, bool JOB = false>
 RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, RTD_AS3 uint32_t *wv, uint32_t n1, uint32_t n2, Counters &cnt,
-                           StageStats &ss, uint64_t &sampleCount) {
+                           StageStats &ss, uint64_t &sampleCount, const JobCtl *job = nullptr) {
     const int lane = threadIdx.x & 63;
     const uint32_t P = (uint32_t) p.chunk;
     const uint32_t SW = 7u * P; // words per slot: acc [P][3] then pix [P][4]
@@ -936,6 +959,7 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
         }
         __builtin_amdgcn_wave_barrier();
         RTD_CENSUS(ss.flushes++;)
+        if constexpr (JOB) { if (lane == 0) job_publish(*job, npx); }
     };
 
     for (;;) {
@@ -955,11 +979,14 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                 uint32_t npx = 0;
                 if (lane == 0) { // guided self-scheduling over the cost-ordered list: big ranges first, single pixels at the end
                     const unsigned long long seen = __hip_atomic_load(p.queue_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (seen < nList) {
+                    bool open = seen < nList;
+                    if constexpr (JOB) open = open && !job_stop_requested(*job);
+                    if (open) {
                         unsigned long long want = (nList - seen) / (2ull * p.total_waves);
                         want = want < 1ull ? 1ull : (want > (unsigned long long) P ? (unsigned long long) P : want);
                         first = atomicAdd(p.queue_b, want);
-                        if (first < nList) npx = (uint32_t) ((nList - first < want) ? (nList - first) : want);
+                        if constexpr (JOB) npx = (uint32_t) rtjob::clip_reservation(first, want, nList, job->limit);
+                        else if (first < nList) npx = (uint32_t) ((nList - first < want) ? (nList - first) : want);
                     }
                 }
                 npx = __builtin_amdgcn_readfirstlane(npx);
@@ -1119,200 +1146,100 @@ RTD_INLINE uint32_t stage_nodes32(const RenderParams &p, unsigned char *smem) {
 // MODE: one of rtmode::Mode (rt_modes.h: the table of the fifteen modes, what each does and what follows from it).  The parameter stays
 // an int so that every kernel keeps its symbol; everything the kernel asks of it is read from the mode's description D.
 // TEX: the scene has parameterised textures (see `reflection`).
+// JOB: the stoppable variant of a frame pass (render_job_kernel below).  In front of a unit's reservation lane 0 polls the job's stop word:
+// set, the wave reserves nothing and leaves as it does when the queue is exhausted; a unit at or beyond the job's budget is not
+// rendered.  A fused unit's pixels are final when the unit ends, a pass-A unit's early-stopping pixels when its decision is made.
 template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX>
 __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr rtmode::ModeDesc D = rtmode::mode_desc(MODE);
-    constexpr bool FUSED = D.pass == rtmode::Pass::FUSED, PASS_A = D.pass == rtmode::Pass::A, PASS_B = D.pass == rtmode::Pass::B;
-    constexpr bool RAYS = D.pass == rtmode::Pass::RAY_LIST, CAM = D.pass == rtmode::Pass::CAMERA_HITS;
-    constexpr bool MAP = D.map, LOG = D.ray_log;
-    constexpr bool FP = D.pixels == rtmode::Pixels::FOOTPRINTS;  // the pixels are the caller's footprints
-    constexpr bool PX = D.pixels == rtmode::Pixels::LIST && !CAM; // the pixels are a caller's list of the frame's, rendered as the frame's are
+    constexpr bool JOB = false;
+    const JobCtl *const job = nullptr;
+#include "rt_render_body.inc"
+}
+
+// The stoppable variant of the frame passes (rtmode::FRAME_FUSED, FRAME_PASS_A, FRAME_PASS_B), under a symbol of its own: the timed variant
+// only, at blocks of 256 and 1024 threads.  PASS: the mode's number.
+template <bool LDS, int BLOCK, int PASS, bool TEX>
+__global__ void __launch_bounds__(BLOCK) render_job_kernel(const RenderParams p, const JobCtl job_ctl) {
+    static_assert(PASS == rtmode::FRAME_FUSED || PASS == rtmode::FRAME_PASS_A || PASS == rtmode::FRAME_PASS_B, "a frame pass");
+    constexpr bool COUNT = false, JOB = true;
+    constexpr int MODE = PASS;
+    const JobCtl *const job = &job_ctl;
+#include "rt_render_body.inc"
+}
+
+// ---- a job's finishing kernels (rt_job_plan.h is the definition; these write what it says) ----
+// What the job's kernels left, where the finishing kernels and rt_render_job_wait find it.  In the job's control block (host memory).
+struct JobResult {
+    long long n_present, complete;      // present pixels; 1: every pixel is present
+    long long done_a, done_b, n_list;   // the counters, clamped (rtjob::clamp_done); the live list's length (0 for the fused kernel)
+    unsigned long long samples;         // counters[4] at the job's end: every sample traced, discarded ones included
+};
+// One thread, first: the counters' final values become done_a / done_b (device words the next kernels read, and the result's)
+__global__ void job_seal_kernel(const unsigned int *queue, const unsigned long long *queue_b, const unsigned int *live_count, rtjob::Plan pl, long long limit_a,
+                                long long limit_b, unsigned long long *done /* [3]: done_a, done_b, n_present */, JobResult *res) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const uint64_t n_list = pl.passes == 2 ? (uint64_t) *live_count : 0u;
+    done[0] = rtjob::clamp_done((uint64_t) *queue, rtjob::units_of(pl), limit_a);
+    done[1] = pl.passes == 2 ? rtjob::clamp_done((uint64_t) *queue_b, n_list, limit_b) : 0u;
+    done[2] = 0u;
+    res->done_a = (long long) done[0]; res->done_b = (long long) done[1]; res->n_list = (long long) n_list;
+}
+// present[lp] from the prefix of units, for every local pixel
+__global__ void __launch_bounds__(256) job_units_kernel(rtjob::Plan pl, const unsigned long long *done, uint8_t *present) {
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull, done_a = done[0];
+    for (unsigned long long lp = (unsigned long long) blockIdx.x * 256ull + threadIdx.x; lp < pl.n_local; lp += stride) present[lp] = rtjob::unit_done(pl, lp, done_a) ? 1u : 0u;
+}
+// ... less the live list's entries that pass B did not reach (two passes; the list holds local pixels below n_local, each once)
+__global__ void __launch_bounds__(256) job_pending_kernel(const unsigned int *list, const unsigned int *live_count, const unsigned long long *done, uint8_t *present) {
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull, n_list = (unsigned long long) *live_count, done_b = done[1];
+    for (unsigned long long i = (unsigned long long) blockIdx.x * 256ull + threadIdx.x; i < n_list; i += stride)
+        if (rtjob::entry_pending(i, done_b)) present[list[i]] = 0u;
+}
+// The absent pixels' PixelStats and colour zeroed (pass A's partial sums are discarded: the output does not depend on where the stop
+// fell inside a pixel), the present ones counted.
+__global__ void __launch_bounds__(256) job_zero_kernel(unsigned long long n_local, const uint8_t *present, int32_t *accum, uint8_t *rgb, unsigned long long *done) {
     const int lane = threadIdx.x & 63;
-    // the wave's index as a SCALAR: everything derived from it (the wave's LDS scratch, its park pools) then has a scalar base, and the
-    // pools' field addresses are scalar base + 32-bit lane offset instead of 64-bit vector arithmetic kept alive across the loop
-    const int wave = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
-
-    // LDS part: the whole scene (LDS variants), or as much of the tree as fits (the timed variant of a larger scene), or nothing
-    const uint32_t ldsNodes = (!LDS && !COUNT) ? stage_nodes32<BLOCK>(p, smem) : 0u;
-    const uint32_t sceneBytes = LDS ? stage_scene<BLOCK, !COUNT>(p, smem) : (uint32_t) ((!LDS && !COUNT) ? p.lds_node_bytes : 0);
-    SceneView<LDS> scv = make_view<LDS, !COUNT>(p, smem);
-    scv.lds_lim = (int) ldsNodes;
-    scv.lds_thr = p.lds_node_thr;
-    const SceneView<LDS> &sc = scv;
-    const uint32_t P = (uint32_t) p.chunk;
-    RTD_AS3 uint32_t *wv = (RTD_AS3 uint32_t *) (smem + sceneBytes) + (size_t) wave * rtmode::wave_words(MODE, P);
-    RTD_AS3 uint32_t *acc = wv;
-    RTD_AS3 uint32_t *pix = wv + 6u * P;
-    RTD_AS3 uint32_t *live = pix + 4u * P;
-    RTD_AS3 uint32_t *cand = live + P; // (fused and pass A; pass B keeps its own behind the two slots)
-    unsigned char *pool = p.park_pool + ((size_t) blockIdx.x * (BLOCK / 64) + (size_t) wave) * (size_t) RTD_PARK_ENTRY_BYTES *
-                                        (size_t) (p.park + (p.park_l_lds ? 0 : p.park_l) + (TEX ? p.park : 0));
-    // the Lambert pools in LDS (if any) follow the waves' scratch
-    RTD_AS3 unsigned char *poolLds = (RTD_AS3 unsigned char *) (smem + sceneBytes) + (size_t) (BLOCK / 64) * rtmode::wave_words(MODE, P) * 4u +
-                                     (size_t) wave * (size_t) RTD_PARK_L_LDS_BYTES * (size_t) p.park_l;
-
-    const uint64_t nLocal = PX ? p.ray_n : (uint64_t) p.n_rows * (uint64_t) p.cols; // (a pixel list: cols is the frame's)
-    const uint32_t k = (uint32_t) p.k;
-    const uint32_t n1 = (PASS_B && p.first_b != 0) ? (uint32_t) p.first_b : 2u * k + 1u; // (pass B of an extension starts where the buffer ends)
-    const int n2s = p.spp - (int) n1; // Scene.fs:191
-    const uint32_t n2 = n2s > 0 ? (uint32_t) n2s : 0u;
-
-    const unsigned long long tStart = COUNT ? __builtin_amdgcn_s_memrealtime() : 0ull;
-    Counters cnt; cnt.rays = cnt.aabb = cnt.prim = cnt.refl = 0;
-    StageStats ss; ss.refill = ss.trips = ss.leaf = ss.shade = ss.refillLanes = ss.shadeLanes = ss.slow = ss.slowLanes = ss.parkedLanes = 0;
-    ss.tRefill = ss.tSlow = ss.tWalk = ss.tShade = 0ull;
-    ss.tLoop = ss.tLeaf = ss.tUnb = ss.tCam = ss.tLamb = 0ull;
-    ss.loopTrips = ss.loopLanes = 0ull;
-#ifdef RTD_STAGE_CLOCKS
-    ss.turns = ss.lambBatches = ss.lambLanes = ss.newRefills = ss.newItems = ss.unparkL = ss.unparkA = ss.storeBlocksL = ss.storeLanesL = ss.storeBlocksA = 0u;
-    ss.lightBatches = ss.lightLanes = ss.missLanes = ss.ranges = ss.flushes = ss.leafLanes = ss.unparkBatchesL = ss.unparkBatchesA = 0u;
-    for (int i = 0; i < 8; ++i) ss.slowLanesByStyle[i] = ss.slowBatchesByStyle[i] = 0u;
-#endif
-    uint32_t earlyCount = 0;
-    uint64_t sampleCount = 0; // Scene.traceOnce calls = sum of PixelStats.Count
-
-    if constexpr (RAYS) run_rays<LDS, COUNT, TEX, D.hits>(p, sc, pool, poolLds, cnt, ss);
-    else if constexpr (CAM) run_camera_hits<LDS, COUNT>(p, sc, pool, poolLds, wv, cnt, ss);
-    else if (PASS_B) run_stream<LDS, COUNT, TEX, FP, MAP, PX>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount);
-    else
-    for (;;) {
-        uint32_t unit = 0;
-        if (lane == 0) unit = atomicAdd(p.queue, 1u);
-        unit = __builtin_amdgcn_readfirstlane(unit);
-        const unsigned long long first = (unsigned long long) unit * P;
-        if (first >= nLocal) break;
-        const uint32_t npx = (uint32_t) ((nLocal - first < (unsigned long long) P) ? (nLocal - first) : (unsigned long long) P);
-
-        // per-pixel coordinates (Scene.fs:219,226) and stream key; clear the accumulators
-        for (uint32_t i = (uint32_t) lane; i < 6u * P; i += 64u) acc[i] = 0u;
-        if (PASS_A && (uint32_t) lane < P) acc[10u * P + lane] = 0u;
-        unsigned long long lp = 0; // local pixel of lane j < npx
-        if ((uint32_t) lane < npx) {
-            lp = first + (uint32_t) lane;
-            if constexpr (FP) footprint_setup(p, lp, pix, lane);
-            else {
-                uint32_t c2;
-                const uint32_t c1 = pixel_setup<LDS, COUNT, D.pixels>(p, sc, lp, pix, lane, c2);
-                cand[lane * 2] = c1;
-                cand[lane * 2 + 1] = c2;
-            }
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull;
+    const unsigned long long trips = (n_local + stride - 1ull) / stride; // uniform over the grid: every lane of a wave makes every ballot
+    unsigned long long n = 0ull;
+    for (unsigned long long t = 0; t < trips; ++t) {
+        const unsigned long long lp = t * stride + (unsigned long long) blockIdx.x * 256ull + threadIdx.x;
+        const bool in = lp < n_local, here = in && present[lp] != 0u;
+        if (in && !here) {
+            i4 z; z.x = z.y = z.z = z.w = 0;
+            ((i4 *) accum)[lp] = z;
+            if (rgb) { rgb[lp * 3 + 0] = 0u; rgb[lp * 3 + 1] = 0u; rgb[lp * 3 + 2] = 0u; }
         }
-        __builtin_amdgcn_wave_barrier();
-
-        // ---- phase 1: 2k+1 samples per pixel, sums split after sample k (Scene.fs:172-182) ----
-        run_items<LDS, COUNT, PASS_A, TEX, LOG, FP>(p, sc, pool, poolLds, acc, pix, cand, live, false, npx * n1, n1, 0u, k + 1u, cnt, ss);
-        __builtin_amdgcn_wave_barrier();
-
-        // ---- decide (Scene.fs:177-188) and compact the pixels that continue ----
-        int sumR = 0, sumG = 0, sumB = 0, count = 0;
-        bool cont = false;
-        if ((uint32_t) lane < npx) {
-            int aR = (int) lds_take(acc + lane * 3 + 0), aG = (int) lds_take(acc + lane * 3 + 1), aB = (int) lds_take(acc + lane * 3 + 2);
-            int bR = (int) lds_take(acc + P * 3 + lane * 3 + 0), bG = (int) lds_take(acc + P * 3 + lane * 3 + 1),
-                bB = (int) lds_take(acc + P * 3 + lane * 3 + 2);
-            int c1 = (int) k + 1;
-            count = (int) n1;
-            sumR = aR + bR; sumG = aG + bG; sumB = aB + bB;
-            // PixelStats.mean (Pixel.fs:103-108) is integer division; Pixel.difference (Pixel.fs:113-116) is L1
-            int oR = (aR / c1) & 0xFF, oG = (aG / c1) & 0xFF, oB = (aB / c1) & 0xFF;
-            int nR = (sumR / count) & 0xFF, nG = (sumG / count) & 0xFF, nB = (sumB / count) & 0xFF;
-            int diff = abs(nR - oR) + abs(nG - oG) + abs(nB - oB);
-            if (diff == 0) earlyCount++;
-            cont = (diff != 0) && (n2 > 0u);
-        }
-        const unsigned long long liveMask = __builtin_amdgcn_ballot_w64(cont);
-        const uint32_t nLive = (uint32_t) __popcll(liveMask);
-        const uint32_t pos = lane_rank(liveMask);
-        if (FUSED) {
-            if (cont) live[pos] = (uint32_t) lane;
-        } else if (nLive > 0u) { // pass A: hand the pixel over to pass B, with its cost estimate
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(p.live_count, nLive);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (cont) p.pairs[base + pos] = ((unsigned long long) acc[10u * P + lane] << 32) | (unsigned long long) (uint32_t) lp;
-        }
-        __builtin_amdgcn_wave_barrier();
-
-        // ---- phase 2: the remaining spp-2k-1 samples of the surviving pixels (Scene.fs:191-192) ----
-        if (FUSED && nLive > 0u) {
-            run_items<LDS, COUNT, false, TEX, LOG, FP>(p, sc, pool, poolLds, acc, pix, cand, live, true, nLive * n2, n2, n1, 0xFFFFFFFFu, cnt, ss);
-            __builtin_amdgcn_wave_barrier();
-        }
-
-        // ---- PixelStats and mean out: one 16-byte store per pixel ----
-        if ((uint32_t) lane < npx) {
-            if (FUSED && cont) {
-                sumR += (int) lds_take(acc + lane * 3 + 0);
-                sumG += (int) lds_take(acc + lane * 3 + 1);
-                sumB += (int) lds_take(acc + lane * 3 + 2);
-                count += (int) n2;
-            }
-            sampleCount += (uint64_t) count;
-            i4 out; out.x = count; out.y = sumR; out.z = sumG; out.w = sumB;
-            ((i4 *) p.accum)[lp] = out;
-            if (p.rgb) {
-                p.rgb[lp * 3 + 0] = (uint8_t) (sumR / count);
-                p.rgb[lp * 3 + 1] = (uint8_t) (sumG / count);
-                p.rgb[lp * 3 + 2] = (uint8_t) (sumB / count);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
+        n += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(here));
     }
-
-    // ---- counters: one wave reduction and a few atomics per wave per launch ----
-    uint64_t e = wave_sum_u64(earlyCount), s = wave_sum_u64(sampleCount);
-    if (COUNT) {
-        uint64_t a = wave_sum_u64(cnt.rays), b = wave_sum_u64(cnt.aabb), c = wave_sum_u64(cnt.prim), dd = wave_sum_u64(cnt.refl);
-        if (lane == 0) {
-            atomicAdd(&p.counters[0], (unsigned long long) a);
-            atomicAdd(&p.counters[1], (unsigned long long) b);
-            atomicAdd(&p.counters[2], (unsigned long long) c);
-            atomicAdd(&p.counters[3], (unsigned long long) dd);
-            const unsigned long long tEnd = __builtin_amdgcn_s_memrealtime();
-            atomicAdd(&p.counters[14], tEnd - tStart);                         // sum of wave lifetimes
-            atomicMax(&p.counters[15], tEnd);                                  // last wave to finish
-            atomicMax(&p.counters[7], 0x4000000000000000ull - tStart);         // (2^62 - earliest start)
-        }
-    }
-    if ((COUNT || RTD_CLK) && lane == 0) {
-        atomicAdd(&p.counters[8], (unsigned long long) ss.refill);
-        atomicAdd(&p.counters[9], (unsigned long long) ss.trips);
-        atomicAdd(&p.counters[10], (unsigned long long) ss.leaf);
-        atomicAdd(&p.counters[11], (unsigned long long) ss.shade);
-        atomicAdd(&p.counters[12], (unsigned long long) ss.refillLanes);
-        atomicAdd(&p.counters[13], (unsigned long long) ss.shadeLanes);
-        atomicAdd(&p.counters[20], (unsigned long long) ss.slow);
-        atomicAdd(&p.counters[21], (unsigned long long) ss.slowLanes);
-        atomicAdd(&p.counters[22], (unsigned long long) ss.parkedLanes);
-        atomicAdd(&p.counters[23], ss.tRefill);
-        atomicAdd(&p.counters[24], ss.tSlow);
-        atomicAdd(&p.counters[25], ss.tWalk);
-        atomicAdd(&p.counters[26], ss.tShade);
-        if (RTD_CLK) {
-            atomicAdd(&p.counters[27], ss.tLoop);
-            atomicAdd(&p.counters[28], ss.tLeaf);
-            atomicAdd(&p.counters[29], ss.tUnb);
-            atomicAdd(&p.counters[30], ss.tCam);
-            atomicAdd(&p.counters[31], ss.tLamb);
-            if (!COUNT) { atomicAdd(&p.counters[14], ss.loopTrips); atomicAdd(&p.counters[15], ss.loopLanes); } // (the counting variant keeps its wave lifetimes there)
-#ifdef RTD_STAGE_CLOCKS
-            if (!COUNT && PASS_B) { // the census describes pass B's timed kernel
-                const uint32_t cz[16] = {ss.turns, ss.lambBatches, ss.lambLanes, ss.newRefills, ss.newItems, ss.unparkL, ss.unparkA, ss.storeBlocksL, ss.storeLanesL,
-                                         ss.storeBlocksA, ss.lightBatches, ss.lightLanes, ss.missLanes, ss.ranges, ss.flushes, ss.leafLanes};
-                for (int i = 0; i < 16; ++i) atomicAdd(&g_census[i], (unsigned long long) cz[i]);
-                for (int i = 0; i < 8; ++i) { atomicAdd(&g_census[16 + i], (unsigned long long) ss.slowLanesByStyle[i]); atomicAdd(&g_census[24 + i], (unsigned long long) ss.slowBatchesByStyle[i]); }
-                // the stage counts of rt_last_stage_stats, for this kernel alone (those sum pass A and pass B)
-                const unsigned long long sz[12] = {ss.refill, ss.trips, ss.leaf, ss.shade, ss.refillLanes, ss.shadeLanes, ss.slow, ss.slowLanes, ss.loopTrips, ss.loopLanes,
-                                                   ss.unparkBatchesL, ss.unparkBatchesA};
-                for (int i = 0; i < 12; ++i) atomicAdd(&g_census[36 + i], sz[i]);
-            }
-#endif
-        }
-    }
-    if (lane == 0) {
-        atomicAdd(&p.counters[4], (unsigned long long) s);
-        atomicAdd(&p.counters[5], (unsigned long long) e);
+    if (lane == 0 && n != 0ull) atomicAdd(&done[2], n);
+}
+// One thread, last: the result, and the exact count as the progress mirror's final value
+__global__ void job_result_kernel(unsigned long long n_local, const unsigned long long *done, const unsigned long long *counters, JobResult *res,
+                                  unsigned long long *progress, uint32_t *finished) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    res->n_present = (long long) done[2];
+    res->complete = done[2] == n_local ? 1 : 0;
+    res->samples = counters[4];
+    __hip_atomic_store(progress, done[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(finished, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); // last: a host that sees it sees the count
+}
+// rt_render_job_finish: the absent pixels' list holds LOCAL pixels (rt_missing_pixels_device's kernels over `present`); the pixel-list
+// launch wants the frame's
+__global__ void __launch_bounds__(256) job_global_list_kernel(unsigned long long n, const int32_t *local, rtjob::Shard shard, int32_t *global) {
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull;
+    for (unsigned long long i = (unsigned long long) blockIdx.x * 256ull + threadIdx.x; i < n; i += stride)
+        global[i] = (int32_t) rtjob::global_pixel(shard, (uint64_t) (uint32_t) local[i]);
+}
+// ... and its results go back by local pixel: the 16-byte PixelStats, the colour, and the presence byte (every entry is a different pixel)
+__global__ void __launch_bounds__(256) job_scatter_kernel(unsigned long long n, const int32_t *local, const int32_t *accum_list, const uint8_t *rgb_list,
+                                                          int32_t *accum, uint8_t *rgb, uint8_t *present) {
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull;
+    for (unsigned long long i = (unsigned long long) blockIdx.x * 256ull + threadIdx.x; i < n; i += stride) {
+        const unsigned long long lp = (unsigned long long) (uint32_t) local[i];
+        ((i4 *) accum)[lp] = ((const i4 *) accum_list)[i];
+        if (rgb) { rgb[lp * 3 + 0] = rgb_list[i * 3 + 0]; rgb[lp * 3 + 1] = rgb_list[i * 3 + 1]; rgb[lp * 3 + 2] = rgb_list[i * 3 + 2]; }
+        present[lp] = 1u;
     }
 }
 

@@ -742,6 +742,21 @@ static std::string format_pixel_map(const uint8_t *rgb, int32_t rows, int32_t co
         }
     return s;
 }
+// ... for the pixels with a nonzero presence byte only: the spill ImageOutput.resume (ImageOutput.fs:131-161) has made so far when a run is
+// interrupted, in row-major order (rt_format_pixel_map_present)
+static std::string format_pixel_map_present(const uint8_t *rgb, const uint8_t *present, int32_t rows, int32_t cols) {
+    std::string s;
+    for (int32_t r = 0; r < rows; ++r)
+        for (int32_t c = 0; c < cols; ++c) {
+            const size_t g = (size_t) r * (size_t) cols + (size_t) c;
+            if (!present[g]) continue;
+            const uint8_t *p = rgb + g * 3u;
+            append_ascii_int_ref(s, r); s.push_back(',');
+            append_ascii_int_ref(s, c); s.push_back('\n');
+            s.push_back((char) p[0]); s.push_back((char) p[1]); s.push_back((char) p[2]);
+        }
+    return s;
+}
 // Returns the number of pixels set, or -1 when a (row, col) lies outside the image (the reference would throw).
 // A truncated tail is ignored exactly as the reference's `go` does (ImageOutput.fs:69-106).
 static int64_t parse_pixel_map(const uint8_t *data, size_t n, int32_t rows, int32_t cols, uint8_t *rgb, uint8_t *present) {

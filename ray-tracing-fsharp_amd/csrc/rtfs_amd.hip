@@ -3,6 +3,8 @@
 // There is NO CPU fallback: every compute entry point returns RT_ERR_NO_DEVICE when no HIP device is visible.
 #include "../../include/rtfs_amd.h"
 #include "rt_device.h"
+#include "rt_job_kernels.h"
+#include "rt_job_plan.h"
 #include "rt_jpeg_kernels.h"
 #include "rt_launch_plan.h"
 #include "rt_output.h"
@@ -2735,6 +2737,404 @@ int rt_resume_ppm(const rt_scene *scene, const rt_camera *camera, int32_t max_w,
 int rt_resume_png(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, uint32_t flags,
                   const char *map_path, int32_t gamma_correct, const char *out_path, const rt_render_options *options, rt_stats *stats) {
     return resume_file("rt_resume_png", rto::FMT_PNG, scene, camera, max_w, max_h, seed, device, flags, map_path, gamma_correct, out_path, options, stats);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// render jobs (DESIGN.md "Render jobs"; rt_job_plan.h, rt_render_kernel.h's JobCtl and finishing kernels, rt_job_kernels.h): a frame
+// shard's render launched and left running, with progress the host reads, a stop word the kernels poll, and a partial frame whose
+// present set rt_job_plan.h defines
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+
+// The job's control block: pinned, mapped, coherent host memory (hipHostMalloc).  The device polls `stop`, mirrors its count of final
+// pixels to `progress`, and the finishing kernels leave the result and, last of all, `finished`.
+struct JobControl {
+    uint32_t stop, finished;
+    unsigned long long progress;
+    JobResult res;
+};
+// The job's device words, between the launch's scratch and its workspace
+struct JobWords {
+    unsigned long long done;     // JobCtl::done
+    unsigned long long seal[3];  // done_a, done_b, n_present (job_seal_kernel .. job_result_kernel)
+};
+enum { JOB_WORDS_BYTES = 64 };
+static_assert(sizeof(JobWords) <= JOB_WORDS_BYTES, "the job's words fit their slot");
+
+typedef void (*job_fn)(const RenderParams, const JobCtl);
+template <int BLOCK, int PASS, bool TEX> job_fn pick_job_lds(bool lds) { return lds ? render_job_kernel<true, BLOCK, PASS, TEX> : render_job_kernel<false, BLOCK, PASS, TEX>; }
+template <int PASS> job_fn pick_job_pass(const rtp::Pass &q) {
+    if (q.block == 256) return q.tex ? pick_job_lds<256, PASS, true>(q.lds) : pick_job_lds<256, PASS, false>(q.lds);
+    return q.tex ? pick_job_lds<1024, PASS, true>(q.lds) : pick_job_lds<1024, PASS, false>(q.lds);
+}
+job_fn pick_job_kernel(const rtp::Pass &q) { // the frame passes at blocks of 256 and 1024; anything else is not built
+    if (q.count || (q.block != 256 && q.block != 1024)) return nullptr;
+    return q.mode == rtmode::FRAME_FUSED ? pick_job_pass<rtmode::FRAME_FUSED>(q) : q.mode == rtmode::FRAME_PASS_A ? pick_job_pass<rtmode::FRAME_PASS_A>(q) :
+           q.mode == rtmode::FRAME_PASS_B ? pick_job_pass<rtmode::FRAME_PASS_B>(q) : nullptr;
+}
+
+thread_local int64_t g_job_limits[2] = {-1, -1};
+thread_local int64_t g_last_job_plan[8] = {0};
+
+} // namespace
+
+struct rt_render_job {
+    JobControl *ctl = nullptr;
+    int device = -1;
+    hipStream_t st = nullptr;
+    Pending pd;
+    // what rt_render_job_finish renders with
+    const rt_scene *scene = nullptr;
+    rt_camera camera{};
+    int32_t max_w = 0, max_h = 0, row_first = 0, row_stride = 1, n_rows = 0;
+    uint64_t seed = 0;
+    uint32_t flags = 0;
+    bool has_options = false;
+    rt_render_options options{};
+    void *d_accum = nullptr, *d_rgb = nullptr, *d_present = nullptr;
+    int64_t pixels_total = 0;
+    int64_t plan[8] = {0}; // rt_dev_last_job_plan's words (done_a, done_b and n_list after the wait)
+    mutable std::atomic<long long> seen{0}; // the most the progress mirror has shown (racing device stores may regress it)
+    std::mutex mu;          // wait / finish / destroy
+    bool launched = false, waited = false;
+    rt_job_result result{};
+    rt_stats stats{};
+};
+
+// Plans and enqueues the job on job->st (arguments checked, the device current): enqueue()'s sequence for a fresh frame shard with the
+// stoppable kernels, then the finishing kernels, all up front.  The plan is plan_launch's for the same arguments, but for the block:
+// the job kernels are built for 256 and 1024 threads, and a request for 512 or 768 runs at 1024 (as the list modes do).
+static int enqueue_job(rt_render_job *j, const int64_t limits[2]) {
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceScene *ds = nullptr;
+    RT_TRY(device_scene(const_cast<rt_scene *>(j->scene), j->device, &ds));
+    const rth::HostScene &h = j->scene->host;
+    hipStream_t st = j->st;
+    RenderParams p{};
+    p.max_w = j->max_w; p.max_h = j->max_h;
+    p.spp = j->camera.samples_per_pixel;
+    p.depth = j->camera.bounce_depth;
+    p.seed_key = mix64(j->seed + 0x9E3779B97F4A7C15ull); // seed_key(), host side
+    p.cols = 2 * j->max_w + 1;
+    p.row_first = j->row_first; p.row_stride = j->row_stride; p.n_rows = j->n_rows;
+    p.accum = (int32_t *) j->d_accum;
+    p.rgb = (uint8_t *) j->d_rgb;
+    p.off = h.off;
+    p.scene_image = ds->image;
+    p.tex = ds->tex;
+    p.texels = ds->texels;
+    p.obj_to_orig = ds->obj_to_orig;
+    rtp::Job job;
+    job.kind = rtp::Job::FRAME;
+    job.n_rows = (uint64_t) j->n_rows; job.max_w = j->max_w; job.spp = j->camera.samples_per_pixel;
+    Settings set = resolve_settings(j->has_options ? &j->options : nullptr);
+    if (set.block != 0 && set.block != 256) set.block = 1024;
+
+    rtp::LaunchPlan plan = rtp::plan_begin(scene_size(h), set, false, job, ds->cu_count);
+    const int block = plan.one.block;
+    job_fn fn = pick_job_kernel(plan.one);
+    if (!fn) return fail(RT_ERR_HIP, "no job kernel is built for this launch");
+    RT_TRY(allow_full_lds((const void *) fn));
+    int perCu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, (const void *) fn, block, plan.one.lds_bytes));
+    if (perCu < 1) return fail(RT_ERR_HIP, "render job kernel does not fit on a CU (occupancy 0)");
+    rtp::plan_finish(plan, perCu);
+    if (plan.error) return fail(RT_ERR_HIP, plan.error);
+    const size_t pairsBytes = plan.pairs_bytes, listBytes = plan.list_bytes, sortBytes = plan.sort_bytes, poolBytes = plan.pool_bytes;
+    job_fn fa = nullptr, fb = nullptr;
+    if (plan.two_pass) {
+        fa = pick_job_kernel(plan.a); fb = pick_job_kernel(plan.b);
+        if (!fa || !fb) return fail(RT_ERR_HIP, "no job kernel is built for this launch");
+        RT_TRY(allow_full_lds((const void *) fa));
+        RT_TRY(allow_full_lds((const void *) fb));
+    }
+    const rtjob::Plan jp{plan.two_pass ? 2 : 1, (uint32_t) (plan.two_pass ? plan.a.chunk : plan.one.chunk), (uint64_t) plan.pixels};
+    int64_t *w = j->plan;
+    w[0] = jp.passes; w[1] = jp.chunk; w[2] = (int64_t) rtjob::units_of(jp); w[3] = 0; w[4] = 0; w[5] = 0; w[6] = block; w[7] = plan.one.tex ? 1 : 0;
+
+    Pending &cl = j->pd;
+    unsigned char *scr = nullptr;
+    HIP_TRY(hipMallocAsync((void **) &scr, RT_SCRATCH_BYTES + JOB_WORDS_BYTES + pairsBytes + listBytes + sortBytes + poolBytes, st));
+    cl.scr = scr; cl.st = st; cl.device = j->device; cl.t0 = t0;
+    cl.pixels = plan.pixels; cl.waves = plan.waves;
+    HIP_TRY(hipEventCreate(&cl.a));
+    HIP_TRY(hipEventCreate(&cl.b));
+    LaunchScratch *ls = (LaunchScratch *) scr;
+    JobWords *jw = (JobWords *) (scr + RT_SCRATCH_BYTES);
+    unsigned char *ws = scr + RT_SCRATCH_BYTES + JOB_WORDS_BYTES;
+    p.counters = ls->counters;
+    p.queue = &ls->queue;
+    p.queue_b = &ls->queue_b;
+    p.live_count = &ls->live_count;
+    p.cam_ptr = &ls->cam;
+    p.park_pool = ws + pairsBytes + listBytes + sortBytes;
+    hipLaunchKernelGGL(launch_init_kernel, dim3(1), dim3(64), 0, st, scr, camera_params(&j->camera, j->max_w, j->max_h));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(jw, 0, JOB_WORDS_BYTES, st));
+    JobControl *dctl = nullptr; // the control block as the device addresses it
+    HIP_TRY(hipHostGetDevicePointer((void **) &dctl, j->ctl, 0));
+    JobCtl ctl{};
+    ctl.stop = &dctl->stop; ctl.progress = &dctl->progress; ctl.done = &jw->done;
+    HIP_TRY(hipEventRecord(cl.a, st));
+    if (!plan.two_pass) {
+        set_plan_fields(p, plan.one);
+        ctl.limit = limits[0];
+        hipLaunchKernelGGL(fn, dim3((unsigned) plan.one.grid), dim3((unsigned) block), plan.one.lds_bytes, st, p, ctl);
+        HIP_TRY(hipGetLastError());
+    } else {
+        unsigned int *sortBuf = (unsigned int *) (ws + pairsBytes + listBytes);
+        HIP_TRY(hipMemsetAsync(sortBuf, 0, sortBytes, st));
+        p.pairs = (unsigned long long *) ws;
+        p.live_list = (const unsigned int *) (ws + pairsBytes);
+        RenderParams pa = p;
+        set_plan_fields(pa, plan.a);
+        set_plan_fields(p, plan.b);
+        const uint32_t n1 = (uint32_t) (2 * p.k + 1);
+        JobCtl ca = ctl, cb = ctl;
+        ca.limit = limits[0]; cb.limit = limits[1];
+        hipLaunchKernelGGL(fa, dim3((unsigned) plan.a.grid), dim3((unsigned) block), plan.a.lds_bytes, st, pa, ca);
+        hipLaunchKernelGGL(sort_hist_kernel, dim3(256), dim3(256), 0, st, (const unsigned long long *) p.pairs, (const unsigned int *) p.live_count, n1, sortBuf);
+        hipLaunchKernelGGL(sort_offsets_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) sortBuf, sortBuf + RTD_COST_BUCKETS);
+        hipLaunchKernelGGL(sort_scatter_kernel, dim3(256), dim3(256), 0, st, (const unsigned long long *) p.pairs, (const unsigned int *) p.live_count, n1,
+                           (const unsigned int *) (sortBuf + RTD_COST_BUCKETS), sortBuf + 2 * RTD_COST_BUCKETS, (unsigned int *) (ws + pairsBytes));
+        hipLaunchKernelGGL(fb, dim3((unsigned) plan.b.grid), dim3((unsigned) block), plan.b.lds_bytes, st, p, cb);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("two-pass job launch: ") + hipGetErrorString(e));
+    }
+    // the finishing kernels: the present set (rt_job_plan.h), absent pixels zeroed, the count, the result -- before the scratch is released
+    const unsigned long long nLocal = plan.pixels;
+    const unsigned long long want = (nLocal + 255ull) / 256ull, most = (unsigned long long) ds->cu_count * 8ull;
+    const unsigned fgrid = (unsigned) (want < most ? want : most);
+    hipLaunchKernelGGL(job_seal_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) p.queue, (const unsigned long long *) p.queue_b, (const unsigned int *) p.live_count, jp,
+                       (long long) limits[0], (long long) limits[1], jw->seal, &dctl->res);
+    hipLaunchKernelGGL(job_units_kernel, dim3(fgrid), dim3(256), 0, st, jp, (const unsigned long long *) jw->seal, (uint8_t *) j->d_present);
+    if (plan.two_pass)
+        hipLaunchKernelGGL(job_pending_kernel, dim3(fgrid), dim3(256), 0, st, p.live_list, (const unsigned int *) p.live_count, (const unsigned long long *) jw->seal,
+                           (uint8_t *) j->d_present);
+    hipLaunchKernelGGL(job_zero_kernel, dim3(fgrid), dim3(256), 0, st, nLocal, (const uint8_t *) j->d_present, p.accum, p.rgb, jw->seal);
+    hipLaunchKernelGGL(job_result_kernel, dim3(1), dim3(64), 0, st, nLocal, (const unsigned long long *) jw->seal, (const unsigned long long *) p.counters, &dctl->res,
+                       &dctl->progress, &dctl->finished);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(cl.b, st));
+    cl.launched = true;
+    j->launched = true;
+    return RT_OK;
+}
+
+static void job_free(rt_render_job *j) { // (the device current, the stream idle)
+    j->pd.release();
+    if (j->ctl) (void) hipHostFree(j->ctl);
+    delete j;
+}
+
+extern "C" {
+
+int rt_dev_set_job_limits(int64_t limit_a, int64_t limit_b) {
+    if (limit_a < -1 || limit_b < -1) return fail(RT_ERR_INVALID_ARGUMENT, "a job limit is -1 (none) or a count >= 0");
+    g_job_limits[0] = limit_a; g_job_limits[1] = limit_b;
+    return RT_OK;
+}
+
+int rt_dev_last_job_plan(int64_t out[8]) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    for (int i = 0; i < 8; ++i) out[i] = g_last_job_plan[i];
+    return RT_OK;
+}
+
+int rt_render_job_start(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, int32_t row_first,
+                        int32_t row_stride, int32_t n_rows, uint32_t flags, void *d_accum, void *d_rgb, void *d_present, void *stream,
+                        const rt_render_options *options, rt_render_job **out) {
+    RT_TRY(check_frame(scene, camera, max_w, max_h, row_first, row_stride, n_rows, d_accum, "d_accum is NULL", options));
+    if (n_rows > 0 && !d_present) return fail(RT_ERR_INVALID_ARGUMENT, "d_present is NULL");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    RT_TRY(check_list_frame(max_w, max_h));
+    if (flags & RT_RENDER_COUNTERS) return fail(RT_ERR_UNSUPPORTED, "a render job has no counting variant (RT_RENDER_COUNTERS)");
+    return guarded("rt_render_job_start", [&]() {
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        const int64_t limits[2] = {g_job_limits[0], g_job_limits[1]}; // consumed by this job
+        g_job_limits[0] = g_job_limits[1] = -1;
+        rt_render_job *j = new rt_render_job();
+        j->device = device; j->st = (hipStream_t) stream;
+        j->scene = scene; j->camera = *camera;
+        j->max_w = max_w; j->max_h = max_h; j->row_first = row_first; j->row_stride = row_stride; j->n_rows = n_rows;
+        j->seed = seed; j->flags = flags;
+        if (options) { // (only the bytes the caller's struct has)
+            j->has_options = true;
+            memcpy(&j->options, options, options->struct_size < sizeof(rt_render_options) ? options->struct_size : sizeof(rt_render_options));
+        }
+        j->d_accum = d_accum; j->d_rgb = d_rgb; j->d_present = d_present;
+        j->pixels_total = (int64_t) n_rows * (int64_t) (2 * max_w + 1);
+        hipError_t e = hipHostMalloc((void **) &j->ctl, sizeof(JobControl), hipHostMallocMapped | hipHostMallocCoherent);
+        if (e != hipSuccess) { j->ctl = nullptr; job_free(j); return fail(RT_ERR_HIP, std::string("hipHostMalloc: ") + hipGetErrorString(e)); }
+        memset(j->ctl, 0, sizeof(JobControl));
+        int rc = RT_OK;
+        if (j->pixels_total == 0) { // an empty shard: nothing to launch, complete at once
+            j->ctl->res.complete = 1;
+            j->ctl->finished = 1u;
+        } else rc = enqueue_job(j, limits);
+        if (rc != RT_OK) { // whatever was launched polls the control block: wait for it before the block goes
+            (void) hipStreamSynchronize(j->st);
+            job_free(j);
+            return rc;
+        }
+        for (int i = 0; i < 8; ++i) g_last_job_plan[i] = j->plan[i]; // (done_a, done_b and n_list: after the wait)
+        *out = j;
+        return (int) RT_OK;
+    });
+}
+
+int rt_render_job_progress(const rt_render_job *job, rt_job_progress *progress) {
+    if (!job) return fail(RT_ERR_INVALID_ARGUMENT, "job is NULL");
+    if (!progress || progress->struct_size < sizeof(rt_job_progress)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_job_progress.struct_size is not set");
+    const uint32_t finished = __atomic_load_n(&job->ctl->finished, __ATOMIC_ACQUIRE), stop = __atomic_load_n(&job->ctl->stop, __ATOMIC_RELAXED);
+    long long now = (long long) __atomic_load_n(&job->ctl->progress, __ATOMIC_RELAXED);
+    if (now > (long long) job->pixels_total) now = (long long) job->pixels_total;
+    long long best = job->seen.load(std::memory_order_relaxed);
+    while (now > best && !job->seen.compare_exchange_weak(best, now, std::memory_order_relaxed)) {}
+    progress->state = finished ? 2 : (stop ? 1 : 0);
+    progress->pixels_total = job->pixels_total;
+    progress->pixels_final = now > best ? now : best;
+    return RT_OK;
+}
+
+int rt_render_job_stop(rt_render_job *job) {
+    if (!job) return fail(RT_ERR_INVALID_ARGUMENT, "job is NULL");
+    __atomic_store_n(&job->ctl->stop, 1u, __ATOMIC_RELAXED);
+    return RT_OK;
+}
+
+int rt_render_job_wait(rt_render_job *job, rt_job_result *result, rt_stats *stats) {
+    if (!job) return fail(RT_ERR_INVALID_ARGUMENT, "job is NULL");
+    if (result && result->struct_size < sizeof(rt_job_result)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_job_result.struct_size is not set");
+    std::lock_guard<std::mutex> lock(job->mu);
+    if (!job->waited) {
+        DeviceGuard guard;
+        RT_TRY(guard.enter(job->device));
+        HIP_TRY(hipStreamSynchronize(job->st));
+        const JobResult r = job->ctl->res;
+        float ms = 0.f;
+        if (job->launched) HIP_TRY(hipEventElapsedTime(&ms, job->pd.a, job->pd.b));
+        memset(&job->stats, 0, sizeof(job->stats));
+        job->stats.pixels = (uint64_t) r.n_present;
+        job->stats.samples = r.samples;
+        job->stats.kernel_ms = ms;
+        job->stats.total_ms = job->launched ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - job->pd.t0).count() : 0.0;
+        job->result.struct_size = (uint32_t) sizeof(rt_job_result);
+        job->result.complete = (int32_t) r.complete;
+        job->result.stop_requested = __atomic_load_n(&job->ctl->stop, __ATOMIC_RELAXED) ? 1 : 0;
+        job->result.pixels_total = job->pixels_total;
+        job->result.n_present = r.n_present;
+        job->plan[3] = r.n_list; job->plan[4] = r.done_a; job->plan[5] = r.done_b;
+        job->seen.store((long long) r.n_present, std::memory_order_relaxed); // the exact count: no mirrored value exceeds it
+        job->pd.release();
+        job->waited = true;
+    }
+    for (int i = 0; i < 8; ++i) g_last_job_plan[i] = job->plan[i];
+    if (result) { const uint32_t size = result->struct_size; *result = job->result; result->struct_size = size; }
+    if (stats) *stats = job->stats;
+    return RT_OK;
+}
+
+int rt_render_job_finish(rt_render_job *job, void *stream, rt_stats *stats) {
+    if (!job) return fail(RT_ERR_INVALID_ARGUMENT, "job is NULL");
+    std::lock_guard<std::mutex> lock(job->mu);
+    if (!job->waited) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_job_finish needs a preceding rt_render_job_wait");
+    if (job->result.complete) return nothing_to_do(stats);
+    DeviceGuard guard;
+    RT_TRY(guard.enter(job->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t st = (hipStream_t) stream;
+    const int32_t cols = 2 * job->max_w + 1;
+    const size_t npx = (size_t) job->pixels_total;
+    StreamBuf lists; // the absent pixels as local indices [npx] int32, then as the frame's
+    lists.st = st;
+    HIP_TRY(hipMallocAsync((void **) &lists.p, npx * 8u, st));
+    int64_t missing = 0;
+    {
+        FormatPending fp;
+        RT_TRY(enqueue_missing(job->d_present, job->n_rows, cols, lists.p, npx, nullptr, st, fp));
+        RT_TRY(finish_missing(fp, lists.p, npx, &missing));
+    }
+    rt_stats local;
+    memset(&local, 0, sizeof(local));
+    if (missing > 0) {
+        const size_t n = (size_t) missing, rgb_at = n * 16u;
+        const int32_t *d_local = (const int32_t *) lists.p;
+        int32_t *d_global = (int32_t *) (lists.p + npx * 4u);
+        StreamBuf outb; // accum [n][4] int32, then rgb [n][3]
+        outb.st = st;
+        HIP_TRY(hipMallocAsync((void **) &outb.p, rgb_at + n * 3u, st));
+        const rtjob::Shard shard{cols, job->row_first, job->row_stride, job->n_rows};
+        const unsigned g = grid_for(n);
+        hipLaunchKernelGGL(job_global_list_kernel, dim3(g), dim3(256), 0, st, (unsigned long long) n, d_local, shard, d_global);
+        HIP_TRY(hipGetLastError());
+        {
+            Pending pd;
+            RT_TRY(launch_pixels(job->scene, &job->camera, job->max_w, job->max_h, job->seed, job->device, n, d_global, job->flags, outb.p,
+                                 job->d_rgb ? outb.p + rgb_at : nullptr, stream, job->has_options ? &job->options : nullptr, true, pd));
+            RT_TRY(collect_stats(pd, &local));
+        }
+        hipLaunchKernelGGL(job_scatter_kernel, dim3(g), dim3(256), 0, st, (unsigned long long) n, d_local, (const int32_t *) outb.p,
+                           (const uint8_t *) (job->d_rgb ? outb.p + rgb_at : nullptr), (int32_t *) job->d_accum, (uint8_t *) job->d_rgb, (uint8_t *) job->d_present);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    job->result.complete = 1;
+    job->result.n_present = job->pixels_total;
+    job->seen.store((long long) job->pixels_total, std::memory_order_relaxed);
+    __atomic_store_n(&job->ctl->progress, (unsigned long long) job->pixels_total, __ATOMIC_RELAXED);
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+void rt_render_job_destroy(rt_render_job *job) {
+    if (!job) return;
+    DeviceGuard guard;
+    if (guard.enter(job->device) == RT_OK && !job->waited && job->launched) (void) hipStreamSynchronize(job->st); // the kernels poll the control block
+    job_free(job);
+}
+
+int64_t rt_format_pixel_map_present(const uint8_t *rgb, const uint8_t *present, int32_t rows, int32_t cols, uint8_t *out, size_t out_capacity) {
+    if (!rgb || !present || rows <= 0 || cols <= 0) { fail(RT_ERR_INVALID_ARGUMENT, "bad image"); return -RT_ERR_INVALID_ARGUMENT; }
+    return guarded<int64_t>("rt_format_pixel_map_present", [&]() {
+        std::string s = rth::format_pixel_map_present(rgb, present, rows, cols);
+        if (out && out_capacity >= s.size()) memcpy(out, s.data(), s.size());
+        return (int64_t) s.size();
+    }, -RT_ERR_HOST);
+}
+
+int rt_format_pixel_map_present_device(int32_t device, const void *d_rgb, const void *d_present, int32_t rows, int32_t cols, void *d_out, size_t out_capacity,
+                                       void *d_bytes, void *stream, int64_t *bytes) {
+    if (!d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "d_rgb is NULL");
+    if (!d_present) return fail(RT_ERR_INVALID_ARGUMENT, "d_present is NULL");
+    RT_TRY(check_image_size(rows, cols));
+    if (d_out && out_capacity == 0) return fail(RT_ERR_INVALID_ARGUMENT, "d_out is given but out_capacity is 0");
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    hipStream_t st = (hipStream_t) stream;
+    const uint32_t npx = (uint32_t) ((uint64_t) rows * (uint64_t) cols);
+    const uint32_t n_tiles = (npx + (uint32_t) RTO_TILE_PIXELS - 1u) / (uint32_t) RTO_TILE_PIXELS;
+    FormatPending fp;
+    HIP_TRY(hipMallocAsync((void **) &fp.scr, RTO_SCRATCH_HEAD + (size_t) n_tiles * sizeof(unsigned long long), st));
+    fp.st = st;
+    rto::FormatScratch *head = (rto::FormatScratch *) fp.scr;
+    unsigned long long *tiles = (unsigned long long *) (fp.scr + RTO_SCRATCH_HEAD);
+    hipLaunchKernelGGL(rtjob::present_sums_kernel, dim3(n_tiles), dim3(RTO_BLOCK), 0, st, (const unsigned char *) d_present, npx, (uint32_t) cols, tiles);
+    hipLaunchKernelGGL(rto::format_scan_kernel, dim3(1), dim3(RTO_SCAN_THREADS), 0, st, tiles, n_tiles, 0ull, head, (long long *) d_bytes, (unsigned long long) out_capacity,
+                       d_out ? 1 : 0);
+    if (d_out)
+        hipLaunchKernelGGL(rtjob::present_scatter_kernel, dim3(n_tiles), dim3(RTO_BLOCK), 0, st, (const unsigned char *) d_rgb, (const unsigned char *) d_present, npx,
+                           (uint32_t) cols, (const unsigned long long *) tiles, (const rto::FormatScratch *) head, (unsigned char *) d_out);
+    HIP_TRY(hipGetLastError());
+    if (!bytes) return RT_OK;
+    const FormatJob fj{rto::FMT_MAP, d_rgb, rows, cols, false, d_out, out_capacity, d_bytes};
+    return finish_format(fp, fj, bytes);
 }
 
 } // extern "C"

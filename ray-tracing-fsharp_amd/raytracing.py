@@ -960,6 +960,167 @@ class Scene:
 
         return float(rowsIter), Image(rowsIter, colsIter, force)
 
+    def render_job(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, *, seed: int = 0, device: Optional[int] = None,
+                   row_first: int = 0, row_stride: int = 1, n_rows: Optional[int] = None, accum=None, rgb=True, present=None,
+                   options: Optional[A.rt_render_options] = None) -> "RenderJob":
+        """rt_render_job_start: render_rows' shard as a JOB -- launched and left running, with progress(), stop(), wait() and finish()
+        (Scene.fs:196-236 watched and interrupted; ImageOutput.fs:131-161's spill).  The job's buffers live on the GPU: with `accum` a
+        contiguous int32 torch tensor [n_rows, cols, 4] there the job renders INTO it on torch's current stream and its accum / rgb /
+        present are tensors; with accum None or a numpy array of that shape the buffers are the job's own and accum / rgb / present
+        come back as arrays (a given array is filled by wait() and finish()).  rgb: False for no colour buffer; on the tensor route
+        `rgb` and `present` may be the caller's own contiguous uint8 tensors [n_rows, cols, 3] and [n_rows, cols] on accum's device."""
+        torch = _torch()
+        rows, cols = 2 * maxHeightCoord + 1, 2 * maxWidthCoord + 1
+        if n_rows is None:
+            n_rows = max(0, (rows - row_first + row_stride - 1) // row_stride)
+        host_out = None
+        if accum is not None and _is_torch(accum):
+            route, buf, _ = _frame(accum, cols, device, options)
+            if buf.shape[0] != n_rows:
+                raise ValueError(f"accum must hold the shard's {n_rows} rows")
+        else:
+            if accum is not None and (not isinstance(accum, np.ndarray) or accum.dtype != np.int32 or accum.shape != (n_rows, cols, 4)):
+                raise ValueError(f"accum must be an int32 array [{n_rows}, {cols}, 4] or such a tensor on a GPU")
+            host_out = accum
+            route = _Tensors(torch.device("cuda", torch.cuda.current_device() if device is None else device))
+            buf = route.make((n_rows, cols, 4), "i32")
+        def own(t, shape, name):
+            if t.dtype != torch.uint8 or tuple(t.shape) != shape or t.device != route.where or not t.is_contiguous() or host_out is not None or accum is None:
+                raise ValueError(f"{name} must be a contiguous uint8 tensor {list(shape)} on accum's device, with accum a tensor")
+            return t
+
+        colour = own(rgb, (n_rows, cols, 3), "rgb") if _is_torch(rgb) else (route.make((n_rows, cols, 3), "u8") if rgb else None)
+        present = own(present, (n_rows, cols), "present") if present is not None else route.make((n_rows, cols), "u8")
+        handle = C.c_void_p()
+        stream = torch.cuda.current_stream(route.where).cuda_stream
+        check(lib.rt_render_job_start(self._h, C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, route.device, row_first, row_stride, n_rows,
+                                      0, route.ptr(buf), route.ptr(colour), route.ptr(present), stream, _ref(options), C.byref(handle)))
+        return RenderJob(self, handle, route, stream, buf, colour, present, host_out, accum is not None and _is_torch(accum))
+
+    def render_watch(self, progressIncrement: Callable[[float], None], should_stop: Callable[[], bool], maxWidthCoord: int, maxHeightCoord: int,
+                     camera: Camera, *, seed: int = 0, device: Optional[int] = None, poll_seconds: float = 0.0005,
+                     options: Optional[A.rt_render_options] = None):
+        """Scene.render watched (Scene.fs:196-236): the frame as a render job, polled while the GPU works.  `progressIncrement 1.0` is
+        called once per row's worth of final pixels (Scene.fs:232) -- `rows` times in all when the frame completes, fewer when it is
+        stopped -- and the job is asked to stop as soon as should_stop() answers true.  Returns (rgb [rows, cols, 3] with absent
+        pixels zero, present [rows, cols] bool, the partial pixel map's bytes -- ImageOutput.resume's spill, which Scene.resume takes)."""
+        import time
+
+        cols = 2 * maxWidthCoord + 1
+        ticks = 0
+        with self.render_job(maxWidthCoord, maxHeightCoord, camera, seed=seed, device=device, options=options) as job:
+            while True:
+                pr = job.progress()
+                while ticks < pr["pixels_final"] // cols:
+                    progressIncrement(1.0)
+                    ticks += 1
+                if pr["state"] == 2:
+                    break
+                if pr["state"] == 0 and should_stop():
+                    job.stop()
+                time.sleep(poll_seconds)
+            res = job.wait()
+            while ticks < res["n_present"] // cols:
+                progressIncrement(1.0)
+                ticks += 1
+            return job.rgb, job.present, job.pixel_map()
+
+
+class RenderJob:
+    """A render job (rt_render_job_*; DESIGN.md "Render jobs").  Use as a context manager, or call close()."""
+
+    def __init__(self, scene: Scene, handle, route, stream, accum, rgb, present, host_out, tensors: bool):
+        self._scene, self._h, self._route, self._stream = scene, handle, route, stream  # (the scene must outlive the job)
+        self._accum, self._rgb, self._present, self._host_out, self._tensors = accum, rgb, present, host_out, tensors
+        self.result: Optional[dict] = None
+
+    def progress(self) -> dict:
+        """rt_render_job_progress: {state (0 running, 1 stop requested, 2 finished), pixels_total, pixels_final}; never blocks."""
+        p = A.rt_job_progress()
+        check(lib.rt_render_job_progress(self._h, C.byref(p)))
+        return {"state": p.state, "pixels_total": p.pixels_total, "pixels_final": p.pixels_final}
+
+    def stop(self) -> None:
+        """rt_render_job_stop: from any thread, also while another sits in wait()."""
+        check(lib.rt_render_job_stop(self._h))
+
+    def wait(self) -> dict:
+        """rt_render_job_wait -> {complete, stop_requested, pixels_total, n_present, stats}."""
+        r, st = A.rt_job_result(), A.rt_stats()
+        check(lib.rt_render_job_wait(self._h, C.byref(r), C.byref(st)))
+        self.result = {"complete": bool(r.complete), "stop_requested": bool(r.stop_requested), "pixels_total": r.pixels_total,
+                       "n_present": r.n_present, "stats": st.as_dict()}
+        self._copy_out()
+        return self.result
+
+    def finish(self) -> dict:
+        """rt_render_job_finish: the absent pixels rendered and scattered in; afterwards the buffers are render_rows' -> the statistics."""
+        st = A.rt_stats()
+        check(lib.rt_render_job_finish(self._h, self._stream, C.byref(st)))
+        if self.result is not None:
+            self.result = dict(self.result, complete=True, n_present=self.result["pixels_total"])
+        self._copy_out()
+        return st.as_dict()
+
+    def plan(self) -> dict:
+        """rt_dev_last_job_plan of the calling thread (this job's after its wait())."""
+        w = (C.c_int64 * 8)()
+        check(lib.rt_dev_last_job_plan(w))
+        return dict(zip(("passes", "chunk", "units_a", "n_list", "done_a", "done_b", "block", "textured"), (int(x) for x in w)))
+
+    def _copy_out(self) -> None:
+        if self._host_out is not None:
+            self._host_out[...] = self._accum.cpu().numpy()
+
+    def _out(self, t):
+        if t is None or self._tensors:
+            return t
+        return t.cpu().numpy()
+
+    @property
+    def accum(self):
+        return self._out(self._accum)
+
+    @property
+    def rgb(self):
+        return self._out(self._rgb)
+
+    @property
+    def present(self):
+        """[n_rows, cols] bool (after wait()): the pixels that have every sample the frame gives them."""
+        p = self._present.bool()
+        return p if self._tensors else p.cpu().numpy()
+
+    def pixel_map(self) -> bytes:
+        """rt_format_pixel_map_present_device: ImageOutput.resume's records of the present pixels, row-major -- the partial spill.
+        (A shard's rows are numbered as the shard's own: use whole frames for a map Scene.resume is to take.)"""
+        if self._rgb is None:
+            raise ValueError("the job was started with rgb=False")
+        torch = _torch()
+        rows, cols = int(self._present.shape[0]), int(self._present.shape[1])
+        if rows == 0:
+            return b""
+        cap = _size(lib.rt_pixel_map_bytes(rows, cols))
+        out = torch.empty(cap, dtype=torch.uint8, device=self._route.where)
+        n = C.c_int64(0)
+        check(lib.rt_format_pixel_map_present_device(self._route.device, self._rgb.data_ptr(), self._present.data_ptr(), rows, cols, out.data_ptr(), cap,
+                                                     None, self._stream, C.byref(n)))
+        return out[: n.value].cpu().numpy().tobytes()
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h:
+            lib.rt_render_job_destroy(h)
+
+    def __enter__(self) -> "RenderJob":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        self.close()
+
 
 # ---- ImageOutput.fs -------------------------------------------------------------------------------------------------
 class PixelOutput:
@@ -1011,6 +1172,20 @@ class ImageOutput:
                                                  torch.cuda.current_stream(t.device).cuda_stream, C.byref(n)))
             return out[: n.value].cpu().numpy().tobytes()
         return _format_host(lib.rt_format_pixel_map, pixels)
+
+    @staticmethod
+    def formatPixelMapPresent(pixels, present) -> bytes:
+        """rt_format_pixel_map_present: formatPixelMap's records for the pixels with present[row, col] set only, row-major -- the spill an
+        interrupted ImageOutput.resume (ImageOutput.fs:131-161) leaves.  numpy arrays [rows, cols, 3] uint8 and [rows, cols] bool or uint8."""
+        px = np.ascontiguousarray(pixels, dtype=np.uint8)
+        pr = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
+        if px.ndim != 3 or px.shape[2] != 3 or pr.shape != px.shape[:2]:
+            raise ValueError("pixels must be [rows, cols, 3] and present [rows, cols]")
+        head = (_u8(px), _u8(pr), px.shape[0], px.shape[1])
+        n = _size(lib.rt_format_pixel_map_present(*head, None, 0))
+        buf = C.create_string_buffer(max(n, 1))
+        lib.rt_format_pixel_map_present(*head, buf, n)
+        return buf.raw[:n]
 
     @staticmethod
     def toPpm(progressIncrement: Callable[[float], None], image: "Image", path: str) -> str:
