@@ -93,8 +93,24 @@ enum rt_texture_kind {
     RT_TEXTURE_COLOUR = 0,    /* ParameterisedTexture.Colour */
     RT_TEXTURE_CHECKERED = 1, /* ParameterisedTexture.Checkered (even, odd, gridSize), Texture.fs:56-62 */
     RT_TEXTURE_IMAGE = 2,     /* ParameterisedTexture.Image rows (Texture.fs:63-67) */
-    RT_TEXTURE_UV_RAMP = 3    /* the two ParameterisedTexture.Arbitrary closures of SampleImages.fs:606-627 */
+    RT_TEXTURE_UV_RAMP = 3,   /* the two ParameterisedTexture.Arbitrary closures of SampleImages.fs:606-627 */
+    /* 4 is not a kind and never will be: it stays RT_ERR_UNSUPPORTED, as does every number above 5 (bindings and tests use 4 and 17 as
+     * stand-ins for "a closure that was not lowered"). */
+    RT_TEXTURE_PROGRAM = 5    /* Texture.Arbitrary / ParameterisedTexture.Arbitrary (Texture.fs:8,24) lowered to an expression program:
+                                 csrc/rt_texprog.h is the definition (encoding, check, evaluation, the byte rule); DESIGN.md
+                                 "Texture programs".  `texels` points at the program's bytes (copied at creation, as texels are), `width` is
+                                 their count, `height` is 1; map_centre / map_radius are read as for every root record.  The program sees
+                                 U, V (interpret's x, y -- what Checkered and Image see) and the strike point.  It may be the root a
+                                 hittable wears or the even / odd child of a Checkered record.  A malformed program is
+                                 RT_ERR_INVALID_ARGUMENT; rt_last_error() names the record, the instruction and the reason.  On the routes
+                                 that take rt_texels_source its source must be RT_TEXELS_RECORD, and rt_scene_set_texels_device refuses
+                                 it (both RT_ERR_INVALID_ARGUMENT).  A scene that holds a program runs kernels of its own (built for
+                                 blocks of 256 and 1024 threads: 512 and 768 run at 1024); every other scene runs what it always ran. */
 };
+/* rt_texprog.h's check of a program's n bytes, without a GPU: 0 = a program the scene routes accept; otherwise RT_ERR_INVALID_ARGUMENT
+ * with rt_last_error() = "program: instruction K: <reason>" (unknown opcode, constant index out of range, stack underflow, stack depth
+ * above 8, not exactly three results, too long, non-finite constant, byte count does not match the header). */
+int rt_texture_program_check(const uint8_t *program, size_t n);
 
 enum rt_ramp_source { RT_RAMP_CONST = 0, RT_RAMP_U = 1, RT_RAMP_V = 2 };
 enum rt_walk_tree { RT_WALK_TREE_SAH = 0, RT_WALK_TREE_REFERENCE = 1, RT_WALK_TREE_TUNED = 2 /* reported after rt_scene_tune; not a creation option */ };

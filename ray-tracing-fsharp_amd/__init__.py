@@ -8,7 +8,7 @@ from ._lib import LIB_PATH, RtError, lib  # noqa: F401
 from .raytracing import (Camera, CameraHits, CameraPaths, TracePaths, Colour, FloatProducer, Hittable, Image, ImageOutput, InfinitePlane, InfinitePlaneStyle, LoadImage,  # noqa: F401
                          ParameterisedTexture, Pixel, PixelOutput, Png, Point, RenderJob, RenderResult, Scene, Sphere, SphereStyle, Texture,
                          UnitVector, Vector, HITTABLE_DTYPE, TextureTable, hittable_records, tree_make, tree_make_host, walk_tree_make, walk_tree_make_host)
-from . import hooks, sample_images  # noqa: F401
+from . import hooks, sample_images, texprog  # noqa: F401
 
 
 def device_count() -> int:

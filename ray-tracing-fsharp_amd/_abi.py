@@ -15,6 +15,7 @@ RT_HITTABLE_SPHERE, RT_HITTABLE_UNBOUNDED_SPHERE, RT_HITTABLE_INFINITE_PLANE = r
 RT_PLANE_LIGHT_SOURCE, RT_PLANE_PURE_REFLECTION, RT_PLANE_LAMBERT_REFLECTION, RT_PLANE_FUZZED_REFLECTION = range(4)
 # rt_texture_kind
 RT_TEXTURE_COLOUR, RT_TEXTURE_CHECKERED, RT_TEXTURE_IMAGE, RT_TEXTURE_UV_RAMP = range(4)
+RT_TEXTURE_PROGRAM = 5  # (4 is no kind: it stays RT_ERR_UNSUPPORTED)
 RT_RAMP_CONST, RT_RAMP_U, RT_RAMP_V = range(3)
 RT_WALK_TREE_SAH, RT_WALK_TREE_REFERENCE, RT_WALK_TREE_TUNED = range(3)
 

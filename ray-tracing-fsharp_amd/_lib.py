@@ -220,6 +220,7 @@ SIGNATURES = {
     "rt_scene_set_texels_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "rt_dev_scene_texels": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, _P(C.c_size_t), _u32p]),  # texel_off[n_textures]
     "rt_dev_last_texture_plan": (C.c_int, [_P(C.c_int64)]),  # out[8]
+    "rt_texture_program_check": (C.c_int, [C.c_char_p, C.c_size_t]),
     "rt_dev_float_producer": (C.c_int, [C.c_int32, _u32p, C.c_int32, _dp]),
     "rt_dev_stream_state": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32, _u64p, _u32p, _u32p]),
     "rt_dev_bbox_hits": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _i32p]),

@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "rt_trig.h"
+#include "rt_texprog.h"
 
 #pragma clang fp contract(off)
 
@@ -956,6 +957,9 @@ RTD_INLINE uint32_t ramp_byte(double v) { // byte (v * 255.0) (RayTracing.App/Sa
 // stage of its own (stage_tex): a call anywhere in the kernel's loop makes every value that lives across it compete for the few
 // callee-saved registers (measured: 136 SGPR and 40 VGPR spills against 17 and 0 without the call, config 5 25 % slower).
 // The unit hooks and the single-lane helpers call the out-of-line copy below.
+// PROG: the arm of texture programs (RT_TEXTURE_PROGRAM, rt_texprog.h) is compiled in.  Only the kernels that a scene with at least one
+// program record runs have it (render_prog_kernel and its kin, texture_colour_at_prog): the others are at 128 VGPRs with spills already.
+template <bool PROG = false>
 RTD_INLINE uint32_t texture_colour_at_inline(const TexRec *tex, const uint8_t *texels, int id, V3 p, double *uv) {
     const TexRec root = tex[id];
     if (root.kind == 0u) return root.rgb; // ParameterisedTexture.toTexture's Colour case (Texture.fs:71)
@@ -995,12 +999,19 @@ RTD_INLINE uint32_t texture_colour_at_inline(const TexRec *tex, const uint8_t *t
             }
             return c;
         }
+        if constexpr (PROG) {
+            // the program's bytes stay in global memory (lanes of a wave may be on different programs); its stack is eight registers
+            if (t.kind == 5u) return rtxp::eval(texels + t.texel_off, x, y, p.x, p.y, p.z);
+        }
         return t.rgb; // Colour
     }
     return RTD_BLACK;
 }
 __device__ __noinline__ uint32_t texture_colour_at(const TexRec *tex, const uint8_t *texels, int id, V3 p, double *uv) {
     return texture_colour_at_inline(tex, texels, id, p, uv);
+}
+__device__ __noinline__ uint32_t texture_colour_at_prog(const TexRec *tex, const uint8_t *texels, int id, V3 p, double *uv) {
+    return texture_colour_at_inline<true>(tex, texels, id, p, uv);
 }
 
 // ---- Hittable.Reflection (Hittable.fs:8-12 -> Sphere.reflection Sphere.fs:150-300, InfinitePlane.reflection
@@ -1025,7 +1036,8 @@ RTD_INLINE int textured(i2 m) {
     const int style = (m.x >> 2) & 7;
     return (texId >= 0 && (isPlane ? style == 0 : style != 1)) ? texId : -1;
 }
-template <bool LDS, bool TEX = true>
+// TEX = 2: ... with the arm of texture programs (texture_colour_at_prog): the unit hooks, and the kernels of scenes that hold a program.
+template <bool LDS, int TEX>
 RTD_INLINE bool reflection(const SceneView<LDS> &sc, int obj, V3 strike, V3 &o, V3 &d, uint32_t &colour, Rng &rng, uint32_t texPre = RTD_NO_TEX) {
     const i2 m = sc.meta[obj];
     const bool isPlane = (m.x & 3) == (int) RTD_KIND_PLANE;
@@ -1037,7 +1049,7 @@ RTD_INLINE bool reflection(const SceneView<LDS> &sc, int obj, V3 strike, V3 &o, 
     if (texPre != RTD_NO_TEX) texColour = texPre;
     else if (TEX) {
         const int texId = textured(m);
-        if (texId >= 0) texColour = texture_colour_at(sc.tex, sc.texels, texId, strike, nullptr);
+        if (texId >= 0) texColour = TEX == 2 ? texture_colour_at_prog(sc.tex, sc.texels, texId, strike, nullptr) : texture_colour_at(sc.tex, sc.texels, texId, strike, nullptr);
     }
 
     V3 n;              // normal.Vector (possibly flipped)
@@ -1350,7 +1362,7 @@ RTD_INLINE uint32_t trace_ray(const SceneView<LDS> &sc, int maxCount, V3 o, V3 d
         if (obj < 0) return RTD_BLACK;
         V3 strike = walk(o, d, t);
         if (COUNT) cnt.refl++;
-        if (reflection<LDS>(sc, obj, strike, o, d, colour, rng)) return colour;
+        if (reflection<LDS, 2>(sc, obj, strike, o, d, colour, rng)) return colour; // (the unit hook: every kind, programs included)
         bounces = bounces + 1;
     }
     return RTD_HOTPINK;

@@ -35,6 +35,7 @@ struct SceneSize {
     int32_t n_nodes = 0;                     // records of the depth-ordered node32 section
     uint64_t n_objects = 0;
     bool tex = false;                        // has parameterised textures
+    bool prog = false;                       // ... at least one of them a texture program (RT_TEXTURE_PROGRAM): the kernels with that arm run
 };
 // A frame shard (rtmode::FRAME_* [0..3, 9]), a caller's ray list (RAYS_TRACE [4] paths, RAYS_HIT [5] hit queries) or a caller's footprint
 // list (FOOTPRINTS_* [6..8, 10]: planned as a FRAME of n pixels -- chunk widening, fused or two passes, placement, pools -- run by the
@@ -65,6 +66,7 @@ struct Job {
 // plan owns.
 struct Pass {
     bool lds = false, count = false, tex = false;
+    bool prog = false; // tex, and the scene holds a texture program: render_prog_kernel (rtmode::is_built_prog: blocks of 256 and 1024 only)
     int block = 1024, mode = rtmode::FRAME_FUSED;
     uint64_t grid = 0;
     size_t lds_bytes = 0;
@@ -151,7 +153,7 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     pl.scene = sc; pl.set = set; pl.job = job; pl.cu_count = cu_count;
     Pass &q = pl.one;
     Settings eff = set; // (a footprint list asked to run at 512 or 768 threads runs at 1024: residency is decided at the block that runs)
-    if (job.list() && eff.block != 0 && eff.block != 256) eff.block = 1024;
+    if ((job.list() || sc.prog) && eff.block != 0 && eff.block != 256) eff.block = 1024; // (a scene with texture programs: likewise, frames included)
     q.lds = lds_resident(sc, eff, count); // (ray lists too: the render's decision, taken at the block the settings ask for)
     q.count = count;
     q.park = set.park < 0 ? 0 : (set.park ? set.park : RTD_PARK_DEFAULT);
@@ -167,6 +169,7 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
         q.block = default_block(set) == 256 ? 256 : 1024;
         q.mode = rtmode::mode_of({job.source(), job.kind == Job::CAMERA_HITS ? rtmode::Pass::CAMERA_HITS : rtmode::Pass::RAY_LIST, false, false, job.kind != Job::TRACE});
         q.tex = job.kind == Job::TRACE && sc.tex;
+        q.prog = q.tex && sc.prog;
         q.chunk = set.chunk ? set.chunk : RTD_MAX_CHUNK; // rays per run of the queue (a wave takes as many runs at once as it has idle lanes)
         if (job.kind != Job::TRACE) q.park = 0;
         if (job.kind == Job::CAMERA_HITS) {
@@ -184,6 +187,8 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     q.mode = rtmode::mode_of({job.source(), rtmode::Pass::FUSED, false, job.ray_log && !job.list()});
     if (!rtmode::built_for_every_block(q.mode)) q.block = q.block == 256 ? 256 : 1024; // (a list: as the ray lists)
     q.tex = sc.tex;               // otherwise the variant compiled without the texture call: no scratch, no VGPR spills
+    q.prog = sc.tex && sc.prog;
+    if (q.prog) q.block = q.block == 256 ? 256 : 1024; // (the program variants: as the lists)
     const int half = job.spp / 2;
     q.k = half < 5 ? half : 5; // min 5 (spp / 2), Scene.fs:172
     // Units of the fused kernel: 16 pixels -- except for frames of few samples per pixel (always fused: the two-pass rule needs

@@ -101,6 +101,10 @@ constexpr bool is_built(int mode, int block, bool tex) {
     return is_mode(mode) && (built_for_every_block(mode) || block == 256 || block == 1024) && (!tex || has_textured_variant(mode));
 }
 
+// The variant with the arm of texture programs (render_prog_kernel, a scene that holds an RT_TEXTURE_PROGRAM record): every mode that has a
+// textured variant, at blocks of 256 and 1024 threads only, as the list modes are -- frames too (a launch asking for 512 or 768 runs at 1024).
+constexpr bool is_built_prog(int mode, int block) { return has_textured_variant(mode) && (block == 256 || block == 1024); }
+
 constexpr bool round_trip(int m = 0) { return m == MODE_COUNT || (mode_of(mode_desc(m)) == m && round_trip(m + 1)); }
 static_assert(round_trip(), "number -> description -> number holds for every mode: no two modes share a description");
 static_assert(mode_of(mode_desc(MODE_COUNT)) == -1 && mode_of(mode_desc(-1)) == -1, "a number outside the table is no mode");

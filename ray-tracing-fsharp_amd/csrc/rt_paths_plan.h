@@ -17,6 +17,7 @@ struct PathsPlan {
     bool lds = false;       // the route: the scene staged into LDS and walked by the filter loop (timed variant, LDS-resident scene)
     bool count = false;     // the counting variant: always over the exact records in global memory
     bool tex = false;       // the scene has parameterised textures
+    bool prog = false;      // ... one of them a texture program: paths_prog_kernel
     size_t lds_bytes = 0;   // dynamic LDS: the timed image of the scene, or nothing (a wave keeps no scratch in LDS)
     bool lds_resident = false; // the render's own answer for this scene and these settings, whichever route runs
     uint64_t slots = 0;
@@ -33,6 +34,7 @@ static inline PathsPlan plan_begin(const rtp::SceneSize &sc, const rtp::Settings
     pl.chunk = set.chunk ? set.chunk : RTPP_CHUNK_DEFAULT;
     pl.count = count;
     pl.tex = sc.tex;
+    pl.prog = sc.tex && sc.prog;
     pl.lds_resident = rtp::lds_resident(sc, set, false) && sc.lds32_total <= RT_LDS_BYTES; // the render's residency rule (below 16384 objects)
     pl.lds = !count && pl.lds_resident && allow_lds;
     pl.lds_bytes = pl.lds ? (size_t) sc.lds32_total : 0u;

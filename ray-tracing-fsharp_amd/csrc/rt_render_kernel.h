@@ -205,7 +205,7 @@ enum { L_IDLE = 0, L_WALK = 1, L_DONE = 2, L_SLOW = 3, L_LAMB = 4, L_TEX = 5 };
 // LOG: the kernel may be asked to log rays (rt_scene_tune's probe): only the fused mode's instantiations carry that code -- the
 // log's four kernel arguments otherwise sit in scalar registers across the whole loop of the two-pass kernels, which have none to spare
 // FP: the pixels are the caller's footprints (rtmode::Pixels::FOOTPRINTS): a sample's ray comes from footprint_ray instead of camera_ray
-template <bool LDS, bool COUNT, bool TEX, bool LOG, bool FP = false>
+template <bool LDS, bool COUNT, int TEX, bool LOG, bool FP = false>
 struct Sched {
     const RenderParams &p;
     const SceneView<LDS> &sc;
@@ -409,7 +409,7 @@ struct Sched {
         if (__builtin_amdgcn_ballot_w64(st == L_TEX) == 0ull) return;
         if (st == L_TEX) {
             const V3 strike = walk(o, d, w.bestLen);
-            texc = texture_colour_at_inline(sc.tex, sc.texels, textured(sc.meta[w.best]), strike, nullptr);
+            texc = texture_colour_at_inline<TEX == 2>(sc.tex, sc.texels, textured(sc.meta[w.best]), strike, nullptr);
             st = L_SLOW;
         }
     }
@@ -588,7 +588,7 @@ struct Sched {
 
 // Trace `total` items of the current unit.  Item i belongs to pixel slot map[i / per] (or i / per when map is null)
 // and is sample s_base + i % per of that pixel; its colour is added to accumulator slot (sample < split ? 0 : 1).
-template <bool LDS, bool COUNT, bool COST, bool TEX, bool LOG, bool FP>
+template <bool LDS, bool COUNT, bool COST, int TEX, bool LOG, bool FP>
 RTD_INLINE void run_items(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, RTD_AS3 uint32_t *acc, const RTD_AS3 uint32_t *pix,
                           const RTD_AS3 uint32_t *cand, const RTD_AS3 uint32_t *live, bool use_live, uint32_t total, uint32_t per, uint32_t s_base,
                           uint32_t split, Counters &cnt, StageStats &ss) {
@@ -657,7 +657,7 @@ RTD_INLINE void run_items(const RenderParams &p, const SceneView<LDS> &sc, unsig
 // candidates: those are a camera's), and every stage is Sched's, so parked paths carry the ray index in slotOff as they carry a
 // pixel's accumulator word in a render.  Where a render adds an ended path's colour to its pixel, the ray's colour and final rng
 // state are stored; RAYS_HIT instead stores (hit, strike) once the walk and the unbounded tests are done, and shades nothing.
-template <bool LDS, bool COUNT, bool TEX, bool HIT>
+template <bool LDS, bool COUNT, int TEX, bool HIT>
 RTD_INLINE void run_rays(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, Counters &cnt, StageStats &ss) {
     const int lane = threadIdx.x & 63;
     const uint32_t P = (uint32_t) p.chunk;
@@ -920,7 +920,7 @@ RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc,
 // JOB (a render job, render_job_kernel): in front of a reservation lane 0 polls the job's stop word -- set: nothing is reserved, exactly as when
 // the list is exhausted, and the ranges already reserved are finished and flushed as usual -- and clips the reservation to the job's
 // budget; a flushed range's pixels are final and are published (job_publish).
-template <bool LDS, bool COUNT, bool TEX, bool FP, bool MAP = false, bool PX = false, bool JOB = false>
+template <bool LDS, bool COUNT, int TEX, bool FP, bool MAP = false, bool PX = false, bool JOB = false>
 RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, RTD_AS3 uint32_t *wv, uint32_t n1, uint32_t n2, Counters &cnt,
                            StageStats &ss, uint64_t &sampleCount, const JobCtl *job = nullptr) {
     const int lane = threadIdx.x & 63;
@@ -1161,6 +1161,27 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
 template <bool LDS, int BLOCK, int PASS, bool TEX>
 __global__ void __launch_bounds__(BLOCK) render_job_kernel(const RenderParams p, const JobCtl job_ctl) {
     static_assert(PASS == rtmode::FRAME_FUSED || PASS == rtmode::FRAME_PASS_A || PASS == rtmode::FRAME_PASS_B, "a frame pass");
+    constexpr bool COUNT = false, JOB = true;
+    constexpr int MODE = PASS;
+    const JobCtl *const job = &job_ctl;
+#include "rt_render_body.inc"
+}
+
+// The variants of both for a scene that holds at least one texture program (RT_TEXTURE_PROGRAM): the textured kernels with the program arm
+// of texture_colour_at_inline compiled in, under symbols of their own, so that every kernel above stays exactly what it was.  Built for
+// blocks of 256 and 1024 threads and for the modes that have a textured variant (rtmode::is_built_prog).  TEX = 2 inside the body: what is
+// true of a textured kernel (the texture park pool, stage_tex) is true of these.
+template <bool LDS, bool COUNT, int BLOCK, int MODE>
+__global__ void __launch_bounds__(BLOCK) render_prog_kernel(const RenderParams p) {
+    constexpr int TEX = 2;
+    constexpr bool JOB = false;
+    const JobCtl *const job = nullptr;
+#include "rt_render_body.inc"
+}
+template <bool LDS, int BLOCK, int PASS>
+__global__ void __launch_bounds__(BLOCK) render_prog_job_kernel(const RenderParams p, const JobCtl job_ctl) {
+    static_assert(PASS == rtmode::FRAME_FUSED || PASS == rtmode::FRAME_PASS_A || PASS == rtmode::FRAME_PASS_B, "a frame pass");
+    constexpr int TEX = 2;
     constexpr bool COUNT = false, JOB = true;
     constexpr int MODE = PASS;
     const JobCtl *const job = &job_ctl;

@@ -397,6 +397,7 @@ struct HostScene {
     std::vector<rtd::TexRec> texRecs;
     std::vector<uint8_t> texelBlob; // (a scene whose texels were placed on a device: empty until the host mirror is fetched)
     uint64_t texelBytes = 0;        // the blob's size on every route
+    bool hasPrograms = false;       // at least one RT_TEXTURE_PROGRAM record: the launch plan picks the kernels with that arm
     std::vector<int32_t> objToOrig; // object-table index -> index in `hittables`
     std::vector<int32_t> origToObj;
     FlatTree tree;     // BoundingBoxTree.make's tree; prim = object-table index (= the leaf's depth-first rank)
@@ -450,6 +451,17 @@ static std::string build_textures(const rt_texture *tex, size_t ntex, HostScene 
         case RT_TEXTURE_IMAGE:
             if ((!t.texels && !(external && external[i])) || t.width <= 0 || t.height <= 0) return "texture " + std::to_string(i) + ": image without texels";
             break;
+        case RT_TEXTURE_PROGRAM: { // rt_texprog.h: `texels` is the program, `width` its byte count, `height` 1
+            if (external && external[i]) return "texture " + std::to_string(i) + ": a program's bytes come from the record";
+            if (!t.texels || t.width <= 0 || t.height != 1) return "texture " + std::to_string(i) + ": program without bytes (texels, width = byte count, height = 1)";
+            int where = -1;
+            const int why = rtxp::check(t.texels, (size_t) t.width, &where);
+            if (why != rtxp::OK)
+                return "texture " + std::to_string(i) + ": program: " + (where >= 0 ? (why == rtxp::NONFINITE_CONST ? "constant " : "instruction ") + std::to_string(where) + ": " : std::string()) +
+                       rtxp::reason_text(why);
+            s.hasPrograms = true;
+            break;
+        }
         default: status = RT_ERR_UNSUPPORTED; return "texture " + std::to_string(i) + ": Texture.Arbitrary closures cannot cross the C ABI";
         }
         s.texRecs[i] = r;
@@ -458,12 +470,16 @@ static std::string build_textures(const rt_texture *tex, size_t ntex, HostScene 
     // the blob: images in index order, each zero-padded to a multiple of 16 (rt_texture_plan.h)
     std::vector<uint64_t> off(ntex);
     s.texelBytes = rtt::texel_layout(kind.data(), width.data(), height.data(), ntex, RT_TEXTURE_IMAGE, off.data());
+    // ... then the programs, in index order, each zero-padded to a multiple of 16: behind the images, so that no image's place depends on them
+    for (size_t i = 0; i < ntex; ++i)
+        if (kind[i] == RT_TEXTURE_PROGRAM) { off[i] = s.texelBytes; s.texelBytes += align16((size_t) width[i]); }
+    if (s.hasPrograms && s.texelBytes > rtt::MAX_BLOB) { status = RT_ERR_UNSUPPORTED; return "the texels and programs exceed 4 GiB: texel offsets are 32 bits wide"; }
     if (external && s.texelBytes > rtt::MAX_BLOB) { status = RT_ERR_UNSUPPORTED; return "the image textures' texels exceed 4 GiB: texel offsets are 32 bits wide"; }
     if (!external) s.texelBlob.assign((size_t) s.texelBytes, 0);
     for (size_t i = 0; i < ntex; ++i) {
         if (off[i] == rtt::NO_BYTE) continue;
         s.texRecs[i].texel_off = (uint32_t) off[i]; // (32 bits: above 4 GiB the offset wraps on this route, as it always did -- DESIGN.md "Textures from device memory")
-        if (!external) memcpy(s.texelBlob.data() + (size_t) off[i], tex[i].texels, (size_t) rtt::image_bytes(width[i], height[i]));
+        if (!external) memcpy(s.texelBlob.data() + (size_t) off[i], tex[i].texels, kind[i] == RT_TEXTURE_PROGRAM ? (size_t) width[i] : (size_t) rtt::image_bytes(width[i], height[i]));
     }
     status = RT_OK;
     return std::string();

@@ -225,6 +225,7 @@ static rtp::SceneSize scene_size(const rth::HostScene &h) {
     sc.n_nodes = h.off.n_nodes;
     sc.n_objects = h.nBounded + h.nUnbounded;
     sc.tex = !h.texRecs.empty();
+    sc.prog = h.hasPrograms;
     return sc;
 }
 // The decision a timed render with default options takes (rt_scene_info.lds_resident, the pixel_candidates hook)
@@ -269,8 +270,23 @@ template <int MODE, bool TEX> static render_fn pick_mode(const rtp::Pass &q) {
 }
 // q.mode against every mode of the table in turn.  tex: the scene has parameterised textures (otherwise the variant compiled without
 // the texture call: no scratch, no VGPR spills)
+// ... and the variants with the arm of texture programs (q.prog: the scene holds one), rtmode::is_built_prog
+template <bool LDS, bool COUNT, int BLOCK, int MODE> static render_fn prog_kernel_if_built() {
+    if constexpr (rtmode::is_built_prog(MODE, BLOCK)) return render_prog_kernel<LDS, COUNT, BLOCK, MODE>;
+    else return nullptr;
+}
+template <int BLOCK, int MODE> static render_fn pick_prog_variant(bool lds, bool count) {
+    if (lds) return count ? prog_kernel_if_built<true, true, BLOCK, MODE>() : prog_kernel_if_built<true, false, BLOCK, MODE>();
+    return count ? prog_kernel_if_built<false, true, BLOCK, MODE>() : prog_kernel_if_built<false, false, BLOCK, MODE>();
+}
+static_assert(rtmode::is_built_prog(rtmode::FRAME_FUSED, 256) && rtmode::is_built_prog(rtmode::FRAME_PASS_B, 1024) && !rtmode::is_built_prog(rtmode::FRAME_FUSED, 512) &&
+              !rtmode::is_built_prog(rtmode::RAYS_HIT, 1024), "the program variants: blocks of 256 and 1024, the modes that shade (rt_launch_plan.h plans exactly these)");
+template <int MODE> static render_fn pick_prog_mode(const rtp::Pass &q) { // (another block: nullptr, and the launch fails -- no kernel is substituted)
+    return q.block == 1024 ? pick_prog_variant<1024, MODE>(q.lds, q.count) : q.block == 256 ? pick_prog_variant<256, MODE>(q.lds, q.count) : nullptr;
+}
 template <int MODE = rtmode::FRAME_FUSED> static render_fn pick_kernel(const rtp::Pass &q) {
-    if constexpr (MODE < rtmode::MODE_COUNT) return q.mode == MODE ? (q.tex ? pick_mode<MODE, true>(q) : pick_mode<MODE, false>(q)) : pick_kernel<MODE + 1>(q);
+    if constexpr (MODE < rtmode::MODE_COUNT)
+        return q.mode == MODE ? (q.prog ? pick_prog_mode<MODE>(q) : q.tex ? pick_mode<MODE, true>(q) : pick_mode<MODE, false>(q)) : pick_kernel<MODE + 1>(q);
     else return nullptr;
 }
 
@@ -357,6 +373,14 @@ size_t rt_abi_offsetof(int which, int field) {
     }
 #undef F
 #undef RT_OFFS
+}
+
+int rt_texture_program_check(const uint8_t *program, size_t n) {
+    int where = -1;
+    const int why = rtxp::check(program, n, &where);
+    if (why == rtxp::OK) return RT_OK;
+    return fail(RT_ERR_INVALID_ARGUMENT, std::string("program: ") + (where >= 0 ? (why == rtxp::NONFINITE_CONST ? "constant " : "instruction ") + std::to_string(where) + ": " : std::string()) +
+                                             rtxp::reason_text(why));
 }
 
 int rt_set_launch_config(int32_t block_threads, int32_t chunk_pixels, int32_t blocks_per_cu) {
@@ -618,11 +642,11 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
     const rtp::Job &j = pl.job;
     put(1);
     put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : (j.kind == rtp::Job::HIT ? 2 : (j.kind == rtp::Job::FOOTPRINTS ? 3 : (j.kind == rtp::Job::PIXELS ? 4 : 5)))));
-    put((int64_t) sc.lds_total); put((int64_t) sc.lds32_total); put(sc.n_nodes); put((int64_t) sc.n_objects); put(sc.tex);
+    put((int64_t) sc.lds_total); put((int64_t) sc.lds32_total); put(sc.n_nodes); put((int64_t) sc.n_objects); put((int) sc.tex + (int) sc.prog);
     put(s.block); put(s.chunk); put(s.blocks_per_cu); put(s.yield); put(s.refill); put(s.passes); put(s.park);
     put(pl.one.count); put(j.ray_log); put((int64_t) j.n_rows); put(j.max_w); put(j.spp); put((int64_t) j.n); put(pl.cu_count); put(per_cu);
     const rtp::Pass &q = pl.one;
-    put(q.lds); put(q.count); put(q.block); put(q.mode); put(q.tex); put((int64_t) q.lds_bytes); put(pl.two_pass);
+    put(q.lds); put(q.count); put(q.block); put(q.mode); put((int) q.tex + (int) q.prog); put((int64_t) q.lds_bytes); put(pl.two_pass);
     put((int64_t) pl.pairs_bytes); put((int64_t) pl.list_bytes); put((int64_t) pl.sort_bytes); put((int64_t) pl.pool_bytes); put((int64_t) pl.waves);
     put(pl.error ? 1 : 0);
     for (const rtp::Pass *r : {&pl.one, &pl.a, &pl.b}) {
@@ -1620,6 +1644,11 @@ template <bool TEX, int BLOCK> static paths_fn pick_paths_variant(bool lds, bool
     return lds ? paths_kernel<true, false, TEX, BLOCK> : paths_kernel<false, false, TEX, BLOCK>;
 }
 static paths_fn pick_paths_kernel(const rtpp::PathsPlan &pl) { // blocks of 256 and 1024 only; TEX only where the scene has parameterised textures
+    if (pl.prog) {
+        if (pl.count) return pl.block == 256 ? paths_prog_kernel<false, true, 256> : paths_prog_kernel<false, true, 1024>;
+        if (pl.lds) return pl.block == 256 ? paths_prog_kernel<true, false, 256> : paths_prog_kernel<true, false, 1024>;
+        return pl.block == 256 ? paths_prog_kernel<false, false, 256> : paths_prog_kernel<false, false, 1024>;
+    }
     if (pl.block == 256) return pl.tex ? pick_paths_variant<true, 256>(pl.lds, pl.count) : pick_paths_variant<false, 256>(pl.lds, pl.count);
     return pl.tex ? pick_paths_variant<true, 1024>(pl.lds, pl.count) : pick_paths_variant<false, 1024>(pl.lds, pl.count);
 }
@@ -1696,7 +1725,7 @@ static int enqueue_paths(const rt_scene *scene, int32_t device, PathParams q, ui
     {
         int64_t *o = g_last_paths_plan;
         o[0] = plan.block; o[1] = (int64_t) plan.grid; o[2] = plan.chunk; o[3] = (int64_t) plan.lds_bytes; o[4] = plan.lds ? 1 : 0;
-        o[5] = plan.count ? 1 : 0; o[6] = plan.tex ? 1 : 0; o[7] = (int64_t) plan.slots;
+        o[5] = plan.count ? 1 : 0; o[6] = plan.tex ? (plan.prog ? 2 : 1) : 0; o[7] = (int64_t) plan.slots;
     }
     q.chunk = plan.chunk;
 
@@ -2766,6 +2795,10 @@ static_assert(sizeof(JobWords) <= JOB_WORDS_BYTES, "the job's words fit their sl
 typedef void (*job_fn)(const RenderParams, const JobCtl);
 template <int BLOCK, int PASS, bool TEX> job_fn pick_job_lds(bool lds) { return lds ? render_job_kernel<true, BLOCK, PASS, TEX> : render_job_kernel<false, BLOCK, PASS, TEX>; }
 template <int PASS> job_fn pick_job_pass(const rtp::Pass &q) {
+    if (q.prog) {
+        if (q.block == 256) return q.lds ? render_prog_job_kernel<true, 256, PASS> : render_prog_job_kernel<false, 256, PASS>;
+        return q.lds ? render_prog_job_kernel<true, 1024, PASS> : render_prog_job_kernel<false, 1024, PASS>;
+    }
     if (q.block == 256) return q.tex ? pick_job_lds<256, PASS, true>(q.lds) : pick_job_lds<256, PASS, false>(q.lds);
     return q.tex ? pick_job_lds<1024, PASS, true>(q.lds) : pick_job_lds<1024, PASS, false>(q.lds);
 }
@@ -3234,7 +3267,7 @@ __global__ void k_reflection(const RenderParams p, int n, const int32_t *obj, co
     V3 o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
     uint32_t c = ld_rgb(col_in + i * 3);
     Rng g; g.x = rng[i * 4]; g.y = rng[i * 4 + 1]; g.z = rng[i * 4 + 2]; g.w = rng[i * 4 + 3];
-    bool ab = reflection<false>(sc, obj[i], mk(s[0], s[1], s[2]), o, d, c, g);
+    bool ab = reflection<false, 2>(sc, obj[i], mk(s[0], s[1], s[2]), o, d, c, g);
     absorbed[i] = ab ? 1 : 0;
     st_rgb(col_out + i * 3, c);
     double *ro = ray_out + i * 6;
@@ -3357,11 +3390,11 @@ __global__ void k_trace_ray(const RenderParams p, int depth, int n, const double
     st_rgb(col_out + i * 3, c);
     rng[i * 4] = g.x; rng[i * 4 + 1] = g.y; rng[i * 4 + 2] = g.z; rng[i * 4 + 3] = g.w;
 }
-__global__ void k_texture(const RenderParams p, int tex, int n, const double *pts, double *uv, uint8_t *col) {
+__global__ void k_texture(const RenderParams p, int tex, int n, const double *pts, double *uv, uint8_t *col, int prog) { // prog: the scene holds a texture program
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double u[2] = {__builtin_nan(""), __builtin_nan("")};
-    uint32_t c = texture_colour_at(p.tex, p.texels, tex, mk(pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]), u);
+    uint32_t c = prog ? texture_colour_at_prog(p.tex, p.texels, tex, mk(pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]), u) : texture_colour_at(p.tex, p.texels, tex, mk(pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]), u);
     if (uv) { uv[i * 2] = u[0]; uv[i * 2 + 1] = u[1]; }
     st_rgb(col + i * 3, c);
 }
@@ -3631,7 +3664,7 @@ int rt_dev_texture_colour_at(int32_t device, const rt_scene *scene, int32_t text
         auto dp = dev_in(points, (size_t) n * 3);
         auto duv = dev_out(uv_out, uv_out ? (size_t) n * 2 : 0);
         auto dc = dev_out(colour_out, (size_t) n * 3);
-        return hook_run([&] { launch_n(k_texture, n, p, texture, n, dp.p, duv.p, dc.p); }, dp, duv, dc);
+        return hook_run([&] { launch_n(k_texture, n, p, texture, n, dp.p, duv.p, dc.p, scene->host.hasPrograms ? 1 : 0); }, dp, duv, dc);
     });
 }
 
@@ -4588,6 +4621,7 @@ static int check_sources(const rt_texture *textures, size_t n_textures, const rt
         if (q.flags & ~RT_TEXELS_TOP_FIRST) return fail(RT_ERR_INVALID_ARGUMENT, who + "unknown flag bit");
         if (q.kind == RT_TEXELS_RECORD) continue;
         const rt_texture &t = textures[i];
+        if (t.kind == RT_TEXTURE_PROGRAM) return fail(RT_ERR_INVALID_ARGUMENT, who + "a program's bytes come from the record (RT_TEXELS_RECORD)");
         if (t.kind != RT_TEXTURE_IMAGE) return fail(RT_ERR_INVALID_ARGUMENT, who + "texels for a texture that is not an image");
         if (!q.data) return fail(RT_ERR_INVALID_ARGUMENT, who + "data is NULL");
         if (q.kind == RT_TEXELS_DEVICE && t.width > 0 && t.height > 0 && q.bytes < rtt::image_bytes(t.width, t.height))
@@ -4639,6 +4673,13 @@ static int place_texels(const rth::HostScene &h, const rt_texture *textures, siz
     std::vector<rtt::ImageEntry> table;
     bool any = false;
     for (size_t i = 0; i < n_textures; ++i) {
+        if (textures[i].kind == RT_TEXTURE_PROGRAM) { // its bytes, from the record (check_sources), zero-padded; of_image_kernel leaves the range alone
+            const size_t off = h.texRecs[i].texel_off, bytes = (size_t) textures[i].width, padded = (bytes + 15u) & ~(size_t) 15u;
+            HIP_TRY(hipMemcpyAsync(blob.p + off, textures[i].texels, bytes, hipMemcpyHostToDevice, st));
+            if (padded > bytes) HIP_TRY(hipMemsetAsync(blob.p + off + bytes, 0, padded - bytes, st));
+            plan[6] += (int64_t) bytes;
+            continue;
+        }
         if (textures[i].kind != RT_TEXTURE_IMAGE) continue;
         const rt_texels_source &q = ts.src[i];
         const int32_t w = textures[i].width, hgt = textures[i].height;
@@ -4747,6 +4788,7 @@ int rt_scene_set_texels_device(rt_scene *scene, int32_t texture, int32_t device,
         rth::HostScene &h = scene->host;
         if (texture < 0 || (size_t) texture >= h.texRecs.size()) return fail(RT_ERR_INVALID_ARGUMENT, "texture index out of range");
         const rtd::TexRec &r = h.texRecs[(size_t) texture];
+        if (r.kind == RT_TEXTURE_PROGRAM) return fail(RT_ERR_INVALID_ARGUMENT, "texture " + std::to_string(texture) + " is a program: its bytes are fixed at creation");
         if (r.kind != RT_TEXTURE_IMAGE) return fail(RT_ERR_INVALID_ARGUMENT, "texture " + std::to_string(texture) + " is not an image");
         if ((uint64_t) bytes < rtt::image_bytes(r.width, r.height)) return fail(RT_ERR_INVALID_ARGUMENT, "bytes is below width * height * 3");
         DeviceGuard guard;

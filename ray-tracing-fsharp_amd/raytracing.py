@@ -20,6 +20,7 @@ from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _abi as A
+from . import texprog
 from ._lib import RtError, check, lib
 
 TOLERANCE = 0.00000001  # Float.fs:82
@@ -121,6 +122,7 @@ class _ParamTex:
     bitmap: object = None          # ofImageDevice: a torch uint8 [H, W, 3] tensor on a GPU, rows top first (the device reverses them)
     jpeg: Optional[bytes] = None   # ofJpeg: a baseline JPEG file's bytes (decoded on the device, rows reversed there)
     size: Tuple[int, int] = (0, 0)  # (height, width) of a bitmap / jpeg image
+    program: Optional[bytes] = None  # Program: the bytes of csrc/rt_texprog.h (texprog.compile_program)
 
 
 class ParameterisedTexture:  # Texture.fs:19-24
@@ -185,7 +187,26 @@ class ParameterisedTexture:  # Texture.fs:19-24
         return _ParamTex(A.RT_TEXTURE_UV_RAMP, pixel=Pixel(*const), ramp=tuple(src))
 
     @staticmethod
-    def Arbitrary(_f: Callable) -> _ParamTex:
+    def Program(red, green, blue) -> _ParamTex:
+        """`ParameterisedTexture.Arbitrary (fun x y -> Texture.Arbitrary (fun p -> pixel))` as three expressions (texprog: U, V, PX, PY,
+        PZ, numbers, operators, sin, floor, sqrt, abs, minimum, maximum, lt, le, flt, select), one per channel; each value becomes a byte
+        as F#'s `byte` does.  Compiled here and checked by the library (rt_texture_program_check); evaluated on the GPU."""
+        return _ParamTex(A.RT_TEXTURE_PROGRAM, program=texprog.compile_program(red, green, blue))
+
+    @staticmethod
+    def Arbitrary(f: Callable) -> _ParamTex:
+        """`f` is called once with the symbolic U and V.  A (red, green, blue) triple of expressions, a Texture.Program or a
+        Texture.Colour is lowered to a record; a closure that gives anything else cannot cross the C ABI."""
+        try:
+            got = f(texprog.U, texprog.V)
+            if isinstance(got, Texture) and got.pixel is not None:
+                return ParameterisedTexture.Colour(got.pixel)
+            if isinstance(got, Texture) and got.param is not None and got.param.kind == A.RT_TEXTURE_PROGRAM:
+                return got.param
+            if isinstance(got, (tuple, list)) and not isinstance(got, Pixel) and len(got) == 3:
+                return ParameterisedTexture.Program(*got)
+        except texprog.NotAnExpression:  # (only the language's own refusals: any other error of the closure is the caller's to see)
+            pass
         raise RtError(A.RT_ERR_UNSUPPORTED, "Texture.Arbitrary closures cannot cross the C ABI; use UvRamp/Checkered/Image")
 
     @staticmethod
@@ -206,6 +227,12 @@ class Texture:  # Texture.fs:6-8
     @staticmethod
     def Colour(p: Pixel) -> "Texture":
         return Texture(pixel=Pixel(*p))
+
+    @staticmethod
+    def Program(red, green, blue) -> "Texture":
+        """`Texture.Arbitrary (fun p -> pixel)`: three expressions over the strike point (texprog.PX, PY, PZ); there is no (u, v) map,
+        so U and V are those of the unit sphere at the origin."""
+        return Texture(param=ParameterisedTexture.Program(red, green, blue))
 
 
 # ---- Sphere.fs / InfinitePlane.fs / Hittable.fs ------------------------------------------------------------------------
@@ -375,6 +402,11 @@ def _flatten(objects: Sequence[Hittable]):
             r.texels = t.image.ctypes.data
         elif t.kind == A.RT_TEXTURE_UV_RAMP:
             r.ramp_src[:] = t.ramp
+        elif t.kind == A.RT_TEXTURE_PROGRAM:
+            buf = np.frombuffer(t.program, dtype=np.uint8)
+            keep.append(buf)
+            r.height, r.width = 1, len(t.program)
+            r.texels = buf.ctypes.data
         r.rgb[:] = t.pixel
         texs.append(r)
         srcs.append(src)
