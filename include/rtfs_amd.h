@@ -525,6 +525,50 @@ int rt_camera_hits_device(const rt_scene *scene, const rt_camera *camera, int32_
                           void *d_hit_index, void *d_strike /* may be NULL */, void *d_rays_out /* may be NULL */,
                           void *stream, const rt_render_options *options, rt_stats *stats);
 
+/* ---- Camera hits over a batch of views: the above for n_views cameras and ONE list, in ONE launch ---------------------------
+ * The object-id buffers, strike points (depth) and camera rays of a turntable, a fly-through or the training views of a learned
+ * model: what rt_render_views' K frames SEE.  Scene.hitObject (Scene.fs:62-91) of Scene.traceOnce's ray (Scene.fs:129-143), as above.
+ *
+ * cameras[v] and seeds[v] (seeds == NULL: every view uses `seed`) describe view v; every view is a frame of
+ * rows = 2*max_height_coord+1 by cols = 2*max_width_coord+1 pixels.  The list (`pixels`, n entries; NULL: entry i is pixel i), the
+ * sample range and the frame size are SHARED by the views.  Every output is [n_views][n][n_samples](...): slot
+ * (v*n + i)*n_samples + (s - sample_first) holds view v, entry i, sample s.
+ *
+ * View v's slice of every output IS what rt_camera_hits(scene, &cameras[v], max_width_coord, max_height_coord,
+ * seeds ? seeds[v] : seed, device, n, pixels, sample_first, n_samples, ...) writes, bit for bit -- NaN positions and the -1 / -2
+ * codes included -- for any launch settings and both kernel variants: the stream is keyed (seed, pixel, sample) and nothing else.
+ * The cameras need NOT share samples_per_pixel or bounce_depth (they are checked, as by rt_camera_hits, and not otherwise used), and
+ * a scene that holds a texture program is taken: nothing is shaded.  `cameras` and `seeds` are HOST pointers in both variants and are
+ * fully read before the call returns.
+ *
+ * Argument checks come before any device call, nothing is written when one fails: RT_ERR_INVALID_ARGUMENT for a NULL scene,
+ * n_views < 0, a NULL cameras with n_views > 0, anything rt_camera_hits refuses (camera, geometry, sample range, n * n_samples,
+ * a NULL hit_index with n > 0, pixels == NULL with n > rows*cols, options) -- reported for the first offending view --
+ * and n_views * n * n_samples > INT32_MAX.  n_views = 0 or n = 0 is a no-op returning RT_OK with zeroed stats (with n_views = 0 only the
+ * scene, n_views and the options are checked: there is no view to report for).  A list with an entry outside [0, rows*cols) is
+ * malformed as for rt_camera_hits: the host variant refuses it on the host; the device variant checks the shared list ONCE on the
+ * stream, in front of the launch, writes NO output in any view and returns RT_ERR_INVALID_ARGUMENT when stats is given.
+ *
+ * stats: pixels = n_views*n, samples = n_views*n*n_samples, reflections 0, kernel_ms, total_ms; under RT_RENDER_COUNTERS the counting
+ * variant's rays, aabb_tests and prim_tests, summed over the views.  The device variant follows rt_camera_hits_device's contract
+ * (stream, scratch, stats == NULL, current device, options: chunk_pixels counts list entries per work unit -- a unit never spans two
+ * views, csrc/rt_views_plan.h -- and a block of 512 or 768 threads runs as 1024).
+ * Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */
+int rt_camera_hits_views(const rt_scene *scene, const rt_camera *cameras, int32_t n_views,
+                         int32_t max_width_coord, int32_t max_height_coord,
+                         const uint64_t *seeds /* n_views, or NULL: every view uses `seed` */, uint64_t seed,
+                         int32_t device, size_t n, const int32_t *pixels /* ONE list shared by all views; NULL: entry i is pixel i */,
+                         int32_t sample_first, int32_t n_samples, uint32_t flags,
+                         int32_t *hit_index /* [n_views][n][n_samples] */, double *strike /* ...[3], may be NULL */,
+                         double *rays_out /* ...[6], may be NULL */, rt_stats *stats);
+int rt_camera_hits_views_device(const rt_scene *scene, const rt_camera *cameras, int32_t n_views,
+                                int32_t max_width_coord, int32_t max_height_coord,
+                                const uint64_t *seeds, uint64_t seed,
+                                int32_t device, size_t n, const void *d_pixels /* may be NULL */,
+                                int32_t sample_first, int32_t n_samples, uint32_t flags,
+                                void *d_hit_index, void *d_strike /* may be NULL */, void *d_rays_out /* may be NULL */,
+                                void *stream, const rt_render_options *options, rt_stats *stats);
+
 /* ---- Path records: the vertices of each sample's path ---------------------------------------------------------------------
  * A SLOT is one path: follow Scene.traceRay maxCount scene &ray (Scene.fs:93-114) from {Ray = ray; Colour = White}.  Every loop
  * iteration in which hitObject answers ValueSome (object, strikePoint) is VERTEX j = 0, 1, ... of the path.  Per vertex:
@@ -982,7 +1026,9 @@ int rt_last_stage_stats(uint64_t out[16]);
  *   [0]      1 once this thread has planned a launch (all words are 0 before)
  *   [1..21]  inputs: kind (0 frame shard, 1 traceRays list, 2 hitObject list, 3 footprint list: n pixels,
  *            4 pixel list: n pixels, 5 camera hits: n list entries, spp = n_samples, 6 batch of views: n views of n_rows rows each, run by
- *            the render_views kernels at the frame passes' mode numbers) lds_total lds32_total n_nodes n_obj has_tex
+ *            the render_views kernels at the frame passes' mode numbers, 7 camera hits over a batch of views: kind 5's words, n the
+ *            shared list's entries, planned over n_views * n * n_samples rays and run by the camera_hits_views kernels at mode 14)
+ *            lds_total lds32_total n_nodes n_obj has_tex
  *            s_block s_chunk s_bpc s_yield s_refill s_passes s_park (the resolved settings, 0 = "the plan decides") count log
  *            n_rows max_w spp n cu_count per_cu (what the occupancy query answered, before blocks_per_cu)
  *   [22..34] q_lds q_count q_block q_mode q_tex q_lds_bytes two_pass pairs list sort pool waves error
@@ -995,7 +1041,8 @@ int rt_last_stage_stats(uint64_t out[16]);
  *            the same job gets it with passes = 2.
  *   [78]     1 for an extension by map (rt_render_extend_map*, rt_render_footprints_extend_map*), else 0.  Such a launch reports
  *            first_sample 12 and spp = the cap (it is planned as the extension 12 -> cap) and pass B's mode as 9 (frame) or 10
- *            (footprints), its lds_bytes and chunk following from the map variant's larger per-wave scratch.  [79] is 0.
+ *            (footprints), its lds_bytes and chunk following from the map variant's larger per-wave scratch.
+ *   [79]     n_views of camera hits over a batch of views (kind 7), else 0.
  * A call that fails before its plan is complete (bad arguments, no kernel built for the launch, occupancy 0) leaves the previous
  * launch's report in place: read it after a call that returned RT_OK.
  * An added diagnostic symbol only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */

@@ -116,6 +116,12 @@ SIGNATURES = {
                                  C.c_uint32, _i32p, _dp, _dp, _P(A.rt_stats)]),
     "rt_camera_hits_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_size_t, C.c_void_p, C.c_int32,
                                         C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(A.rt_render_options), _P(A.rt_stats)]),
+    # (stats bound as an untyped pointer, as rt_render_views': Scene.cameraHitsViews calls this pair itself)
+    "rt_camera_hits_views": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_int32, _u64p, C.c_uint64, C.c_int32, C.c_size_t, _i32p,
+                                       C.c_int32, C.c_int32, C.c_uint32, _i32p, _dp, _dp, C.c_void_p]),
+    "rt_camera_hits_views_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_int32, _u64p, C.c_uint64, C.c_int32, C.c_size_t,
+                                              C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              _P(A.rt_render_options), _P(A.rt_stats)]),
     "rt_camera_paths": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_size_t, _i32p, C.c_int32, C.c_int32,
                                   C.c_uint32, _P(A.rt_path_outputs), _P(A.rt_stats)]),
     "rt_camera_paths_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_size_t, C.c_void_p, C.c_int32,

@@ -44,11 +44,14 @@ struct SceneSize {
 // the same n) or the camera hits of such a list (CAMERA_HITS [14], rt_camera_hits: n entries x spp samples, planned by the ray lists' rules
 // over n * spp rays, with units of chunk ENTRIES and the wave scratch their pix and candidate words need) or a batch of views
 // (rt_render_views: n_views frames of n_rows x (2 max_w + 1) pixels, planned by the pixel rules as ONE frame of as many pixels and run by
-// render_views_kernel at blocks of 256 or 1024 threads, with the units of rt_views_plan.h -- none spans two views)
+// render_views_kernel at blocks of 256 or 1024 threads, with the units of rt_views_plan.h -- none spans two views) or the camera hits of ONE
+// list for a batch of views (CAMERA_HITS with n_views >= 1, rt_camera_hits_views: planned by CAMERA_HITS' rules over n_views * n * spp rays and
+// run by camera_hits_views_kernel, with rt_views_plan.h's units over the list's n entries -- n_views * ceil(n / chunk) of them.  Not a
+// member of Kind: tests/test_views_host.py pins the enumeration's text; rt_dev_last_launch_plan reports such a job as kind 7)
 struct Job {
     enum Kind { FRAME, TRACE, HIT, FOOTPRINTS, PIXELS, CAMERA_HITS, VIEWS } kind = FRAME;
     uint64_t n_rows = 0; int32_t max_w = 0, spp = 1; // FRAME; VIEWS: one view's
-    uint32_t n_views = 0;                            // VIEWS
+    uint32_t n_views = 0;                            // VIEWS; CAMERA_HITS: 0 = rt_camera_hits, >= 1 = the views of rt_camera_hits_views
     bool ray_log = false;                            // FRAME: rt_scene_tune's probe
     uint64_t n = 0;                                  // TRACE, HIT: rays; FOOTPRINTS, PIXELS: pixels (with spp); CAMERA_HITS: list entries (spp: n_samples)
     int32_t first_sample = 0;                        // FRAME, FOOTPRINTS, PIXELS: 0 = a fresh render; >= RTD_EXTEND_MIN_DONE: an EXTENSION of a buffer that
@@ -56,8 +59,11 @@ struct Job {
                                                      // CAMERA_HITS: sample_first, any value >= 0 (nothing is extended)
     bool map = false;                                // an extension BY MAP (rt_render_extend_map): every pixel from its own Count to its own target <= spp.
                                                      // Planned as the extension RTD_EXTEND_MIN_DONE -> spp (first_sample is that) with the map variant's scratch
+    bool camera_hits_views() const { return kind == CAMERA_HITS && n_views != 0; } // camera hits over a batch of views
     bool extend() const { return kind != CAMERA_HITS && first_sample != 0; }
-    uint64_t ray_count() const { return kind == CAMERA_HITS ? n * (uint64_t) spp : n; } // TRACE, HIT, CAMERA_HITS: what the grid is sized by
+    uint64_t ray_count() const { // TRACE, HIT, CAMERA_HITS: what the grid is sized by
+        return kind == CAMERA_HITS ? (uint64_t) (n_views ? n_views : 1u) * n * (uint64_t) spp : n;
+    }
     bool list() const { return kind == FOOTPRINTS || kind == PIXELS; }  // n pixels in list order: a frame of one row to the plan
     bool views() const { return kind == VIEWS; }
     bool pixels() const { return kind == FRAME || kind == VIEWS || list(); } // planned by the pixel rules, not the ray lists'
@@ -66,6 +72,7 @@ struct Job {
     // the units of `chunk` pixels that the fused kernel or pass A hands out
     uint64_t unit_count(int chunk) const {
         if (kind == VIEWS) return rtviews::units_of(rtviews::Plan{(uint32_t) view_pixels(), (uint32_t) chunk, n_views});
+        if (camera_hits_views()) return rtviews::units_of(rtviews::Plan{(uint32_t) n, (uint32_t) chunk, n_views}); // (units of list ENTRIES)
         return (pixel_count() + (uint64_t) chunk - 1) / (uint64_t) chunk;
     }
     rtmode::Pixels source() const { // where the job's kernels find their pixels
@@ -78,7 +85,8 @@ struct Job {
 struct Pass {
     bool lds = false, count = false, tex = false;
     bool prog = false; // tex, and the scene holds a texture program: render_prog_kernel (rtmode::is_built_prog: blocks of 256 and 1024 only)
-    bool views = false; // a batch of views: render_views_kernel<lds, count, block, mode, tex> (a frame pass; blocks of 256 and 1024 only)
+    bool views = false; // a batch of views: render_views_kernel<lds, count, block, mode, tex> (a frame pass; blocks of 256 and 1024 only), or,
+                        // with mode CAMERA_HITS, camera_hits_views_kernel<lds, count, block>
     int block = 1024, mode = rtmode::FRAME_FUSED;
     uint64_t grid = 0;
     size_t lds_bytes = 0;
@@ -184,6 +192,7 @@ static inline LaunchPlan plan_begin(const SceneSize &sc, const Settings &set, bo
         q.prog = q.tex && sc.prog;
         q.chunk = set.chunk ? set.chunk : RTD_MAX_CHUNK; // rays per run of the queue (a wave takes as many runs at once as it has idle lanes)
         if (job.kind != Job::TRACE) q.park = 0;
+        q.views = job.camera_hits_views();
         if (job.kind == Job::CAMERA_HITS) {
             // a unit is chunk list ENTRIES, each spp items: about a wave's worth of items per unit unless the caller says otherwise (a
             // unit is set up once and handed out without draining, so small units cost one atomic each and balance the waves best)

@@ -1,7 +1,8 @@
     // rt_render_body.inc -- the body of render_kernel<LDS, COUNT, BLOCK, MODE, TEX> and of render_job_kernel<LDS, BLOCK, PASS, TEX>
     // (rt_render_kernel.h), included once in each.  The includer provides LDS, COUNT, BLOCK, MODE and TEX, the kernel argument `p`, and the
     // job policy: `constexpr bool JOB` and `const JobCtl *job` (null without a job), and `constexpr bool VIEWS` (render_views_kernel: a batch of
-    // views, rt_views_plan.h -- a unit lies inside one view and `pu` is the kernel's parameters with THAT view's camera and seed key).  Text and not a function, so that render_kernel
+    // views, rt_views_plan.h -- a unit lies inside one view and `pu` is the kernel's parameters with THAT view's camera and seed key; also
+    // camera_hits_views_kernel, the one includer with MODE = CAMERA_HITS and VIEWS).  Text and not a function, so that render_kernel
     // compiles to exactly what it did when these lines stood in it: as a shared inline function the same lines gave every
     // instantiation another instruction stream and 55 of the 304 other resource figures (NOTES.md, round 28).
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -56,7 +57,7 @@
     uint64_t sampleCount = 0; // Scene.traceOnce calls = sum of PixelStats.Count
 
     if constexpr (RAYS) run_rays<LDS, COUNT, TEX, D.hits>(p, sc, pool, poolLds, cnt, ss);
-    else if constexpr (CAM) run_camera_hits<LDS, COUNT>(p, sc, pool, poolLds, wv, cnt, ss);
+    else if constexpr (CAM) run_camera_hits<LDS, COUNT, VIEWS>(p, sc, pool, poolLds, wv, cnt, ss);
     else if (PASS_B) run_stream<LDS, COUNT, TEX, FP, MAP, PX, JOB, VIEWS>(p, sc, pool, poolLds, wv, n1, n2, cnt, ss, sampleCount, job);
     else {
     std::conditional_t<VIEWS, RenderParams, const RenderParams &> pu = p;

@@ -92,11 +92,13 @@ struct RenderParams {
     int32_t cam_sample_first, cam_n_samples;
     // a batch of views (render_views_kernel, rt_render_views; rt_views_plan.h): read only there.  n_rows, cols, max_w, max_h are ONE view's
     // (row_first = 0, row_stride = 1); accum and rgb hold the batch, view after view; cam_ptr and seed_key are unused -- a unit (a
-    // pass-B range) reads the camera and the seed key of ITS view through scalar pointers
+    // pass-B range) reads the camera and the seed key of ITS view through scalar pointers.  Camera hits over a batch (rt_camera_hits_views)
+    // reuse view_cams, view_keys, view_pixels, view_units and n_views beside the camera-hit fields: ray_hit, ray_strike and cam_rays_out
+    // hold the batch, view after view
     const CameraParams *view_cams; // [n_views]
     const uint64_t *view_keys;     // [n_views]: seed_key() of each view's seed
     const unsigned int *view_end;  // [n_views] (pass B): the list index at which each view's entries end (views_sort_scan_kernel)
-    uint32_t view_pixels;          // pixels of one view: n_rows * cols
+    uint32_t view_pixels;          // pixels of one view: n_rows * cols (camera hits over a batch, camera_hits_views_kernel: the list's entries, = ray_n)
     uint32_t view_units;           // units of one view in the fused kernel / pass A: rtviews::units_per_view at this launch's chunk
     uint32_t n_views, view_pad;
 };
@@ -821,6 +823,16 @@ template <typename LP> RTD_INLINE void footprint_setup(const RenderParams &p, LP
     pix[lane * 4 + 3] = (uint32_t) (pkey >> 32);
 }
 
+// A batch of views (render_views_kernel): the camera and the seed key of `view` into the copy of the kernel's parameters that the unit's (the
+// range's) set-up and its new items read.  Scalar pointers: the view is wave-uniform.  (A function template, so that the kernels without
+// views, where the copy is a reference to the const parameters, never see the assignments.)
+template <bool VIEWS, class Params> RTD_INLINE void set_view(Params &pu, const RenderParams &p, uint32_t view) {
+    if constexpr (VIEWS) {
+        pu.cam_ptr = p.view_cams + view;
+        pu.seed_key = p.view_keys[view];
+    }
+}
+
 // Camera hits (rtmode::CAMERA_HITS [14], rt_camera_hits): Scene.hitObject (Scene.fs:62-91) of the ray Scene.traceOnce (Scene.fs:129-143) gives sample s
 // of a frame's pixel, for samples [cam_sample_first, cam_sample_first + cam_n_samples) of the caller's list entries [0, p.ray_n) -- the
 // pixel modes' unit set-up (pixel_setup) feeding RAYS_HIT's tail.  A wave takes a unit of p.chunk entries from the global queue and writes, once per
@@ -830,7 +842,11 @@ template <typename LP> RTD_INLINE void footprint_setup(const RenderParams &p, LP
 // last item is handed out: nothing drains at a unit's end.  There is no shading, so no park pool and no stage but the walk; a lane
 // whose walk is done runs the unbounded tests and stores (hit, strike, ray).  In the timed variant a camera ray starts from its
 // pixel's candidates exactly as a frame's does; the counting variant walks from the root.
-template <bool LDS, bool COUNT>
+// VIEWS (a batch of views, camera_hits_views_kernel, rt_camera_hits_views): the ONE list of p.view_pixels entries is answered for each of
+// p.n_views cameras.  A unit is p.chunk entries inside one view (rtviews::unit_of: the last unit of a view is short), `pu` is the kernel's
+// parameters with the camera and the seed key of the unit being HANDED OUT -- pixel_setup and start_item read them, a started item has
+// copied what it needs -- and the unit's first item has slot (view * entries + first) * cam_n_samples.
+template <bool LDS, bool COUNT, bool VIEWS = false>
 RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc, unsigned char *pool, RTD_AS3 unsigned char *poolLds, RTD_AS3 uint32_t *wv, Counters &cnt,
                                 StageStats &ss) {
     const int lane = threadIdx.x & 63;
@@ -838,7 +854,8 @@ RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc,
     const uint32_t per = (uint32_t) p.cam_n_samples;
     RTD_AS3 uint32_t *pix = wv;           // [P][4]
     RTD_AS3 uint32_t *cand = wv + 4u * P; // [P][2]
-    Sched<LDS, COUNT, false, false> L(p, sc, cnt, ss, pool, poolLds);
+    std::conditional_t<VIEWS, RenderParams, const RenderParams &> pu = p;
+    Sched<LDS, COUNT, false, false> L(pu, sc, cnt, ss, pool, poolLds);
     // wave-uniform: items [next, total) of the current unit are not handed out yet; the unit's first item has output slot slot0
     uint32_t next = 0, total = 0, slot0 = 0;
     bool exhausted = false;
@@ -872,6 +889,23 @@ RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc,
                 uint32_t unit = 0;
                 if (lane == 0) unit = atomicAdd(p.queue, 1u);
                 unit = __builtin_amdgcn_readfirstlane(unit);
+                if constexpr (VIEWS) { // the unit's view, its entries inside the list, the view's camera and seed key (all wave-uniform)
+                    if ((unsigned long long) unit >= (unsigned long long) p.n_views * p.view_units) exhausted = true;
+                    else {
+                        const rtviews::Plan pl{p.view_pixels, P, p.n_views};
+                        const rtviews::Unit u = rtviews::unit_of(pl, p.view_units, unit);
+                        set_view<VIEWS>(pu, p, u.view);
+                        __builtin_amdgcn_wave_barrier(); // (the last unit's words have all been read)
+                        if ((uint32_t) lane < u.npx) { // a busy lane too: nothing of its path's state is touched
+                            uint32_t c2;
+                            const uint32_t c1 = pixel_setup<LDS, COUNT, rtmode::Pixels::LIST, true>(pu, sc, u.first + (uint32_t) lane, pix, lane, c2);
+                            cand[lane * 2] = c1;
+                            cand[lane * 2 + 1] = c2;
+                        }
+                        __builtin_amdgcn_wave_barrier();
+                        next = 0u; total = u.npx * per; slot0 = rtviews::first_slot(pl, u.view, u.first, per);
+                    }
+                } else { // (the lines rt_camera_hits' kernels have always had, kept apart so that they compile to what they did)
                 const unsigned long long first = (unsigned long long) unit * P;
                 if (first >= p.ray_n) exhausted = true;
                 else {
@@ -886,6 +920,7 @@ RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc,
                     }
                     __builtin_amdgcn_wave_barrier();
                     next = 0u; total = npx * per; slot0 = (uint32_t) first * per;
+                }
                 }
             }
             const uint32_t avail = total - next;
@@ -916,16 +951,6 @@ RTD_INLINE void run_camera_hits(const RenderParams &p, const SceneView<LDS> &sc,
             L.st = L_IDLE; L.w.off = L.end;
         }
         if (COUNT || RTD_CLK) { const unsigned long long t3 = __builtin_amdgcn_s_memtime(); ss.tRefill += t1 - t0; ss.tWalk += t2 - t1; ss.tShade += t3 - t2; }
-    }
-}
-
-// A batch of views (render_views_kernel): the camera and the seed key of `view` into the copy of the kernel's parameters that the unit's (the
-// range's) set-up and its new items read.  Scalar pointers: the view is wave-uniform.  (A function template, so that the kernels without
-// views, where the copy is a reference to the const parameters, never see the assignments.)
-template <bool VIEWS, class Params> RTD_INLINE void set_view(Params &pu, const RenderParams &p, uint32_t view) {
-    if constexpr (VIEWS) {
-        pu.cam_ptr = p.view_cams + view;
-        pu.seed_key = p.view_keys[view];
     }
 }
 
@@ -1236,6 +1261,18 @@ __global__ void __launch_bounds__(BLOCK) render_views_kernel(const RenderParams 
     static_assert(PASS == rtmode::FRAME_FUSED || PASS == rtmode::FRAME_PASS_A || PASS == rtmode::FRAME_PASS_B, "a frame pass");
     constexpr bool JOB = false, VIEWS = true;
     constexpr int MODE = PASS;
+    const JobCtl *const job = nullptr;
+#include "rt_render_body.inc"
+}
+
+// Camera hits over a batch of views (rt_camera_hits_views; DESIGN.md "Camera hits over a batch of views"): rtmode::CAMERA_HITS under a symbol of its
+// own, so that every kernel above stays exactly what it was.  A unit is chunk entries of the shared list inside ONE view and reads that
+// view's camera and seed key through scalar pointers (run_camera_hits<.., VIEWS>).  Both variants, blocks of 256 and 1024 threads; nothing
+// is shaded, so there is no textured form.
+template <bool LDS, bool COUNT, int BLOCK>
+__global__ void __launch_bounds__(BLOCK) camera_hits_views_kernel(const RenderParams p) {
+    constexpr int MODE = rtmode::CAMERA_HITS;
+    constexpr bool TEX = false, JOB = false, VIEWS = true;
     const JobCtl *const job = nullptr;
 #include "rt_render_body.inc"
 }

@@ -44,6 +44,11 @@ RTVIEWS_HD Unit unit_of(const Plan &pl, uint32_t upv, uint32_t u) {
 RTVIEWS_HD uint64_t batch_pixel(const Plan &pl, uint32_t view, uint32_t g) { return (uint64_t) view * (uint64_t) pl.pixels_per_view + (uint64_t) g; }
 RTVIEWS_HD uint32_t view_of(uint32_t pixels_per_view, uint32_t batch_px) { return batch_px / pixels_per_view; }
 
+// Camera hits over a batch (rt_camera_hits_views): the entries of the ONE list stand where a view's pixels do (pixels_per_view = n), each
+// with n_samples output slots; the slot of the first item of a unit that starts at entry `first` of `view`.
+// n_views * n * n_samples <= INT32_MAX (the entry points refuse more), so every slot fits 32 bits
+RTVIEWS_HD uint32_t first_slot(const Plan &pl, uint32_t view, uint32_t first, uint32_t n_samples) { return (view * pl.pixels_per_view + first) * n_samples; }
+
 // Pass B: how many of the list entries [first, first + n) a range may take when the view of entry `first` ends at list index view_end
 // (> first: the list is ordered by view and entry `first` is one of that view's)
 RTVIEWS_HD uint32_t range_in_view(uint64_t first, uint32_t n, uint64_t view_end) {

@@ -294,8 +294,14 @@ template <int PASS> static render_fn pick_views_pass(const rtp::Pass &q) {
     if (q.block == 256) return q.tex ? pick_views_variant<256, PASS, true>(q.lds, q.count) : pick_views_variant<256, PASS, false>(q.lds, q.count);
     return q.tex ? pick_views_variant<1024, PASS, true>(q.lds, q.count) : pick_views_variant<1024, PASS, false>(q.lds, q.count);
 }
+// ... and the camera hits of such a batch (camera_hits_views_kernel): both variants at blocks of 256 and 1024 -- 8 kernels
+template <int BLOCK> static render_fn pick_camera_hits_views(bool lds, bool count) {
+    if (lds) return count ? camera_hits_views_kernel<true, true, BLOCK> : camera_hits_views_kernel<true, false, BLOCK>;
+    return count ? camera_hits_views_kernel<false, true, BLOCK> : camera_hits_views_kernel<false, false, BLOCK>;
+}
 static render_fn pick_views_kernel(const rtp::Pass &q) {
     if (q.prog || (q.block != 256 && q.block != 1024)) return nullptr;
+    if (q.mode == rtmode::CAMERA_HITS) return q.tex ? nullptr : q.block == 256 ? pick_camera_hits_views<256>(q.lds, q.count) : pick_camera_hits_views<1024>(q.lds, q.count);
     return q.mode == rtmode::FRAME_FUSED ? pick_views_pass<rtmode::FRAME_FUSED>(q) : q.mode == rtmode::FRAME_PASS_A ? pick_views_pass<rtmode::FRAME_PASS_A>(q) :
            q.mode == rtmode::FRAME_PASS_B ? pick_views_pass<rtmode::FRAME_PASS_B>(q) : nullptr;
 }
@@ -658,7 +664,7 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
     const rtp::Job &j = pl.job;
     put(1);
     put(j.kind == rtp::Job::FRAME ? 0 : (j.kind == rtp::Job::TRACE ? 1 : (j.kind == rtp::Job::HIT ? 2 : (j.kind == rtp::Job::FOOTPRINTS ? 3 : (j.kind == rtp::Job::PIXELS ? 4 :
-        (j.kind == rtp::Job::CAMERA_HITS ? 5 : 6))))));
+        (j.kind == rtp::Job::CAMERA_HITS ? (j.n_views ? 7 : 5) : 6))))));
     put((int64_t) sc.lds_total); put((int64_t) sc.lds32_total); put(sc.n_nodes); put((int64_t) sc.n_objects); put((int) sc.tex + (int) sc.prog);
     put(s.block); put(s.chunk); put(s.blocks_per_cu); put(s.yield); put(s.refill); put(s.passes); put(s.park);
     put(pl.one.count); put(j.ray_log); put((int64_t) j.n_rows); put(j.max_w); put(j.spp); put(j.views() ? (int64_t) j.n_views : (int64_t) j.n); put(pl.cu_count); put(per_cu);
@@ -672,7 +678,8 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
     }
     put(j.first_sample); // [77]: 0 = a fresh render, else the samples_done of an extension (by map: RTD_EXTEND_MIN_DONE); camera hits: sample_first
     put(j.map ? 1 : 0);  // [78]: 1 = an extension by map
-    static_assert(1 + 21 + 13 + 3 * 14 + 2 <= RT_LAUNCH_PLAN_WORDS, "rt_dev_last_launch_plan's words");
+    put(j.camera_hits_views() ? (int64_t) j.n_views : 0); // [79]: the views of camera hits over a batch (kind 7: [19] is the list's n, as kind 5's)
+    static_assert(1 + 21 + 13 + 3 * 14 + 3 <= RT_LAUNCH_PLAN_WORDS, "rt_dev_last_launch_plan's words");
     while (n < RT_LAUNCH_PLAN_WORDS) put(0);
 }
 
@@ -681,7 +688,7 @@ static void remember_plan(const rtp::LaunchPlan &pl, int per_cu) {
 // for the device.  `p` arrives with the caller's own fields filled (camera and rows and buffers, or the ray list's pointers); the
 // scene's and the plan's are set here.  With want_stats the launch is bracketed by events and its scratch is kept in `pd` for
 // collect_stats.
-// A batch of views (job.kind == VIEWS): the per-view cameras and seed keys, which get a section of their own behind the workspace.
+// A batch of views (job.kind == VIEWS, or CAMERA_HITS with n_views >= 1): the per-view cameras and seed keys, which get a section of their own behind the workspace.
 struct ViewsArgs { std::vector<CameraParams> cams; std::vector<uint64_t> keys; };
 static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, const Settings &set, uint32_t flags, void *stream, RenderParams p,
                    const CameraParams &cam, bool want_stats, Pending &pd, const ViewsArgs *views = nullptr) {
@@ -758,7 +765,7 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
         HIP_TRY(hipGetLastError());
         p.view_cams = cams; p.view_keys = keys;
         p.n_views = (uint32_t) nv;
-        p.view_pixels = (uint32_t) job.view_pixels();
+        p.view_pixels = job.camera_hits_views() ? (uint32_t) job.n : (uint32_t) job.view_pixels(); // (camera hits: the list's entries)
     }
     if (grid > 0) {
         if (want_stats) HIP_TRY(hipEventRecord(cl.a, st));
@@ -1747,6 +1754,89 @@ int rt_camera_hits(const rt_scene *scene, const rt_camera *camera, int32_t max_w
         return launch_camera_hits(scene, camera, max_w, max_h, seed, device, n, d[0], sample_first, n_samples, flags, d[1], d[2], d[3], nullptr, nullptr, want_stats, pd);
     }));
     camera_hits_counts(stats, n, n_samples);
+    return RT_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// camera hits over a batch of views (DESIGN.md "Camera hits over a batch of views"): the above for n_views cameras and ONE list in ONE
+// launch; view v's slice of every output is rt_camera_hits' answer for cameras[v] and seed v (camera_hits_views_kernel, rt_views_plan.h)
+// ------------------------------------------------------------------------------------------------------------
+// Every argument check both entry points make, before anything touches a device: rt_camera_hits' own for every view (the first offending
+// view reports), then the batch's bound.  The cameras need not share samples_per_pixel or bounce_depth -- nothing here traces beyond the
+// camera ray -- and a scene with a texture program is taken: nothing is shaded.
+static int check_camera_hits_views(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, size_t n, const void *pixels,
+                                   int32_t sample_first, int32_t n_samples, const void *hit_index, const rt_render_options *options) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (n_views < 0) return fail(RT_ERR_INVALID_ARGUMENT, "n_views must be >= 0");
+    if (n_views > 0 && !cameras) return fail(RT_ERR_INVALID_ARGUMENT, "cameras is NULL");
+    for (int32_t v = 0; v < n_views; ++v) RT_TRY(check_camera_hits(scene, &cameras[v], max_w, max_h, n, pixels, sample_first, n_samples, hit_index, options));
+    if (n_views > 0 && (uint64_t) n_views * (uint64_t) n * (uint64_t) n_samples > (uint64_t) INT32_MAX) // (n * n_samples <= INT32_MAX: no overflow)
+        return fail(RT_ERR_INVALID_ARGUMENT, "more than INT32_MAX output slots (n_views * n * n_samples)");
+    return check_options(options);
+}
+
+// Enqueues the one launch on `stream` (n_views > 0, n > 0, arguments checked): launch_camera_hits' fields with the batch's outputs, the
+// per-view cameras and seed keys for enqueue() to stage; cameras and seeds are read HERE, before the call returns.
+static int launch_camera_hits_views(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds,
+                                    uint64_t seed, int32_t device, size_t n, const void *d_pixels, int32_t sample_first, int32_t n_samples, uint32_t flags,
+                                    void *d_hit_index, void *d_strike, void *d_rays_out, void *stream, const rt_render_options *options, bool want_stats,
+                                    Pending &pd) {
+    RenderParams p{};
+    p.max_w = max_w; p.max_h = max_h;
+    p.spp = cameras[0].samples_per_pixel;
+    p.depth = cameras[0].bounce_depth;
+    p.cols = 2 * max_w + 1;
+    p.row_first = 0; p.row_stride = 1; p.n_rows = 1;
+    p.pixel_list = (const int32_t *) d_pixels;
+    p.ray_n = n; // (one view's: the kernel reads view_pixels, which enqueue() sets to the same)
+    p.ray_hit = (int32_t *) d_hit_index;
+    p.ray_strike = (double *) d_strike;
+    p.cam_rays_out = (double *) d_rays_out;
+    p.cam_sample_first = sample_first; p.cam_n_samples = n_samples;
+    ViewsArgs va;
+    va.cams.reserve((size_t) n_views); va.keys.reserve((size_t) n_views);
+    for (int32_t v = 0; v < n_views; ++v) {
+        va.cams.push_back(camera_params(&cameras[v], max_w, max_h));
+        va.keys.push_back(mix64((seeds ? seeds[v] : seed) + 0x9E3779B97F4A7C15ull)); // seed_key(), host side
+    }
+    rtp::Job job;
+    job.kind = rtp::Job::CAMERA_HITS;
+    job.n_views = (uint32_t) n_views; // (>= 1: the batch)
+    job.n = n; job.spp = n_samples; job.first_sample = sample_first;
+    return enqueue(scene, device, job, resolve_settings(options), flags, stream, p, va.cams[0], want_stats, pd, &va);
+}
+
+extern "C" {
+
+int rt_camera_hits_views_device(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds,
+                                uint64_t seed, int32_t device, size_t n, const void *d_pixels, int32_t sample_first, int32_t n_samples, uint32_t flags,
+                                void *d_hit_index, void *d_strike, void *d_rays_out, void *stream, const rt_render_options *options, rt_stats *stats) {
+    RT_TRY(check_camera_hits_views(scene, cameras, n_views, max_w, max_h, n, d_pixels, sample_first, n_samples, d_hit_index, options));
+    const bool nothing = n_views == 0 || n == 0;
+    RT_TRY(run_device(device, stats, nothing, [&](bool want_stats, Pending &pd) {
+        return launch_camera_hits_views(scene, cameras, n_views, max_w, max_h, seeds, seed, device, n, d_pixels, sample_first, n_samples, flags, d_hit_index,
+                                        d_strike, d_rays_out, stream, options, want_stats, pd);
+    }));
+    if (!nothing) camera_hits_counts(stats, (size_t) n_views * n, n_samples);
+    return RT_OK;
+}
+
+// The host variant checks the shared list here, once, before anything touches a device.
+int rt_camera_hits_views(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds, uint64_t seed,
+                         int32_t device, size_t n, const int32_t *pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, int32_t *hit_index,
+                         double *strike, double *rays_out, rt_stats *stats) {
+    RT_TRY(check_camera_hits_views(scene, cameras, n_views, max_w, max_h, n, pixels, sample_first, n_samples, hit_index, nullptr));
+    const bool nothing = n_views == 0 || n == 0;
+    if (pixels && !nothing) RT_TRY(check_pixel_entries(pixels, n, max_w, max_h));
+    const size_t slots = nothing ? 0u : (size_t) n_views * n * (size_t) n_samples;
+    RT_TRY(run_host(device, stats, nothing, {{pixels, n * 4u, SEG_IN}, {hit_index, slots * 4u, SEG_OUT}, {strike, slots * 24u, SEG_OUT}, {rays_out, slots * 48u, SEG_OUT}},
+                    [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_camera_hits_views(scene, cameras, n_views, max_w, max_h, seeds, seed, device, n, d[0], sample_first, n_samples, flags, d[1], d[2], d[3], nullptr,
+                                        nullptr, want_stats, pd);
+    }));
+    if (!nothing) camera_hits_counts(stats, (size_t) n_views * n, n_samples);
     return RT_OK;
 }
 

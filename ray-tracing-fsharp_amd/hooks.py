@@ -173,6 +173,8 @@ def last_launch_plan():
     inp["first_sample"] = w[at]  # word 77: 0 = a fresh render, else the samples_done of an extension (pass B alone: A_ words 0)
                                  # (camera hits, kind 5: sample_first)
     inp["map"] = w[at + 1]       # word 78: 1 = an extension by map (first_sample is then 12, spp the cap, B_mode 9 or 10)
+    if inp["kind"] == 7:         # camera hits over a batch of views: kind 5's words (n: the list's entries), and word 79: the views
+        inp["n_views"] = w[at + 2]
     return {"in": inp, "out": out}
 
 

@@ -953,6 +953,37 @@ class Scene:
                           sample_first, n_samples, _flags(counters), route.ptr(hit), route.ptr(sk), route.ptr(ry), stats=stats, options=options)
         return CameraHits(hit, sk, ry, st)
 
+    def cameraHitsViews(self, maxWidthCoord: int, maxHeightCoord: int, cameras: Sequence[Camera], pixels=None, *, seeds: Optional[Sequence[int]] = None,
+                        seed: int = 0, sample_first: int = 0, n_samples: int = 1, n: Optional[int] = None, strike: bool = True, rays: bool = True,
+                        tensors: bool = False, device: Optional[int] = None, counters: bool = False, stats: bool = True,
+                        options: Optional[A.rt_render_options] = None) -> CameraHits:
+        """rt_camera_hits_views: cameraHits for K cameras over this scene and ONE list of pixels in ONE launch -> CameraHits(hit_index
+        [K, n, n_samples], strike [K, n, n_samples, 3], rays [K, n, n_samples, 6], stats).  View v's slice is, bit for bit, cameraHits
+        with cameras[v], seed seeds[v] (seeds=None: `seed` for every view) and the same pixels, sample range and geometry; the cameras
+        need not share SamplesPerPixel or BounceDepth, and a scene that holds a texture program is taken.  stats sums the views'
+        (pixels = K * n).  Arrays and tensors exactly as for cameraHits: a tensor list goes through rt_camera_hits_views_device on
+        torch.cuda.current_stream() and the results are tensors (stats=False: no wait for the device; a list with an entry outside
+        the frame then goes unreported and nothing is written in any view)."""
+        if not isinstance(n_samples, int) or not isinstance(sample_first, int):
+            raise TypeError("sample_first and n_samples must be ints")
+        cams = list(cameras)
+        k = len(cams)
+        if seeds is not None and len(seeds) != k:
+            raise ValueError(f"seeds must hold one seed per camera ({k}), not {len(seeds)}")
+        route, px, count = _pixel_list(pixels, n, tensors, maxWidthCoord, maxHeightCoord, device, options)
+        per = max(n_samples, 0)
+        shape = _lead(route, (k, count, per), k * count * per)
+        hit = route.make(shape, "i32")
+        sk = route.make(shape + (3,), "f64") if strike else None
+        ry = route.make(shape + (6,), "f64") if rays else None
+        abi = (A.rt_camera * max(k, 1))(*[c.to_abi() for c in cams])
+        keys = None if seeds is None else (C.c_uint64 * max(k, 1))(*[int(s) for s in seeds])
+        # (the route's entry point and tail, as Scene._launch gives them; the pair is not in _ROUTED, whose twelve pairs tests/test_abi.py pins)
+        st = self._call(getattr(lib, "rt_camera_hits_views" + route.suffix), abi if k else None, k, maxWidthCoord, maxHeightCoord, keys, seed, route.device,
+                        count, route.ptr(px), sample_first, n_samples, _flags(counters), route.ptr(hit), route.ptr(sk), route.ptr(ry), *route.tail(options),
+                        stats=stats or not route.suffix)
+        return CameraHits(hit, sk, ry, st)
+
     @staticmethod
     def _path_buffers(route, lead, max_vertices, records, first_ray=False, summary_entries=None):
         """The output buffers of a path call, shaped lead + (...), and the rt_path_outputs that names them."""

@@ -3,6 +3,7 @@ parent's functions have an identical instruction stream here (labels normalised,
 figures; functions that differ only in hexadecimal constants and offsets (the arguments behind a RenderParams that grew) are named as such.
   python scripts/device_code_compare.py PARENT_CSRC BRANCH_CSRC            -> profiles/rNN/device_code_vs_parent.txt
   python scripts/device_code_compare.py PARENT_CSRC BRANCH_CSRC --views    -> ... then the views kernels beside their twins (resources_views.txt)
+  python scripts/device_code_compare.py PARENT_CSRC BRANCH_CSRC --camera-hits-views -> ... then the camera-hits-views kernels beside their twins
   python scripts/device_code_compare.py PARENT_CSRC BRANCH_CSRC SYMBOL     -> ... then a diff of one function"""
 import re, sys, collections
 def funcs(path):
@@ -70,6 +71,24 @@ if len(sys.argv) > 3 and sys.argv[3] == '--views':
         dv, dt = (dict(x.split(': ') for x in r if ': ' in x) for r in (rb[n], rb[twin]))
         if int(dv['VGPRs Spill']) > 0 and int(dt['VGPRs Spill']) == 0: worse.append(n)
     print(f"# views kernels that spill VGPRs where the twin does not: {len(worse)} {worse}")
+elif len(sys.argv) > 3 and sys.argv[3] == '--camera-hits-views':
+    print()
+    print("# Resource figures of the camera-hits-views kernels beside their twins (make asm, -Rpass-analysis=kernel-resource-usage)")
+    print("# camera_hits_views_kernel<LDS, COUNT, BLOCK> vs render_kernel<LDS, COUNT, BLOCK, 14, false>")
+    def fig(r):
+        d = dict(x.split(': ') for x in r if ': ' in x)
+        return f"VGPRs {d['VGPRs']}, SGPRs {d['TotalSGPRs']}, scratch {d['ScratchSize [bytes/lane]']} B/lane, VGPR spills {d['VGPRs Spill']}, SGPR spills {d['SGPRs Spill']}, occupancy {d['Occupancy [waves/SIMD]']}"
+    worse, seen = [], 0
+    for n in sorted(rb):
+        m = re.match(r'_ZN3rtd\d+camera_hits_views_kernelILb(\d)ELb(\d)ELi(\d+)EEE', n)
+        if not m: continue
+        seen += 1
+        twin = [t for t in rb if re.match(rf'_ZN3rtd13render_kernelILb{m.group(1)}ELb{m.group(2)}ELi{m.group(3)}ELi14ELb0EEE', t)][0]
+        print(f"lds={m.group(1)} count={m.group(2)} block={m.group(3)}")
+        print("   views: " + fig(rb[n])); print("   twin:  " + fig(rb[twin]))
+        dv, dt = (dict(x.split(': ') for x in r if ': ' in x) for r in (rb[n], rb[twin]))
+        if (int(dv['VGPRs Spill']) > 0 and int(dt['VGPRs Spill']) == 0) or (int(dv['ScratchSize [bytes/lane]']) > 0 and int(dt['ScratchSize [bytes/lane]']) == 0): worse.append(n)
+    print(f"# kernels listed: {seen}; that use scratch or spill VGPRs where the twin does not: {len(worse)} {worse}")
 elif len(sys.argv) > 3:
     import difflib
     n = sys.argv[3]
