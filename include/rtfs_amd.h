@@ -639,6 +639,67 @@ int rt_trace_paths_device(const rt_scene *scene, int32_t device, size_t n, const
  * lds_resident (1: the filter loop over the scene in LDS ran), counting, textured, slots.  All 0 before the first launch. */
 int rt_dev_last_paths_plan(int64_t out[8]);
 
+/* ---- Surface records at hits: normal, side, colour, tint and texture coordinates ---------------------------------------------
+ * What the surface is like where a ray strikes: the values Hittable.Reflection (Hittable.fs:8-12) forms from the object, the strike
+ * point and the incoming ray's origin, for any list of hits -- rt_hit_objects', rt_camera_hits', the vertices of path records.
+ * A SLOT is (hit_index, strike, origin): hit_index indexes rt_scene_create's array as every hit query returns it, `rays` holds six
+ * doubles per slot of which only the origin (the first three) is read.  Per slot, with obj = hittables[hit_index]:
+ *   no surface   hit_index -1 or -2, or a component of strike or origin that is not finite (the reference throws or converts out of
+ *                range there): normal and uv NaN, inside 0, colour and tint 0,0,0.
+ *   spheres      (Sphere.fs:150-200)  n0 = Ray.make' strike (strike - centre) (Sphere.normal, Sphere.fs:65-66; ValueNone: normal is three
+ *                NaN, the rest of the record stays defined); inside = (Float.compare |centre - origin|^2 radius^2 <> Greater) <>
+ *                (Float.compare radius 0.0 = Less); normal = inside ? -1.0 * n0 : n0.  colour: LightSourceCap -- its Pixel when
+ *                Float.compare strike.x (centre.x + (radius - radius / 4.0)) = Greater, else Black (Sphere.fs:190-200); every other style
+ *                -- Texture.colourAt strike texture (the plain Pixel without a texture; programs included).
+ *   planes       (InfinitePlane.fs:43-99)  normal as given, never flipped; inside 0; colour: Texture.colourAt for LightSource, the
+ *                plane's Pixel otherwise.
+ *   tint         the colour Reflection leaves a WHITE LightRay with: `colour` for LightSource / LightSourceCap (Pixel.combine White c = c),
+ *                Pixel.darken albedo colour for every other style.
+ *   uv           Sphere.planeMapInverse map_radius map_centre strike (Sphere.fs:55-61) where the style carries a parameterised texture whose
+ *                root record is not RT_TEXTURE_COLOUR; NaN, NaN elsewhere.
+ * normal, inside and colour are bit for bit what the render's reflection uses; tint is bit for bit colour_after of the first vertex of
+ * rt_trace_paths for the same ray.  Every element of every non-NULL output is written by every successful call.
+ *
+ * Argument checks come before any device call, nothing is written when one fails: RT_ERR_INVALID_ARGUMENT for a NULL scene, a NULL
+ * hit_index / strike / rays with n > 0, out NULL or of another struct_size, every output NULL, n > INT32_MAX, bad options.  n = 0 is a
+ * no-op returning RT_OK with zeroed stats.  An index outside [-2, n_hittables) makes the LIST malformed, as an out-of-frame entry of a
+ * pixel list does: the host variant refuses it on the host; the device variant finds it on the device, in front of the launch and on the
+ * same stream, writes NO output and returns RT_ERR_INVALID_ARGUMENT when stats is given.
+ * stats: samples = n, kernel_ms, total_ms; every other count 0.  RT_RENDER_COUNTERS is accepted and changes nothing.  The device
+ * variant follows rt_camera_hits_device's contract (enqueued on `stream`, stream-ordered scratch, any number of calls in flight,
+ * stats == NULL returns after the launch, the caller's current device is restored); options are checked and not used.
+ *
+ * rt_camera_surfaces: the arguments of rt_camera_hits up to flags; hit_index and strike (each may be NULL here) are bit for bit
+ * rt_camera_hits'; the surface record of slot i*n_samples + (s - sample_first) is that of what the slot's camera ray strikes first
+ * (every origin is camera->view_origin).  List semantics, refusals and a malformed list are rt_camera_hits'; stats are its own with
+ * kernel_ms the sum of both kernels.  A scene that holds a texture program is taken.
+ * Added symbols and one added struct only (rt_abi_sizeof(13)) -- no existing struct, field or symbol changed, so RT_ABI_VERSION stays 7. */
+typedef struct rt_surface_outputs { /* every pointer may be NULL; host pointers for the host variants, device pointers for *_device */
+    uint32_t struct_size;           /* sizeof(rt_surface_outputs) */
+    void *normal;                   /* double [slots][3] */
+    void *inside;                   /* uint8  [slots]    */
+    void *colour;                   /* uint8  [slots][3] */
+    void *tint;                     /* uint8  [slots][3] */
+    void *uv;                       /* double [slots][2] */
+} rt_surface_outputs;
+int rt_surfaces(const rt_scene *scene, int32_t device, size_t n, const int32_t *hit_index, const double *strike /* n*3 */,
+                const double *rays /* n*6, only the origins are read */, uint32_t flags, const rt_surface_outputs *out, rt_stats *stats);
+int rt_surfaces_device(const rt_scene *scene, int32_t device, size_t n, const void *d_hit_index, const void *d_strike, const void *d_rays,
+                       uint32_t flags, const rt_surface_outputs *out, void *stream, const rt_render_options *options, rt_stats *stats);
+int rt_camera_surfaces(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                       uint64_t seed, int32_t device, size_t n, const int32_t *pixels /* NULL: entry i is pixel i, n <= rows*cols */,
+                       int32_t sample_first, int32_t n_samples, uint32_t flags,
+                       int32_t *hit_index /* n*n_samples, may be NULL */, double *strike /* n*n_samples*3, may be NULL */,
+                       const rt_surface_outputs *out, rt_stats *stats);
+int rt_camera_surfaces_device(const rt_scene *scene, const rt_camera *camera, int32_t max_width_coord, int32_t max_height_coord,
+                              uint64_t seed, int32_t device, size_t n, const void *d_pixels /* may be NULL */,
+                              int32_t sample_first, int32_t n_samples, uint32_t flags,
+                              void *d_hit_index /* may be NULL */, void *d_strike /* may be NULL */,
+                              const rt_surface_outputs *out, void *stream, const rt_render_options *options, rt_stats *stats);
+/* Diagnostic: the plan (csrc/rt_surface_plan.h) of the calling THREAD's last surface launch: slots, tile slots, grid, block, 1 if the
+ * program variant ran, 1 if the texture phase was enabled, textured slots evaluated (-1 when stats == NULL), 0.  All 0 before the first. */
+int rt_dev_last_surface_plan(int64_t out[8]);
+
 /* ---- Extending a rendered buffer to a higher sample count --------------------------------------------------------------
  * render at a, then extend a -> b  ==  render at b, for every PixelStats word and every rgb byte, for any 12 <= a <= b
  * (DESIGN.md "Extending a frame"): sample s of a pixel is the same ray tree whenever it is traced, the sums are integers, and
@@ -987,7 +1048,7 @@ int rt_device_count(void);         /* 0 when no HIP device is visible (never an 
 const char *rt_last_error(void);   /* thread-local message of the last failing call */
 int rt_abi_version(void);
 /* sizeof of the ABI structs as compiled: 0 rt_hittable, 1 rt_texture, 2 rt_camera, 3 rt_scene_info, 4 rt_stats,
- * 5 rt_render_options, 6 rt_scene_options, 7 rt_tune_info (bindings check their mirrors). */
+ * 5 rt_render_options, 6 rt_scene_options, 7 rt_tune_info, 9 rt_path_outputs, 13 rt_surface_outputs (bindings check their mirrors). */
 size_t rt_abi_sizeof(int which);
 /* Byte offset of field number `field` (declaration order, from 0) of struct `which` (numbering of rt_abi_sizeof), or
  * (size_t)-1 past the last field: a binding in another language asserts its own layout against these at start-up

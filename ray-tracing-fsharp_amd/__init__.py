@@ -5,7 +5,7 @@ mirror of the reference's construction/render API over that ABI.  Import fails l
 """
 from . import _abi  # noqa: F401
 from ._lib import LIB_PATH, RtError, lib  # noqa: F401
-from .raytracing import (Camera, CameraHits, CameraPaths, TracePaths, Colour, FloatProducer, Hittable, Image, ImageOutput, InfinitePlane, InfinitePlaneStyle, LoadImage,  # noqa: F401
+from .raytracing import (Camera, CameraHits, CameraPaths, Surfaces, TracePaths, Colour, FloatProducer, Hittable, Image, ImageOutput, InfinitePlane, InfinitePlaneStyle, LoadImage,  # noqa: F401
                          ParameterisedTexture, Pixel, PixelOutput, Png, Point, RenderJob, RenderResult, Scene, Sphere, SphereStyle, Texture,
                          UnitVector, Vector, HITTABLE_DTYPE, TextureTable, hittable_records, tree_make, tree_make_host, walk_tree_make, walk_tree_make_host)
 from . import hooks, sample_images, texprog  # noqa: F401

@@ -117,6 +117,15 @@ class rt_path_outputs(C.Structure):
         super().__init__(struct_size=C.sizeof(rt_path_outputs), **kw)
 
 
+class rt_surface_outputs(C.Structure):
+    """The outputs of rt_surfaces / rt_camera_surfaces: host pointers in the host variants, device pointers in the _device ones."""
+    _fields_ = [("struct_size", C.c_uint32), ("normal", C.c_void_p), ("inside", C.c_void_p), ("colour", C.c_void_p), ("tint", C.c_void_p),
+                ("uv", C.c_void_p)]
+
+    def __init__(self, **kw):
+        super().__init__(struct_size=C.sizeof(rt_surface_outputs), **kw)
+
+
 class rt_jpeg_info(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
                 ("restart_interval", C.c_int32), ("entropy_bytes", C.c_int64)]
@@ -169,3 +178,4 @@ RT_PATH_SUMMARY_WORDS = 16
 # numbering of rt_abi_sizeof / rt_abi_offsetof
 ABI_STRUCTS = (rt_hittable, rt_texture, rt_camera, rt_scene_info, rt_stats, rt_render_options, rt_scene_options, rt_tune_info)
 ABI_STRUCT_PATH_OUTPUTS = 9  # rt_path_outputs (8 stays unused: the C smoke test probes it as "no such struct")
+ABI_STRUCT_SURFACE_OUTPUTS = 13  # rt_surface_outputs

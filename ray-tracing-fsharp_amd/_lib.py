@@ -131,6 +131,16 @@ SIGNATURES = {
     "rt_trace_paths_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32,
                                         C.c_int32, C.c_uint32, _P(A.rt_path_outputs), C.c_void_p, _P(A.rt_render_options), _P(A.rt_stats)]),
     "rt_dev_last_paths_plan": (C.c_int, [_P(C.c_int64)]),  # out[8]
+    # (stats bound as an untyped pointer, as rt_render_views': Scene.surfaces and Scene.cameraSurfaces call these pairs themselves)
+    "rt_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t, _i32p, _dp, _dp, C.c_uint32, _P(A.rt_surface_outputs), C.c_void_p]),
+    "rt_surfaces_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, _P(A.rt_surface_outputs),
+                                     C.c_void_p, _P(A.rt_render_options), _P(A.rt_stats)]),
+    "rt_camera_surfaces": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_size_t, _i32p, C.c_int32, C.c_int32,
+                                     C.c_uint32, _i32p, _dp, _P(A.rt_surface_outputs), C.c_void_p]),
+    "rt_camera_surfaces_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_size_t, C.c_void_p, C.c_int32,
+                                            C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, _P(A.rt_surface_outputs), C.c_void_p,
+                                            _P(A.rt_render_options), _P(A.rt_stats)]),
+    "rt_dev_last_surface_plan": (C.c_int, [_P(C.c_int64)]),  # out[8]
     "rt_render_extend": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_uint32, C.c_int32, _i32p, _u8p, _P(A.rt_stats)]),
     "rt_render_extend_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32,
@@ -261,7 +271,7 @@ def check(code):
         raise RtError(code, (lib.rt_last_error() or b"").decode("utf-8", "replace"))
 
 
-for _i, _t in list(enumerate(A.ABI_STRUCTS)) + [(A.ABI_STRUCT_PATH_OUTPUTS, A.rt_path_outputs)]:  # sizes and every field offset of the ctypes mirrors against the library as compiled
+for _i, _t in list(enumerate(A.ABI_STRUCTS)) + [(A.ABI_STRUCT_PATH_OUTPUTS, A.rt_path_outputs), (A.ABI_STRUCT_SURFACE_OUTPUTS, A.rt_surface_outputs)]:  # sizes and every field offset of the ctypes mirrors against the library as compiled
     if lib.rt_abi_sizeof(_i) != C.sizeof(_t):
         raise ImportError(f"ABI mismatch for {_t.__name__}: library {lib.rt_abi_sizeof(_i)} vs ctypes {C.sizeof(_t)}")
     for _k, (_fname, *_rest) in enumerate(_t._fields_):

@@ -16,6 +16,8 @@
 #include "rt_scene.h"
 #include "rt_scene_kernels.h"
 #include "rt_scene_plan.h"
+#include "rt_surface_kernels.h"
+#include "rt_surface_plan.h"
 #include "rt_texture_kernels.h"
 #include "rt_texture_plan.h"
 #include "rt_tree_kernels.h"
@@ -117,6 +119,7 @@ struct DeviceScene {
     TexRec *tex = nullptr;
     uint8_t *texels = nullptr;
     int32_t *obj_to_orig = nullptr; // HostScene::objToOrig (the ray-list hit queries answer in rt_scene_create's indices)
+    int32_t *orig_to_obj = nullptr; // its inverse, made on the device by the first surface query (surface_inverse_map); freed with the scene
     int cu_count = 0;
 };
 
@@ -156,6 +159,7 @@ static std::atomic<int> g_walk_tree{RT_WALK_TREE_SAH};
 static thread_local unsigned long long g_last_stage_stats[16] = {0};
 static thread_local int64_t g_last_launch_plan[RT_LAUNCH_PLAN_WORDS] = {0};
 static thread_local int64_t g_last_paths_plan[8] = {0};
+static thread_local int64_t g_last_surface_plan[8] = {0};
 // rt_dev_last_texture_plan: [0..4] of this thread's last rt_scene_create_*textures call; [5..7] (kernel launches, texel bytes host->device,
 // texel bytes device->host) count on from it through rt_scene_set_texels_device and the lazy fetch of the texels
 static thread_local int64_t g_last_texture_plan[8] = {0};
@@ -359,6 +363,7 @@ size_t rt_abi_sizeof(int which) {
     case 10: return sizeof(rt_jpeg_info);
     case 11: return sizeof(rt_jpeg_stats);
     case 12: return sizeof(rt_texels_source);
+    case 13: return sizeof(rt_surface_outputs);
     default: return 0;
     }
 }
@@ -391,6 +396,8 @@ size_t rt_abi_offsetof(int which, int field) {
     case 9: RT_OFFS(rt_path_outputs, F(rt_path_outputs, struct_size), F(rt_path_outputs, max_vertices), F(rt_path_outputs, n_vertices), F(rt_path_outputs, end),
                     F(rt_path_outputs, colour), F(rt_path_outputs, first_ray), F(rt_path_outputs, hit_index), F(rt_path_outputs, strike),
                     F(rt_path_outputs, colour_after), F(rt_path_outputs, ray_after), F(rt_path_outputs, summary))
+    case 13: RT_OFFS(rt_surface_outputs, F(rt_surface_outputs, struct_size), F(rt_surface_outputs, normal), F(rt_surface_outputs, inside),
+                     F(rt_surface_outputs, colour), F(rt_surface_outputs, tint), F(rt_surface_outputs, uv))
     default: return (size_t) -1;
     }
 #undef F
@@ -487,6 +494,7 @@ void rt_scene_destroy(rt_scene *s) {
         (void) hipFree(kv.second.tex);
         (void) hipFree(kv.second.texels);
         (void) hipFree(kv.second.obj_to_orig);
+        (void) hipFree(kv.second.orig_to_obj);
     }
     if (s->src.keep && hipSetDevice(s->src.device) == hipSuccess) (void) hipFree(s->src.keep);
     if (prev >= 0 && (!s->dev.empty() || s->src.keep)) (void) hipSetDevice(prev);
@@ -1754,6 +1762,280 @@ int rt_camera_hits(const rt_scene *scene, const rt_camera *camera, int32_t max_w
         return launch_camera_hits(scene, camera, max_w, max_h, seed, device, n, d[0], sample_first, n_samples, flags, d[1], d[2], d[3], nullptr, nullptr, want_stats, pd);
     }));
     camera_hits_counts(stats, n, n_samples);
+    return RT_OK;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// surface records (DESIGN.md "Surface records"): normal, side, colour, tint and uv at a list of hits (surface_kernel, rt_surface_plan.h),
+// and the same for what each pixel sample's camera ray strikes first (the camera-hits launch above, then surface_kernel on its stream)
+// ------------------------------------------------------------------------------------------------------------
+static int check_surface_outputs(const rt_surface_outputs *out) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (out->struct_size != sizeof(rt_surface_outputs)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_surface_outputs.struct_size is not sizeof(rt_surface_outputs)");
+    if (!out->normal && !out->inside && !out->colour && !out->tint && !out->uv) return fail(RT_ERR_INVALID_ARGUMENT, "every output is NULL");
+    return RT_OK;
+}
+// Every argument check of rt_surfaces / rt_surfaces_device, made before anything touches a device.
+static int check_surfaces(const rt_scene *scene, size_t n, const void *hit_index, const void *strike, const void *rays, const rt_surface_outputs *out,
+                          const rt_render_options *options) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (n > 0 && !hit_index) return fail(RT_ERR_INVALID_ARGUMENT, "hit_index is NULL");
+    if (n > 0 && !strike) return fail(RT_ERR_INVALID_ARGUMENT, "strike is NULL");
+    if (n > 0 && !rays) return fail(RT_ERR_INVALID_ARGUMENT, "rays is NULL");
+    RT_TRY(check_surface_outputs(out));
+    RT_TRY(check_count(n, "slots"));
+    return check_options(options);
+}
+static int32_t scene_hittables(const rt_scene *scene) { return scene->host.off.n_bounded + scene->host.off.n_unbounded; }
+
+// (`device` current.)  The inverse of obj_to_orig, made once per (scene, device) under the scene's mutex and finished before the mutex is
+// given up, so every later launch on any stream finds it complete.  rt_scene_tune swaps the image and keeps the object table, so it holds.
+static int surface_inverse_map(rt_scene *s, DeviceScene *ds, int32_t n) {
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (ds->orig_to_obj || n <= 0) return RT_OK;
+    if (!ds->obj_to_orig) return fail(RT_ERR_HIP, "the scene has no object table on this device");
+    int32_t *inv = nullptr;
+    HIP_TRY(hipMalloc((void **) &inv, (size_t) n * sizeof(int32_t)));
+    hipError_t e = hipMemset(inv, 0, (size_t) n * sizeof(int32_t));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(surface_inverse_map_kernel, dim3(((unsigned) n + 255u) / 256u), dim3(256), 0, nullptr, (const int32_t *) ds->obj_to_orig, n, inv);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) { (void) hipFree(inv); return fail(RT_ERR_HIP, std::string("surface_inverse_map: ") + hipGetErrorString(e)); }
+    ds->orig_to_obj = inv;
+    return RT_OK;
+}
+
+struct SurfaceJob {
+    size_t slots = 0;
+    const void *hit_index = nullptr, *strike = nullptr, *origins = nullptr;
+    uint32_t slots_per_origin = 1, origin_stride = 6;
+    rt_surface_outputs out{};
+    const unsigned int *bad = nullptr; // the camera route: the camera launch's LaunchScratch::ext_malformed.  null: the list is checked here
+};
+// What a surface launch leaves behind: events around the kernel and its two words (bad entries; textured slots evaluated).
+struct SurfacePending {
+    hipEvent_t a = nullptr, b = nullptr;
+    unsigned char *words = nullptr;
+    hipStream_t st = nullptr;
+    bool checked = false;
+    std::chrono::steady_clock::time_point t0;
+    void release() {
+        if (a) (void) hipEventDestroy(a);
+        if (b) (void) hipEventDestroy(b);
+        if (words) (void) hipFreeAsync(words, st);
+        a = b = nullptr; words = nullptr;
+    }
+    ~SurfacePending() { release(); }
+};
+#define RT_SURFACE_WORDS_BYTES 16 /* [0] bad entries (uint32) [8] textured slots evaluated (uint64) */
+
+// Enqueues the list check (unless the job brings its own verdict) and the surface kernel on `stream` (slots > 0, arguments checked).
+static int launch_surfaces(const rt_scene *scene, int32_t device, const SurfaceJob &job, void *stream, bool want_stats, SurfacePending &sp) {
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    sp.t0 = std::chrono::steady_clock::now();
+    DeviceScene *ds = nullptr;
+    RT_TRY(device_scene(const_cast<rt_scene *>(scene), device, &ds));
+    const rth::HostScene &h = scene->host;
+    const int32_t nh = scene_hittables(scene);
+    RT_TRY(surface_inverse_map(const_cast<rt_scene *>(scene), ds, nh));
+    hipStream_t st = (hipStream_t) stream;
+    const rtp::SceneSize sz = scene_size(h);
+    const rtsf::SurfacePlan plan = rtsf::plan((uint64_t) job.slots, ds->cu_count, sz.tex, sz.prog, job.out.colour || job.out.tint || job.out.uv);
+    {
+        int64_t *o = g_last_surface_plan;
+        o[0] = (int64_t) plan.slots; o[1] = plan.tile; o[2] = (int64_t) plan.grid; o[3] = plan.block; o[4] = plan.prog; o[5] = plan.tex_phase; o[6] = -1; o[7] = 0;
+    }
+    sp.st = st;
+    sp.checked = job.bad == nullptr;
+    if (sp.checked || want_stats) {
+        HIP_TRY(hipMallocAsync((void **) &sp.words, RT_SURFACE_WORDS_BYTES, st));
+        HIP_TRY(hipMemsetAsync(sp.words, 0, RT_SURFACE_WORDS_BYTES, st));
+    }
+    if (want_stats) {
+        HIP_TRY(hipEventCreate(&sp.a));
+        HIP_TRY(hipEventCreate(&sp.b));
+        HIP_TRY(hipEventRecord(sp.a, st));
+    }
+    SurfaceParams p{};
+    p.scene_image = ds->image; p.off = h.off; p.tex = ds->tex; p.texels = ds->texels;
+    p.orig_to_obj = ds->orig_to_obj; p.n_hittables = nh;
+    p.tex_phase = plan.tex_phase ? 1u : 0u;
+    p.hit_index = (const int32_t *) job.hit_index; p.strike = (const double *) job.strike;
+    p.origin_base = (const double *) job.origins; p.slots_per_origin = job.slots_per_origin; p.origin_stride = job.origin_stride;
+    p.slots = (uint64_t) job.slots;
+    p.normal = (double *) job.out.normal; p.inside = (uint8_t *) job.out.inside; p.colour = (uint8_t *) job.out.colour;
+    p.tint = (uint8_t *) job.out.tint; p.uv = (double *) job.out.uv;
+    p.bad = job.bad ? job.bad : (const unsigned int *) sp.words;
+    p.textured = want_stats ? (unsigned long long *) (sp.words + 8) : nullptr;
+    if (sp.checked) { // in front of the launch, on the same stream: is every entry an index of the scene, -1 or -2?
+        const unsigned long long want = ((unsigned long long) job.slots + 255ull) / 256ull, most = (unsigned long long) ds->cu_count * 8ull;
+        hipLaunchKernelGGL(surface_list_check_kernel, dim3((unsigned) (want < most ? want : most)), dim3(256), 0, st, p.hit_index, (unsigned long long) job.slots, nh,
+                           (unsigned int *) sp.words);
+    }
+    if (plan.prog) hipLaunchKernelGGL(surface_kernel<true>, dim3((unsigned) plan.grid), dim3(RTSF_BLOCK), 0, st, p);
+    else hipLaunchKernelGGL(surface_kernel<false>, dim3((unsigned) plan.grid), dim3(RTSF_BLOCK), 0, st, p);
+    HIP_TRY(hipGetLastError());
+    if (want_stats) HIP_TRY(hipEventRecord(sp.b, st));
+    else sp.release();
+    return RT_OK;
+}
+// Waits for the launch's stream; a malformed list is reported here.  kernel_ms: the surface kernel's (with its list check).
+static int collect_surfaces(SurfacePending &sp, float *kernel_ms) {
+    HIP_TRY(hipStreamSynchronize(sp.st));
+    unsigned int bad = 0u;
+    unsigned long long textured = 0ull;
+    HIP_TRY(hipMemcpy(&bad, sp.words, sizeof(bad), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&textured, sp.words + 8, sizeof(textured), hipMemcpyDeviceToHost));
+    if (sp.checked && bad != 0u) {
+        sp.release();
+        return fail(RT_ERR_INVALID_ARGUMENT, "hit_index has an entry outside [-2, n_hittables); nothing was written");
+    }
+    HIP_TRY(hipEventElapsedTime(kernel_ms, sp.a, sp.b));
+    g_last_surface_plan[6] = (int64_t) textured;
+    sp.release();
+    return RT_OK;
+}
+static void surface_stats(rt_stats *stats, size_t slots, float kernel_ms, std::chrono::steady_clock::time_point t0) {
+    if (!stats) return;
+    memset(stats, 0, sizeof(*stats));
+    stats->samples = (uint64_t) slots;
+    stats->kernel_ms = kernel_ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+static SurfaceJob ray_surface_job(size_t n, const void *hit_index, const void *strike, const void *rays, const rt_surface_outputs &out) {
+    SurfaceJob j;
+    j.slots = n; j.hit_index = hit_index; j.strike = strike; j.origins = rays; j.out = out;
+    return j;
+}
+static int run_surfaces_device(const rt_scene *scene, int32_t device, const SurfaceJob &job, void *stream, rt_stats *stats) {
+    DeviceGuard guard; // (launch_surfaces enters it again: a no-op then) so that collect_surfaces runs on the device too
+    RT_TRY(guard.enter(device));
+    SurfacePending sp;
+    RT_TRY(launch_surfaces(scene, device, job, stream, stats != nullptr, sp));
+    if (!stats) return RT_OK;
+    float ms = 0.f;
+    RT_TRY(collect_surfaces(sp, &ms));
+    surface_stats(stats, job.slots, ms, sp.t0);
+    return RT_OK;
+}
+// the five outputs as staging segments, in rt_surface_outputs' order
+#define RT_SURFACE_OUT_SEGMENTS(o, slots) {(o).normal, (slots) * 24u, SEG_OUT}, {(o).inside, (slots), SEG_OUT}, {(o).colour, (slots) * 3u, SEG_OUT}, \
+                                          {(o).tint, (slots) * 3u, SEG_OUT}, {(o).uv, (slots) * 16u, SEG_OUT}
+static rt_surface_outputs staged_surface_outputs(const rt_surface_outputs &host, void *const *d) { // d: the five segments above, on the device
+    rt_surface_outputs o = host;
+    o.normal = d[0]; o.inside = d[1]; o.colour = d[2]; o.tint = d[3]; o.uv = d[4];
+    return o;
+}
+
+extern "C" {
+
+int rt_surfaces_device(const rt_scene *scene, int32_t device, size_t n, const void *d_hit_index, const void *d_strike, const void *d_rays, uint32_t flags,
+                       const rt_surface_outputs *out, void *stream, const rt_render_options *options, rt_stats *stats) {
+    (void) flags; // RT_RENDER_COUNTERS is accepted and changes nothing: there is one variant
+    RT_TRY(check_surfaces(scene, n, d_hit_index, d_strike, d_rays, out, options));
+    if (n == 0) return nothing_to_do(stats);
+    return run_surfaces_device(scene, device, ray_surface_job(n, d_hit_index, d_strike, d_rays, *out), stream, stats);
+}
+
+// The host variant checks the list here, before anything touches a device.
+int rt_surfaces(const rt_scene *scene, int32_t device, size_t n, const int32_t *hit_index, const double *strike, const double *rays, uint32_t flags,
+                const rt_surface_outputs *out, rt_stats *stats) {
+    (void) flags;
+    RT_TRY(check_surfaces(scene, n, hit_index, strike, rays, out, nullptr));
+    if (n == 0) return nothing_to_do(stats);
+    const int32_t nh = scene_hittables(scene);
+    for (size_t i = 0; i < n; ++i)
+        if (!rtsf::list_entry_ok(hit_index[i], nh)) return fail(RT_ERR_INVALID_ARGUMENT, "hit_index has an entry outside [-2, n_hittables)");
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    const auto t0 = std::chrono::steady_clock::now();
+    Staging st;
+    RT_TRY(st.in({{hit_index, n * 4u, SEG_IN}, {strike, n * 24u, SEG_IN}, {rays, n * 48u, SEG_IN}, RT_SURFACE_OUT_SEGMENTS(*out, n)}));
+    rt_stats local;
+    RT_TRY(run_surfaces_device(scene, device, ray_surface_job(n, st.dev[0], st.dev[1], st.dev[2], staged_surface_outputs(*out, st.dev + 3)), nullptr, &local));
+    RT_TRY(st.out());
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
+int rt_dev_last_surface_plan(int64_t out[8]) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "out is NULL");
+    for (int i = 0; i < 8; ++i) out[i] = g_last_surface_plan[i];
+    return RT_OK;
+}
+
+int rt_camera_surfaces_device(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                              const void *d_pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, void *d_hit_index, void *d_strike,
+                              const rt_surface_outputs *out, void *stream, const rt_render_options *options, rt_stats *stats) {
+    RT_TRY(check_camera_hits(scene, camera, max_w, max_h, n, d_pixels, sample_first, n_samples, /* hit_index may be NULL here */ scene, options));
+    RT_TRY(check_surface_outputs(out));
+    if (n == 0) return nothing_to_do(stats);
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    const size_t slots = n * (size_t) n_samples;
+    hipStream_t st = (hipStream_t) stream;
+    // what the caller does not want of the camera hits lives in stream-ordered scratch, given back behind the surface kernel
+    struct Temp {
+        unsigned char *p = nullptr;
+        hipStream_t st = nullptr;
+        ~Temp() { if (p) (void) hipFreeAsync(p, st); }
+    } tmp;
+    tmp.st = st;
+    const size_t hitBytes = d_hit_index ? 0u : (slots * 4u + 15u) & ~(size_t) 15u, strikeBytes = d_strike ? 0u : slots * 24u;
+    if (hitBytes + strikeBytes) HIP_TRY(hipMallocAsync((void **) &tmp.p, hitBytes + strikeBytes, st));
+    void *hit = d_hit_index ? d_hit_index : (void *) tmp.p;
+    void *strike = d_strike ? d_strike : (void *) (tmp.p + hitBytes);
+    // the camera launch keeps its scratch (its statistics are asked for) until the surface kernel is enqueued: the kernel reads the
+    // list's verdict and the one origin of every slot, camera->view_origin, from it
+    Pending pd;
+    RT_TRY(launch_camera_hits(scene, camera, max_w, max_h, seed, device, n, d_pixels, sample_first, n_samples, flags, hit, strike, nullptr, stream, options, true, pd));
+    SurfaceJob job;
+    job.slots = slots; job.hit_index = hit; job.strike = strike; job.out = *out;
+    job.origins = pd.scr + offsetof(LaunchScratch, cam) + offsetof(CameraParams, eye);
+    job.slots_per_origin = (uint32_t) slots; job.origin_stride = 3;
+    job.bad = (const unsigned int *) (pd.scr + offsetof(LaunchScratch, ext_malformed));
+    SurfacePending sp;
+    RT_TRY(launch_surfaces(scene, device, job, stream, stats != nullptr, sp));
+    if (!stats) { pd.release(); return RT_OK; }
+    RT_TRY(collect_stats(pd, stats)); // (a list with an entry outside the frame is reported here)
+    float ms = 0.f;
+    RT_TRY(collect_surfaces(sp, &ms));
+    stats->kernel_ms += ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pd.t0).count();
+    camera_hits_counts(stats, n, n_samples);
+    return RT_OK;
+}
+
+// The host variant checks a list here, before anything touches a device.
+int rt_camera_surfaces(const rt_scene *scene, const rt_camera *camera, int32_t max_w, int32_t max_h, uint64_t seed, int32_t device, size_t n,
+                       const int32_t *pixels, int32_t sample_first, int32_t n_samples, uint32_t flags, int32_t *hit_index, double *strike,
+                       const rt_surface_outputs *out, rt_stats *stats) {
+    RT_TRY(check_camera_hits(scene, camera, max_w, max_h, n, pixels, sample_first, n_samples, scene, nullptr));
+    RT_TRY(check_surface_outputs(out));
+    if (pixels) RT_TRY(check_pixel_entries(pixels, n, max_w, max_h));
+    if (n == 0) return nothing_to_do(stats);
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t slots = n * (size_t) n_samples;
+    Staging st;
+    RT_TRY(st.in({{pixels, n * 4u, SEG_IN}, {hit_index, slots * 4u, SEG_OUT}, {strike, slots * 24u, SEG_OUT}, RT_SURFACE_OUT_SEGMENTS(*out, slots)}));
+    const rt_surface_outputs dev = staged_surface_outputs(*out, st.dev + 3);
+    rt_stats local;
+    RT_TRY(rt_camera_surfaces_device(scene, camera, max_w, max_h, seed, device, n, st.dev[0], sample_first, n_samples, flags, st.dev[1], st.dev[2], &dev, nullptr, nullptr, &local));
+    RT_TRY(st.out());
+    if (stats) {
+        *stats = local;
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
     return RT_OK;
 }
 

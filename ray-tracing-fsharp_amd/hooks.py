@@ -153,6 +153,17 @@ def last_paths_plan():
     return dict(zip(PATHS_PLAN, w)) if w[0] else None
 
 
+SURFACE_PLAN = ("slots", "tile", "grid", "block", "program", "texture_phase", "textured", "reserved")
+
+
+def last_surface_plan():
+    """The plan (csrc/rt_surface_plan.h) of the calling thread's last surface launch (Scene.surfaces / Scene.cameraSurfaces), or None
+    before the first.  textured: the slots the texture phase evaluated, -1 when no statistics were asked for."""
+    w = (C.c_int64 * 8)()
+    check(lib.rt_dev_last_surface_plan(w))
+    return dict(zip(SURFACE_PLAN, w)) if w[0] else None
+
+
 def last_launch_plan():
     """The launch plan (csrc/rt_launch_plan.h) of the calling thread's last launch as the library executed it: {"in": the planner's
     inputs, "out": its decisions}, keyed as launch_plan_table.cpp's lines are (F_ for a fused or ray-list launch, A_ and B_ for a

@@ -521,6 +521,16 @@ class CameraHits(NamedTuple):
     stats: Optional[dict]
 
 
+class Surfaces(NamedTuple):
+    """Surface records, one per slot in the shape of the hits they belong to (a field not asked for is None)."""
+    normal: Optional[np.ndarray]  # [..., 3] float64: the normal Reflection uses (flipped when inside); NaN at a no-surface slot
+    inside: Optional[np.ndarray]  # [...] uint8: 1 where the incoming ray's origin counts as inside the sphere
+    colour: Optional[np.ndarray]  # [..., 3] uint8: Texture.colourAt strike / the Pixel / the cap rule
+    tint: Optional[np.ndarray]    # [..., 3] uint8: the colour Reflection leaves a White ray with
+    uv: Optional[np.ndarray]      # [..., 2] float64: Sphere.planeMapInverse of the strike where a parameterised texture is evaluated, else NaN
+    stats: Optional[dict]
+
+
 class CameraPaths(NamedTuple):
     """Path records of camera paths, [n, n_samples, ...] in list order (a field not asked for is None)."""
     n_vertices: np.ndarray             # [n, n_samples] int32: vertices the path has (not capped by max_vertices)
@@ -983,6 +993,60 @@ class Scene:
                         count, route.ptr(px), sample_first, n_samples, _flags(counters), route.ptr(hit), route.ptr(sk), route.ptr(ry), *route.tail(options),
                         stats=stats or not route.suffix)
         return CameraHits(hit, sk, ry, st)
+
+    @staticmethod
+    def _surface_buffers(route, lead, normal, inside, colour, tint, uv):
+        """The output buffers of a surface call, shaped lead + (...), and the rt_surface_outputs that names them."""
+        bufs = {"normal": route.make(lead + (3,), "f64") if normal else None, "inside": route.make(lead, "u8") if inside else None,
+                "colour": route.make(lead + (3,), "u8") if colour else None, "tint": route.make(lead + (3,), "u8") if tint else None,
+                "uv": route.make(lead + (2,), "f64") if uv else None}
+        return bufs, A.rt_surface_outputs(**{f: C.cast(route.ptr(b), C.c_void_p).value for f, b in bufs.items()})
+
+    def surfaces(self, hit_index, strike, rays, *, normal: bool = True, inside: bool = True, colour: bool = True, tint: bool = True, uv: bool = False,
+                 device: Optional[int] = None, counters: bool = False, stats: bool = True, options: Optional[A.rt_render_options] = None) -> Surfaces:
+        """rt_surfaces: what the surface is like at a list of hits -- hit_index [n] int32 (as hitObject returns it), strike [n, 3] and
+        rays [n, 6] float64 (only the origins are read) -> Surfaces(normal [n, 3], inside [n], colour [n, 3], tint [n, 3], uv [n, 2],
+        stats): the normal and the inside flag Hittable.Reflection forms, the surface's colour (Texture.colourAt strike, the Pixel, the
+        cap rule), the colour a White ray leaves with, and the texture coordinates.  A slot with hit_index < 0 or a strike or origin
+        that is not finite has no surface: NaN normal and uv, zeros elsewhere.  numpy arrays / torch tensors exactly as for hitObject
+        (tensors: rt_surfaces_device on torch.cuda.current_stream(); stats=False: no wait for the device, and an index outside the
+        scene's objects then goes unreported and nothing is written)."""
+        route, h = _route(hit_index, "hit_index", "i32", None, device, options)
+        n = h.shape[0]
+        if route.suffix:
+            sk, r = _tensor_arg(strike, "strike", ("f64",), 3), _tensor_arg(rays, "rays", ("f64",), 6)
+            if sk.device != route.where or r.device != route.where:
+                raise ValueError("strike and rays must be on hit_index's device")
+        else:
+            sk, r = _array_arg(strike, "strike", "f64", 3), _array_arg(rays, "rays", "f64", 6)
+        if sk.shape[0] != n or r.shape[0] != n:
+            raise ValueError("strike must be [n, 3] and rays [n, 6] for n hits")
+        bufs, out = Scene._surface_buffers(route, (n,), normal, inside, colour, tint, uv)
+        # (the route's entry point and tail, as Scene._launch gives them; the pair is not in _ROUTED, whose twelve pairs tests/test_abi.py pins)
+        st = self._call(getattr(lib, "rt_surfaces" + route.suffix), route.device, n, route.ptr(h), route.ptr(sk), route.ptr(r), _flags(counters),
+                        C.byref(out), *route.tail(options), stats=stats or not route.suffix)
+        return Surfaces(stats=st, **bufs)
+
+    def cameraSurfaces(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, pixels=None, *, sample_first: int = 0, n_samples: int = 1,
+                       seed: int = 0, n: Optional[int] = None, hit_index: bool = True, strike: bool = True, normal: bool = True, inside: bool = True,
+                       colour: bool = True, tint: bool = True, uv: bool = False, tensors: bool = False, device: Optional[int] = None,
+                       counters: bool = False, stats: bool = True, options: Optional[A.rt_render_options] = None):
+        """rt_camera_surfaces: cameraHits and the surface record of every hit in one call -> (CameraHits(hit_index [n, n_samples], strike
+        [n, n_samples, 3], None, stats), Surfaces([n, n_samples, ...])): albedo, normal and uv buffers of a frame without a host trip.
+        hit_index and strike are cameraHits' bit for bit (hit_index=False / strike=False: not returned, None).  Lists, tensors=,
+        device=, stats= and options= exactly as for cameraHits."""
+        if not isinstance(n_samples, int) or not isinstance(sample_first, int):
+            raise TypeError("sample_first and n_samples must be ints")
+        route, px, count = _pixel_list(pixels, n, tensors, maxWidthCoord, maxHeightCoord, device, options)
+        per = max(n_samples, 0)
+        shape = _lead(route, (count, per), count * per)
+        hit = route.make(shape, "i32") if hit_index else None
+        sk = route.make(shape + (3,), "f64") if strike else None
+        bufs, out = Scene._surface_buffers(route, shape, normal, inside, colour, tint, uv)
+        st = self._call(getattr(lib, "rt_camera_surfaces" + route.suffix), C.byref(camera.to_abi()), maxWidthCoord, maxHeightCoord, seed, route.device, count,
+                        route.ptr(px), sample_first, n_samples, _flags(counters), route.ptr(hit), route.ptr(sk), C.byref(out), *route.tail(options),
+                        stats=stats or not route.suffix)
+        return CameraHits(hit, sk, None, st), Surfaces(stats=st, **bufs)
 
     @staticmethod
     def _path_buffers(route, lead, max_vertices, records, first_ray=False, summary_entries=None):
