@@ -801,6 +801,71 @@ int rt_render_footprints_extend_map_device(const rt_scene *scene, int32_t device
                                            uint32_t flags, const void *d_targets, void *d_accum, void *d_rgb, void *stream,
                                            const rt_render_options *options, rt_stats *stats);
 
+/* ---- Continuing a batch of views: Scene.render (Scene.fs:157-236) at a higher sample count, for n_views frames in ONE launch ----
+ * rt_render_extend and rt_render_extend_map for the buffer of rt_render_views: a turntable previewed at 16 spp and refined to 100, or
+ * refined view by view and region by region.  Continuing K views one rt_render_extend_device call each builds K lists, stages the
+ * scene K times and idles through K tails; the batch call builds one list, orders it by view, and runs one pass B over all of it.
+ * Measured on one MI355X (NOTES.md, round 34): 64 views of a 71x41 frame continued from 16 to 100 spp take 1.81 ms as ONE call and
+ * 20.97 ms as 64 rt_render_extend_device calls back to back on one stream (a factor of 11.6); by a map with per-view targets from
+ * {16, 40, 100} 1.41 ms against 13.93 ms (9.9).  ONE view of 2401x1601 continued from 100 to 500 spp costs 13 % more kernel time than
+ * rt_render_extend_device: the batch form is for many small views.
+ *
+ * The contract is rt_render_extend's and rt_render_extend_map's, word for word, applied to batch pixel G = v*rows*cols + g (view v,
+ * pixel g of its frame); cameras, seeds, geometry and buffers as rt_render_views takes them.
+ *   rt_render_views_extend      samples_done >= 12; the target is the cameras' shared samples_per_pixel.  A pixel with
+ *                               Count == samples_done is continued with samples samples_done .. target-1 of the stream keyed
+ *                               (seed of view v, g, sample); Count == 11 is final; any other Count makes the buffer MALFORMED.
+ *                               Afterwards view v is rt_render with cameras[v], seed v and the target count, in every PixelStats word
+ *                               and every rgb byte.
+ *   rt_render_views_extend_map  targets is [n_views][rows][cols] int32, one per batch pixel; the classes are those of "Extending by
+ *                               map" above with cap = the cameras' shared samples_per_pixel.  Every view may have a budget of its own,
+ *                               only noisy views or regions may be refined, views that stand at different Counts may be brought to a
+ *                               common one.  Afterwards every pixel equals that pixel of a direct render of its view at spp = its
+ *                               Count.
+ * If ANY view holds even one malformed pixel the call continues NO pixel of ANY view: no byte of accum or rgb is written, and the
+ * status is RT_ERR_INVALID_ARGUMENT from the host variants and from the device variants when stats is given; with stats == NULL the
+ * untouched buffers are the caller's evidence.  Otherwise rgb, when given, is written for every pixel of every view.
+ *
+ * Buffers are interchangeable: a slice the batch call continued is a frame's buffer that rt_render_extend_device continues with
+ * cameras[v]; K frames of rt_render_device laid out [K][rows][cols][4] are a batch's buffer that these calls continue.
+ *
+ * Argument checks come before any device call, nothing is written when one fails: everything rt_render_views rejects, with its
+ * message (a scene that holds a texture program included: RT_ERR_UNSUPPORTED), then samples_done < 12 or a target below
+ * samples_done (uniform), cap < 12 or a NULL targets with n_views > 0 (by map).  n_views = 0, and a target equal to samples_done,
+ * are no-ops returning RT_OK with zeroed stats.  `cameras` and `seeds` are HOST pointers and are fully read before the call returns.
+ *
+ * stats describe this call alone, summed over the views: samples = the samples added, pixels = n_views*rows*cols, pixels_early =
+ * the final pixels found, kernel_ms = list building, ordering and pass B; under RT_RENDER_COUNTERS the counters of render(a) plus
+ * extend(a -> b) equal render(b)'s.  The device variants follow rt_render_views_device's contract: enqueued on `stream`,
+ * stream-ordered scratch, any number of calls in flight, with stats == NULL the call returns right after the launch, the caller's
+ * current device is left as it was; d_targets is on `device`, like d_accum, and must not change until the launch has finished.
+ * options: as for rt_render_views; `passes` is accepted and ignored.
+ * Added symbols only -- no struct, field or existing symbol changed, so RT_ABI_VERSION stays 7. */
+int rt_render_views_extend(const rt_scene *scene, const rt_camera *cameras, int32_t n_views,
+                           int32_t max_width_coord, int32_t max_height_coord,
+                           const uint64_t *seeds /* n_views, or NULL: every view uses `seed` */, uint64_t seed,
+                           int32_t device, uint32_t flags, int32_t samples_done,
+                           int32_t *accum /* in, out: [n_views][rows][cols][4] */, uint8_t *rgb /* out, may be NULL */,
+                           rt_stats *stats);
+int rt_render_views_extend_device(const rt_scene *scene, const rt_camera *cameras, int32_t n_views,
+                                  int32_t max_width_coord, int32_t max_height_coord,
+                                  const uint64_t *seeds, uint64_t seed,
+                                  int32_t device, uint32_t flags, int32_t samples_done,
+                                  void *d_accum, void *d_rgb, void *stream,
+                                  const rt_render_options *options, rt_stats *stats);
+int rt_render_views_extend_map(const rt_scene *scene, const rt_camera *cameras, int32_t n_views,
+                               int32_t max_width_coord, int32_t max_height_coord,
+                               const uint64_t *seeds, uint64_t seed,
+                               int32_t device, uint32_t flags, const int32_t *targets /* [n_views][rows][cols] */,
+                               int32_t *accum /* in, out */, uint8_t *rgb /* out, may be NULL */,
+                               rt_stats *stats);
+int rt_render_views_extend_map_device(const rt_scene *scene, const rt_camera *cameras, int32_t n_views,
+                                      int32_t max_width_coord, int32_t max_height_coord,
+                                      const uint64_t *seeds, uint64_t seed,
+                                      int32_t device, uint32_t flags, const void *d_targets,
+                                      void *d_accum, void *d_rgb, void *stream,
+                                      const rt_render_options *options, rt_stats *stats);
+
 /* ---- Output side (ImageOutput.fs:11-30,163-197) -------------------------------------------------- */
 uint8_t rt_gamma_correct(uint8_t b); /* PixelOutput.correct (ImageOutput.fs:11-18) */
 /* ImageOutput.writePpm gammaCorrect pixels file (ImageOutput.fs:163-197): P3, no trailing newline. */

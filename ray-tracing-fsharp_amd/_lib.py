@@ -112,6 +112,15 @@ SIGNATURES = {
                                   C.c_void_p]),
     "rt_render_views_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_int32, _u64p, C.c_uint64, C.c_int32, C.c_uint32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, _P(A.rt_render_options), _P(A.rt_stats)]),
+    # (stats bound as an untyped pointer, as rt_render_views': Scene.extendViews and Scene.extendViewsMap call these pairs themselves)
+    "rt_render_views_extend": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_int32, _u64p, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32,
+                                         _i32p, _u8p, C.c_void_p]),
+    "rt_render_views_extend_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_int32, _u64p, C.c_uint64, C.c_int32, C.c_uint32,
+                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, _P(A.rt_render_options), _P(A.rt_stats)]),
+    "rt_render_views_extend_map": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_int32, _u64p, C.c_uint64, C.c_int32, C.c_uint32, _i32p,
+                                             _i32p, _u8p, C.c_void_p]),
+    "rt_render_views_extend_map_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_int32, _u64p, C.c_uint64, C.c_int32, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(A.rt_render_options), _P(A.rt_stats)]),
     "rt_camera_hits": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_size_t, _i32p, C.c_int32, C.c_int32,
                                  C.c_uint32, _i32p, _dp, _dp, _P(A.rt_stats)]),
     "rt_camera_hits_device": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_size_t, C.c_void_p, C.c_int32,

@@ -54,7 +54,7 @@ struct Job {
     uint32_t n_views = 0;                            // VIEWS; CAMERA_HITS: 0 = rt_camera_hits, >= 1 = the views of rt_camera_hits_views
     bool ray_log = false;                            // FRAME: rt_scene_tune's probe
     uint64_t n = 0;                                  // TRACE, HIT: rays; FOOTPRINTS, PIXELS: pixels (with spp); CAMERA_HITS: list entries (spp: n_samples)
-    int32_t first_sample = 0;                        // FRAME, FOOTPRINTS, PIXELS: 0 = a fresh render; >= RTD_EXTEND_MIN_DONE: an EXTENSION of a buffer that
+    int32_t first_sample = 0;                        // FRAME, FOOTPRINTS, PIXELS, VIEWS: 0 = a fresh render; >= RTD_EXTEND_MIN_DONE: an EXTENSION of a buffer that
                                                      // holds this many samples per continued pixel, to spp (rt_render_extend): pass B alone
                                                      // CAMERA_HITS: sample_first, any value >= 0 (nothing is extended)
     bool map = false;                                // an extension BY MAP (rt_render_extend_map): every pixel from its own Count to its own target <= spp.
@@ -99,7 +99,8 @@ struct LaunchPlan {
     bool two_pass = false;
     Pass one;  // the fused kernel or the ray-list kernel; with two_pass only its (kernel, block, lds_bytes) were used, for the occupancy
     Pass a, b; // two_pass: pass A and pass B of the job's pixels (rtmode::Pass::A, ::B); the three sort kernels run between them
-               // (an extension: two_pass with pass B only -- a.grid = 0, its list comes from the list-building kernel, unordered)
+               // (an extension: two_pass with pass B only -- a.grid = 0, its list comes from the list-building kernel, unordered; a batch's
+               // extension, rt_render_views_extend*: from the batch's list builder and the batch's ordering, by view)
     size_t pairs_bytes = 0, list_bytes = 0, sort_bytes = 0, pool_bytes = 0; // workspace sections behind the launch's scratch, in this order
     uint64_t pixels = 0, waves = 0;                                         // what the statistics report
     const char *error = nullptr; // plan_finish: the launch cannot be made (reported as RT_ERR_HIP, after the scratch was allocated: as before)
@@ -280,7 +281,9 @@ static inline void plan_finish(LaunchPlan &pl, int per_cu) {
         return;
     }
     // workspace: pairs[nLocal] u64, list[nLocal] u32, hist/offsets/cursor[64] u32 (an extension: the list alone, nothing is sorted)
-    pl.pairs_bytes = ext ? 0u : ((size_t) nLocal * 8u + 15u) & ~(size_t) 15u;
+    // (the extension of a batch of views, rt_render_views_extend*: its list must be ordered by view, so its list builder writes pairs and the
+    // batch's ordering runs -- pairs and keys as the batch's fresh render has them)
+    pl.pairs_bytes = ext && !pl.job.views() ? 0u : ((size_t) nLocal * 8u + 15u) & ~(size_t) 15u;
     pl.list_bytes = ((size_t) nLocal * 4u + 15u) & ~(size_t) 15u;
     pl.sort_bytes = ext ? 0u : (3u * RTD_COST_BUCKETS * 4u + 15u) & ~(size_t) 15u;
     if (pl.job.views()) // the keys of the batch's ordering (views_sort_*_kernel), then where each view's entries end

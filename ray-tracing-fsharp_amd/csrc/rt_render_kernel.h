@@ -1258,7 +1258,8 @@ __global__ void __launch_bounds__(BLOCK) render_prog_job_kernel(const RenderPara
 // scenes, blocks of 256 and 1024 threads; no texture programs.  PASS: the mode's number.
 template <bool LDS, bool COUNT, int BLOCK, int PASS, bool TEX>
 __global__ void __launch_bounds__(BLOCK) render_views_kernel(const RenderParams p) {
-    static_assert(PASS == rtmode::FRAME_FUSED || PASS == rtmode::FRAME_PASS_A || PASS == rtmode::FRAME_PASS_B, "a frame pass");
+    // (FRAME_PASS_B_MAP: pass B of a batch's extension by map, rt_render_views_extend_map -- run_stream with MAP and VIEWS both on)
+    static_assert(PASS == rtmode::FRAME_FUSED || PASS == rtmode::FRAME_PASS_A || PASS == rtmode::FRAME_PASS_B || PASS == rtmode::FRAME_PASS_B_MAP, "a frame pass");
     constexpr bool JOB = false, VIEWS = true;
     constexpr int MODE = PASS;
     const JobCtl *const job = nullptr;
@@ -1613,6 +1614,74 @@ __global__ void __launch_bounds__(256) views_sort_scatter_kernel(const unsigned 
         const unsigned long long pr = pairs[i];
         const uint32_t k = views_pair_key(pr, n1, pixels_per_view, buckets);
         list[base[k] + atomicAdd(&views_local[k], 1u)] = (unsigned int) (pr & 0xFFFFFFFFull);
+    }
+}
+
+// ---- continuing a batch of views (rt_render_views_extend, rt_render_views_extend_map): the PAIRS of the batch's ordering from the stored PixelStats ----
+// extend_list_kernel and extend_map_list_kernel over the batch's n = n_views * pixels_per_view pixels, with the same classes, the same
+// count of final pixels (counters[5]) and of foreign ones (`foreign`) -- but pass B of a batch wants its list ordered by view and
+// view_end[] filled, which a compaction of one atomic per wave does not give.  So the continued pixels leave as pairs (cost << 32 | batch
+// pixel), as pass A's do, and views_sort_hist / _scan / _scatter order them: by view, inside a view by decreasing cost.  The cost word is
+// the samples to add -- the same for every pixel of a uniform extension, target - Count under a map (a view's longest jobs first); the
+// host passes the sort kernels a divisor that spreads 0 .. cap over the cost buckets.  A view with no continued pixel gets no pair, so
+// its keys count nothing and view_end[v] == view_end[v - 1]: no list entry is of that view and no range opens in it.  The seal
+// (extend_seal_kernel) runs behind the ordering and before anything that writes; no result depends on the order.
+__global__ void __launch_bounds__(256) views_extend_list_kernel(const int32_t *accum, unsigned long long n, int32_t done, int32_t target, unsigned long long *pairs,
+                                                                unsigned int *live_count, unsigned long long *counters, unsigned int *foreign) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull;
+    const unsigned long long trips = (n + stride - 1ull) / stride; // uniform over the grid: every lane of a wave makes every ballot
+    const unsigned long long cost = (unsigned long long) (uint32_t) (target - done) << 32;
+    unsigned long long nFinal = 0ull, nForeign = 0ull;
+    for (unsigned long long t = 0; t < trips; ++t) {
+        const unsigned long long i = t * stride + (unsigned long long) blockIdx.x * 256ull + threadIdx.x;
+        int count = RTD_EARLY_COUNT;
+        if (i < n) count = ((const i4 *) accum)[i].x;
+        const bool cont = i < n && count == done, foreignPx = i < n && count != done && count != RTD_EARLY_COUNT;
+        const unsigned long long liveMask = __builtin_amdgcn_ballot_w64(cont);
+        const uint32_t nLive = (uint32_t) __popcll(liveMask);
+        if (nLive > 0u) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(live_count, nLive);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (cont) pairs[base + lane_rank(liveMask)] = cost | (unsigned long long) (uint32_t) i; // (base + rank < n: every pixel is appended at most once)
+        }
+        nForeign += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(foreignPx));
+        nFinal += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(i < n && count == RTD_EARLY_COUNT));
+    }
+    if (lane == 0) {
+        if (nFinal != 0ull) atomicAdd(&counters[5], nFinal);
+        if (nForeign != 0ull) atomicAdd(foreign, (unsigned int) nForeign); // (n < 2^31: the sum cannot wrap to 0)
+    }
+}
+__global__ void __launch_bounds__(256) views_extend_map_list_kernel(const int32_t *accum, const int32_t *targets, unsigned long long n, int32_t cap,
+                                                                    unsigned long long *pairs, unsigned int *live_count, unsigned long long *counters,
+                                                                    unsigned int *foreign) {
+    const int lane = threadIdx.x & 63;
+    const unsigned long long stride = (unsigned long long) gridDim.x * 256ull;
+    const unsigned long long trips = (n + stride - 1ull) / stride; // uniform over the grid: every lane of a wave makes every ballot
+    unsigned long long nFinal = 0ull, nForeign = 0ull;
+    for (unsigned long long t = 0; t < trips; ++t) {
+        const unsigned long long i = t * stride + (unsigned long long) blockIdx.x * 256ull + threadIdx.x;
+        int count = RTD_EARLY_COUNT, target = 0;
+        if (i < n) { count = ((const i4 *) accum)[i].x; target = targets[i]; }
+        const bool fin = i < n && count == RTD_EARLY_COUNT;
+        const bool foreignPx = i < n && !fin && (count < RTD_EARLY_COUNT || target > cap);
+        const bool cont = i < n && !fin && !foreignPx && target > count;
+        const unsigned long long liveMask = __builtin_amdgcn_ballot_w64(cont);
+        const uint32_t nLive = (uint32_t) __popcll(liveMask);
+        if (nLive > 0u) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(live_count, nLive);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (cont) pairs[base + lane_rank(liveMask)] = ((unsigned long long) (uint32_t) (target - count) << 32) | (unsigned long long) (uint32_t) i;
+        }
+        nForeign += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(foreignPx));
+        nFinal += (unsigned long long) __popcll(__builtin_amdgcn_ballot_w64(fin));
+    }
+    if (lane == 0) {
+        if (nFinal != 0ull) atomicAdd(&counters[5], nFinal);
+        if (nForeign != 0ull) atomicAdd(foreign, (unsigned int) nForeign); // (n < 2^31: the sum cannot wrap to 0)
     }
 }
 

@@ -307,7 +307,8 @@ static render_fn pick_views_kernel(const rtp::Pass &q) {
     if (q.prog || (q.block != 256 && q.block != 1024)) return nullptr;
     if (q.mode == rtmode::CAMERA_HITS) return q.tex ? nullptr : q.block == 256 ? pick_camera_hits_views<256>(q.lds, q.count) : pick_camera_hits_views<1024>(q.lds, q.count);
     return q.mode == rtmode::FRAME_FUSED ? pick_views_pass<rtmode::FRAME_FUSED>(q) : q.mode == rtmode::FRAME_PASS_A ? pick_views_pass<rtmode::FRAME_PASS_A>(q) :
-           q.mode == rtmode::FRAME_PASS_B ? pick_views_pass<rtmode::FRAME_PASS_B>(q) : nullptr;
+           q.mode == rtmode::FRAME_PASS_B ? pick_views_pass<rtmode::FRAME_PASS_B>(q) :
+           q.mode == rtmode::FRAME_PASS_B_MAP ? pick_views_pass<rtmode::FRAME_PASS_B_MAP>(q) : nullptr; // (pass B of a batch's extension by map: 16 more)
 }
 template <int MODE = rtmode::FRAME_FUSED> static render_fn pick_kernel(const rtp::Pass &q) {
     if (MODE == rtmode::FRAME_FUSED && q.views) return pick_views_kernel(q);
@@ -802,13 +803,41 @@ static int enqueue(const rt_scene *scene, int32_t device, const rtp::Job &job, c
             const unsigned long long nLocal = plan.pixels; // (< 2^32: the plan's condition for a list)
             const unsigned long long want = (nLocal + 255ull) / 256ull, most = (unsigned long long) ds->cu_count * 8ull;
             const unsigned listGrid = (unsigned) (want < most ? want : most);
+            if (views) {
+                // a batch of views: the list builders of the batch write PAIRS (samples to add, batch pixel); the seal; then the batch's
+                // ordering -- by view, inside a view longest job first -- which also fills view_end, what clips pass B's ranges.  A
+                // sealed buffer has no pair: every key counts nothing, every view_end is 0, and pass B opens no range
+                unsigned long long *pairs = (unsigned long long *) (scr + RT_SCRATCH_BYTES);
+                unsigned int *sortBuf = (unsigned int *) (scr + RT_SCRATCH_BYTES + pairsBytes + listBytes);
+                HIP_TRY(hipMemsetAsync(sortBuf, 0, sortBytes, st));
+                p.pairs = pairs;
+                if (job.map)
+                    hipLaunchKernelGGL(views_extend_map_list_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, p.ext_targets, nLocal, p.spp, pairs,
+                                       p.live_count, p.counters, &ls->ext_foreign);
+                else
+                    hipLaunchKernelGGL(views_extend_list_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, nLocal, job.first_sample, p.spp, pairs,
+                                       p.live_count, p.counters, &ls->ext_foreign);
+                hipLaunchKernelGGL(extend_seal_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) &ls->ext_foreign, p.live_count, &ls->ext_malformed);
+                const uint32_t buckets = rtviews::sort_buckets(p.n_views, RTD_COST_BUCKETS);
+                unsigned int *viewEnd = sortBuf + (size_t) p.n_views * buckets;
+                p.view_end = viewEnd;
+                const uint64_t nKeys = (uint64_t) p.n_views * buckets;
+                const uint32_t ldsKeys = nKeys <= (uint64_t) VIEWS_SORT_LDS_KEYS ? (uint32_t) nKeys : 0u;
+                // cost_bucket's divisor: a cost is at most spp samples, and 4 * spp / (spp / 16 + 1) < 64 = RTD_COST_BUCKETS
+                const uint32_t costDiv = (uint32_t) p.spp / 16u + 1u;
+                hipLaunchKernelGGL(views_sort_hist_kernel, dim3(256), dim3(256), (size_t) ldsKeys * 4u, st, (const unsigned long long *) pairs,
+                                   (const unsigned int *) p.live_count, costDiv, p.view_pixels, buckets, ldsKeys, sortBuf);
+                hipLaunchKernelGGL(views_sort_scan_kernel, dim3(1), dim3(256), 0, st, sortBuf, p.n_views, buckets, viewEnd);
+                hipLaunchKernelGGL(views_sort_scatter_kernel, dim3(256), dim3(256), (size_t) ldsKeys * 8u, st, (const unsigned long long *) pairs,
+                                   (const unsigned int *) p.live_count, costDiv, p.view_pixels, buckets, ldsKeys, sortBuf, list);
+            } else
             if (job.map) // every pixel against its own target (p.spp is the cap); the seal is the same
                 hipLaunchKernelGGL(extend_map_list_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, p.ext_targets, nLocal, p.spp, list,
                                    p.live_count, p.counters, &ls->ext_foreign);
             else
                 hipLaunchKernelGGL(extend_list_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, nLocal, job.first_sample, list, p.live_count,
                                    p.counters, &ls->ext_foreign);
-            hipLaunchKernelGGL(extend_seal_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) &ls->ext_foreign, p.live_count, &ls->ext_malformed);
+            if (!views) hipLaunchKernelGGL(extend_seal_kernel, dim3(1), dim3(64), 0, st, (const unsigned int *) &ls->ext_foreign, p.live_count, &ls->ext_malformed);
             if (p.rgb && job.map) // the final pixels AND the ones left as they are; pass B writes the continued ones'
                 hipLaunchKernelGGL(extend_map_rest_rgb_kernel, dim3(listGrid), dim3(256), 0, st, (const int32_t *) p.accum, p.ext_targets, nLocal,
                                    (const unsigned int *) &ls->ext_malformed, p.rgb);
@@ -1641,7 +1670,8 @@ static int check_views(const rt_scene *scene, const rt_camera *cameras, int32_t 
 // Enqueues the batch on `stream` (n_views > 0, arguments checked): one view's geometry in the frame's RenderParams fields, the batch's
 // buffers, the per-view cameras and seed keys for enqueue() to stage; cameras and seeds are read HERE, before the call returns.
 static int launch_views(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds, uint64_t seed,
-                        int32_t device, uint32_t flags, void *d_accum, void *d_rgb, void *stream, const rt_render_options *options, bool want_stats, Pending &pd) {
+                        int32_t device, uint32_t flags, void *d_accum, void *d_rgb, void *stream, const rt_render_options *options, bool want_stats, Pending &pd,
+                        int32_t first_sample = 0, const void *d_targets = nullptr) { // as launch_render's: an extension of the batch; by map (first_sample is then RTD_EXTEND_MIN_DONE)
     RenderParams p{};
     p.max_w = max_w; p.max_h = max_h;
     p.spp = cameras[0].samples_per_pixel;
@@ -1660,6 +1690,9 @@ static int launch_views(const rt_scene *scene, const rt_camera *cameras, int32_t
     job.kind = rtp::Job::VIEWS;
     job.n_views = (uint32_t) n_views;
     job.n_rows = (uint64_t) (2 * max_h + 1); job.max_w = max_w; job.spp = cameras[0].samples_per_pixel;
+    job.first_sample = first_sample;
+    job.map = d_targets != nullptr;
+    p.ext_targets = (const int32_t *) d_targets;
     return enqueue(scene, device, job, resolve_settings(options), flags, stream, p, va.cams[0], want_stats, pd, &va);
 }
 
@@ -1679,6 +1712,71 @@ int rt_render_views(const rt_scene *scene, const rt_camera *cameras, int32_t n_v
     const size_t px = n_views > 0 ? (size_t) n_views * (size_t) (2 * max_w + 1) * (size_t) (2 * max_h + 1) : 0u;
     return run_host(device, stats, n_views == 0, {{accum, px * 16u, SEG_OUT}, {rgb, px * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
         return launch_views(scene, cameras, n_views, max_w, max_h, seeds, seed, device, flags, d[0], d[1], nullptr, nullptr, want_stats, pd);
+    });
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
+// continuing a batch of views (DESIGN.md "Continuing a batch of views"): rt_render_extend and rt_render_extend_map (Scene.fs:157-236 at a higher
+// sample count) for the n_views frames of a batch in ONE launch -- the batch's list builders, the batch's ordering, then pass B of the
+// views kernels from first_b on (uniform) or over per-pixel ranges (by map: render_views_kernel<.., FRAME_PASS_B_MAP, ..>)
+// ------------------------------------------------------------------------------------------------------------
+// Every argument check of the uniform pair, before anything touches a device: the batch's, then the extension's.  (No view: there is no
+// camera to take the target from, and only samples_done itself is looked at.)
+static int check_views_extend(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const void *accum,
+                              const rt_render_options *options, int32_t samples_done) {
+    RT_TRY(check_views(scene, cameras, n_views, max_w, max_h, accum, options));
+    return check_extend(n_views > 0 ? cameras[0].samples_per_pixel : samples_done, samples_done);
+}
+// ... and of the pair by map: the cap is the cameras' shared samples_per_pixel
+static int check_views_extend_map(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const void *targets,
+                                  const void *accum, const rt_render_options *options) {
+    RT_TRY(check_views(scene, cameras, n_views, max_w, max_h, accum, options));
+    if (n_views == 0) return RT_OK;
+    return check_extend_map(cameras[0].samples_per_pixel, (size_t) n_views, targets);
+}
+static size_t views_pixels(int32_t n_views, int32_t max_w, int32_t max_h) { // (checked: at most INT32_MAX)
+    return n_views > 0 ? (size_t) n_views * (size_t) (2 * max_w + 1) * (size_t) (2 * max_h + 1) : 0u;
+}
+
+extern "C" {
+
+int rt_render_views_extend_device(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds,
+                                  uint64_t seed, int32_t device, uint32_t flags, int32_t samples_done, void *d_accum, void *d_rgb, void *stream,
+                                  const rt_render_options *options, rt_stats *stats) {
+    RT_TRY(check_views_extend(scene, cameras, n_views, max_w, max_h, d_accum, options, samples_done));
+    const bool nothing = n_views == 0 || cameras[0].samples_per_pixel == samples_done; // nothing to add
+    return run_device(device, stats, nothing, [&](bool want_stats, Pending &pd) {
+        return launch_views(scene, cameras, n_views, max_w, max_h, seeds, seed, device, flags, d_accum, d_rgb, stream, options, want_stats, pd, samples_done);
+    });
+}
+
+int rt_render_views_extend(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds, uint64_t seed,
+                           int32_t device, uint32_t flags, int32_t samples_done, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
+    RT_TRY(check_views_extend(scene, cameras, n_views, max_w, max_h, accum, nullptr, samples_done));
+    const bool nothing = n_views == 0 || cameras[0].samples_per_pixel == samples_done;
+    const size_t px = views_pixels(n_views, max_w, max_h);
+    return run_host(device, stats, nothing, {{accum, px * 16u, SEG_INOUT}, {rgb, px * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_views(scene, cameras, n_views, max_w, max_h, seeds, seed, device, flags, d[0], d[1], nullptr, nullptr, want_stats, pd, samples_done);
+    });
+}
+
+int rt_render_views_extend_map_device(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds,
+                                      uint64_t seed, int32_t device, uint32_t flags, const void *d_targets, void *d_accum, void *d_rgb, void *stream,
+                                      const rt_render_options *options, rt_stats *stats) {
+    RT_TRY(check_views_extend_map(scene, cameras, n_views, max_w, max_h, d_targets, d_accum, options));
+    return run_device(device, stats, n_views == 0, [&](bool want_stats, Pending &pd) { // (a map whose every target is reached still goes to the device)
+        return launch_views(scene, cameras, n_views, max_w, max_h, seeds, seed, device, flags, d_accum, d_rgb, stream, options, want_stats, pd, RTD_EXTEND_MIN_DONE, d_targets);
+    });
+}
+
+int rt_render_views_extend_map(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds, uint64_t seed,
+                               int32_t device, uint32_t flags, const int32_t *targets, int32_t *accum, uint8_t *rgb, rt_stats *stats) {
+    RT_TRY(check_views_extend_map(scene, cameras, n_views, max_w, max_h, targets, accum, nullptr));
+    const size_t px = views_pixels(n_views, max_w, max_h);
+    return run_host(device, stats, n_views == 0, {{accum, px * 16u, SEG_INOUT}, {targets, px * 4u, SEG_IN}, {rgb, px * 3u, SEG_OUT}}, [&](void *const *d, bool want_stats, Pending &pd) {
+        return launch_views(scene, cameras, n_views, max_w, max_h, seeds, seed, device, flags, d[0], d[2], nullptr, nullptr, want_stats, pd, RTD_EXTEND_MIN_DONE, d[1]);
     });
 }
 

@@ -939,6 +939,52 @@ class Scene:
                         _flags(counters), route.ptr(out) if k else None, route.ptr(rgb) if k else None, *route.tail(options), stats=stats or not route.suffix)
         return RenderResult(out, rgb, st)
 
+    def extendViews(self, maxWidthCoord: int, maxHeightCoord: int, cameras: Sequence[Camera], accum, samplesDone: int, *,
+                    seeds: Optional[Sequence[int]] = None, seed: int = 0, device: Optional[int] = None, counters: bool = False, stats: bool = True,
+                    options: Optional[A.rt_render_options] = None) -> RenderResult:
+        """rt_render_views_extend: continues `accum` -- renderViews' buffer [K, rows, cols, 4] int32 (or K frames of render_rows stacked),
+        rendered or last extended with samplesDone (>= 12) samples per pixel -- to the cameras' shared SamplesPerPixel, all K views in
+        ONE launch (Scene.fs:157-236 at the higher count); view v is then, bit for bit, render_rows with cameras[v] and seed seeds[v] at that
+        count.  Everything but the sample count as in the call that made the buffer.  A numpy array is copied and a new one returned; a
+        contiguous int32 torch tensor on a GPU is continued IN PLACE through rt_render_views_extend_device on torch.cuda.current_stream()
+        (stats=False: no wait for the device; a malformed buffer then goes unreported and unchanged).  stats describe the extension alone."""
+        return self._extend_views("rt_render_views_extend", maxWidthCoord, maxHeightCoord, cameras, accum, None, (samplesDone,), seeds, seed, device,
+                                  counters, stats, options)
+
+    def extendViewsMap(self, maxWidthCoord: int, maxHeightCoord: int, cameras: Sequence[Camera], accum, targets, *,
+                       seeds: Optional[Sequence[int]] = None, seed: int = 0, device: Optional[int] = None, counters: bool = False, stats: bool = True,
+                       options: Optional[A.rt_render_options] = None) -> RenderResult:
+        """rt_render_views_extend_map: continues every pixel of `accum` [K, rows, cols, 4] from its own Count to targets[v, row, col] (int32
+        [K, rows, cols]) in ONE launch; the classes of extend_rows_map, the cameras' shared SamplesPerPixel the upper bound on every target.
+        Every view may have a budget of its own.  Each pixel is then, bit for bit, that pixel of render_rows of its view at its Count.
+        Arrays and tensors as for extendViews; with a tensor accum, `targets` must be a tensor on the same device."""
+        return self._extend_views("rt_render_views_extend_map", maxWidthCoord, maxHeightCoord, cameras, accum, targets, None, seeds, seed, device,
+                                  counters, stats, options)
+
+    def _extend_views(self, base, maxWidthCoord, maxHeightCoord, cameras, accum, targets, done, seeds, seed, device, counters, stats, options):
+        cams = list(cameras)
+        k = len(cams)
+        rows, cols = 2 * maxHeightCoord + 1, 2 * maxWidthCoord + 1
+        if seeds is not None and len(seeds) != k:
+            raise ValueError(f"seeds must hold one seed per camera ({k}), not {len(seeds)}")
+        if _is_torch(accum):
+            if accum.dtype != _torch().int32 or tuple(accum.shape) != (k, rows, cols, 4) or not accum.is_cuda or not accum.is_contiguous():
+                raise ValueError(f"accum must be a contiguous int32 tensor [{k}, {rows}, {cols}, 4] on a GPU")
+            route, out = _Tensors(accum.device, device), accum
+        else:
+            _no_options(options)
+            if not isinstance(accum, np.ndarray) or accum.dtype != np.int32 or accum.shape != (k, rows, cols, 4):
+                raise ValueError(f"accum must be an int32 array [{k}, {rows}, {cols}, 4] or such a tensor on a GPU")
+            route, out = _Arrays(device), np.array(accum, dtype=np.int32, order="C")
+        before = done if done is not None else (route.ptr(_targets(route, targets, (k, rows, cols), f"[{k}, {rows}, {cols}]", "accum's device")),)
+        rgb = route.make((k, rows, cols, 3), "u8")
+        abi = (A.rt_camera * max(k, 1))(*[c.to_abi() for c in cams])
+        keys = None if seeds is None else (C.c_uint64 * max(k, 1))(*[int(s) for s in seeds])
+        # (the route's entry point and tail, as Scene._launch gives them; the pairs are not in _ROUTED, whose twelve pairs tests/test_abi.py pins)
+        st = self._call(getattr(lib, base + route.suffix), abi if k else None, k, maxWidthCoord, maxHeightCoord, keys, seed, route.device, _flags(counters),
+                        *before, route.ptr(out) if k else None, route.ptr(rgb) if k else None, *route.tail(options), stats=stats or not route.suffix)
+        return RenderResult(out, rgb, st)
+
     def cameraHits(self, maxWidthCoord: int, maxHeightCoord: int, camera: Camera, pixels=None, *, sample_first: int = 0, n_samples: int = 1,
                    seed: int = 0, n: Optional[int] = None, strike: bool = True, rays: bool = True, tensors: bool = False, device: Optional[int] = None,
                    counters: bool = False, stats: bool = True, options: Optional[A.rt_render_options] = None) -> CameraHits:
