@@ -964,6 +964,47 @@ int rt_render_png(const rt_scene *scene, const rt_camera *camera, int32_t max_wi
                   uint64_t seed, int32_t device, uint32_t flags, int32_t gamma_correct, const char *path,
                   const rt_render_options *options, rt_stats *stats);
 
+/* ---- PNG files of a batch of views (DESIGN.md "PNG files of a batch of views") ----------------------------------------------
+ * rt_render_views leaves K frames in one device buffer; these calls turn them into K files without K encodes.  Image v is bytes
+ * [v*rows*cols*3, (v+1)*rows*cols*3) of d_rgb, which is n_views*rows*cols*3 uint8 on `device` with any byte alignment (images
+ * 1..K-1 start misaligned whenever rows*cols*3 is no multiple of 4).  The output is the K files behind one another with no padding:
+ * offsets[v] is the first byte of file v, offsets[n_views] the total length, and bytes [offsets[v], offsets[v+1]) are exactly what
+ * rt_format_png(image v, rows, cols, gamma_correct, ...) writes.  Nothing of one image reaches another's file.  The same FOUR launches
+ * as one image whatever n_views is (csrc/rt_png_kernels.h): the per-tile kernels run one workgroup per tile of every image, one scan
+ * places all tiles of all files, and one workgroup per image writes its head and tail.
+ * Refused before any device call, nothing written: n_views < 0, a NULL d_rgb with n_views > 0, rows or cols <= 0, more than INT32_MAX
+ * pixels in an image or in the batch, a non-NULL d_out with out_capacity == 0 (RT_ERR_INVALID_ARGUMENT); RT_ERR_UNSUPPORTED where
+ * rt_format_png says so for one image.  n_views = 0 is RT_OK: no kernel runs, and 0 is stored to offsets[0] where offsets are asked for.
+ * Added symbols only, so RT_ABI_VERSION stays 7. */
+
+/* n_views * rt_png_max_bytes(rows, cols), in closed form.  Negative statuses as rt_png_max_bytes, and -RT_ERR_INVALID_ARGUMENT for
+ * n_views < 0 or more than INT32_MAX pixels in the batch. */
+int64_t rt_png_views_max_bytes(int32_t n_views, int32_t rows, int32_t cols);
+/* rt_format_png_device's contract with the offsets in the place of its length: everything is enqueued on `stream` with stream-ordered
+ * scratch and nothing synchronises unless `offsets` is given; the caller's current device is left as it was.  d_out == NULL computes
+ * the offsets only.  A capacity below offsets[n_views] is found ON THE DEVICE in front of the writing kernels: no byte of d_out is
+ * written, d_offsets still receives the needed values, and the call returns RT_ERR_INVALID_ARGUMENT when `offsets` is given and RT_OK
+ * otherwise.  Bytes at and beyond the total are never written. */
+int rt_format_png_views_device(int32_t device, const void *d_rgb, int32_t n_views, int32_t rows, int32_t cols,
+                               int32_t gamma_correct, void *d_out /* may be NULL: offsets only */, size_t out_capacity,
+                               void *d_offsets /* int64[n_views+1] on the device, may be NULL */, void *stream,
+                               int64_t *offsets /* host, n_views+1; may be NULL */);
+/* The K files written: a device buffer of rt_png_views_max_bytes, the encode, ONE device-to-host copy of exactly offsets[n_views]
+ * bytes, then paths[v] for v = 0..K-1, one file open at a time (K may pass the descriptor limit).  Synchronises.  A NULL paths or
+ * paths[v] is RT_ERR_INVALID_ARGUMENT before any device work.  The first file that cannot be opened or is written short gives
+ * RT_ERR_IO naming that path; the files written before it stay. */
+int rt_write_png_views_device(const char *const *paths, int32_t device, const void *d_rgb, int32_t n_views, int32_t rows,
+                              int32_t cols, int32_t gamma_correct, void *stream);
+/* rt_render_views_device into buffers of the call's own, then the encode, the one copy and the K files: the pixels never visit the
+ * host as rgb.  File v is byte for byte rt_format_png of view v of rt_render_views for the same arguments.  Rejects what
+ * rt_render_views rejects (the same check list; a scene that holds a texture program is RT_ERR_UNSUPPORTED), then a NULL paths or
+ * paths[v].  stats (may be NULL) as rt_render_views fills them, total_ms covering the whole call, files included. */
+int rt_render_views_png(const rt_scene *scene, const rt_camera *cameras, int32_t n_views,
+                        int32_t max_width_coord, int32_t max_height_coord,
+                        const uint64_t *seeds /* n_views, or NULL: every view uses `seed` */, uint64_t seed,
+                        int32_t device, uint32_t flags, int32_t gamma_correct, const char *const *paths,
+                        const rt_render_options *options, rt_stats *stats);
+
 /* ---- Resuming from a pixel map, on the device (DESIGN.md "Resuming from a pixel map") ------------------
  * Program.fs:39-50 spills the frame as a pixel map (ImageOutput.toPpm), reads it back (ImageOutput.readPixelMap, ImageOutput.fs:46-113),
  * insists that it is complete (ImageOutput.assertComplete, ImageOutput.fs:199-200) and writes the PNG.  These calls are the read-back

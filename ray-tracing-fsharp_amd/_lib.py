@@ -194,6 +194,12 @@ SIGNATURES = {
     "rt_write_png_device": (C.c_int, [C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rt_render_png": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32, C.c_char_p,
                                 _P(A.rt_render_options), _P(A.rt_stats)]),
+    "rt_png_views_max_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "rt_format_png_views_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p, _P(C.c_int64)]),
+    "rt_write_png_views_device": (C.c_int, [_P(C.c_char_p), C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "rt_render_views_png": (C.c_int, [C.c_void_p, _P(A.rt_camera), C.c_int32, C.c_int32, C.c_int32, _u64p, C.c_uint64, C.c_int32, C.c_uint32, C.c_int32,
+                                      _P(C.c_char_p), _P(A.rt_render_options), _P(A.rt_stats)]),
     "rt_pixel_map_chunk_bytes": (C.c_int32, []),
     "rt_pixel_map_tile_bytes": (C.c_int32, []),
     "rt_pixel_map_scan_tiles": (C.c_int32, []),

@@ -328,6 +328,50 @@ template <class Put> RTP_HD void write_tail(uint32_t adler, uint32_t crc_tiles, 
     for (uint32_t i = 0u; i < (uint32_t) TAIL_BYTES; ++i) put(i, t[i]);
 }
 
+// ---- a batch of equal-sized images: K files behind one another, offsets by ONE scan (DESIGN.md "PNG files of a batch of views") ----
+// An image has tile_count + 1 scan entries, its tiles and then its TAIL: entry (v, t) is tile t of image v, entry (v, tiles) the bytes between
+// image v's last tile and image v + 1's first -- v's TAIL_BYTES and, but behind the last image, the next file's HEAD_BYTES.  The scan starts
+// at HEAD_BYTES (file 0's head), so a scanned tile entry is the offset of that tile, a scanned tail entry the offset of that file's last 25
+// bytes, and the scan's total is the length of all files: no byte is charged twice or left out, and the capacity decision is exact.
+// -DRTP_VIEWS_MUTANT=1..3 (tests/c/png_views_table.cpp's own builds, CPU only): three wrong layouts that the table must catch.
+#ifndef RTP_VIEWS_MUTANT
+#define RTP_VIEWS_MUTANT 0
+#endif
+RTP_HD uint64_t views_image_entries(uint64_t tiles) { return tiles + 1u; }
+RTP_HD uint64_t views_entry_count(uint64_t n_views, uint64_t tiles) { return n_views * views_image_entries(tiles); }
+RTP_HD uint64_t views_entry(uint64_t v, uint64_t t, uint64_t tiles) { // t == tiles: the image's tail entry
+#if RTP_VIEWS_MUTANT == 2
+    return v * views_image_entries(tiles) + t - (v ? 1u : 0u);
+#else
+    return v * views_image_entries(tiles) + t;
+#endif
+}
+RTP_HD uint64_t views_first_bytes() { return (uint64_t) HEAD_BYTES; } // in front of entry 0
+// What the entries that are not tiles count: t == tiles -> the tail and the next head; every other entry counts its tile's bytes.
+RTP_HD uint64_t views_tail_entry_bytes(uint64_t v, uint64_t n_views) {
+#if RTP_VIEWS_MUTANT == 1
+    return (uint64_t) TAIL_BYTES + (v > 0u ? (uint64_t) HEAD_BYTES : 0u); // the head in front of image v charged behind image v
+#else
+    return (uint64_t) TAIL_BYTES + (v + 1u < n_views ? (uint64_t) HEAD_BYTES : 0u);
+#endif
+}
+// From the scanned entries (offsets): where file v starts and ends, and its IDAT chunk's length.  `total` is the scan's total.
+template <class Scanned> RTP_HD uint64_t views_file_start(Scanned scanned, uint64_t v, uint64_t tiles) { return (uint64_t) scanned[views_entry(v, 0u, tiles)] - (uint64_t) HEAD_BYTES; }
+template <class Scanned> RTP_HD uint64_t views_file_end(Scanned scanned, uint64_t v, uint64_t tiles) { return (uint64_t) scanned[views_entry(v, tiles, tiles)] + (uint64_t) TAIL_BYTES; }
+template <class Scanned> RTP_HD uint32_t views_idat_length(Scanned scanned, uint64_t v, uint64_t tiles, uint64_t total) {
+#if RTP_VIEWS_MUTANT == 3
+    (void) scanned; (void) v; (void) tiles;
+    return (uint32_t) (total - (uint64_t) HEAD_BYTES - (uint64_t) TAIL_BYTES + (uint64_t) IDAT_EXTRA);
+#else
+    (void) total;
+    return (uint32_t) ((uint64_t) scanned[views_entry(v, tiles, tiles)] - (uint64_t) scanned[views_entry(v, 0u, tiles)] + (uint64_t) IDAT_EXTRA);
+#endif
+}
+// The writing kernels run only into a buffer that holds every file whole.
+RTP_HD bool views_go(uint64_t total, uint64_t capacity, bool have_out) { return have_out && total <= capacity; }
+// the K files of images whose every tile is stored: no batch is longer
+RTP_HD uint64_t views_max_bytes(uint64_t n_views, uint64_t rows, uint64_t cols) { return n_views * max_bytes(rows, cols); }
+
 // ---- the host formatter: the same functions in loops ----
 // One tile: f[0 .. n) filtered bytes into out (zeroed, at least STORED_HEAD + n bytes); returns the tile's byte count.  out == nullptr: the count only.
 static inline uint32_t format_tile(const uint8_t *f, uint32_t n, uint8_t *out, BuildScratch &s, TilePlan &p) {

@@ -14,6 +14,9 @@
 //   png_finish_kernel   ONE workgroup: the partial sums combined in order (rtp::crc_combine / adler_combine, as a tree), then the 43 bytes in
 //                       front of the tiles and the 25 behind them
 // Each thread owns RTO_PNG_TILE_BYTES / RTO_BLOCK = 64 consecutive filtered bytes.
+// The per-tile and per-image work is in device functions (png_tile_plan, png_scatter_tile, png_finish_image) that take the image's first byte
+// and the tile's index inside its image: the four kernels above run them for one image, the png_views_* kernels at the end of this file
+// for the K equal-sized images of a batch, still in four launches.
 #pragma once
 
 #include "rt_output.h"
@@ -60,9 +63,10 @@ template <class Fn> __device__ inline void png_walk_tokens(const uint8_t *f, con
     }
 }
 
-// What both per-tile kernels start with: L.f, the thread's part of it, and L.plan.  N: the filtered stream's length.
-__device__ inline PngThread png_tile_plan(PngLds &L, const unsigned char *rgb, uint32_t N, uint32_t cols, const GammaTable &gamma) {
-    const uint32_t T = (uint32_t) RTO_PNG_TILE_BYTES, S = 1u + 3u * cols, i0 = blockIdx.x * T;
+// What both per-tile kernels start with: L.f, the thread's part of it, and L.plan.  rgb: the image's first byte; tile: the tile's index
+// inside its image; N: the image's filtered stream's length.  No byte in front of rgb is read: the Sub filter's halo stops there.
+__device__ inline PngThread png_tile_plan(PngLds &L, const unsigned char *rgb, uint32_t tile, uint32_t N, uint32_t cols, const GammaTable &gamma) {
+    const uint32_t T = (uint32_t) RTO_PNG_TILE_BYTES, S = 1u + 3u * cols, i0 = tile * T;
     PngThread th;
     th.n = N - i0 < T ? N - i0 : T;
     // the source bytes of filtered bytes i0 .. i0 + n - 1: filtered byte (r, j >= 1) is source byte r (S - 1) + j - 1; three more in front
@@ -129,21 +133,19 @@ __device__ inline void png_or_bits(uint32_t *words, uint32_t bit, uint32_t value
 __global__ __launch_bounds__(RTO_BLOCK) void png_sums_kernel(const unsigned char *rgb, uint32_t N, uint32_t cols, const GammaTable gamma, unsigned long long *tiles,
                                                              uint32_t n_tiles) {
     __shared__ PngLds L;
-    (void) png_tile_plan(L, rgb, N, cols, gamma);
+    (void) png_tile_plan(L, rgb, blockIdx.x, N, cols, gamma);
     if (threadIdx.x == 0u) {
         tiles[blockIdx.x] = L.plan.bytes;
         if (blockIdx.x == 0u) tiles[n_tiles] = (unsigned long long) rtp::TAIL_BYTES;
     }
 }
 
-__global__ __launch_bounds__(RTO_BLOCK) void png_scatter_kernel(const unsigned char *rgb, uint32_t N, uint32_t cols, const GammaTable gamma,
-                                                                const unsigned long long *tiles, const FormatScratch *head, PngPartial *parts, unsigned char *out) {
-    __shared__ PngLds L;
-    if (!head->go) return; // the same word for every thread of every workgroup
-    const PngThread th = png_tile_plan(L, rgb, N, cols, gamma);
+// One tile of one image written to dst, and its partial sums to *part: the scatter of a frame and of a batch (the whole workgroup calls it).
+__device__ __forceinline__ void png_scatter_tile(PngLds &L, const unsigned char *rgb, uint32_t tile, uint32_t N, uint32_t cols, const GammaTable &gamma, unsigned char *dst,
+                                        PngPartial *part) {
+    const PngThread th = png_tile_plan(L, rgb, tile, N, cols, gamma);
     for (uint32_t w = threadIdx.x; w < (uint32_t) PNG_IO_WORDS; w += blockDim.x) L.io[w] = 0u; // (the source bytes are not needed again)
     __syncthreads();
-    unsigned char *dst = out + tiles[blockIdx.x];
     const uint32_t a_out = (uint32_t) ((uintptr_t) dst & 3u), bytes = L.plan.bytes;
     unsigned char *ob = (unsigned char *) L.io + a_out;
     if (L.plan.btype == (uint32_t) rtp::BT_STORED) {
@@ -154,11 +156,11 @@ __global__ __launch_bounds__(RTO_BLOCK) void png_scatter_kernel(const unsigned c
         uint32_t *words = L.io;
         const uint32_t bit0 = 8u * a_out;
         uint32_t mine = 0u, total;
-        png_walk_tokens(L.f, th, [&mine](uint32_t tok, uint8_t byte) { uint32_t v; mine += rtp::token_bits(plan, tok, byte, v); });
+        png_walk_tokens(L.f, th, [&mine, &plan](uint32_t tok, uint8_t byte) { uint32_t v; mine += rtp::token_bits(plan, tok, byte, v); });
         const uint32_t before = block_exclusive_scan<uint32_t, RTO_BLOCK>(mine, L.wave_tot, total);
         const uint32_t eob_at = plan.body_bits - plan.ll_len[rtp::EOB];
         uint32_t at = bit0 + eob_at - total + before; // the header's bits end where the tokens' begin
-        png_walk_tokens(L.f, th, [&at, words](uint32_t tok, uint8_t byte) {
+        png_walk_tokens(L.f, th, [&at, words, &plan](uint32_t tok, uint8_t byte) {
             uint32_t v;
             const uint32_t nb = rtp::token_bits(plan, tok, byte, v);
             png_or_bits(words, at, v, nb);
@@ -194,17 +196,28 @@ __global__ __launch_bounds__(RTO_BLOCK) void png_scatter_kernel(const unsigned c
     }
     if (threadIdx.x == 0u) {
         const uint32_t M = (uint32_t) rtp::ADLER_MOD;
-        parts[blockIdx.x].crc = pc[0];
-        parts[blockIdx.x].adler = (((th.n + L.adler[1]) % M) << 16) | ((1u + L.adler[0]) % M);
+        part->crc = pc[0];
+        part->adler = (((th.n + L.adler[1]) % M) << 16) | ((1u + L.adler[0]) % M);
     }
 }
 
-// tiles[0 .. n_tiles]: the offsets of the tiles and of the file's tail.
-__global__ __launch_bounds__(RTO_BLOCK) void png_finish_kernel(uint32_t rows, uint32_t cols, uint32_t N, const unsigned long long *tiles, uint32_t n_tiles,
-                                                               const FormatScratch *head, const PngPartial *parts, unsigned char *out) {
-    __shared__ uint32_t pc[RTO_BLOCK], pa[RTO_BLOCK];
-    __shared__ unsigned long long plen[RTO_BLOCK], pun[RTO_BLOCK];
-    if (!head->go) return;
+__global__ __launch_bounds__(RTO_BLOCK) void png_scatter_kernel(const unsigned char *rgb, uint32_t N, uint32_t cols, const GammaTable gamma,
+                                                                const unsigned long long *tiles, const FormatScratch *head, PngPartial *parts, unsigned char *out) {
+    __shared__ PngLds L;
+    if (!head->go) return; // the same word for every thread of every workgroup
+    png_scatter_tile(L, rgb, blockIdx.x, N, cols, gamma, out + tiles[blockIdx.x], parts + blockIdx.x);
+}
+
+struct PngFinishLds {
+    uint32_t pc[RTO_BLOCK], pa[RTO_BLOCK];
+    unsigned long long plen[RTO_BLOCK], pun[RTO_BLOCK];
+};
+
+// (Force-inlined, as png_scatter_tile is: left as a call it takes the calling convention's registers and a scratch frame.)
+// One image's file finished by one workgroup: its tiles' partial sums combined in order, then the 43 bytes at `file` and the 25 behind its
+// last tile.  tiles[0 .. n_tiles]: the offsets, in `out`, of the image's tiles and of its tail; idat: the IDAT chunk's length.
+__device__ __forceinline__ void png_finish_image(PngFinishLds &F, uint32_t rows, uint32_t cols, uint32_t N, const unsigned long long *tiles, uint32_t n_tiles, uint32_t idat,
+                                        const PngPartial *parts, unsigned char *file, unsigned char *out) {
     const uint32_t per = (n_tiles + (uint32_t) RTO_BLOCK - 1u) / (uint32_t) RTO_BLOCK;
     const uint32_t t0 = threadIdx.x * per < n_tiles ? threadIdx.x * per : n_tiles, t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
     uint32_t crc = 0u, adler = 1u;
@@ -215,22 +228,101 @@ __global__ __launch_bounds__(RTO_BLOCK) void png_finish_kernel(uint32_t rows, ui
         crc = rtp::crc_combine(crc, parts[t].crc, bytes); len += bytes;
         adler = rtp::adler_combine(adler, parts[t].adler, n); un += n;
     }
-    pc[threadIdx.x] = crc; pa[threadIdx.x] = adler; plen[threadIdx.x] = len; pun[threadIdx.x] = un;
+    F.pc[threadIdx.x] = crc; F.pa[threadIdx.x] = adler; F.plen[threadIdx.x] = len; F.pun[threadIdx.x] = un;
     __syncthreads();
     for (uint32_t d = 1u; d < (uint32_t) RTO_BLOCK; d <<= 1) {
         if ((threadIdx.x & (2u * d - 1u)) == 0u) {
-            pc[threadIdx.x] = rtp::crc_combine(pc[threadIdx.x], pc[threadIdx.x + d], plen[threadIdx.x + d]); plen[threadIdx.x] += plen[threadIdx.x + d];
-            pa[threadIdx.x] = rtp::adler_combine(pa[threadIdx.x], pa[threadIdx.x + d], pun[threadIdx.x + d]); pun[threadIdx.x] += pun[threadIdx.x + d];
+            F.pc[threadIdx.x] = rtp::crc_combine(F.pc[threadIdx.x], F.pc[threadIdx.x + d], F.plen[threadIdx.x + d]); F.plen[threadIdx.x] += F.plen[threadIdx.x + d];
+            F.pa[threadIdx.x] = rtp::adler_combine(F.pa[threadIdx.x], F.pa[threadIdx.x + d], F.pun[threadIdx.x + d]); F.pun[threadIdx.x] += F.pun[threadIdx.x + d];
         }
         __syncthreads();
     }
     if (threadIdx.x == 0u) {
-        const uint32_t idat = (uint32_t) ((unsigned long long) head->total - (unsigned long long) rtp::HEAD_BYTES - (unsigned long long) rtp::TAIL_BYTES +
-                                          (unsigned long long) rtp::IDAT_EXTRA);
-        rtp::write_head(rows, cols, idat, [out](uint32_t i, uint8_t b) { out[i] = b; });
+        rtp::write_head(rows, cols, idat, [file](uint32_t i, uint8_t b) { file[i] = b; });
         unsigned char *tail = out + tiles[n_tiles];
-        rtp::write_tail(pa[0], rtp::crc_combine(rtp::idat_crc_start(), pc[0], plen[0]), [tail](uint32_t i, uint8_t b) { tail[i] = b; });
+        rtp::write_tail(F.pa[0], rtp::crc_combine(rtp::idat_crc_start(), F.pc[0], F.plen[0]), [tail](uint32_t i, uint8_t b) { tail[i] = b; });
     }
+}
+
+// tiles[0 .. n_tiles]: the offsets of the tiles and of the file's tail.
+__global__ __launch_bounds__(RTO_BLOCK) void png_finish_kernel(uint32_t rows, uint32_t cols, uint32_t N, const unsigned long long *tiles, uint32_t n_tiles,
+                                                               const FormatScratch *head, const PngPartial *parts, unsigned char *out) {
+    __shared__ PngFinishLds F;
+    if (!head->go) return;
+    const uint32_t idat = (uint32_t) ((unsigned long long) head->total - (unsigned long long) rtp::HEAD_BYTES - (unsigned long long) rtp::TAIL_BYTES +
+                                      (unsigned long long) rtp::IDAT_EXTRA);
+    png_finish_image(F, rows, cols, N, tiles, n_tiles, idat, parts, out, out);
+}
+
+// ---- a batch of equal-sized images (rt_png.h "a batch of equal-sized images"; DESIGN.md "PNG files of a batch of views") -------------------
+// Image v is the image_bytes bytes at rgb + v * image_bytes, its file what the kernels above write for it alone; the K files stand behind one
+// another in `out`.  The same four launches whatever K is: workgroup b of the per-tile kernels serves image b / tiles, tile b % tiles, the
+// scan runs over every image's entries at once, and the finish step is one workgroup per image.  `entries` is the batch's scan array
+// (rtp::views_entry), `offsets` its K + 1 file starts.
+struct PngViews {
+    const unsigned char *rgb;
+    unsigned long long image_bytes; // rows * cols * 3
+    uint32_t n_views, tiles;        // tiles per image
+    uint32_t rows, cols, N;         // N: an image's filtered bytes
+};
+
+__global__ __launch_bounds__(RTO_BLOCK) void png_views_sums_kernel(const PngViews b, const GammaTable gamma, unsigned long long *entries) {
+    __shared__ PngLds L;
+    const uint32_t v = blockIdx.x / b.tiles, t = blockIdx.x - v * b.tiles;
+    (void) png_tile_plan(L, b.rgb + (unsigned long long) v * b.image_bytes, t, b.N, b.cols, gamma);
+    if (threadIdx.x == 0u) {
+        entries[rtp::views_entry(v, t, b.tiles)] = L.plan.bytes;
+        if (t == 0u) entries[rtp::views_entry(v, b.tiles, b.tiles)] = rtp::views_tail_entry_bytes(v, b.n_views);
+    }
+}
+
+// format_scan_kernel over the batch's entries (64-bit counts: 2 K entries of 1 x 1 images may pass 2^32), which also leaves the K + 1 file
+// starts: in `offsets` (the call's scratch, for the finish step and the host) and in d_offsets when the caller gave it.
+__global__ __launch_bounds__(RTO_SCAN_THREADS) void png_views_scan_kernel(unsigned long long *entries, const PngViews b, FormatScratch *head, long long *offsets,
+                                                                          long long *d_offsets, unsigned long long capacity, int have_out) {
+    __shared__ unsigned long long wave_tot[RTO_SCAN_THREADS / 64];
+    const unsigned long long n = rtp::views_entry_count(b.n_views, b.tiles), per = rtp::views_image_entries(b.tiles);
+    unsigned long long carry = rtp::views_first_bytes();
+    for (unsigned long long base = 0ull; base < n; base += (unsigned long long) RTO_SCAN_THREADS) {
+        const unsigned long long i = base + threadIdx.x;
+        const unsigned long long c = i < n ? entries[i] : 0ull;
+        unsigned long long trip;
+        const unsigned long long before = block_exclusive_scan<unsigned long long, RTO_SCAN_THREADS>(c, wave_tot, trip);
+        if (i < n) {
+            entries[i] = carry + before;
+            const unsigned long long v = i / per;
+            if (i == rtp::views_entry(v, 0u, b.tiles)) { // an image's first tile: its file starts HEAD_BYTES in front
+                const long long start = (long long) rtp::views_file_start(entries, v, b.tiles);
+                offsets[v] = start;
+                if (d_offsets) d_offsets[v] = start;
+            }
+        }
+        carry += trip;
+    }
+    if (threadIdx.x == 0) {
+        head->total = (long long) carry;
+        head->go = rtp::views_go(carry, capacity, have_out != 0) ? 1u : 0u; // too small a buffer: not one byte of it is written
+        offsets[b.n_views] = (long long) carry;
+        if (d_offsets) d_offsets[b.n_views] = (long long) carry;
+    }
+}
+
+__global__ __launch_bounds__(RTO_BLOCK) void png_views_scatter_kernel(const PngViews b, const GammaTable gamma, const unsigned long long *entries, const FormatScratch *head,
+                                                                      PngPartial *parts, unsigned char *out) {
+    __shared__ PngLds L;
+    if (!head->go) return; // the same word for every thread of every workgroup
+    const uint32_t v = blockIdx.x / b.tiles, t = blockIdx.x - v * b.tiles;
+    png_scatter_tile(L, b.rgb + (unsigned long long) v * b.image_bytes, t, b.N, b.cols, gamma, out + entries[rtp::views_entry(v, t, b.tiles)], parts + blockIdx.x);
+}
+
+// One workgroup per image.  parts: one PngPartial per tile, image by image.
+__global__ __launch_bounds__(RTO_BLOCK) void png_views_finish_kernel(const PngViews b, const unsigned long long *entries, const FormatScratch *head, const PngPartial *parts,
+                                                                     unsigned char *out) {
+    __shared__ PngFinishLds F;
+    if (!head->go) return;
+    const uint32_t v = blockIdx.x;
+    png_finish_image(F, b.rows, b.cols, b.N, entries + rtp::views_entry(v, 0u, b.tiles), b.tiles, rtp::views_idat_length(entries, v, b.tiles, (uint64_t) head->total),
+                     parts + (unsigned long long) v * b.tiles, out + rtp::views_file_start(entries, v, b.tiles), out);
 }
 
 } // namespace rto

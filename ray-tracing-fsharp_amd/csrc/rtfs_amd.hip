@@ -3080,6 +3080,189 @@ int rt_render_png(const rt_scene *scene, const rt_camera *camera, int32_t max_w,
 static int64_t file_max_bytes(int fmt, int32_t rows, int32_t cols) { return fmt == rto::FMT_PNG ? rt_png_max_bytes(rows, cols) : rt_ppm_max_bytes(rows, cols); }
 
 // ------------------------------------------------------------------------------------------------------------
+// PNG files of a batch of views (DESIGN.md "PNG files of a batch of views"): the K equal-sized images of rt_render_views' rgb encoded in the
+// same four launches as one image (rt_png_kernels.h "a batch of equal-sized images"; the layout is rt_png.h's), file v byte for byte
+// rt_format_png of image v
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+struct PngViewsJob {
+    const void *d_rgb;
+    int32_t n_views, rows, cols;
+    bool gamma;
+    void *d_out;
+    size_t capacity;
+    void *d_offsets;
+};
+} // namespace
+
+// Every argument check of the batch encode, before anything touches a device.
+static int check_png_views(const void *d_rgb, int32_t n_views, int32_t rows, int32_t cols, const void *d_out, size_t out_capacity) {
+    if (n_views < 0) return fail(RT_ERR_INVALID_ARGUMENT, "n_views must be >= 0");
+    if (n_views > 0 && !d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "d_rgb is NULL");
+    RT_TRY(check_image_size(rows, cols));
+    if ((uint64_t) n_views * (uint64_t) rows * (uint64_t) cols > (uint64_t) INT32_MAX) return fail(RT_ERR_INVALID_ARGUMENT, "a batch of views holds at most INT32_MAX pixels");
+    if (d_out && out_capacity == 0) return fail(RT_ERR_INVALID_ARGUMENT, "d_out is given but out_capacity is 0");
+    return check_png_size(rows, cols);
+}
+static int check_paths(const char *const *paths, int32_t n_views) {
+    if (!paths) return fail(RT_ERR_INVALID_ARGUMENT, "paths is NULL");
+    for (int32_t v = 0; v < n_views; ++v)
+        if (!paths[v]) return fail(RT_ERR_INVALID_ARGUMENT, "paths[" + std::to_string(v) + "] is NULL");
+    return RT_OK;
+}
+
+// Enqueues the batch encode on `st` (n_views > 0, arguments checked, the device current): sums, scan and -- when there is a buffer -- scatter
+// and finish.  Scratch: the head, the K + 1 file starts, one uint64 per scan entry, one PngPartial per tile.  Never waits for the device.
+static int enqueue_png_views(const PngViewsJob &j, hipStream_t st, FormatPending &fp, size_t &offsets_at) {
+    rto::PngViews b;
+    b.rgb = (const unsigned char *) j.d_rgb;
+    b.image_bytes = (unsigned long long) j.rows * (unsigned long long) j.cols * 3ull;
+    b.n_views = (uint32_t) j.n_views;
+    b.tiles = (uint32_t) rtp::tile_count((uint64_t) j.rows, (uint64_t) j.cols);
+    b.rows = (uint32_t) j.rows; b.cols = (uint32_t) j.cols;
+    b.N = (uint32_t) rtp::filtered_bytes((uint64_t) j.rows, (uint64_t) j.cols);
+    const size_t n_entries = (size_t) rtp::views_entry_count(b.n_views, b.tiles), n_tiles = (size_t) b.n_views * (size_t) b.tiles; // n_tiles <= the batch's pixels
+    offsets_at = RTO_SCRATCH_HEAD;
+    const size_t entries_at = offsets_at + ((size_t) j.n_views + 1u) * sizeof(long long), parts_at = entries_at + n_entries * sizeof(unsigned long long);
+    HIP_TRY(hipMallocAsync((void **) &fp.scr, parts_at + n_tiles * sizeof(rto::PngPartial), st));
+    fp.st = st;
+    rto::FormatScratch *head = (rto::FormatScratch *) fp.scr;
+    long long *offsets = (long long *) (fp.scr + offsets_at);
+    unsigned long long *entries = (unsigned long long *) (fp.scr + entries_at);
+    rto::PngPartial *parts = (rto::PngPartial *) (fp.scr + parts_at);
+    const rto::GammaTable g = gamma_table(j.gamma);
+    hipLaunchKernelGGL(rto::png_views_sums_kernel, dim3((unsigned) n_tiles), dim3(RTO_BLOCK), 0, st, b, g, entries);
+    hipLaunchKernelGGL(rto::png_views_scan_kernel, dim3(1), dim3(RTO_SCAN_THREADS), 0, st, entries, b, head, offsets, (long long *) j.d_offsets,
+                       (unsigned long long) j.capacity, j.d_out ? 1 : 0);
+    if (j.d_out) {
+        hipLaunchKernelGGL(rto::png_views_scatter_kernel, dim3((unsigned) n_tiles), dim3(RTO_BLOCK), 0, st, b, g, (const unsigned long long *) entries,
+                           (const rto::FormatScratch *) head, parts, (unsigned char *) j.d_out);
+        hipLaunchKernelGGL(rto::png_views_finish_kernel, dim3(b.n_views), dim3(RTO_BLOCK), 0, st, b, (const unsigned long long *) entries, (const rto::FormatScratch *) head,
+                           (const rto::PngPartial *) parts, (unsigned char *) j.d_out);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+// Waits for the stream, reads the K + 1 file starts and reports a buffer the device found too small (it wrote none of it).
+static int finish_png_views(FormatPending &fp, const PngViewsJob &j, size_t offsets_at, int64_t *offsets) {
+    HIP_TRY(hipMemcpyAsync(offsets, fp.scr + offsets_at, ((size_t) j.n_views + 1u) * sizeof(int64_t), hipMemcpyDeviceToHost, fp.st));
+    HIP_TRY(hipStreamSynchronize(fp.st));
+    const int64_t total = offsets[j.n_views];
+    if (j.d_out && (unsigned long long) total > (unsigned long long) j.capacity)
+        return fail(RT_ERR_INVALID_ARGUMENT, "out_capacity " + std::to_string(j.capacity) + " below the " + std::to_string(total) + " bytes needed");
+    return RT_OK;
+}
+// The K files of a device batch in host memory (the device current, n_views > 0): the encode into d_files, the offsets, and ONE device-to-host
+// copy of exactly the files.  Waits for the stream.
+static int png_views_to_host(const void *d_rgb, int32_t n_views, int32_t rows, int32_t cols, bool gamma, hipStream_t st, unsigned char *d_files, size_t capacity,
+                             std::vector<int64_t> &offsets, std::unique_ptr<char[]> &files) {
+    const PngViewsJob j{d_rgb, n_views, rows, cols, gamma, d_files, capacity, nullptr};
+    FormatPending fp;
+    size_t offsets_at = 0;
+    offsets.assign((size_t) n_views + 1u, 0);
+    RT_TRY(enqueue_png_views(j, st, fp, offsets_at));
+    RT_TRY(finish_png_views(fp, j, offsets_at, offsets.data()));
+    files.reset(new char[(size_t) offsets[(size_t) n_views]]);
+    HIP_TRY(hipMemcpyAsync(files.get(), d_files, (size_t) offsets[(size_t) n_views], hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return RT_OK;
+}
+// paths[v] written for v = 0 .. n_views - 1, one file open at a time (K may pass the descriptor limit); the first that fails ends the call,
+// the files before it stay.
+static int write_png_views(const char *const *paths, int32_t n_views, const char *files, const int64_t *offsets) {
+    for (int32_t v = 0; v < n_views; ++v) {
+        FileCloser file;
+        if (!(file.f = fopen(paths[v], "wb"))) return fail(RT_ERR_IO, std::string("cannot open ") + paths[v]);
+        RT_TRY(write_all(file, paths[v], files + offsets[v], offsets[v + 1] - offsets[v]));
+    }
+    return RT_OK;
+}
+
+extern "C" {
+
+int64_t rt_png_views_max_bytes(int32_t n_views, int32_t rows, int32_t cols) {
+    const unsigned char none = 0; // (no image is looked at: the size checks of the encode, in its order)
+    const int rc = check_png_views(&none, n_views, rows, cols, nullptr, 0);
+    return rc != RT_OK ? -(int64_t) rc : (int64_t) rtp::views_max_bytes((uint64_t) n_views, (uint64_t) rows, (uint64_t) cols);
+}
+
+int rt_format_png_views_device(int32_t device, const void *d_rgb, int32_t n_views, int32_t rows, int32_t cols, int32_t gamma_correct, void *d_out, size_t out_capacity,
+                               void *d_offsets, void *stream, int64_t *offsets) {
+    RT_TRY(check_png_views(d_rgb, n_views, rows, cols, d_out, out_capacity));
+    if (n_views == 0 && !d_offsets) { // no image, no file: nothing for a device to do
+        if (offsets) offsets[0] = 0;
+        return RT_OK;
+    }
+    DeviceGuard guard;
+    RT_TRY(guard.enter(device));
+    if (n_views == 0) {
+        HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(int64_t), (hipStream_t) stream));
+        if (offsets) { offsets[0] = 0; HIP_TRY(hipStreamSynchronize((hipStream_t) stream)); }
+        return RT_OK;
+    }
+    const PngViewsJob j{d_rgb, n_views, rows, cols, gamma_correct != 0, d_out, out_capacity, d_offsets};
+    FormatPending fp;
+    size_t offsets_at = 0;
+    RT_TRY(enqueue_png_views(j, (hipStream_t) stream, fp, offsets_at));
+    return offsets ? finish_png_views(fp, j, offsets_at, offsets) : RT_OK;
+}
+
+int rt_write_png_views_device(const char *const *paths, int32_t device, const void *d_rgb, int32_t n_views, int32_t rows, int32_t cols, int32_t gamma_correct,
+                              void *stream) {
+    RT_TRY(check_png_views(d_rgb, n_views, rows, cols, nullptr, 0));
+    RT_TRY(check_paths(paths, n_views));
+    if (n_views == 0) return RT_OK;
+    return guarded("rt_write_png_views_device", [&]() {
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        const size_t capacity = (size_t) rtp::views_max_bytes((uint64_t) n_views, (uint64_t) rows, (uint64_t) cols);
+        StreamBuf d_files;
+        d_files.st = (hipStream_t) stream;
+        HIP_TRY(hipMallocAsync((void **) &d_files.p, capacity, d_files.st));
+        std::vector<int64_t> offsets;
+        std::unique_ptr<char[]> files;
+        RT_TRY(png_views_to_host(d_rgb, n_views, rows, cols, gamma_correct != 0, d_files.st, d_files.p, capacity, offsets, files));
+        return write_png_views(paths, n_views, files.get(), offsets.data());
+    });
+}
+
+int rt_render_views_png(const rt_scene *scene, const rt_camera *cameras, int32_t n_views, int32_t max_w, int32_t max_h, const uint64_t *seeds, uint64_t seed,
+                        int32_t device, uint32_t flags, int32_t gamma_correct, const char *const *paths, const rt_render_options *options, rt_stats *stats) {
+    RT_TRY(check_views(scene, cameras, n_views, max_w, max_h, scene, options)); // rt_render_views' check list (the buffers are this call's own)
+    RT_TRY(check_paths(paths, n_views));
+    if (n_views == 0) return nothing_to_do(stats);
+    const int32_t rows = 2 * max_h + 1, cols = 2 * max_w + 1;
+    RT_TRY(check_png_size(rows, cols));
+    return guarded("rt_render_views_png", [&]() {
+        const auto t0 = std::chrono::steady_clock::now();
+        DeviceGuard guard;
+        RT_TRY(guard.enter(device));
+        // accum, rgb and the files in ONE allocation from the null stream's pool; the pixels never visit the host as rgb
+        const size_t npx = (size_t) n_views * (size_t) rows * (size_t) cols, capacity = (size_t) rtp::views_max_bytes((uint64_t) n_views, (uint64_t) rows, (uint64_t) cols),
+                     rgb_at = npx * 16u, files_at = rgb_at + ((npx * 3u + 15u) & ~(size_t) 15u);
+        StreamBuf buf;
+        HIP_TRY(hipMallocAsync((void **) &buf.p, files_at + capacity, buf.st));
+        rt_stats local;
+        {
+            Pending pd;
+            RT_TRY(launch_views(scene, cameras, n_views, max_w, max_h, seeds, seed, device, flags, buf.p, buf.p + rgb_at, nullptr, options, true, pd));
+            RT_TRY(collect_stats(pd, &local));
+        }
+        std::vector<int64_t> offsets;
+        std::unique_ptr<char[]> files;
+        RT_TRY(png_views_to_host(buf.p + rgb_at, n_views, rows, cols, gamma_correct != 0, buf.st, buf.p + files_at, capacity, offsets, files));
+        RT_TRY(write_png_views(paths, n_views, files.get(), offsets.data()));
+        if (stats) {
+            *stats = local;
+            stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return (int) RT_OK;
+    });
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------
 // resuming from a pixel map (rt_pixel_map.h, rt_pixel_map_kernels.h; DESIGN.md "Resuming from a pixel map"): ImageOutput.readPixelMap
 // (ImageOutput.fs:46-113) from bytes on the device, the list of the pixels a presence map lacks, the scatter of a rendered list into a
 // frame, and Program.fs:45-50 with the missing pixels rendered where ImageOutput.assertComplete would throw

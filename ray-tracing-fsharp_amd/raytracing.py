@@ -939,6 +939,22 @@ class Scene:
                         _flags(counters), route.ptr(out) if k else None, route.ptr(rgb) if k else None, *route.tail(options), stats=stats or not route.suffix)
         return RenderResult(out, rgb, st)
 
+    def renderViewsPng(self, maxWidthCoord: int, maxHeightCoord: int, cameras: Sequence[Camera], paths: Sequence[str], *, gammaCorrect: bool = True,
+                       seeds: Optional[Sequence[int]] = None, seed: int = 0, device: Optional[int] = None, counters: bool = False,
+                       options: Optional[A.rt_render_options] = None) -> dict:
+        """rt_render_views_png: renderViews |> Png.writeViews in one call -- the K views rendered in one launch, encoded as K PNGs in the
+        four launches one image takes, copied out once and written to paths[v]; file v is byte for byte Png.format of renderViews' rgb[v]
+        for the same arguments, and the pixels never visit the host as rgb.  Returns the statistics (total_ms covers the files)."""
+        cams, names = list(cameras), [str(p) for p in paths]
+        k = len(cams)
+        _one_path_per_view(names, k)
+        if seeds is not None and len(seeds) != k:
+            raise ValueError(f"seeds must hold one seed per camera ({k}), not {len(seeds)}")
+        abi = (A.rt_camera * max(k, 1))(*[c.to_abi() for c in cams])
+        keys = None if seeds is None else (C.c_uint64 * max(k, 1))(*[int(s) for s in seeds])
+        return self._call(lib.rt_render_views_png, abi if k else None, k, maxWidthCoord, maxHeightCoord, keys, seed, 0 if device is None else device,
+                          _flags(counters), int(bool(gammaCorrect)), _path_array(names), _ref(options))
+
     def extendViews(self, maxWidthCoord: int, maxHeightCoord: int, cameras: Sequence[Camera], accum, samplesDone: int, *,
                     seeds: Optional[Sequence[int]] = None, seed: int = 0, device: Optional[int] = None, counters: bool = False, stats: bool = True,
                     options: Optional[A.rt_render_options] = None) -> RenderResult:
@@ -1492,6 +1508,55 @@ class Png:
         for _ in range(_write_image("png", gammaCorrect, pixels, output) - 1):
             incrementProgress(1.0)
 
+    @staticmethod
+    def formatViewsDevice(gammaCorrect: bool, pixels):
+        """rt_format_png_views_device on torch.cuda.current_stream(), without waiting for the device: the K images of a contiguous uint8
+        tensor [K, rows, cols, 3] on a GPU (renderViews' rgb) encoded in the four launches one image takes -> (data, offsets): a uint8
+        tensor of rt_png_views_max_bytes(K, rows, cols) bytes and an int64 tensor of K + 1; file v is data[offsets[v]:offsets[v + 1]],
+        byte for byte Png.format of image v, and nothing at or beyond offsets[K] is written."""
+        t = _views_tensor(pixels)
+        torch = _torch()
+        k, rows, cols = int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+        cap = _size(lib.rt_png_views_max_bytes(k, rows, cols))
+        data = torch.empty(cap, dtype=torch.uint8, device=t.device)
+        offsets = torch.empty(k + 1, dtype=torch.int64, device=t.device)
+        check(lib.rt_format_png_views_device(t.device.index, t.data_ptr() if k else None, k, rows, cols, int(bool(gammaCorrect)), data.data_ptr() if cap else None,
+                                             cap, offsets.data_ptr(), torch.cuda.current_stream(t.device).cuda_stream, None))
+        return data, offsets
+
+    @staticmethod
+    def formatViews(gammaCorrect: bool, pixels) -> List[bytes]:
+        """The K files of a batch [K, rows, cols, 3].  A torch tensor on a GPU is encoded there (formatViewsDevice) and only the files are
+        copied back; a numpy array is Png.format image by image on the host, which needs no GPU."""
+        if _is_torch(pixels):
+            data, offsets = Png.formatViewsDevice(gammaCorrect, pixels)
+            at = offsets.cpu().tolist()
+            files = data[: at[-1]].cpu().numpy().tobytes()
+            return [files[a:b] for a, b in zip(at[:-1], at[1:])]
+        px = np.ascontiguousarray(pixels, dtype=np.uint8)
+        if px.ndim != 4 or px.shape[3] != 3:
+            raise ValueError(f"pixels must have shape [K, rows, cols, 3], not {list(px.shape)}")
+        return [Png.format(gammaCorrect, image) for image in px]
+
+    @staticmethod
+    def writeViews(gammaCorrect: bool, pixels, paths: Sequence[str]) -> None:
+        """paths[v] = the PNG of image v of a batch [K, rows, cols, 3].  A torch tensor on a GPU goes through rt_write_png_views_device on
+        torch.cuda.current_stream(): one encode and one copy for all files; a numpy array takes rt_write_png per image."""
+        names = [str(p) for p in paths]
+        if _is_torch(pixels):
+            t = _views_tensor(pixels)
+            k = int(t.shape[0])
+            _one_path_per_view(names, k)
+            check(lib.rt_write_png_views_device(_path_array(names), t.device.index, t.data_ptr() if k else None, k, int(t.shape[1]), int(t.shape[2]),
+                                                int(bool(gammaCorrect)), _torch().cuda.current_stream(t.device).cuda_stream))
+            return
+        px = np.ascontiguousarray(pixels, dtype=np.uint8)
+        if px.ndim != 4 or px.shape[3] != 3:
+            raise ValueError(f"pixels must have shape [K, rows, cols, 3], not {list(px.shape)}")
+        _one_path_per_view(names, px.shape[0])
+        for image, name in zip(px, names):
+            _write_image("png", gammaCorrect, image, name)
+
 
 class LoadImage:
     """LoadImage.fromResource (RayTracing.App/LoadImage.fs:9-18): a baseline JPEG to the bitmap ParameterisedTexture.ofImage takes --
@@ -1912,3 +1977,20 @@ def _image_tensor(t):
     if t.dim() != 3 or t.shape[2] != 3:
         raise ValueError(f"pixels must have shape [rows, cols, 3], not {list(t.shape)}")
     return _bytes_tensor(t)
+
+
+def _views_tensor(t):
+    """A batch of images [K, rows, cols, 3] uint8 for the batch's device output entry points."""
+    if t.dim() != 4 or t.shape[3] != 3:
+        raise ValueError(f"pixels must have shape [K, rows, cols, 3], not {list(t.shape)}")
+    return _bytes_tensor(t)
+
+
+def _one_path_per_view(paths, k: int) -> None:
+    if len(paths) != k:
+        raise ValueError(f"paths must hold one path per view ({k}), not {len(paths)}")
+
+
+def _path_array(paths):
+    """const char *const paths[] for the batch's file-writing entry points (never an empty array: the library looks at the pointer)."""
+    return (C.c_char_p * max(len(paths), 1))(*[p.encode() for p in paths])
